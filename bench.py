@@ -12,9 +12,15 @@ N > 1 (weak scaling, the shape of configs[3]): every rank searches its own 32-co
 grid on the same IF snapshot, then ONE all-gather (RCCL, torch.distributed) of the per-(code, bin)
 {max, argmax, sum} metrics, and every rank replays the decision on the gathered grid.
 
-Also reported (not part of `value`): the tracking leg of configs[2] (32 channels, 25 Msps, E/P/L + DLL/PLL),
-the roofline of the dominant kernel (acq_corr_kernel) from HIP events recorded inside the timed region on
-the stream the kernels run on, and the CPU oracle ("port" of the reference) timed on this host's cores.
+A plain run sets up, warms up, times --steps dwells and prints the line, whose `roofline` comes from HIP events
+recorded inside the timed region on the stream the kernels run on.  With --full it also measures what is not
+part of `value`, each in runs of its own: the tracking leg of configs[2] (32 channels, 25 Msps, E/P/L +
+DLL/PLL), the other BASELINE geometries, the receiver chain, the front-end, the measured copy ceiling and the
+CPU oracle ("port" of the reference) timed on this host's cores.
+
+--dump-outputs DIR writes what the last timed dwell computed, as a caller of the path receives it, to DIR/*.npy
+(float32 / float64): the {max, argmax, sum} metrics per (PRN, bin) and the decision per PRN.  The inputs are
+seeded, so two runs with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -187,6 +193,11 @@ def main():
                          "co-executing launches would pollute the per-kernel averages of a rocprofv3 --stats run)")
     ap.add_argument("--launch-timeout", type=float, default=float(os.environ.get("GM_BENCH_LAUNCH_TIMEOUT", "1500")),
                     help="--gpus N > 1 started without a launcher: seconds the parent waits for its N ranks before it ends them")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the informative legs (tracking, receiver chain, other geometries, front-end, copy ceiling, "
+                         "host-buffer API, CPU baselines); a plain run times the headline dwell only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -230,7 +241,7 @@ def main():
     # copy stream the lowest and the front-end stream the highest priority (their own queues: 216 x behind four torch streams, 220 x without);
     # the leg still runs first — a receiver process creates its receiver's streams first.
     receiver_first = None
-    if rank == 0 and world == 1 and os.environ.get("GM_BENCH_NO_RECEIVER") != "1":
+    if args.full and rank == 0 and world == 1 and os.environ.get("GM_BENCH_NO_RECEIVER") != "1":
         try:
             receiver_first = receiver_leg(A.ca_code_table(), A, T, synth, not args.no_cpu_baseline)
         except Exception as e:
@@ -411,10 +422,18 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
+    if args.dump_outputs and rank == 0:
+        # the metrics block the last timed dwell's decision read, and that decision
+        if world > 1:
+            grid = gat2[(args.steps - 1) & 1] if native_comm else keep
+        else:
+            grid = d_gather if native_comm else d_metrics
+        dump_outputs(args.dump_outputs, grid, eng.fetch_results(world * P), world * P, D)
+
     # the exchange alone (all-gather + regroup of the 3*P*D-word blocks, no search in front), in order on the stream:
     # what a dwell would pay for it without the overlap
     exchange_us = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             def xchg():
                 if debug_gloo:      # rehearsal: through host memory
@@ -536,13 +555,14 @@ def main():
                      "whole_step_algorithmic_GBs": (corr_bytes + mix_bytes) * args.steps / elapsed / 1e9},
     }
     del keep
-    if rank == 0 and world == 1:
+    # the informative legs below run with --full only (--three-dwells: its own switch); a plain run measures the headline
+    if args.full and rank == 0 and world == 1:
         try:
             c = hbm_ceiling(torch, dev)
             out["roofline"]["measured_d2d_copy_GBs"] = c      # the measured copy ceiling beside the 8 TB/s peak
         except Exception as e:
             out["roofline"]["measured_d2d_copy_GBs"] = repr(e)
-    if rank == 0:
+    if args.full and rank == 0:
         # the drop-in host-buffer entry (gm_acq_search: H2D of the 160 KB snapshot + kernels + D2H of results);
         # PCIe-inclusive, reported for DESIGN.md, never `value`
         eng.search(xi8)
@@ -564,7 +584,7 @@ def main():
             out["fine_doppler"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ configs[1] with ONE integration ("also report M = 1")
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             out["cfg2_single_integration"] = m1_leg(torch, dev, stream, sc, A, synth, xi8)
         except Exception as e:
@@ -578,14 +598,14 @@ def main():
             out["config"]["three_dwells_in_flight"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ configs[3]'s Galileo part (informative, no reference code)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             out["cfg4_galileo_geometry"] = cfg4_leg(torch, dev, A, synth)
         except Exception as e:
             out["cfg4_galileo_geometry"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ configs[3] as written: the 90-code mixed grid, sharded
-    if os.environ.get("GM_BENCH_NO_GRID") != "1":
+    if args.full and os.environ.get("GM_BENCH_NO_GRID") != "1":
         try:
             g4 = cfg4_grid_leg(torch, dev, stream, ca, A, synth, world, rank, dist, debug_gloo, native_comm)
             if rank == 0:
@@ -595,14 +615,14 @@ def main():
                 out["cfg4_grid"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ configs[0] geometry on the GPU (informative)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             out["cfg1_geometry"] = cfg1_leg(torch, dev, stream, ca, A, synth, with_cpu=not args.no_cpu_baseline)
         except Exception as e:
             out["cfg1_geometry"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ tracking leg (configs[2]), rank-local
-    if not args.no_tracking:
+    if args.full and not args.no_tracking:
         try:
             out["tracking"] = tracking_leg(torch, dev, stream, ca, T, synth, world, dist,
                                            0.0 if (args.no_cpu_baseline or rank != 0) else min(args.cpu_seconds, 8.0))
@@ -610,7 +630,7 @@ def main():
             out["tracking"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ the same kernel with 256 channels (informative)
-    if rank == 0 and world == 1 and not args.no_tracking and os.environ.get("GM_BENCH_NO_TRK256") != "1":   # (off in the counter passes: same grid size as C = 32)
+    if args.full and rank == 0 and world == 1 and not args.no_tracking and os.environ.get("GM_BENCH_NO_TRK256") != "1":   # (off in the counter passes: same grid size as C = 32)
         try:
             t256 = tracking_leg(torch, dev, stream, ca, T, synth, 1, dist, 0.0, C=256)
             out["tracking_256ch"] = {k: t256[k] for k in ("value", "unit", "channels_per_gpu", "ms_per_epoch", "channels_locked", "roofline")}
@@ -618,7 +638,7 @@ def main():
             out["tracking_256ch"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ configs[4] geometry (informative, no reference code)
-    if not args.no_tracking and os.environ.get("GM_BENCH_NO_CFG5") != "1":      # every rank takes part (strong scaling at N > 1)
+    if args.full and not args.no_tracking and os.environ.get("GM_BENCH_NO_CFG5") != "1":      # every rank takes part (strong scaling at N > 1)
         try:
             c5 = cfg5_leg(torch, stream, T, world, rank, dist, dev, debug_gloo)
         except Exception as e:
@@ -627,7 +647,7 @@ def main():
             out["cfg5_geometry"] = c5
 
     # ------------------------------------------------------------------ digital front-end, informative
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             out["frontend"] = frontend_leg(torch, dev, not args.no_cpu_baseline)
         except Exception as e:
@@ -638,7 +658,7 @@ def main():
         out["receiver"] = receiver_first          # (measured at the start of this process: see there)
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N = 1 only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(sc, args.cpu_seconds)
 
     eng.close()
@@ -688,6 +708,23 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+RESULT_FIELDS = ("code_phase_samples", "code_phase_chips", "carrier_freq", "mag_relative", "sample_global_index", "doppler_bin")
+
+
+def dump_outputs(path, d_grid, results, n_prn, D):
+    """--dump-outputs: the metrics block a dwell's decision reads ([3][n_prn][D] words: max f32, argmax u32, sum f32,
+    include/gnss_mi355x.h) and the decision per PRN (found, and each AcquisitionResult field; 0 where nothing was found)."""
+    os.makedirs(path, exist_ok=True)
+    words = d_grid.detach().cpu().numpy().astype(np.int32).reshape(3, n_prn, D)
+    np.save(os.path.join(path, "metrics_max.npy"), words[0].view(np.float32))
+    np.save(os.path.join(path, "metrics_argmax.npy"), words[1].view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "metrics_sum.npy"), words[2].view(np.float32))
+    np.save(os.path.join(path, "found.npy"), np.array([r is not None for r in results], np.float64))
+    np.save(os.path.join(path, "prn.npy"), np.array([r["prn"] if r else 0 for r in results], np.float64))
+    for k in RESULT_FIELDS:
+        np.save(os.path.join(path, k + ".npy"), np.array([r[k] if r else 0 for r in results], np.float64))
 
 
 def m1_leg(torch, dev, stream, sc, A, synth, xi8):

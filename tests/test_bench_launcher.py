@@ -132,3 +132,35 @@ def test_config_head_fits_the_drivers_parse():
     # every head key is one the line actually carries
     for k in multi:
         assert ('"%s"' % k) in src.replace(body, ""), k
+
+
+def test_help_lists_full_and_dump_outputs():
+    """A plain run times the headline only; the informative legs need --full, the outputs --dump-outputs."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_writes_the_metrics_block_and_the_decision(tmp_path):
+    """bench.py --dump-outputs: the [3][P][D] metrics words (max f32, argmax u32, sum f32) and the decision per PRN, each as a
+    float32 / float64 .npy with the values the words and the results hold."""
+    import numpy as np
+    import torch
+    b = _bench()
+    P, D = 3, 4
+    mx = (np.arange(P * D, dtype=np.float32) * 1.25 + 0.5).reshape(P, D)
+    am = (np.arange(P * D, dtype=np.uint32) * 977 + 3).reshape(P, D)
+    sm = (np.arange(P * D, dtype=np.float32) * -3.5 + 1e6).reshape(P, D)
+    words = np.concatenate([mx.view(np.int32).ravel(), am.view(np.int32).ravel(), sm.view(np.int32).ravel()])
+    hit = dict(prn=2, code_phase_samples=7123, code_phase_chips=911.25, carrier_freq=-1250.0, fs=8e6, mag_relative=12.5,
+               sample_global_index=80000, doppler_bin=15)
+    out = tmp_path / "out"
+    b.dump_outputs(str(out), torch.from_numpy(words), [None, hit, None], P, D)
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()), {k: a.dtype for k, a in got.items()}
+    assert np.array_equal(got["metrics_max"], mx) and np.array_equal(got["metrics_sum"], sm)
+    assert np.array_equal(got["metrics_argmax"], am.astype(np.float64))
+    assert got["found"].tolist() == [0.0, 1.0, 0.0] and got["prn"].tolist() == [0.0, 2.0, 0.0]
+    for k in b.RESULT_FIELDS:
+        assert got[k].tolist() == [0.0, float(hit[k]), 0.0], k

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/pmc_sq
 rm -rf $OUT && mkdir -p $OUT
-ARGS="--steps 6 --warmup 2 --no-cpu-baseline ${BENCH_EXTRA:---no-tracking}"
+ARGS="--full --steps 6 --warmup 2 --no-cpu-baseline ${BENCH_EXTRA:---no-tracking}"
 cd /tmp
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $OUT/a -o run -- python3 $R/bench.py $ARGS > $OUT/a.log 2>&1 || exit 1
 echo "pass a done"

@@ -1,7 +1,7 @@
 for v in "" _vILP _vTRK; do
   L=$PWD/gnss-sdr-rs_amd/lib/libgnss_mi355x$v.so
   echo "== ${v:-default}"
-  GM_LIB_PATH=$L timeout -k 10 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-tracking 2>/dev/null | python3 -c "
+  GM_LIB_PATH=$L timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-tracking 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
