@@ -30,7 +30,15 @@ class AcqCfg(C.Structure):
                 ("n_bins", C.c_uint32), ("doppler_hz", C.c_void_p), ("tables", C.c_void_p),
                 ("table_freq", C.c_void_p), ("n_prn", C.c_uint32), ("prn_ids", C.c_void_p), ("codes", C.c_void_p),
                 ("code_len", C.c_uint32), ("code_rate", C.c_float), ("threshold", C.c_float),
-                ("decision_mode", C.c_int32), ("strict_sum_order", C.c_int32), ("reference_products", C.c_int32)]
+                ("decision_mode", C.c_int32), ("strict_sum_order", C.c_int32), ("reference_products", C.c_int32),
+                ("any_length", C.c_int32)]
+
+
+class AcqPlan(C.Structure):
+    _fields_ = [("form", C.c_int32), ("base", C.c_uint32), ("q", C.c_uint32), ("transform_len", C.c_uint32)]
+
+
+ACQ_FORM_LDS, ACQ_FORM_COMPOSITE, ACQ_FORM_LONG, ACQ_FORM_LONG_PADDED = 0, 1, 2, 3   # gm_acq_form
 
 
 class TrkState(C.Structure):
@@ -82,6 +90,7 @@ SIGNATURES = {
     "gm_fft_power_spectrum_f32": (_i, [_sz, _vp, _vp]),
     "gm_rfft_f32": (_i, [_sz, _vp, _vp]),
     "gm_fft_supported_sizes": (_i, [_vp, _i]),
+    "gm_acq_plan_info": (_i, [C.c_uint32, C.c_int32, C.POINTER(AcqPlan)]),
     "gm_acq_create": (_i, [C.POINTER(AcqCfg), C.POINTER(_vp)]),
     "gm_acq_destroy": (_i, [_vp]),
     "gm_acq_search": (_i, [_vp, _vp, _sz, _i, _u64, _u64, _vp, _vp]),

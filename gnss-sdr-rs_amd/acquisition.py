@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AcqCfg, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
+from ._lib import AcqCfg, AcqPlan, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
 
 PRN_SEARCH_ACQUISITION_TOTAL = 32      # do_acquisition.rs:22
 FREQ_SEARCH_ACQUISITION_HZ = 14e3      # :20
@@ -72,6 +72,17 @@ def b1i_codes(prns=range(1, 38), n_chips=2046):
 
 
 DECIDE_REFERENCE, DECIDE_BEST_BIN = 0, 1   # gm_decision_mode
+ACQ_FORMS = {0: "lds", 1: "composite", 2: "long", 3: "long_padded"}   # gm_acq_form
+
+
+def plan_info(fft_size, any_length=False):
+    """gm_acq_plan_info: (status, dict(form, base, q, transform_len)) — the path gm_acq_create takes for this fft_size
+    (status 0), or the status it returns (the dict is then None).  Host only, no device needed."""
+    o = AcqPlan()
+    st = lib().gm_acq_plan_info(int(fft_size), int(bool(any_length)), C.byref(o))
+    if st:
+        return st, None
+    return st, dict(form=ACQ_FORMS[o.form], base=int(o.base), q=int(o.q), transform_len=int(o.transform_len))
 
 
 class AcquisitionEngine:
@@ -80,7 +91,7 @@ class AcquisitionEngine:
 
     def __init__(self, fs, f_if, fft_size, doppler_hz=None, prn_ids=None, n_integrations=LONG_SAMPLES_LENGTH,
                  tables=None, codes=None, code_rate=1.023e6, threshold=7.0, decision_mode=0, strict_sum_order=False, reference_products=False,
-                 device=None):
+                 device=None, any_length=False):
         _lib.init(device if device is not None else (_lib._initialised or 0))
         self.fs, self.f_if, self.fft_size, self.M = float(fs), float(f_if), int(fft_size), int(n_integrations)
         self.prn_ids = np.ascontiguousarray(prn_ids if prn_ids is not None else np.arange(1, 33), np.uint8)
@@ -107,12 +118,20 @@ class AcquisitionEngine:
         cfg.decision_mode = decision_mode
         cfg.strict_sum_order = int(bool(strict_sum_order))
         cfg.reference_products = int(bool(reference_products))
+        cfg.any_length = int(bool(any_length))      # every multiple of 8 in [1024, 2^18] (gm_acq_cfg.any_length)
+        self.any_length = bool(any_length)
         self.P = int(cfg.n_prn)
         h = C.c_void_p()
         check(lib().gm_acq_create(C.byref(cfg), C.byref(h)), "gm_acq_create")
         self._h = h
         self.table_freq = np.zeros(self.D, np.float32)
         check(lib().gm_acq_tables(self._h, None, _p(self.table_freq)), "gm_acq_tables")
+
+    def plan_info(self):
+        """The path this handle's fft_size runs on: dict(form, base, q, transform_len) (module-level plan_info)."""
+        st, info = plan_info(self.fft_size, self.any_length)
+        check(st, "gm_acq_plan_info")
+        return info
 
     def close(self):
         if getattr(self, "_h", None):

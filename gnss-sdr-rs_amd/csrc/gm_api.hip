@@ -332,6 +332,13 @@ struct gm_acq {
     cf* d_comp_twn = nullptr;              // [Q][Nb] inverse twiddles W_N^{-n1 k2}, paired positions
     float* d_planes = nullptr;             // composite sizes with strict_sum_order: the accumulated power planes [P * D][N] (launch_plane_strict_sum)
     cf* d_code_comb = nullptr;             // Q > 1: [P][Q][Q][Nb] conj(code) x W_Q^{-n1 k1} x W_N^{-n1 k2}, what comp corr multiplies the spectra by
+    // any-length sizes (gm_acq_cfg.any_length, acq_long.hip): transform length L = Q * Nb (L = N native, L >= 2N padded); Q may be 1
+    const gm::LongOps* lng = nullptr;
+    uint32_t L = 0, long_lim = 0, long_slab = 0;   // L; the signal's extension (N native, 2N padded); (worker, bin) items per slab
+    float long_scale = 1.0f;               // (N / L)^2
+    cf* d_long_code = nullptr;             // [P][L] natural code spectra (native: d_code_fft itself)
+    cf* d_long_z = nullptr;                // [long_slab][M][L] the inverse's intermediate
+    float* d_long_part = nullptr;          // [3][P * D][Q] partial {max, argmax, sum}
     // gm_acq_decide_dev on the metrics of the last search, on a handle of an in-LDS size: the decision is NOT launched but kept here
     // and rides along with the next search's stage F (PlanOps::mix_fft: trailing workgroups) — anything else that consumes or
     // invalidates it (fetch, synchronize, another decide, a stream change, timing) launches decide_kernel first (acq_flush_decision)
@@ -371,6 +378,9 @@ struct gm_acq {
         uint32_t *d_rowarg = nullptr, *d_sat_worker = nullptr, *d_sat_cp = nullptr, *d_peak_idx = nullptr;
     } fine;
 };
+
+// the fused single-LDS-buffer kernels (acq_kernels.hip): neither a composite nor an any-length size
+static bool acq_fused(const gm_acq* a) { return a->Q == 1 && !a->lng; }
 
 static int acq_set_mask(gm_acq* a, uint64_t mask) {
     std::vector<uint32_t> wl;
@@ -670,6 +680,8 @@ int gm_acq_destroy(gm_acq* a) {
     if (!a) return GM_OK;
     if (a->device >= 0) hipSetDevice(a->device);
     hipFree(a->d_planes);
+    if (a->d_long_code != a->d_code_fft) hipFree(a->d_long_code);
+    hipFree(a->d_long_z); hipFree(a->d_long_part);
     hipFree(a->d_comp_tmp); hipFree(a->d_comp_twn); hipFree(a->d_code_comb); hipFree(a->d_split_scratch); hipFree(a->d_split_counter);
     hipFree(a->fine.d_chips); hipFree(a->fine.d_tw1); hipFree(a->fine.d_tw2); hipFree(a->fine.d_B); hipFree(a->fine.d_mean);
     hipFree(a->fine.d_rowmax); hipFree(a->fine.d_rowarg); hipFree(a->fine.d_sat_worker); hipFree(a->fine.d_sat_cp);
@@ -691,6 +703,55 @@ int gm_acq_destroy(gm_acq* a) {
     return GM_OK;
 }
 
+// Which path serves an fft_size — the one rule behind gm_acq_plan_info and gm_acq_create.  In-LDS plan, else Q x base composite
+// (acq_composite.hip), else with any_length the long path (acq_long.hip): L = N over the largest base that divides N with Q <= 32,
+// else the smallest Q x base >= 2N (equal lengths: the larger base).  *pl: the base plan, *comp / *lng: the composite / long kernels.
+static int acq_choose(uint32_t n, int32_t any_length, gm_acq_plan* info, const gm::PlanOps** pl, const gm::CompOps** comp,
+                      const gm::LongOps** lng) {
+    gm_acq_plan o{GM_ACQ_FORM_LDS, n, 1, n};
+    const gm::PlanOps* p = nullptr;
+    const gm::CompOps* c = nullptr;
+    const gm::LongOps* l = nullptr;
+    if (!n) return GM_ERR_INVALID_ARG;
+    if (n % 8) return GM_ERR_ALIGNMENT;
+    if ((p = gm::find_plan(int(n)))) {
+    } else if ((c = gm::find_comp(n))) {
+        p = gm::find_plan(c->nb);
+        o = gm_acq_plan{GM_ACQ_FORM_COMPOSITE, uint32_t(c->nb), uint32_t(c->q), n};
+    } else if (any_length && n >= 1024 && n <= 262144) {
+        int nl = 0;
+        const gm::LongOps* bases = gm::long_bases(&nl);
+        for (int i = 0; i < nl && !l; ++i)       // largest base first
+            if (n % uint32_t(bases[i].nb) == 0 && n / uint32_t(bases[i].nb) <= 32) {
+                l = &bases[i];
+                o = gm_acq_plan{GM_ACQ_FORM_LONG, uint32_t(l->nb), n / uint32_t(l->nb), n};
+            }
+        if (!l) {
+            uint64_t best = 0;
+            for (int i = 0; i < nl; ++i) {
+                const uint64_t nb = uint64_t(bases[i].nb), q = (2 * uint64_t(n) + nb - 1) / nb;
+                if (q <= 32 && (!best || q * nb < best)) { best = q * nb; l = &bases[i]; }
+            }
+            if (l) o = gm_acq_plan{GM_ACQ_FORM_LONG_PADDED, uint32_t(l->nb), uint32_t(best / uint64_t(l->nb)), uint32_t(best)};
+        }
+        if (l) p = gm::find_plan(l->nb);
+    }
+    if (!p) return GM_ERR_UNSUPPORTED_N;
+    if (info) *info = o;
+    if (pl) *pl = p;
+    if (comp) *comp = c;
+    if (lng) *lng = l;
+    return GM_OK;
+}
+
+int gm_acq_plan_info(uint32_t fft_size, int32_t any_length, gm_acq_plan* out) {
+    const int rc = acq_choose(fft_size, any_length, out, nullptr, nullptr, nullptr);
+    if (rc == GM_ERR_ALIGNMENT) return set_err(rc, "fft_size % 8 != 0");
+    if (rc == GM_ERR_UNSUPPORTED_N) return set_err(rc, "no acquisition path for this fft_size (gm_acq_cfg.any_length: multiples of 8 in [1024, 262144])");
+    if (rc) return set_err(rc, "fft_size is required");
+    return GM_OK;
+}
+
 int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     if (!cfg || !out) return set_err(GM_ERR_INVALID_ARG, "null cfg/out");
     *out = nullptr;
@@ -699,21 +760,21 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     if (!cfg->tables && !cfg->doppler_hz) return set_err(GM_ERR_INVALID_ARG, "doppler_hz or tables required");
     if (cfg->tables && !cfg->table_freq) return set_err(GM_ERR_INVALID_ARG, "table_freq required with tables");
     if (cfg->fft_size % 8) return set_err(GM_ERR_ALIGNMENT, "fft_size % 8 != 0");
-    const gm::PlanOps* pl = gm::find_plan(int(cfg->fft_size));
+    const gm::PlanOps* pl = nullptr;
     const gm::CompOps* comp = nullptr;
-    uint32_t comp_q = 1;
-    if (pl && !cfg->strict_sum_order && !cfg->reference_products && gm::diag_int("GM_COMP_BASE", 0) > 0) {      // diagnostic: a size with a fused plan through the composite path
+    const gm::LongOps* lng = nullptr;
+    gm_acq_plan form{};
+    if (acq_choose(cfg->fft_size, cfg->any_length, &form, &pl, &comp, &lng) != GM_OK) pl = nullptr;
+    uint32_t comp_q = comp ? uint32_t(comp->q) : 1;
+    if (pl && !comp && !lng && !cfg->strict_sum_order && !cfg->reference_products && gm::diag_int("GM_COMP_BASE", 0) > 0) {      // diagnostic: a size with a fused plan through the composite path
         const gm::CompOps* c = gm::find_comp(cfg->fft_size);
-        if (c && c->nb == gm::diag_int("GM_COMP_BASE", 0)) pl = nullptr;
+        if (c && c->nb == gm::diag_int("GM_COMP_BASE", 0)) { comp = c; pl = gm::find_plan(c->nb); comp_q = uint32_t(c->q); }
     }
-    if (!pl) {   // N = Q * Nb with Nb one of the composite base plans (largest first): acq_composite.hip
-        comp = gm::find_comp(cfg->fft_size);
-        if (comp) { pl = gm::find_plan(comp->nb); comp_q = uint32_t(comp->q); }
-    }
-    if (!pl) return set_err(GM_ERR_UNSUPPORTED_N, "no in-LDS FFT plan for this fft_size, nor Q x {16384, 16368, 16000, 8192, 8184, 8000, 6000, 5000, 4000} with Q in {2,3,4,5,6,8}");
+    if (!pl) return set_err(GM_ERR_UNSUPPORTED_N, cfg->any_length ? "no acquisition path for this fft_size (any_length: multiples of 8 in [1024, 262144])"
+                                                                 : "no in-LDS FFT plan for this fft_size, nor Q x {16384, 16368, 16000, 8192, 8184, 8000, 6000, 5000, 4000} with Q in {2,3,4,5,6,8}");
     // (strict_sum_order on a composite size: the kernels also store the power planes and a second kernel sums them in the reference's
     //  order — P * D * N * 4 bytes of planes: 189 MB at the configs[3] Galileo geometry)
-    if (cfg->reference_products && comp_q > 1)
+    if (cfg->reference_products && (comp_q > 1 || lng))
         return set_err(GM_ERR_INVALID_ARG, "reference_products needs an fft_size with an in-LDS plan (gm_fft_supported_sizes)");
     if (int rc = ensure_device(g_device)) return rc;
 
@@ -722,7 +783,14 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     a->cfg = *cfg;
     a->plan = pl;
     a->N = cfg->fft_size; a->D = cfg->n_bins; a->M = cfg->n_integrations; a->P = cfg->n_prn;
-    a->Q = comp_q; a->Nb = uint32_t(pl->n); a->comp = comp;
+    a->Q = lng ? form.q : comp_q; a->Nb = uint32_t(pl->n); a->comp = comp;
+    a->lng = lng;
+    if (lng) {
+        a->L = form.transform_len;
+        a->long_lim = form.form == GM_ACQ_FORM_LONG_PADDED ? 2 * cfg->fft_size : cfg->fft_size;
+        const double r = double(cfg->fft_size) / double(a->L);
+        a->long_scale = float(r * r);
+    }
     if (cfg->threshold == 0.0f) a->cfg.threshold = 7.0f;
     a->code_rate = cfg->codes ? (cfg->code_rate > 0 ? cfg->code_rate : CA_RATE) : CA_RATE;
     a->prn_ids.assign(cfg->prn_ids, cfg->prn_ids + a->P);
@@ -763,7 +831,7 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     }
     // inverse twiddles: the in-LDS correlation kernel's own plan (CorrPlanOf) for a size that fits one LDS image, the registered plan's
     // (what the composite kernels run on) for Q x base
-    const bool twi_corr = a->Q == 1;
+    const bool twi_corr = acq_fused(a);
     std::vector<cf> twf(size_t(pl->tw_total) + 1), twi(size_t(twi_corr ? pl->tw_total_corr : pl->tw_total) + 1);
     pl->fill_tw(twf.data(), false);
     if (twi_corr) pl->fill_tw_corr(twi.data());
@@ -785,13 +853,13 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     HIPA(hipMalloc(&a->d_tw_mix, twm.size() * 8));
     HIPA(hipMalloc(&a->d_code_samples, P * N));
     HIPA(hipMalloc(&a->d_code_fft, P * N * 8));
-    HIPA(hipMalloc(&a->d_spectra, D * M * N * 8));
+    HIPA(hipMalloc(&a->d_spectra, D * M * (a->lng ? size_t(a->L) : N) * 8));
     a->samples_cap = M * N * 8;
     HIPA(hipMalloc(&a->d_samples, a->samples_cap));
     HIPA(hipMalloc(&a->d_metrics, 3 * P * D * 4));
     HIPA(hipMemsetAsync(a->d_metrics, 0, 3 * P * D * 4, a->stream));
     HIPA(hipMalloc(&a->d_worker_list, P * 4));
-    if (a->Q == 1 && pl->split_slab && M >= 2) {
+    if (acq_fused(a) && pl->split_slab && M >= 2) {
         // planes the tail split can ever use for THIS handle: every item cut (small grids: P*D items x M planes), or per XCD one
         // resident round of parts (64 slots; an item's M planes each) — never more than GM_CORR_SPLIT_MAX_SLABS
         // (a one-PRN AcquisitionWorker handle at N = 16368 takes 290 planes = 19 MB instead of 2560 = 251 MB)
@@ -814,14 +882,38 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     HIPA(hipMemcpy(a->d_prn_ids, a->prn_ids.data(), P, hipMemcpyHostToDevice));
     a->dev_prn_ids = a->prn_ids;
     // replica spectra: forward FFT of the resampled code (:136-138)
-    int (*fill_order)(uint16_t*) = a->Q == 1 ? pl->fill_order : comp->fill_order;
-    if (const int n_order = fill_order(nullptr)) {      // this (base) size's correlation plan reads a permuted spectrum
+    int (*fill_order)(uint16_t*) = a->lng ? nullptr : (a->Q == 1 ? pl->fill_order : comp->fill_order);
+    if (const int n_order = fill_order ? fill_order(nullptr) : 0) {      // this (base) size's correlation plan reads a permuted spectrum
         std::vector<uint16_t> order(static_cast<size_t>(n_order), 0);
         fill_order(order.data());
         HIPA(hipMalloc(&a->d_order, order.size() * sizeof(uint16_t)));
         HIPA(hipMemcpy(a->d_order, order.data(), order.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
-    if (a->Q == 1) {
+    if (a->lng) {     // the signal's two forward steps on the chips (zero-padded to L), natural order
+        const size_t L = a->L;
+        if (L == N) a->d_long_code = a->d_code_fft;
+        else HIPA(hipMalloc(&a->d_long_code, P * L * 8));
+        a->lng->fwd_sub(a->stream, nullptr, GM_FMT_C32, nullptr, a->d_code_samples, a->d_tw_fwd, a->d_long_code, uint32_t(P), a->Q,
+                        uint32_t(N), uint32_t(N), 1);
+        gm::launch_long_fwd_post(a->stream, a->d_long_code, uint32_t(P), a->Q, a->Nb);
+        // the inverse's intermediate, per slab of (worker, bin) items: at most 128 MiB (inside the 256 MiB Infinity Cache beside the
+        // spectra it reads), at least one item, and a grid of at most 65535 rows of C1
+        size_t slab = (size_t(128) << 20) / (M * L * 8);
+        if (slab < 1) slab = 1;
+        if (slab > P * D) slab = P * D;
+        if (slab * M > 65535) slab = 65535 / M;
+        a->long_slab = uint32_t(slab);
+        HIPA(hipMalloc(&a->d_long_z, slab * M * L * 8));
+        HIPA(hipMalloc(&a->d_long_part, 3 * P * D * a->Q * 4));
+        if (cfg->strict_sum_order) HIPA(hipMalloc(&a->d_planes, P * D * N * sizeof(float)));
+        if (L != N) {     // gm_acq_code_fft's length-N spectrum (the API's view): the same chips through the any-length FFT (Bluestein)
+            std::vector<gm_c32> cb(P * N);
+            for (size_t i = 0; i < P * N; ++i) { cb[i].re = float(code_samples[i]); cb[i].im = 0.0f; }
+            HIPA(hipStreamSynchronize(a->stream));
+            if ((rc = gm_fft_c2c_f32(N, 0, cb.data(), P))) return fail(rc);
+            HIPA(hipMemcpy(a->d_code_fft, cb.data(), P * N * 8, hipMemcpyHostToDevice));
+        }
+    } else if (a->Q == 1) {
         pl->code_fft(a->stream, a->d_code_samples, a->d_tw_fwd, a->d_code_fft, int(P));
         HIPA(hipMalloc(&a->d_code_fft_paired, P * N * 8));
         pl->pair_codes(a->stream, a->d_code_fft, a->d_code_fft_paired, int(P));
@@ -895,6 +987,9 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
         std::swap(a->d_spectra, ah.d_spectra_alt);
         HIPC(hipStreamWaitEvent(a->stream, ah.ev_f, 0));
         tickets_cleared = false;
+    } else if (a->lng) {
+        a->lng->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_fwd, a->d_spectra, a->D * a->M, a->Q, a->N, a->long_lim, a->M);
+        gm::launch_long_fwd_post(a->stream, a->d_spectra, a->D * a->M, a->Q, a->Nb);
     } else if (a->Q == 1) {
         a->plan->mix_fft(a->stream, d_samples, fmt, a->d_tables, a->d_tw_mix, a->d_spectra, int(a->D), int(a->M), a->d_split_counter, a->d_order,
                          a->dec_deferred ? &a->dec_args : nullptr);
@@ -909,7 +1004,21 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
     }
     if (t) HIPC(hipEventRecord(ev[1], a->stream));
     if (ah.side) HIPC(hipEventRecord(ah.ev_s, a->stream));
-    if (a->Q == 1) {
+    if (a->lng) {
+        if (a->n_workers) {
+            const size_t part = size_t(a->P) * a->D * a->Q;
+            gm::LongCorrArgs la{};
+            la.spectra = a->d_spectra; la.code_fft = a->d_long_code; la.tw_inv = a->d_tw_inv; la.Z = a->d_long_z;
+            la.pmax = a->d_long_part; la.parg = reinterpret_cast<uint32_t*>(a->d_long_part + part); la.psum = a->d_long_part + 2 * part;
+            la.mmax = reinterpret_cast<float*>(met); la.margmax = met + PD; la.msum = reinterpret_cast<float*>(met + 2 * PD);
+            la.planes = a->d_planes; la.worker_list = a->d_worker_list;
+            la.n_workers = a->n_workers; la.n_bins = a->D; la.n_int = a->M; la.Q = a->Q; la.Nb = a->Nb; la.N = a->N;
+            la.slab_items = a->long_slab; la.scale = a->long_scale;
+            gm::launch_long_corr(a->stream, a->lng, la);
+            if (a->d_planes)      // strict_sum_order: the plane sums once more, in is_good_satellite's own order (:229-235)
+                gm::launch_plane_strict_sum(a->stream, a->d_planes, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(a->D), uint32_t(a->N));
+        }
+    } else if (a->Q == 1) {
         a->plan->corr(a->stream, a->d_spectra, a->plan->code_paired ? a->d_code_fft_paired : a->d_code_fft, a->d_tw_inv, reinterpret_cast<float*>(met), met + PD,
                       reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(a->D), int(a->M),
                       a->d_split_scratch, a->split_planes, a->d_split_counter, a->cfg.strict_sum_order ? 1 : 0, tickets_cleared ? 1 : 0,
@@ -941,7 +1050,7 @@ int gm_acq_search_prepared_dev(gm_acq* a, uint64_t token, void* d_metrics) {
     if (!token || !ah.valid || ah.token != token)
         return set_err(GM_ERR_INVALID_ARG, "no such preparation (token stale, consumed, replaced or dropped)");
     if (int rc = ensure_device(a->device)) return rc;
-    if (a->Q != 1) {                        // composite sizes prepare nothing: the whole search runs now, from the samples named then,
+    if (!acq_fused(a)) {                    // composite and any-length sizes prepare nothing: the whole search runs now, from the samples named then,
         ah.valid = false;                   // behind what `ready_stream` held at the time of gm_acq_prepare_dev
         if (ah.comp_wait) { HIPC(hipStreamWaitEvent(a->stream, ah.ev_in, 0)); ah.comp_wait = false; }
         return acq_search_common(a, ah.samples, ah.fmt, d_metrics, false);
@@ -961,7 +1070,7 @@ int gm_acq_prepare_dev(gm_acq* a, const void* d_samples, int fmt, void* ready_st
     *token = 0;
     gm_acq::Ahead& ah = a->ahead;
     if (int rc = ensure_device(a->device)) return rc;
-    if (a->Q != 1) {                        // composite sizes: nothing is prepared, gm_acq_search_prepared_dev does all of it —
+    if (!acq_fused(a)) {                    // composite and any-length sizes: nothing is prepared, gm_acq_search_prepared_dev does all of it —
         // but the ordering promise is the same: the samples are complete once the work queued on `ready_stream` so far has run, so
         // the event is recorded NOW and the search waits for it on the handle's stream (the token used to be handed
         // out before `ready_stream` was looked at)
@@ -1035,7 +1144,7 @@ int gm_acq_decide_dev(gm_acq* a, const void* d_metrics, uint32_t n_prn, const ui
     da.best_bin_mode = a->cfg.decision_mode == GM_DECIDE_BEST_BIN ? 1 : 0;
     da.local_tail = local_tail;
     da.results = a->d_results; da.found = a->d_found;
-    if (a->defer_decisions && a->Q == 1 && !(a->tm.on && a->tm.this_call) && met == a->last_metrics && a->D <= 64) {
+    if (a->defer_decisions && acq_fused(a) && !(a->tm.on && a->tm.this_call) && met == a->last_metrics && a->D <= 64) {
         a->dec_args = da;          // runs with the next gm_acq_search_dev's stage F, or at the next flush point
         a->dec_deferred = true;
         return GM_OK;

@@ -124,6 +124,37 @@ const CompOps* find_comp(uint32_t n);
 // for the planes of the listed workers (o = worker * n_bins + bin)
 void launch_plane_strict_sum(hipStream_t, const float* planes, float* msum, const uint32_t* worker_list, int n_workers, int n_bins, uint32_t N);
 
+// any-length sizes (gm_acq_cfg.any_length, acq_long.hip): L = Q * nb with Q in [1, 32] at run time, native (L = N) or padded (L >= 2N)
+struct LongOps {
+    int nb;            // base in-LDS plan length
+    // F1: Q in-LDS transforms of length nb per item over the decimated length-L inputs; element n < lim is sample n mod N (signal:
+    // carrier mix fused; codes: int8 chips), the rest zero.  A[item][n1][k2], natural order
+    void (*fwd_sub)(hipStream_t, const void* samples, int fmt, const cf* tables, const int8_t* code_samples, const cf* tw_fwd,
+                    cf* A, uint32_t n_items, uint32_t Q, uint32_t N, uint32_t lim, uint32_t n_int);
+    // C2: items [item0, item0 + n_slab) of the bin-major (bin, worker) list, one workgroup per (item, n1) -> partials [item][n1]
+    void (*corr_inv)(hipStream_t, const cf* Z, const cf* tw_inv, float* pmax, uint32_t* parg, float* psum, float* planes,
+                     const uint32_t* worker_list, uint32_t n_workers, uint32_t n_bins, uint32_t item0, uint32_t n_slab, uint32_t Q,
+                     uint32_t N, uint32_t n_int, float scale);
+};
+// the base plans, largest first
+const LongOps* long_bases(int* n);
+// F2: twiddle + Q-point DFT across n1, in place -> natural order (nothing for Q = 1)
+void launch_long_fwd_post(hipStream_t, cf* X, uint32_t n_items, uint32_t Q, uint32_t Nb);
+struct LongCorrArgs {
+    const cf* spectra;                     // [n_bins][n_int][L] natural
+    const cf* code_fft;                    // [codes][L] natural (not conjugated)
+    const cf* tw_inv;                      // the base plan's inverse twiddles
+    cf* Z;                                 // [slab_items][n_int][L]
+    float *pmax, *psum; uint32_t* parg;    // partials [n_workers * n_bins][Q]
+    float *mmax, *msum; uint32_t* margmax; // metric words, o = worker * n_bins + bin
+    float* planes;                         // strict_sum_order: [codes * n_bins][N], else null
+    const uint32_t* worker_list;
+    uint32_t n_workers, n_bins, n_int, Q, Nb, N, slab_items;
+    float scale;                           // (N / L)^2
+};
+// C1 + C2 per slab, then C3
+void launch_long_corr(hipStream_t, const LongOps*, const LongCorrArgs&);
+
 // elementwise apply_doppler_shift (doppler_shift.rs:25-58)
 void launch_apply_doppler(hipStream_t, const cf* s, const cf* t, cf* out, size_t n);
 // |X|^2 (fft.rs:27-29)

@@ -89,9 +89,10 @@ class AcquisitionEngine {
 public:
     AcquisitionEngine(float fs, float f_if, uint32_t fft_size, const std::vector<float>& doppler_hz,
                       const std::vector<uint8_t>& prn_ids, uint32_t n_integrations = 10, float threshold = 7.0f,
-                      int decision_mode = GM_DECIDE_REFERENCE) {
+                      int decision_mode = GM_DECIDE_REFERENCE, bool any_length = false) {
         gm_acq_cfg c{};
         c.decision_mode = decision_mode;
+        c.any_length = any_length ? 1 : 0;      // every fft_size % 8 == 0 in [1024, 2^18] (gm_acq_cfg.any_length)
         c.fs = fs; c.f_if = f_if; c.fft_size = fft_size; c.n_integrations = n_integrations;
         c.n_bins = uint32_t(doppler_hz.size()); c.doppler_hz = doppler_hz.data();
         c.n_prn = uint32_t(prn_ids.size()); c.prn_ids = prn_ids.data(); c.threshold = threshold;
@@ -100,7 +101,7 @@ public:
     }
     // caller-built tables, as search_satellite receives them (:160-161)
     AcquisitionEngine(float fs, uint32_t fft_size, const std::vector<DopplerShiftTable>& tables,
-                      const std::vector<uint8_t>& prn_ids, uint32_t n_integrations) {
+                      const std::vector<uint8_t>& prn_ids, uint32_t n_integrations, bool any_length = false) {
         std::vector<gm_c32> flat(tables.size() * size_t(fft_size));
         std::vector<float> freq(tables.size());
         for (size_t d = 0; d < tables.size(); ++d) {
@@ -111,6 +112,7 @@ public:
         gm_acq_cfg c{};
         c.fs = fs; c.fft_size = fft_size; c.n_integrations = n_integrations; c.n_bins = uint32_t(tables.size());
         c.tables = flat.data(); c.table_freq = freq.data(); c.n_prn = uint32_t(prn_ids.size()); c.prn_ids = prn_ids.data();
+        c.any_length = any_length ? 1 : 0;
         n_prn_ = c.n_prn;
         check(gm_acq_create(&c, &h_), "AcquisitionEngine::new");
     }
@@ -177,7 +179,8 @@ public:
                                                       const std::vector<DopplerShiftTable>& doppler_table, size_t local_tail,
                                                       size_t num_integrations) {
         if (!eng_ || key_ != doppler_table.data() || key_n_ != doppler_table.size() || key_m_ != num_integrations) {
-            eng_ = std::make_unique<AcquisitionEngine>(fs_, fft_size_, doppler_table, std::vector<uint8_t>{prn_}, uint32_t(num_integrations));
+            // any_length: the reference plans an FFT of whatever fft_size is (:130-143)
+            eng_ = std::make_unique<AcquisitionEngine>(fs_, fft_size_, doppler_table, std::vector<uint8_t>{prn_}, uint32_t(num_integrations), true);
             key_ = doppler_table.data(); key_n_ = doppler_table.size(); key_m_ = num_integrations;
         }
         return eng_->search(samples_chunk, local_tail)[0];
@@ -398,7 +401,7 @@ inline void run_acquisition(MulticastRingBuffer& multi_buffer, float freq_sampli
     std::vector<uint8_t> prns(PRN_SEARCH_ACQUISITION_TOTAL);
     for (uint8_t p = 0; p < PRN_SEARCH_ACQUISITION_TOTAL; ++p) prns[p] = uint8_t(p + 1);
     AcquisitionEngine workers(freq_sampling_hz, f_if, fft_size, doppler, prns, opt.long_samples_length, 7.0f,
-                              opt.decision_mode);                                                            // :252-271
+                              opt.decision_mode, true);      // any_length: fft_size = round(fs / 1 kHz), whatever fs is :252-271
     std::set<uint8_t> active_prns;
     AcquisitionManager acq_manager;
     ctl.stages_ready++;

@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 7   /* 7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
+#define GM_ABI_VERSION 8   /* 8: gm_acq_cfg.any_length, gm_acq_plan_info;
+                              7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
 
 typedef enum {
@@ -118,7 +119,8 @@ typedef struct {
     uint32_t fft_size;         /* samples per code period (do_acquisition.rs:249-251): one of gm_fft_supported_sizes()
                                   (fused in-LDS kernels), or Q x {16000, 8000, 8192, 6000, 5000, 4000}, Q in {2,3,4,5,6,8}
                                   (e.g. 32000 for a 4 ms code at 8 Msps, 25000 for GPS at 25 Msps: composite path,
-                                  transforms decimated in time, no intermediate plane in HBM) */
+                                  transforms decimated in time, no intermediate plane in HBM); with any_length = 1 any
+                                  multiple of 8 in [1024, 262144] (see any_length, gm_acq_plan_info) */
     uint32_t n_integrations;   /* LONG_SAMPLES_LENGTH = 10 (:23) */
     uint32_t n_bins;           /* Doppler bins; reference: 14000/500+1 = 29 (:248) */
     const float *doppler_hz;   /* [n_bins] offsets from f_if, ascending as the reference iterates */
@@ -147,10 +149,38 @@ typedef struct {
                                   own (re = a.re*b.re - a.im*b.im, im = a.re*b.im + a.im*b.re; re*re + im*im) — so that the only
                                   arithmetic on the path that differs from the reference's is the FFT itself (rustfft's plan
                                   cannot be restated here).  ~3 % slower.  In-LDS sizes only.  (ABI 5) */
+    int32_t any_length;        /* 0 (default): only the sizes above — every other fft_size is GM_ERR_UNSUPPORTED_N.
+                                  1: also every fft_size with fft_size % 8 == 0 and 1024 <= fft_size <= 262144 (the reference
+                                  plans any length), on the long path: L = Q x Nb, Q in [1, 32], Nb one of
+                                  {16384, 16000, 10000, 8192, 8000, 4096, 2048}; L = fft_size where such a factorisation exists
+                                  (GM_ACQ_FORM_LONG, e.g. 50000 = 5 x 10000, 200000 = 20 x 10000), else the smallest L >= 2 x fft_size
+                                  (GM_ACQ_FORM_LONG_PADDED: the circular correlation through a zero-padded periodic extension —
+                                  same correlation values, FFT rounding aside, about twice the work per sample).  Sizes the other
+                                  paths serve keep them (bit-identical words).  reference_products = 1 on the long path:
+                                  GM_ERR_INVALID_ARG; strict_sum_order is supported.  gm_acq_plan_info tells which path a size
+                                  takes.  (ABI 8) */
 } gm_acq_cfg;
 typedef enum { GM_DECIDE_REFERENCE = 0, GM_DECIDE_BEST_BIN = 1 } gm_decision_mode;
 
 typedef struct gm_acq gm_acq;
+
+/* How gm_acq_create would run an fft_size (host only, no device needed, like gm_fft_supported_sizes). */
+typedef enum {
+    GM_ACQ_FORM_LDS = 0,          /* one in-LDS transform (gm_fft_supported_sizes): base = transform_len = fft_size, q = 1 */
+    GM_ACQ_FORM_COMPOSITE = 1,    /* q x base, q in {2,3,4,5,6,8}, transform_len = fft_size */
+    GM_ACQ_FORM_LONG = 2,         /* any_length: q x base, q in [1, 32], transform_len = fft_size */
+    GM_ACQ_FORM_LONG_PADDED = 3   /* any_length: q x base = transform_len >= 2 x fft_size */
+} gm_acq_form;
+typedef struct {
+    int32_t form;                 /* gm_acq_form */
+    uint32_t base;                /* the base in-LDS plan length */
+    uint32_t q;                   /* the factor: transform_len = q x base */
+    uint32_t transform_len;
+} gm_acq_plan;
+/* The status gm_acq_create returns for this fft_size and any_length (GM_ERR_INVALID_ARG for 0, GM_ERR_ALIGNMENT for
+ * fft_size % 8 != 0, GM_ERR_UNSUPPORTED_N for a size no path serves); on GM_OK `out` (may be NULL) describes the path.
+ * gm_acq_create makes its choice through this same rule.  (ABI 8) */
+int gm_acq_plan_info(uint32_t fft_size, int32_t any_length, gm_acq_plan *out);
 
 /* = building the Doppler tables (:252-262) + AcquisitionWorker::new for every PRN (:268-271):
  * code replicas resampled, their forward FFTs computed on the GPU, plans/twiddles uploaded. */

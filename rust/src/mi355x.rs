@@ -46,6 +46,7 @@ pub struct GmAcqCfg {               // gm_acq_cfg
     pub decision_mode: i32,          // 0 = the reference's early exit (GM_DECIDE_REFERENCE), 1 = strongest bin
     pub strict_sum_order: i32,       // 1 = is_good_satellite's sum in the reference's 8-lane order (do_acquisition.rs:229-235)
     pub reference_products: i32,     // 1 = x conj(code) and norm_sqr() rounded as num-complex rounds them (no fused multiply-add; :184-192)
+    pub any_length: i32,             // 1 = any fft_size % 8 == 0 in [1024, 2^18] (the long path), as rustfft plans any length (:130-143)
 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct GmTrkState {             // gm_trk_state  <->  the evolving fields of TrackingChannel (do_tracking.rs:88-116)

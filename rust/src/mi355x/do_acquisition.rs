@@ -90,7 +90,8 @@ impl AcquisitionWorker {
             let cfg = GmAcqCfg { fs: self.freq_sampling_hz, f_if: 0.0, fft_size: self.fft_size as u32,
                 n_integrations: num_integrations as u32, n_bins: doppler_table.len() as u32, doppler_hz: std::ptr::null(),
                 tables: flat.as_ptr(), table_freq: freqs.as_ptr(), n_prn: 1, prn_ids: ids.as_ptr(),
-                codes: std::ptr::null(), code_len: 0, code_rate: 0.0, threshold: 7.0, decision_mode: 0, strict_sum_order: 0, reference_products: 0 };
+                codes: std::ptr::null(), code_len: 0, code_rate: 0.0, threshold: 7.0, decision_mode: 0, strict_sum_order: 0, reference_products: 0,
+                any_length: 1 };   // the reference plans any fft_size (:130-143, :249-251)
             let st = unsafe { gm_acq_create(&cfg, &mut self.h) };
             assert_eq!(st, 0, "gm_acq_create: {}", last_error());     // e.g. prn 0 / 33: the reference panics in ::new (:133)
             self.tables_key = key;
@@ -115,7 +116,8 @@ impl AcquisitionEngine {
         let cfg = GmAcqCfg { fs, f_if, fft_size: fft_size as u32, n_integrations: n_int as u32,
             n_bins: doppler_hz.len() as u32, doppler_hz: doppler_hz.as_ptr(), tables: std::ptr::null(),
             table_freq: std::ptr::null(), n_prn: prn_ids.len() as u32, prn_ids: prn_ids.as_ptr(),
-            codes: std::ptr::null(), code_len: 0, code_rate: 0.0, threshold: 7.0, decision_mode: 0, strict_sum_order: 0, reference_products: 0 };
+            codes: std::ptr::null(), code_len: 0, code_rate: 0.0, threshold: 7.0, decision_mode: 0, strict_sum_order: 0, reference_products: 0,
+                any_length: 1 };   // the reference plans any fft_size (:130-143, :249-251)
         let mut h = std::ptr::null_mut();
         if unsafe { gm_acq_create(&cfg, &mut h) } != 0 { return Err(AcqError); }
         Ok(Self { h, n_prn: prn_ids.len() })

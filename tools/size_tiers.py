@@ -1,30 +1,33 @@
 """README's table of transform sizes: which stage-C kernel serves each size the acquisition handle accepts, how many scratch_*
 instructions that kernel carries (tools/so_kernel_stats.py, no GPU), and — with a GPU — its measured time at one common geometry
-(32 codes x 9 bins x 2 integrations, complex int8 samples resident), as ns per transform-sample = t_corr / (P D M N).
+(32 codes x 9 bins x 2 integrations, complex int8 samples resident), as ns per transform-sample = t_corr / (P D M N).  The sizes come
+from gm_acq_plan_info: every in-LDS and composite size, and a few any_length sizes (the long path, acq_long.hip: its stage C is
+C1 + C2 per slab + C3; the per-sample figure is per code-period sample N, not per transform sample L for the padded form).
     python tools/size_tiers.py --measure out.json      (GPU box)      python tools/size_tiers.py --table out.json   (here: markdown)"""
 import json, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-IN_LDS = [8000, 16368, 16384, 16000, 15000, 12000, 10000, 8192, 8184, 6000, 5000, 4096, 4000, 2048, 2000, 1024, 512, 256]
-BASES, QS = [16384, 16368, 16000, 8192, 8184, 8000, 6000, 5000, 4000], (2, 3, 4, 5, 6, 8)
+LONG = [50000, 200000, 61440, 38400, 262136]        # any_length sizes: native 5 x 10000, 20 x 10000, 15 x 4096; padded 38400, 262136
 
 
-def _composite():
-    """every size Q x base the handle accepts, with the base it takes: the largest one that divides the size (acq_composite.hip)"""
-    out = {}
-    for b in BASES:
-        for q in QS:
-            n = q * b
-            if n in IN_LDS:
-                continue
-            best = max(bb for bb in BASES if n % bb == 0 and n // bb in QS)
-            out[n] = (n // best, best)
-    return [out[n] for n in sorted(out)]
+def _plans():
+    """(N, any_length, plan) for every size the handle serves in the in-LDS and composite forms, plus the LONG sample sizes — read from
+    gm_acq_plan_info (the rule gm_acq_create applies), not restated here"""
+    from gnss_sdr_rs_amd import acquisition as A
+    out = []
+    for n in range(8, (1 << 18) + 1, 8):
+        st, info = A.plan_info(n, False)
+        if st == 0:
+            out.append((n, False, info))
+    for n in LONG:
+        st, info = A.plan_info(n, True)
+        if st == 0:
+            out.append((n, True, info))
+    return out
 
 
-COMPOSITE = _composite()
 P, D, M = (int(v) for v in os.environ.get("TIERS_PDM", "32,9,2").split(","))     # TIERS_PDM=32,41,4 TIERS_ONLY=6000,18000: an A/B at another grid
 
 
@@ -35,15 +38,15 @@ def measure(path):
     rng = np.random.default_rng(1)
     out = {}
     only = [int(v) for v in os.environ.get("TIERS_ONLY", "").split(",") if v]
-    for q, base in [(1, n) for n in IN_LDS] + COMPOSITE:
-        N = q * base
+    for N, any_length, info in _plans():
+        q, base = info["q"], info["base"]
         if only and N not in only:
             continue
         fs = N * 1000.0
         dop = (np.arange(D, dtype=np.float32) - D // 2) * 250.0
         x = rng.integers(-60, 60, 2 * M * N, dtype=np.int8)
         try:
-            eng = A.AcquisitionEngine(fs, 0.0, N, doppler_hz=dop, n_integrations=M)
+            eng = A.AcquisitionEngine(fs, 0.0, N, doppler_hz=dop, n_integrations=M, any_length=any_length)
         except Exception as e:
             out[str(N)] = {"error": repr(e)}
             continue
@@ -59,7 +62,7 @@ def measure(path):
             eng.search_dev(d_x.data_ptr(), A.FMT_I8_IQ, d_met.data_ptr())
         torch.cuda.synchronize()
         ts = eng.timing_summary()
-        out[str(N)] = {"q": q, "base": base, "corr_ms": ts["avg_corr_ms"], "mix_fft_ms": ts["avg_mix_fft_ms"],
+        out[str(N)] = {"q": q, "base": base, "form": info["form"], "transform_len": info["transform_len"], "corr_ms": ts["avg_corr_ms"], "mix_fft_ms": ts["avg_mix_fft_ms"],
                        "ns_per_transform_sample": ts["avg_corr_ms"] * 1e6 / (P * D * M * N)}
         eng.close()
         print(N, out[str(N)], flush=True)
@@ -73,7 +76,7 @@ def table(path):
     by = {}
     for r in st.values():
         n = short(r["demangled"])
-        m = re.match(r"void (acq_corr_kernel|acq_corr_ws31_kernel|comp_corr_kernel|comp_corr_ws_kernel)<(?:Hybrid)?(?:Plan|CorrPlan\w*)?<?(\d+)[^>]*>+,? ?(.*)>$", n)
+        m = re.match(r"void (long_corr_inv_kernel)<Plan<(\d+)[^>]*> ?>()$", n) or re.match(r"void (acq_corr_kernel|acq_corr_ws31_kernel|comp_corr_kernel|comp_corr_ws_kernel)<(?:Hybrid)?(?:Plan|CorrPlan\w*)?<?(\d+)[^>]*>+,? ?(.*)>$", n)
         if not m:
             continue
         kern, base, rest = m.group(1), int(m.group(2)), m.group(3)
@@ -86,15 +89,24 @@ def table(path):
             continue                                   # the strict_sum_order (planes) variant
         if kern == "comp_corr_ws_kernel" and flags[-1] == "true":
             continue
+        if kern == "long_corr_inv_kernel":             # one kernel per base, Q at run time
+            by[("long", base)] = (kern, r["scratch_insts"], r["vgpr"], r["lds_bytes"])
+            continue
         q = int(flags[0].rstrip("u")) if kern.startswith("comp") else 1
         by[(q, base)] = (kern, r["scratch_insts"], r["vgpr"], r["lds_bytes"])
     rows = []
-    for q, base in [(1, n) for n in IN_LDS] + COMPOSITE:
-        k = by.get((q, base))
+    for N, _, info in _plans():
+        q, base, form = info["q"], info["base"], info["form"]
+        if form.startswith("long"):
+            k = by.get(("long", base))
+            label = "%d x %d%s" % (q, base, " = %d, padded" % info["transform_len"] if form == "long_padded" else ", long")
+        else:
+            k = by.get((q, base))
+            label = ("%d x %d" % (q, base)) if q > 1 else "in LDS"
         if not k and q == 1 and base == 16368:
             k = next((v for (qq, bb), v in by.items() if v[0] == "acq_corr_ws31_kernel"), None)
-        me = meas.get(str(q * base), {})
-        rows.append((q * base, ("%d x %d" % (q, base)) if q > 1 else "in LDS", k, me))
+        me = meas.get(str(N), {})
+        rows.append((N, label, k, me))
     print("| N | form | stage-C kernel | scratch_* instructions | VGPRs | LDS | stage C, ms (32 x 9 x 2) | ns per transform-sample |")
     print("|---|---|---|---|---|---|---|---|")
     for N, form, k, me in rows:
