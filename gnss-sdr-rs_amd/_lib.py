@@ -31,7 +31,7 @@ class AcqCfg(C.Structure):
                 ("table_freq", C.c_void_p), ("n_prn", C.c_uint32), ("prn_ids", C.c_void_p), ("codes", C.c_void_p),
                 ("code_len", C.c_uint32), ("code_rate", C.c_float), ("threshold", C.c_float),
                 ("decision_mode", C.c_int32), ("strict_sum_order", C.c_int32), ("reference_products", C.c_int32),
-                ("any_length", C.c_int32)]
+                ("any_length", C.c_int32), ("coherent_periods", C.c_uint32)]
 
 
 class AcqPlan(C.Structure):
@@ -122,6 +122,7 @@ SIGNATURES = {
     "gm_acq_metrics": (_i, [_vp, _vp, _vp, _vp]),
     "gm_acq_code_fft": (_i, [_vp, _u32, _vp]),
     "gm_acq_tables": (_i, [_vp, _vp, _vp]),
+    "gm_acq_coherent_phasors": (_i, [_vp, _vp]),
     "gm_acq_enable_timing": (_i, [_vp, _i]),
     "gm_acq_last_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
     "gm_acq_timing_summary": (_i, [_vp, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f)]),

@@ -1,6 +1,7 @@
 """Mirror of the reference's acquisition API over the C ABI (names follow
 src/acquisition/do_acquisition.rs and src/acquisition/doppler_shift.rs)."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -85,13 +86,42 @@ def plan_info(fft_size, any_length=False):
     return st, dict(form=ACQ_FORMS[o.form], base=int(o.base), q=int(o.q), transform_len=int(o.transform_len))
 
 
+def detection_threshold(n_integrations, n_cells, pfa):
+    """The smallest ratio t with n_cells * Q(M, t M) <= pfa, M = n_integrations: the ratio test's threshold for a grid of n_cells cells
+    (PRNs x bins x fft_size) and a false-alarm probability pfa per search.  After the coherent fold a noise cell's accumulated power
+    is Gamma(M) distributed whatever coherent_periods is, and Q(M, x) = exp(-x) sum_{i<M} x^i / i! is its survival function at
+    x = t M (the plane mean estimates the noise power).  Pure Python (bisection to 1e-9)."""
+    M, n_cells, pfa = int(n_integrations), float(n_cells), float(pfa)
+    if M < 1 or n_cells <= 0 or not 0.0 < pfa:
+        raise ValueError("n_integrations >= 1, n_cells > 0, pfa > 0")
+
+    def q(t):
+        x = t * M
+        term, s = 1.0, 1.0
+        for i in range(1, M):
+            term *= x / i
+            s += term
+        return math.exp(-x) * s
+
+    lo, hi = 0.0, 1.0
+    while n_cells * q(hi) > pfa:
+        lo, hi = hi, hi * 2.0
+    while hi - lo > 1e-9 * hi:
+        mid = 0.5 * (lo + hi)
+        if n_cells * q(mid) > pfa:
+            lo = mid
+        else:
+            hi = mid
+    return hi
+
+
 class AcquisitionEngine:
     """The batched replacement of `workers.par_iter_mut()` (do_acquisition.rs:268-271, 302-313):
     all AcquisitionWorkers of one stage in one handle."""
 
     def __init__(self, fs, f_if, fft_size, doppler_hz=None, prn_ids=None, n_integrations=LONG_SAMPLES_LENGTH,
                  tables=None, codes=None, code_rate=1.023e6, threshold=7.0, decision_mode=0, strict_sum_order=False, reference_products=False,
-                 device=None, any_length=False):
+                 device=None, any_length=False, coherent_periods=1):
         _lib.init(device if device is not None else (_lib._initialised or 0))
         self.fs, self.f_if, self.fft_size, self.M = float(fs), float(f_if), int(fft_size), int(n_integrations)
         self.prn_ids = np.ascontiguousarray(prn_ids if prn_ids is not None else np.arange(1, 33), np.uint8)
@@ -120,6 +150,9 @@ class AcquisitionEngine:
         cfg.reference_products = int(bool(reference_products))
         cfg.any_length = int(bool(any_length))      # every multiple of 8 in [1024, 2^18] (gm_acq_cfg.any_length)
         self.any_length = bool(any_length)
+        # K code periods integrated coherently (gm_acq_cfg.coherent_periods): a dwell is K * M periods, M groups of K folded per bin
+        cfg.coherent_periods = int(coherent_periods)
+        self.K = max(1, int(coherent_periods))
         self.P = int(cfg.n_prn)
         h = C.c_void_p()
         check(lib().gm_acq_create(C.byref(cfg), C.byref(h)), "gm_acq_create")
@@ -155,8 +188,8 @@ class AcquisitionEngine:
         return a, FMT_C32, a.size
 
     def search(self, samples_chunk, local_tail=0, prn_mask=0xFFFFFFFFFFFFFFFF):
-        """-> list (one per worker) of AcquisitionResult dict or None"""
-        a, fmt, n = self._fmt(samples_chunk)
+        """-> list (one per worker) of AcquisitionResult dict or None.  samples_chunk: K * M * N samples (coherent_periods K)."""
+        a, fmt, n = self._fmt(samples_chunk)      # (fewer samples: GM_ERR_OUT_OF_RANGE from the library's length check)
         res = (AcqResult * self.P)()
         found = np.zeros(self.P, np.uint8)
         check(lib().gm_acq_search(self._h, _p(a), n, fmt, int(local_tail), int(prn_mask) & (2**64 - 1),
@@ -212,6 +245,13 @@ class AcquisitionEngine:
         t = np.zeros((self.D, self.fft_size), np.complex64)
         check(lib().gm_acq_tables(self._h, _p(t), None), "gm_acq_tables")
         return t
+
+    def coherent_phasors(self):
+        """[n_bins][K] complex64: the coherent fold's phasor words exp(-j 2 pi f_d k N / fs) exactly as the device uses them
+        (gm_acq_coherent_phasors); (1, 0) per bin at K = 1."""
+        r = np.zeros((self.D, self.K), np.complex64)
+        check(lib().gm_acq_coherent_phasors(self._h, _p(r)), "gm_acq_coherent_phasors")
+        return r
 
     # ---- device-resident / asynchronous forms (bench, multi-GPU)
     def set_stream(self, stream_ptr):

@@ -301,6 +301,8 @@ struct gm_acq {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     uint32_t N = 0, D = 0, M = 0, P = 0;
+    uint32_t K = 1;                        // gm_acq_cfg.coherent_periods (0 -> 1): a dwell is K * M periods, M groups of K folded coherently
+    cf* d_rho = nullptr;                   // [D][K] the fold's phasor words (gm_acq_coherent_phasors)
     float code_rate = CA_RATE;
     std::vector<float> table_freq;
     std::vector<uint8_t> prn_ids, dev_prn_ids;
@@ -689,7 +691,7 @@ int gm_acq_destroy(gm_acq* a) {
     if (a->device >= 0) hipSetDevice(a->device);
     hipFree(a->d_tw_mix);
     hipFree(a->d_tables); hipFree(a->d_tw_fwd); hipFree(a->d_tw_inv); hipFree(a->d_code_fft); hipFree(a->d_code_fft_paired); hipFree(a->d_order);
-    hipFree(a->d_spectra); hipFree(a->d_table_freq); hipFree(a->d_code_samples); hipFree(a->d_samples);
+    hipFree(a->d_spectra); hipFree(a->d_rho); hipFree(a->d_table_freq); hipFree(a->d_code_samples); hipFree(a->d_samples);
     hipFree(a->d_metrics); hipFree(a->d_worker_list); if (a->d_results) hipHostFree(a->d_results);
     hipFree(a->d_prn_ids);
     for (auto& e : a->tm.ev) if (e) hipEventDestroy(e);
@@ -760,6 +762,7 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     if (!cfg->tables && !cfg->doppler_hz) return set_err(GM_ERR_INVALID_ARG, "doppler_hz or tables required");
     if (cfg->tables && !cfg->table_freq) return set_err(GM_ERR_INVALID_ARG, "table_freq required with tables");
     if (cfg->fft_size % 8) return set_err(GM_ERR_ALIGNMENT, "fft_size % 8 != 0");
+    if (cfg->coherent_periods > uint32_t(gm::GM_COHERENT_MAX)) return set_err(GM_ERR_INVALID_ARG, "coherent_periods > 32");
     const gm::PlanOps* pl = nullptr;
     const gm::CompOps* comp = nullptr;
     const gm::LongOps* lng = nullptr;
@@ -783,6 +786,7 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     a->cfg = *cfg;
     a->plan = pl;
     a->N = cfg->fft_size; a->D = cfg->n_bins; a->M = cfg->n_integrations; a->P = cfg->n_prn;
+    a->K = cfg->coherent_periods > 1 ? cfg->coherent_periods : 1;
     a->Q = lng ? form.q : comp_q; a->Nb = uint32_t(pl->n); a->comp = comp;
     a->lng = lng;
     if (lng) {
@@ -794,7 +798,7 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     if (cfg->threshold == 0.0f) a->cfg.threshold = 7.0f;
     a->code_rate = cfg->codes ? (cfg->code_rate > 0 ? cfg->code_rate : CA_RATE) : CA_RATE;
     a->prn_ids.assign(cfg->prn_ids, cfg->prn_ids + a->P);
-    const size_t N = a->N, D = a->D, M = a->M, P = a->P;
+    const size_t N = a->N, D = a->D, M = a->M, P = a->P, K = a->K;
     int rc = GM_OK;
     auto fail = [&](int code) { gm_acq_destroy(a); return code; };
 
@@ -808,6 +812,15 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
         for (size_t d = 0; d < D; ++d)
             gm_doppler_table_new(cfg->f_if, cfg->doppler_hz[d], cfg->fs, N, &a->table_freq[d], &tables[d * N]);
     }
+    // the coherent fold's phasors: rho[d][k] = exp(-j 2 pi f_d k N / fs), bin d's table phasor continued to sample k N — in f64 with
+    // the phase reduced to one cycle before cos / sin, then rounded to f32 (K = 1: the single word (1, 0))
+    std::vector<gm_c32> rho(D * K);
+    for (size_t d = 0; d < D; ++d)
+        for (size_t k = 0; k < K; ++k) {
+            const double cyc = double(a->table_freq[d]) * double(k * N) / double(cfg->fs);
+            const double ang = 2.0 * 3.14159265358979323846 * (cyc - ::floor(cyc));
+            rho[d * K + k] = gm_c32{float(::cos(ang)), float(0.0 - ::sin(ang))};      // (0.0 - : k = 0 is (1, +0))
+        }
     // replica samples (AcquisitionWorker::new :132-135)
     std::vector<int8_t> code_samples(P * N);
     a->code_len = cfg->codes ? cfg->code_len : 1023u;
@@ -854,11 +867,13 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     HIPA(hipMalloc(&a->d_code_samples, P * N));
     HIPA(hipMalloc(&a->d_code_fft, P * N * 8));
     HIPA(hipMalloc(&a->d_spectra, D * M * (a->lng ? size_t(a->L) : N) * 8));
-    a->samples_cap = M * N * 8;
+    a->samples_cap = K * M * N * 8;
     HIPA(hipMalloc(&a->d_samples, a->samples_cap));
     HIPA(hipMalloc(&a->d_metrics, 3 * P * D * 4));
     HIPA(hipMemsetAsync(a->d_metrics, 0, 3 * P * D * 4, a->stream));
     HIPA(hipMalloc(&a->d_worker_list, P * 4));
+    HIPA(hipMalloc(&a->d_rho, D * K * 8));
+    HIPA(hipMemcpy(a->d_rho, rho.data(), D * K * 8, hipMemcpyHostToDevice));
     if (acq_fused(a) && pl->split_slab && M >= 2) {
         // planes the tail split can ever use for THIS handle: every item cut (small grids: P*D items x M planes), or per XCD one
         // resident round of parts (64 slots; an item's M planes each) — never more than GM_CORR_SPLIT_MAX_SLABS
@@ -966,6 +981,15 @@ int gm_acq_set_prn_mask(gm_acq* a, uint64_t mask) {
     return acq_set_mask(a, mask);
 }
 
+// stage F's arguments on a coherent handle (gm_acq_cfg.coherent_periods = K >= 2)
+static gm::CohArgs acq_coh_args(const gm_acq* a, const void* d_samples, int fmt, const cf* tw_fwd, cf* out, uint32_t* clear_tickets) {
+    gm::CohArgs c{};
+    c.samples = d_samples; c.fmt = fmt; c.rho = a->d_rho; c.K = a->K; c.tables = a->d_tables; c.tw_fwd = tw_fwd; c.out = out;
+    c.n_bins = a->D; c.n_int = a->M; c.Q = a->Q; c.N = a->N; c.lim = a->long_lim; c.clear_tickets = clear_tickets;
+    c.order = a->lng ? nullptr : a->d_order;
+    return c;
+}
+
 // stage F (unless `prepared`: then the spectra wait in the second buffer) + stage C of one dwell on the handle's stream
 static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_metrics, bool prepared) {
     uint32_t* met = d_metrics ? static_cast<uint32_t*>(d_metrics) : a->d_metrics;
@@ -988,17 +1012,26 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
         HIPC(hipStreamWaitEvent(a->stream, ah.ev_f, 0));
         tickets_cleared = false;
     } else if (a->lng) {
-        a->lng->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_fwd, a->d_spectra, a->D * a->M, a->Q, a->N, a->long_lim, a->M);
+        if (a->K > 1)
+            a->lng->fwd_sub_coh(a->stream, acq_coh_args(a, d_samples, fmt, a->d_tw_fwd, a->d_spectra, nullptr));
+        else
+            a->lng->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_fwd, a->d_spectra, a->D * a->M, a->Q, a->N, a->long_lim, a->M);
         gm::launch_long_fwd_post(a->stream, a->d_spectra, a->D * a->M, a->Q, a->Nb);
     } else if (a->Q == 1) {
-        a->plan->mix_fft(a->stream, d_samples, fmt, a->d_tables, a->d_tw_mix, a->d_spectra, int(a->D), int(a->M), a->d_split_counter, a->d_order,
-                         a->dec_deferred ? &a->dec_args : nullptr);
+        if (a->K > 1)       // (a coherent handle never defers its decision: dec_deferred is false here)
+            a->plan->mix_fft_coh(a->stream, acq_coh_args(a, d_samples, fmt, a->d_tw_mix, a->d_spectra, a->d_split_counter));
+        else
+            a->plan->mix_fft(a->stream, d_samples, fmt, a->d_tables, a->d_tw_mix, a->d_spectra, int(a->D), int(a->M), a->d_split_counter, a->d_order,
+                             a->dec_deferred ? &a->dec_args : nullptr);
         a->dec_deferred = false;
     } else {
-        if (a->comp_post_folded) {     // the sub-transforms ARE what the correlation kernel reads
-            a->comp->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_mix, a->d_spectra, a->D * a->M, a->M, a->d_order);
-        } else {
-            a->comp->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_mix, a->d_comp_tmp, a->D * a->M, a->M, a->d_order);
+        // the sub-transforms ARE what the correlation kernel reads (comp_post_folded), else forward step 2 follows
+        cf* sub = a->comp_post_folded ? a->d_spectra : a->d_comp_tmp;
+        if (a->K > 1)
+            a->comp->fwd_sub_coh(a->stream, acq_coh_args(a, d_samples, fmt, a->d_tw_mix, sub, nullptr));
+        else
+            a->comp->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_mix, sub, a->D * a->M, a->M, a->d_order);
+        if (!a->comp_post_folded) {
             a->comp->fwd_post(a->stream, a->d_comp_tmp, a->d_spectra, a->D * a->M, 1, a->d_order);
         }
     }
@@ -1111,7 +1144,10 @@ int gm_acq_prepare_dev(gm_acq* a, const void* d_samples, int fmt, void* ready_st
         HIPC(hipStreamWaitEvent(ah.side, ah.ev_in, 0));
     }
     ah.valid = false;
-    a->plan->mix_fft(ah.side, d_samples, fmt, a->d_tables, a->d_tw_mix, ah.d_spectra_alt, int(a->D), int(a->M), nullptr, a->d_order, nullptr);
+    if (a->K > 1)
+        a->plan->mix_fft_coh(ah.side, acq_coh_args(a, d_samples, fmt, a->d_tw_mix, ah.d_spectra_alt, nullptr));
+    else
+        a->plan->mix_fft(ah.side, d_samples, fmt, a->d_tables, a->d_tw_mix, ah.d_spectra_alt, int(a->D), int(a->M), nullptr, a->d_order, nullptr);
     HIPC(hipEventRecord(ah.ev_f, ah.side));
     HIPC(hipGetLastError());
     ah.valid = true; ah.samples = d_samples; ah.fmt = fmt; ah.token = *token = ah.next_token++;
@@ -1144,7 +1180,7 @@ int gm_acq_decide_dev(gm_acq* a, const void* d_metrics, uint32_t n_prn, const ui
     da.best_bin_mode = a->cfg.decision_mode == GM_DECIDE_BEST_BIN ? 1 : 0;
     da.local_tail = local_tail;
     da.results = a->d_results; da.found = a->d_found;
-    if (a->defer_decisions && acq_fused(a) && !(a->tm.on && a->tm.this_call) && met == a->last_metrics && a->D <= 64) {
+    if (a->defer_decisions && acq_fused(a) && a->K == 1 && !(a->tm.on && a->tm.this_call) && met == a->last_metrics && a->D <= 64) {
         a->dec_args = da;          // runs with the next gm_acq_search_dev's stage F, or at the next flush point
         a->dec_deferred = true;
         return GM_OK;
@@ -1189,8 +1225,8 @@ int gm_acq_search(gm_acq* a, const void* samples, size_t n_samples, int fmt, uin
                   gm_acq_result* results, uint8_t* found) {
     if (!a || !samples || !results || !found) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (fmt < GM_FMT_C32 || fmt > GM_FMT_I8_REAL) return set_err(GM_ERR_INVALID_ARG, "bad sample format");
-    const size_t need = size_t(a->M) * a->N;
-    if (n_samples < need) return set_err(GM_ERR_OUT_OF_RANGE, "samples_chunk shorter than num_integrations*fft_size");
+    const size_t need = size_t(a->K) * a->M * a->N;
+    if (n_samples < need) return set_err(GM_ERR_OUT_OF_RANGE, "samples_chunk shorter than coherent_periods*num_integrations*fft_size");
     if (int rc = ensure_device(a->device)) return rc;
     const size_t bps = fmt == GM_FMT_C32 ? 8 : (fmt == GM_FMT_I8_IQ ? 2 : 1);
     if (int rc = acq_set_mask(a, prn_mask)) return rc;
@@ -1200,19 +1236,19 @@ int gm_acq_search(gm_acq* a, const void* samples, size_t n_samples, int fmt, uin
     return gm_acq_fetch_results(a, a->P, results, found);
 }
 
-// run()'s snapshot + search (do_acquisition.rs:297-313) against the DEVICE ring: the n_integrations*fft_size
-// samples ending at `head` (local_tail = head - M*N) are copied device-to-device (wrap-aware, like
+// run()'s snapshot + search (do_acquisition.rs:297-313) against the DEVICE ring: the coherent_periods*n_integrations*fft_size
+// samples ending at `head` (local_tail = head - K*M*N) are copied device-to-device (wrap-aware, like
 // copy_to_slice :107-129) and searched; no host round trip of the samples.
 int gm_acq_search_ring(gm_acq* a, gm_ring* ring, uint64_t prn_mask, gm_acq_result* results, uint8_t* found,
                        uint64_t* local_tail_out) {
     if (!a || !ring || !results || !found) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (a->device != ring->device) return set_err(GM_ERR_INVALID_ARG, "ring lives on another device");
-    const size_t need = size_t(a->M) * a->N;
-    if (need > ring->size) return set_err(GM_ERR_OUT_OF_RANGE, "ring smaller than num_integrations*fft_size");
+    const size_t need = size_t(a->K) * a->M * a->N;
+    if (need > ring->size) return set_err(GM_ERR_OUT_OF_RANGE, "ring smaller than coherent_periods*num_integrations*fft_size");
     if (int rc = ensure_device(ring->device)) return rc;
     ring_refresh_head(ring);
     const uint64_t head = ring->head.load(std::memory_order_acquire);
-    if ((int64_t)(head - need) < 0) return set_err(GM_ERR_OUT_OF_RANGE, "not enough samples yet (head < M*N)");   // :299
+    if ((int64_t)(head - need) < 0) return set_err(GM_ERR_OUT_OF_RANGE, "not enough samples yet (head < K*M*N)");   // :299
     if (int rc = ensure_device(a->device)) return rc;
     const uint64_t local_tail = head - need;
     const size_t ps = size_t(local_tail & ring->mask);
@@ -1232,16 +1268,18 @@ int gm_acq_search_ring(gm_acq* a, gm_ring* ring, uint64_t prn_mask, gm_acq_resul
 }
 
 // Fine Doppler: finer_doppler (acquisition_bk.rs:215-302, legacy) for every found result of the last
-// search, on the snapshot that search used (still resident in HBM).  fft_size = 8 * next_pow2((M-1)*N) as N1 x N2.
+// search, on the snapshot that search used (still resident in HBM).  fft_size = 8 * next_pow2((K*M-1)*N) as N1 x N2 (K: coherent_periods).
 int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t* found, uint32_t n_prn, float* fine_freq_hz,
                          uint64_t* peak_index, float* peak_mag, uint64_t* fft_size_out) {
     if (!a || !results || !found) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (n_prn > a->P) return set_err(GM_ERR_INVALID_ARG, "n_prn exceeds the handle's workers");
-    if (a->M < 2) return set_err(GM_ERR_INVALID_ARG, "fine Doppler needs num_integrations >= 2 ((M-1)*N samples after the code phase)");
+    const uint32_t periods = a->K * a->M;                                // the snapshot: K*M periods
+    if (periods < 2) return set_err(GM_ERR_INVALID_ARG, "fine Doppler needs coherent_periods*num_integrations >= 2 ((K*M-1)*N samples after the code phase)");
     if (!a->last_samples) return set_err(GM_ERR_INVALID_ARG, "no search has run on this handle yet");
     if (int rc = ensure_device(a->device)) return rc;
     gm_acq::Fine& f = a->fine;
-    const uint32_t size_use = (a->M - 1) * a->N;                         // :240
+    if (uint64_t(periods - 1) * a->N > (1ull << 21)) return set_err(GM_ERR_UNSUPPORTED_N, "fine-Doppler FFT longer than 2^24");
+    const uint32_t size_use = (periods - 1) * a->N;                      // :240
     if (!f.p1) {
         uint64_t p2 = 1;
         while (p2 < size_use) p2 <<= 1;                                  // next_power_of_two :249
@@ -1272,8 +1310,8 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
     std::vector<uint32_t> workers, cps, slot(n_prn, 0xFFFFFFFFu);
     for (uint32_t p = 0; p < n_prn; ++p) {
         if (!found[p]) continue;
-        if (results[p].code_phase_samples + size_use > uint64_t(a->M) * a->N)
-            return set_err(GM_ERR_OUT_OF_RANGE, "code_phase + (M-1)*N exceeds the snapshot (:260 would panic)");
+        if (results[p].code_phase_samples + size_use > uint64_t(periods) * a->N)
+            return set_err(GM_ERR_OUT_OF_RANGE, "code_phase + (K*M-1)*N exceeds the snapshot (:260 would panic)");
         slot[p] = uint32_t(workers.size());
         workers.push_back(p);
         cps.push_back(uint32_t(results[p].code_phase_samples));
@@ -1302,7 +1340,7 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
     fa.sat_worker = f.d_sat_worker; fa.sat_code_phase = f.d_sat_cp;
     fa.size_use = size_use; fa.N1 = N1; fa.N2 = N2; fa.B = f.d_B; fa.tw1 = f.d_tw1; fa.tw2 = f.d_tw2;
     fa.rowmax = f.d_rowmax; fa.rowarg = f.d_rowarg;
-    gm::launch_fine_mean(a->stream, a->last_samples, a->last_fmt, a->M * a->N, f.d_mean);
+    gm::launch_fine_mean(a->stream, a->last_samples, a->last_fmt, periods * a->N, f.d_mean);
     f.p1->fine_cols(a->stream, fa, int(S));
     f.p2->fine_rows(a->stream, fa, int(S));
     gm::launch_fine_final(a->stream, f.d_rowmax, f.d_rowarg, N1 / uint32_t(f.p2->fine_rows_per_wg), int(S), f.d_peak_pow, f.d_peak_idx);
@@ -1358,6 +1396,13 @@ int gm_acq_tables(gm_acq* a, gm_c32* tables, float* freq) {
     if (int rc = ensure_device(a->device)) return rc;
     if (tables) HIPC(hipMemcpy(tables, a->d_tables, size_t(a->D) * a->N * 8, hipMemcpyDeviceToHost));
     if (freq) memcpy(freq, a->table_freq.data(), a->D * sizeof(float));
+    return GM_OK;
+}
+
+int gm_acq_coherent_phasors(gm_acq* a, gm_c32* out) {
+    if (!a || !out) return set_err(GM_ERR_INVALID_ARG, "null handle/out");
+    if (int rc = ensure_device(a->device)) return rc;
+    HIPC(hipMemcpy(out, a->d_rho, size_t(a->D) * a->K * 8, hipMemcpyDeviceToHost));
     return GM_OK;
 }
 

@@ -23,6 +23,25 @@ struct FineArgs {
     float* rowmax; uint32_t* rowarg;       // [S][N1]
 };
 
+// gm_acq_cfg.coherent_periods: the most code periods one coherent group folds (gm_acq_create refuses more; stage F's LDS holds the phasors)
+constexpr int GM_COHERENT_MAX = 32;
+
+// Stage F of a coherent handle (acq_coherent.hip): the M groups of K consecutive periods of the dwell, each folded with its Doppler
+// bin's phasor words before the carrier mix (CohLoad, acq_device.h).  One argument block for the three forms.
+struct CohArgs {
+    const void* samples; int fmt;          // K * M * N samples
+    const cf* rho; uint32_t K;             // [n_bins][K] phasor words (gm_acq_coherent_phasors)
+    const cf* tables; const cf* tw_fwd;    // the Doppler tables [n_bins][N]; the forward plan's base twiddles
+    cf* out;                               // in-LDS: the spectra; composite / long: the forward sub-transforms A
+    uint32_t n_bins, n_int;                // items = n_bins * n_int
+    uint32_t Q, N, lim;                    // composite / long: Q; long: N and the signal's extension (N native, 2N padded)
+    uint32_t* clear_tickets;               // in-LDS: the tail split's tickets, cleared on the way (PlanOps::mix_fft)
+    const uint16_t* order;                 // in-LDS / composite: the storage order table (PlanOps::fill_order), may be null
+};
+template <class PL> void launch_mix_fft_coh(hipStream_t, const CohArgs&);
+template <class PL> void launch_comp_fwd_sub_coh(hipStream_t, const CohArgs&);
+template <class PL> void launch_long_fwd_sub_coh(hipStream_t, const CohArgs&);
+
 // One entry per shipped transform size: launchers for the kernels instantiated on that plan.
 struct DecideArgs;
 struct PlanOps {
@@ -71,6 +90,9 @@ struct PlanOps {
     // than the registered one since round 6, e.g. N = 8192; empty for prime-factor and hybrid correlation plans)
     int tw_total_corr;
     void (*fill_tw_corr)(cf* tw);
+    // stage F of a coherent handle (gm_acq_cfg.coherent_periods = K >= 2, acq_coherent.hip): mix_fft on the dwell's M groups of K
+    // periods, each folded with its bin's phasor words before the carrier mix; the same spectra, no trailing decision
+    void (*mix_fft_coh)(hipStream_t, const CohArgs&);
 };
 // mean of the snapshot (finer_doppler :236) and the final per-satellite reduction over the rows
 void launch_fine_mean(hipStream_t, const void* samples, int fmt, uint32_t n, float* d_mean);
@@ -118,6 +140,8 @@ struct CompOps {
     // base plans with an order table: forward step 2 folded into the table — comb2[p][n1][n1'][pos] such that a sub-transform's input is
     // sum_n1' A[n1'][pos] * comb2[n1][n1'][pos] on the forward sub-transforms A as fwd_sub leaves them (no fwd_post per dwell)
     void (*fold_post)(hipStream_t, const cf* comb, const uint16_t* order, cf* comb2, uint32_t n_codes);
+    // forward step 1 of a coherent handle's signal (acq_coherent.hip): the M groups folded over K periods; the replicas keep fwd_sub
+    void (*fwd_sub_coh)(hipStream_t, const CohArgs&);
 };
 const CompOps* find_comp(uint32_t n);
 // strict_sum_order on the composite path: msum[o] = is_good_satellite's eight-lane ordered sum (do_acquisition.rs:229-235) of plane o,
@@ -135,6 +159,8 @@ struct LongOps {
     void (*corr_inv)(hipStream_t, const cf* Z, const cf* tw_inv, float* pmax, uint32_t* parg, float* psum, float* planes,
                      const uint32_t* worker_list, uint32_t n_workers, uint32_t n_bins, uint32_t item0, uint32_t n_slab, uint32_t Q,
                      uint32_t N, uint32_t n_int, float scale);
+    // F1 of a coherent handle's signal (acq_coherent.hip): element i of group m is the fold over its K periods; the replicas keep fwd_sub
+    void (*fwd_sub_coh)(hipStream_t, const CohArgs&);
 };
 // the base plans, largest first
 const LongOps* long_bases(int* n);

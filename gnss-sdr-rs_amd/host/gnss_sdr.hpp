@@ -89,10 +89,11 @@ class AcquisitionEngine {
 public:
     AcquisitionEngine(float fs, float f_if, uint32_t fft_size, const std::vector<float>& doppler_hz,
                       const std::vector<uint8_t>& prn_ids, uint32_t n_integrations = 10, float threshold = 7.0f,
-                      int decision_mode = GM_DECIDE_REFERENCE, bool any_length = false) {
+                      int decision_mode = GM_DECIDE_REFERENCE, bool any_length = false, uint32_t coherent_periods = 1) {
         gm_acq_cfg c{};
         c.decision_mode = decision_mode;
         c.any_length = any_length ? 1 : 0;      // every fft_size % 8 == 0 in [1024, 2^18] (gm_acq_cfg.any_length)
+        c.coherent_periods = coherent_periods;  // K periods folded coherently: a dwell is K * n_integrations periods (gm_acq_cfg.coherent_periods)
         c.fs = fs; c.f_if = f_if; c.fft_size = fft_size; c.n_integrations = n_integrations;
         c.n_bins = uint32_t(doppler_hz.size()); c.doppler_hz = doppler_hz.data();
         c.n_prn = uint32_t(prn_ids.size()); c.prn_ids = prn_ids.data(); c.threshold = threshold;
@@ -388,6 +389,8 @@ struct AcquisitionRunOptions {            // the reference's compile-time consta
     double first_round_signal_ms = -1.0;
     // refine every hit's carrier (finer_doppler, acquisition_bk.rs:215-302) before it goes to tracking
     bool fine_doppler = false;
+    // gm_acq_cfg.coherent_periods: K code periods integrated coherently; a round then searches K * long_samples_length periods
+    uint32_t coherent_periods = 1;
     std::function<void(uint64_t head, const std::vector<std::optional<AcquisitionResult>>&)> on_round;   // after every round (may be empty)
 };
 
@@ -401,7 +404,8 @@ inline void run_acquisition(MulticastRingBuffer& multi_buffer, float freq_sampli
     std::vector<uint8_t> prns(PRN_SEARCH_ACQUISITION_TOTAL);
     for (uint8_t p = 0; p < PRN_SEARCH_ACQUISITION_TOTAL; ++p) prns[p] = uint8_t(p + 1);
     AcquisitionEngine workers(freq_sampling_hz, f_if, fft_size, doppler, prns, opt.long_samples_length, 7.0f,
-                              opt.decision_mode, true);      // any_length: fft_size = round(fs / 1 kHz), whatever fs is :252-271
+                              opt.decision_mode, true,       // any_length: fft_size = round(fs / 1 kHz), whatever fs is :252-271
+                              opt.coherent_periods);
     std::set<uint8_t> active_prns;
     AcquisitionManager acq_manager;
     ctl.stages_ready++;
@@ -434,7 +438,8 @@ inline void run_acquisition(MulticastRingBuffer& multi_buffer, float freq_sampli
         auto results = workers.search_ring(multi_buffer.handle(), uint64_t(mask), &local_tail);             // :297-313
         ctl.acq_ns += stage_ns(t0);
         if (!results) { std::this_thread::sleep_for(std::chrono::milliseconds(1)); continue; }              // :324-326
-        const uint64_t head_of_round = local_tail + uint64_t(opt.long_samples_length) * fft_size;
+        const uint64_t head_of_round = local_tail + uint64_t(opt.coherent_periods > 1 ? opt.coherent_periods : 1) *
+                                                    uint64_t(opt.long_samples_length) * fft_size;
         if (opt.fine_doppler) {
             // hits on satellites that are tracked already go nowhere (:315-320 would hand them over again; the mask
             // normally excludes them) — refine only what is about to start a channel

@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 8   /* 8: gm_acq_cfg.any_length, gm_acq_plan_info;
+#define GM_ABI_VERSION 9   /* 9: gm_acq_cfg.coherent_periods, gm_acq_coherent_phasors;
+                              8: gm_acq_cfg.any_length, gm_acq_plan_info;
                               7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
 
@@ -159,6 +160,26 @@ typedef struct {
                                   paths serve keep them (bit-identical words).  reference_products = 1 on the long path:
                                   GM_ERR_INVALID_ARG; strict_sum_order is supported.  gm_acq_plan_info tells which path a size
                                   takes.  (ABI 8) */
+    uint32_t coherent_periods; /* K: code periods integrated coherently.  0 or 1 (default): today's search — every period of the
+                                  dwell is correlated and squared on its own, the n_integrations power planes are added.
+                                  2 .. 32: a dwell is K x n_integrations consecutive periods, M = n_integrations groups of K.
+                                  Group m is folded per Doppler bin d before the carrier mix,
+                                      y[n] = sum_k rho[d][k] x[(m K + k) fft_size + n],  rho[d][k] = exp(-j 2 pi f_d k fft_size / fs),
+                                  f_d = the bin's table_freq: the table's phasor continued to sample k fft_size, so the carrier
+                                  phase runs on across the K periods (rho: f64 with the phase reduced to one cycle, rounded to f32;
+                                  gm_acq_coherent_phasors returns them).  The fold runs in f32 with k ascending, every product and
+                                  sum rounded on its own (num-complex's arithmetic).  Everything after it is today's search on y:
+                                  same metric words, same decisions, same gm_acq_result meaning.  Every path, sample format, code
+                                  family, strict_sum_order, decision mode and reference_products (where accepted) works.  Every
+                                  entry that takes a dwell takes K x n_integrations x fft_size samples; gm_acq_finer_doppler uses
+                                  (K M - 1) x fft_size of them.  > 32: GM_ERR_INVALID_ARG.
+                                  Data bits and secondary (NH) codes are NOT wiped off: a sign change inside a group cancels part
+                                  of it.  Space the Doppler bins at most 1 / (2 K T_code) apart.
+                                  Thresholds: after the fold a noise cell's accumulated power is Gamma(M) distributed whatever K
+                                  is, so the ratio test's false-alarm rate per cell is Q(M, t M) = exp(-t M) sum_{i<M} (t M)^i / i!
+                                  for threshold t.  The default 7 assumes many non-coherent sums: at M = 1 it gives e^-7 per cell
+                                  (several false alarms per 8000-cell plane).  Choose t from the grid's cell count instead
+                                  (acquisition.detection_threshold in the Python package).  (ABI 9) */
 } gm_acq_cfg;
 typedef enum { GM_DECIDE_REFERENCE = 0, GM_DECIDE_BEST_BIN = 1 } gm_decision_mode;
 
@@ -188,7 +209,7 @@ int gm_acq_create(const gm_acq_cfg *cfg, gm_acq **out);
 int gm_acq_destroy(gm_acq *a);
 
 /* The batched equivalent of `workers.par_iter_mut()...search_satellite(...)` (:302-313, :158-226).
- *   samples  : n_integrations*fft_size samples in `fmt`
+ *   samples  : coherent_periods*n_integrations*fft_size samples in `fmt` (coherent_periods 0 counts as 1, everywhere below)
  *   prn_mask : bit i set <-> worker i searched (the (mask >> (prn-1)) & 1 test for the default list)
  *   results[i], found[i] for every worker i (found = 0 <-> None).
  * Identical outcome to the reference loop: ascending-Doppler running best, first bin passing
@@ -201,15 +222,16 @@ int gm_acq_search_i8(gm_acq *a, const int8_t *iq_interleaved, size_t n_samples, 
                      uint64_t prn_mask, gm_acq_result *results, uint8_t *found);
 
 /* run()'s snapshot + fan-out (do_acquisition.rs:297-313) against the device ring mirror: searches the
- * n_integrations*fft_size samples ending at the ring's head (device-to-device, wrap-aware); *local_tail_out =
- * head - M*N.  GM_ERR_OUT_OF_RANGE while head < M*N (the reference skips the round, :299). */
+ * coherent_periods*n_integrations*fft_size samples ending at the ring's head (device-to-device, wrap-aware); *local_tail_out =
+ * head - K*M*N.  GM_ERR_OUT_OF_RANGE while head < K*M*N (the reference skips the round, :299). */
 typedef struct gm_ring gm_ring;
 int gm_acq_search_ring(gm_acq *a, gm_ring *ring, uint64_t prn_mask, gm_acq_result *results, uint8_t *found,
                        uint64_t *local_tail_out);
 
 /* Fine-Doppler refinement after detection (finer_doppler, src/acquisition/acquisition_bk.rs:215-302 —
  * a legacy file outside the reference's module tree): for every found[p], the snapshot of the LAST search on this handle
- * (still in HBM) is code-stripped from results[p].code_phase_samples over (num_integrations-1)*fft_size samples (:240-272),
+ * (still in HBM) is code-stripped from results[p].code_phase_samples over (coherent_periods*num_integrations-1)*fft_size samples
+ * (:240-272; the mean is taken over all K*M*N),
  * mean-removed (:236-237), zero-padded to 8*next_pow2 (:249) and transformed; the first index of the maximum |X| (:276-283)
  * gives fine_freq_hz[p] = (idx*fs)/fft_size (:251-253), i.e. IF + Doppler to fs/fft_size (7.6 Hz at 8 Msps, 10 ms).
  * Indices above fft_size/2 are reported as negative frequencies (the legacy indexes out of bounds there, :285-288, and
@@ -218,8 +240,8 @@ int gm_acq_search_ring(gm_acq *a, gm_ring *ring, uint64_t prn_mask, gm_acq_resul
 int gm_acq_finer_doppler(gm_acq *a, const gm_acq_result *results, const uint8_t *found, uint32_t n_prn,
                          float *fine_freq_hz, uint64_t *peak_index, float *peak_mag, uint64_t *fft_size);
 
-/* Device-resident form: samples already in HBM; kernels are enqueued on the handle's stream and the
- * call returns without synchronising.  d_metrics (optional, may be NULL -> internal buffer) receives
+/* Device-resident form: samples already in HBM (coherent_periods*n_integrations*fft_size of them); kernels are enqueued
+ * on the handle's stream and the call returns without synchronising.  d_metrics (optional, may be NULL -> internal buffer) receives
  * 3*n_prn*n_bins 32-bit words: max f32 [P][D], argmax u32 [P][D], sum f32 [P][D]. */
 int gm_acq_search_dev(gm_acq *a, const void *d_samples, int fmt, void *d_metrics);
 /* Which workers the device-resident form searches (bit i <-> worker i); default: all. */
@@ -281,14 +303,15 @@ int gm_acq_synchronize(gm_acq *a);
  * gm_acq_search_dev (extra workgroups beside the forward transforms, one launch and one kernel boundary fewer per dwell), or
  * at the next gm_acq_synchronize / gm_acq_fetch_results / gm_acq_decide_dev / gm_acq_set_stream, whichever comes first.
  * Until then that metrics block must stay as the search left it; results are the same either way.  Off by default
- * (in-LDS transform sizes with n_bins <= 64 only; other handles accept the call and decide at once as before). */
+ * (in-LDS transform sizes with n_bins <= 64 and coherent_periods <= 1 only; other handles — coherent ones included — accept the
+ * call and decide at once as before). */
 int gm_acq_set_deferred_decision(gm_acq *a, int on);
 /* Stage F (carrier mix + forward transforms) of the NEXT dwell ahead of time: runs on a stream of the handle's own into a second
  * spectrum buffer, beside whatever the handle's stream is doing, as soon as that buffer is free (the stage C that last read it
  * has ended).  The preparation is a SNAPSHOT of d_samples — the counterpart of the reference copying its 10 ms out of the ring
  * before it searches them (do_acquisition.rs:297-301) — and is named by the generation number written to *token (never 0), NOT by
  * the address: gm_acq_search_prepared_dev(a, token, d_metrics) launches stage C on those spectra, and nothing else ever uses
- * them.  gm_acq_search_dev always transforms the samples its own argument holds at that moment, whatever was prepared from the
+ * them (d_samples: coherent_periods*n_integrations*fft_size samples).  gm_acq_search_dev always transforms the samples its own argument holds at that moment, whatever was prepared from the
  * same address before (ABI 5 matched a following search by pointer and format: a caller that refilled the buffer in between —
  * any ring-backed receiver — silently got the old samples' spectra).
  *   ready_stream: a HIP stream (or NULL).  Non-NULL: the samples are complete once the work queued on that stream SO FAR has run
@@ -322,6 +345,9 @@ int gm_acq_metrics(gm_acq *a, float *max, uint32_t *argmax, float *sum);
 int gm_acq_code_fft(gm_acq *a, uint32_t worker, gm_c32 *out);
 /* The table list in use: [n_bins][fft_size] and [n_bins] (either may be NULL). */
 int gm_acq_tables(gm_acq *a, gm_c32 *tables, float *table_freq);
+/* The coherent fold's phasor words [n_bins][coherent_periods] exactly as the device uses them (gm_acq_cfg.coherent_periods);
+ * at coherent_periods 0 or 1 the one word per bin is (1, 0).  (ABI 9) */
+int gm_acq_coherent_phasors(gm_acq *a, gm_c32 *out);
 /* Kernel timing of the last gm_acq_search*_dev call, measured with HIP events on the handle's
  * stream: ms_mix_fft (stage F), ms_corr (stage C, the dominant kernel), ms_decide.  Enable first: on = 1 times every
  * search, on = k > 1 every k-th (an event record costs about 2 us of stream time; four per timed search), 0 disables. */

@@ -47,6 +47,7 @@ pub struct GmAcqCfg {               // gm_acq_cfg
     pub strict_sum_order: i32,       // 1 = is_good_satellite's sum in the reference's 8-lane order (do_acquisition.rs:229-235)
     pub reference_products: i32,     // 1 = x conj(code) and norm_sqr() rounded as num-complex rounds them (no fused multiply-add; :184-192)
     pub any_length: i32,             // 1 = any fft_size % 8 == 0 in [1024, 2^18] (the long path), as rustfft plans any length (:130-143)
+    pub coherent_periods: u32,       // K > 1 = K code periods folded coherently per group; a dwell is K * n_integrations periods (ABI 9)
 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct GmTrkState {             // gm_trk_state  <->  the evolving fields of TrackingChannel (do_tracking.rs:88-116)
@@ -78,6 +79,8 @@ extern "C" {
     // do_acquisition.rs:252-271  (tables + AcquisitionWorker::new for every PRN)
     pub fn gm_acq_create(cfg: *const GmAcqCfg, out: *mut *mut GmAcq) -> c_int;
     pub fn gm_acq_destroy(a: *mut GmAcq) -> c_int;
+    // the coherent fold's phasor words [n_bins][coherent_periods] (gm_acq_cfg.coherent_periods, ABI 9)
+    pub fn gm_acq_coherent_phasors(a: *mut GmAcq, out: *mut Complex32) -> c_int;
     // do_acquisition.rs:302-313 + :158-226  (par_iter over workers / search_satellite)
     pub fn gm_acq_search_c32(a: *mut GmAcq, samples: *const Complex32, n: usize, local_tail: u64,
                              prn_mask: u64, results: *mut GmAcqResult, found: *mut u8) -> c_int;

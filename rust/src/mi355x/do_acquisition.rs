@@ -91,7 +91,8 @@ impl AcquisitionWorker {
                 n_integrations: num_integrations as u32, n_bins: doppler_table.len() as u32, doppler_hz: std::ptr::null(),
                 tables: flat.as_ptr(), table_freq: freqs.as_ptr(), n_prn: 1, prn_ids: ids.as_ptr(),
                 codes: std::ptr::null(), code_len: 0, code_rate: 0.0, threshold: 7.0, decision_mode: 0, strict_sum_order: 0, reference_products: 0,
-                any_length: 1 };   // the reference plans any fft_size (:130-143, :249-251)
+                any_length: 1,     // the reference plans any fft_size (:130-143, :249-251)
+                coherent_periods: 1 };   // one code period per transform, as the reference (:174-193)
             let st = unsafe { gm_acq_create(&cfg, &mut self.h) };
             assert_eq!(st, 0, "gm_acq_create: {}", last_error());     // e.g. prn 0 / 33: the reference panics in ::new (:133)
             self.tables_key = key;
@@ -117,7 +118,8 @@ impl AcquisitionEngine {
             n_bins: doppler_hz.len() as u32, doppler_hz: doppler_hz.as_ptr(), tables: std::ptr::null(),
             table_freq: std::ptr::null(), n_prn: prn_ids.len() as u32, prn_ids: prn_ids.as_ptr(),
             codes: std::ptr::null(), code_len: 0, code_rate: 0.0, threshold: 7.0, decision_mode: 0, strict_sum_order: 0, reference_products: 0,
-                any_length: 1 };   // the reference plans any fft_size (:130-143, :249-251)
+                any_length: 1,     // the reference plans any fft_size (:130-143, :249-251)
+                coherent_periods: 1 };   // one code period per transform, as the reference (:174-193)
         let mut h = std::ptr::null_mut();
         if unsafe { gm_acq_create(&cfg, &mut h) } != 0 { return Err(AcqError); }
         Ok(Self { h, n_prn: prn_ids.len() })
