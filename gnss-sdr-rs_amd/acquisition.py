@@ -115,6 +115,21 @@ def detection_threshold(n_integrations, n_cells, pfa):
     return hi
 
 
+# BeiDou B1I's Neumann-Hoffman secondary code (BDS-SIS-ICD-B1I: 0 0 0 0 0 1 0 0 1 1 0 1 0 1 0 0 1 1 1 0 on the 1 ms periods of one
+# 20 ms data bit; 0 <-> +1 as in b1i_codes): the `secondary` row of set_edge_search for coherent_periods = 20
+NH20 = np.array([1 - 2 * b for b in (0, 0, 0, 0, 0, 1, 0, 0, 1, 1, 0, 1, 0, 1, 0, 0, 1, 1, 1, 0)], np.int8)
+
+
+def edge_dwell_periods(coherent_periods, n_integrations, offsets, secondary=None):
+    """gm_acq_edge_dwell_periods: K * M + offsets[-1] after the argument checks of set_edge_search (GmError INVALID_ARG).  Host only."""
+    off = np.ascontiguousarray(offsets, np.uint32)
+    sec = None if secondary is None else np.ascontiguousarray(secondary, np.int8)
+    out = C.c_uint64(0)
+    check(lib().gm_acq_edge_dwell_periods(int(coherent_periods), int(n_integrations), off.size, _p(off),
+                                          _p(sec) if sec is not None else None, C.byref(out)), "gm_acq_edge_dwell_periods")
+    return out.value
+
+
 class AcquisitionEngine:
     """The batched replacement of `workers.par_iter_mut()` (do_acquisition.rs:268-271, 302-313):
     all AcquisitionWorkers of one stage in one handle."""
@@ -157,6 +172,7 @@ class AcquisitionEngine:
         h = C.c_void_p()
         check(lib().gm_acq_create(C.byref(cfg), C.byref(h)), "gm_acq_create")
         self._h = h
+        self.edge_offsets = None      # set_edge_search: the period offsets of the hypotheses while the edge search is on
         self.table_freq = np.zeros(self.D, np.float32)
         check(lib().gm_acq_tables(self._h, None, _p(self.table_freq)), "gm_acq_tables")
 
@@ -187,14 +203,60 @@ class AcquisitionEngine:
         a = np.ascontiguousarray(a, np.complex64)
         return a, FMT_C32, a.size
 
+    # ---- edge search (gm_acq_set_edge_search): hypotheses about where the coherent groups start, with a secondary code's signs
+    def set_edge_search(self, offsets, secondary=None):
+        """H ascending period offsets (1 <= H <= 32, each 0..63) and an optional row of K entries +-1 (e.g. NH20 at K = 20); an empty
+        list switches the search off.  While it is on a dwell is `dwell_samples` long and the result dicts gain `edge_offset_periods`:
+        the offset of the hypothesis the winning bin chose."""
+        off = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+        sec = None
+        if secondary is not None:
+            sec = np.ascontiguousarray(secondary, np.int8).reshape(-1)
+            if sec.size != self.K:
+                raise ValueError("secondary needs coherent_periods entries")
+        check(lib().gm_acq_set_edge_search(self._h, off.size, _p(off) if off.size else None, _p(sec) if sec is not None else None),
+              "gm_acq_set_edge_search")
+        self.edge_offsets = off.copy() if off.size else None
+
+    @property
+    def dwell_samples(self):
+        """Samples every entry that takes a dwell counts: K * M * N, plus the last offset's periods while the edge search is on."""
+        return (self.K * self.M + (int(self.edge_offsets[-1]) if self.edge_offsets is not None else 0)) * self.fft_size
+
+    def edge_metrics(self):
+        """(max, argmax, sum), each [P][H][D]: the planes of every hypothesis of the last search"""
+        H = self.edge_offsets.size if self.edge_offsets is not None else 0
+        mx = np.zeros((self.P, H, self.D), np.float32)
+        am = np.zeros((self.P, H, self.D), np.uint32)
+        sm = np.zeros((self.P, H, self.D), np.float32)
+        check(lib().gm_acq_edge_metrics(self._h, _p(mx), _p(am), _p(sm)), "gm_acq_edge_metrics")
+        return mx, am, sm
+
+    def edge_choice(self):
+        """[P][D] uint32: the hypothesis index each (worker, bin) cell of the last search chose"""
+        ch = np.zeros((self.P, self.D), np.uint32)
+        check(lib().gm_acq_edge_choice(self._h, _p(ch)), "gm_acq_edge_choice")
+        return ch
+
+    def _dicts(self, res, found, n):
+        out = [res[i].as_dict() if found[i] else None for i in range(n)]
+        if self.edge_offsets is not None and n <= self.P and found[:n].any():
+            off = np.zeros(n, np.uint32)
+            check(lib().gm_acq_result_offsets(self._h, C.cast(res, C.c_void_p), _p(found), n, _p(off)), "gm_acq_result_offsets")
+            for i in range(n):
+                if out[i] is not None:
+                    out[i]["edge_offset_periods"] = int(off[i])
+        return out
+
     def search(self, samples_chunk, local_tail=0, prn_mask=0xFFFFFFFFFFFFFFFF):
-        """-> list (one per worker) of AcquisitionResult dict or None.  samples_chunk: K * M * N samples (coherent_periods K)."""
+        """-> list (one per worker) of AcquisitionResult dict or None.  samples_chunk: K * M * N samples (coherent_periods K);
+        `dwell_samples` of them while the edge search is on."""
         a, fmt, n = self._fmt(samples_chunk)      # (fewer samples: GM_ERR_OUT_OF_RANGE from the library's length check)
         res = (AcqResult * self.P)()
         found = np.zeros(self.P, np.uint8)
         check(lib().gm_acq_search(self._h, _p(a), n, fmt, int(local_tail), int(prn_mask) & (2**64 - 1),
                                   C.cast(res, C.c_void_p), _p(found)), "gm_acq_search")
-        return [res[i].as_dict() if found[i] else None for i in range(self.P)]
+        return self._dicts(res, found, self.P)
 
     def search_ring(self, ring, prn_mask=0xFFFFFFFFFFFFFFFF):
         """run()'s snapshot + fan-out against the device ring (do_acquisition.rs:297-313): -> (results, local_tail),
@@ -207,7 +269,7 @@ class AcquisitionEngine:
         if st == -5:
             return None, None
         check(st, "gm_acq_search_ring")
-        return [res[i].as_dict() if found[i] else None for i in range(self.P)], tail.value
+        return self._dicts(res, found, self.P), tail.value
 
     def finer_doppler(self, results):
         """Fine-Doppler refinement (finer_doppler, acquisition_bk.rs:215-302) of the found results of the LAST search,
@@ -277,7 +339,7 @@ class AcquisitionEngine:
         res = (AcqResult * n)()
         found = np.zeros(n, np.uint8)
         check(lib().gm_acq_fetch_results(self._h, n, C.cast(res, C.c_void_p), _p(found)), "gm_acq_fetch_results")
-        return [res[i].as_dict() if found[i] else None for i in range(n)]
+        return self._dicts(res, found, n)
 
     def synchronize(self):
         check(lib().gm_acq_synchronize(self._h), "gm_acq_synchronize")

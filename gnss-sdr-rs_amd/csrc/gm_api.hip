@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -303,6 +304,23 @@ struct gm_acq {
     uint32_t N = 0, D = 0, M = 0, P = 0;
     uint32_t K = 1;                        // gm_acq_cfg.coherent_periods (0 -> 1): a dwell is K * M periods, M groups of K folded coherently
     cf* d_rho = nullptr;                   // [D][K] the fold's phasor words (gm_acq_coherent_phasors)
+    // gm_acq_set_edge_search (K >= 2): H hypotheses about where the groups start, each with the secondary row's signs in the fold
+    // (acq_edge.hip).  Stage F writes the spectra [H * D][M][.], stage C runs with H * D bins into `d_full`, the reduction picks a
+    // hypothesis per (worker, bin) cell into the ordinary metrics block and `d_choice`.  All buffers are the edge search's own: the
+    // handle's are untouched, so switching it off (H = 0) is the handle as it was.
+    struct Edge {
+        uint32_t H = 0;                    // 0: off
+        std::vector<uint32_t> offsets;     // [H] ascending period offsets
+        uint32_t o_max = 0, neg = 0;       // offsets[H - 1]; bit k set: secondary[k] = -1
+        uint32_t* d_offsets = nullptr;
+        cf* d_spectra = nullptr;           // [H * D][M][L or N]
+        cf* d_tmp = nullptr;               // composite sizes whose forward step 2 runs per dwell: the sub-transforms [H * D * M][N]
+        uint32_t* d_full = nullptr;        // [3][P][H][D] metric words of every hypothesis (gm_acq_edge_metrics)
+        uint32_t* d_choice = nullptr;      // [P][D] the hypothesis each cell of the last search chose (gm_acq_edge_choice)
+        float* d_long_part = nullptr;      // any-length sizes: [3][P * H * D][Q] partials
+        float* d_planes = nullptr;         // strict_sum_order on composite / any-length sizes: [P * H * D][N] power planes
+        gm::EdgeLaunch fwd = nullptr;      // stage F of this handle's form
+    } edge;
     float code_rate = CA_RATE;
     std::vector<float> table_freq;
     std::vector<uint8_t> prn_ids, dev_prn_ids;
@@ -383,6 +401,14 @@ struct gm_acq {
 
 // the fused single-LDS-buffer kernels (acq_kernels.hip): neither a composite nor an any-length size
 static bool acq_fused(const gm_acq* a) { return a->Q == 1 && !a->lng; }
+
+// code periods one dwell holds: K * M, plus the last offset while the edge search is on
+static size_t acq_dwell_periods(const gm_acq* a) { return size_t(a->K) * a->M + (a->edge.H ? a->edge.o_max : 0u); }
+static void acq_edge_free(gm_acq::Edge& e) {
+    hipFree(e.d_offsets); hipFree(e.d_spectra); hipFree(e.d_tmp); hipFree(e.d_full); hipFree(e.d_choice); hipFree(e.d_long_part);
+    hipFree(e.d_planes);
+    e = gm_acq::Edge{};
+}
 
 static int acq_set_mask(gm_acq* a, uint64_t mask) {
     std::vector<uint32_t> wl;
@@ -681,6 +707,7 @@ int gm_rfft_f32(size_t n, const float* in, gm_c32* out) {
 int gm_acq_destroy(gm_acq* a) {
     if (!a) return GM_OK;
     if (a->device >= 0) hipSetDevice(a->device);
+    acq_edge_free(a->edge);
     hipFree(a->d_planes);
     if (a->d_long_code != a->d_code_fft) hipFree(a->d_long_code);
     hipFree(a->d_long_z); hipFree(a->d_long_part);
@@ -992,8 +1019,14 @@ static gm::CohArgs acq_coh_args(const gm_acq* a, const void* d_samples, int fmt,
 
 // stage F (unless `prepared`: then the spectra wait in the second buffer) + stage C of one dwell on the handle's stream
 static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_metrics, bool prepared) {
-    uint32_t* met = d_metrics ? static_cast<uint32_t*>(d_metrics) : a->d_metrics;
-    const size_t PD = size_t(a->P) * a->D;
+    uint32_t* const met_out = d_metrics ? static_cast<uint32_t*>(d_metrics) : a->d_metrics;
+    // edge search: stage C sees H * D bins and writes the block of every hypothesis; the reduction at the end fills met_out
+    const gm_acq::Edge& eg = a->edge;
+    const bool edge = eg.H > 0;
+    const uint32_t Dv = edge ? eg.H * a->D : a->D;
+    uint32_t* met = edge ? eg.d_full : met_out;
+    float* const planes = edge ? eg.d_planes : a->d_planes;
+    const size_t PD = size_t(a->P) * Dv;
     const bool t = a->tm.on && (a->tm.calls++ % a->tm.stride == 0);
     a->tm.this_call = t;
     // a timed dwell measures its own kernels only: a decision still pending from the dwell before runs now, in front of the first
@@ -1011,6 +1044,31 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
         std::swap(a->d_spectra, ah.d_spectra_alt);
         HIPC(hipStreamWaitEvent(a->stream, ah.ev_f, 0));
         tickets_cleared = false;
+    } else if (edge) {
+        // (never prepared: gm_acq_prepare_dev runs nothing ahead while the edge search is on)
+        gm::EdgeArgs c{};
+        c.samples = d_samples; c.fmt = fmt; c.rho = a->d_rho; c.K = a->K; c.offsets = eg.d_offsets; c.H = eg.H; c.neg = eg.neg;
+        c.tables = a->d_tables; c.n_bins = a->D; c.n_int = a->M; c.Q = a->Q; c.N = a->N; c.lim = a->long_lim;
+        c.order = a->lng ? nullptr : a->d_order;
+        const uint32_t items = Dv * a->M;
+        cf* const spectra = eg.d_spectra;
+        if (a->lng) {
+            c.tw_fwd = a->d_tw_fwd; c.out = spectra;
+            eg.fwd(a->stream, c);
+            for (uint32_t i0 = 0; i0 < items; i0 += 65535u)       // (grid rows: at most 65535 per launch)
+                gm::launch_long_fwd_post(a->stream, spectra + size_t(i0) * a->L, items - i0 < 65535u ? items - i0 : 65535u, a->Q, a->Nb);
+        } else if (a->Q == 1) {
+            c.tw_fwd = a->d_tw_mix; c.out = spectra; c.clear_tickets = a->d_split_counter;
+            eg.fwd(a->stream, c);
+            a->dec_deferred = false;
+        } else {
+            c.tw_fwd = a->d_tw_mix; c.out = a->comp_post_folded ? spectra : eg.d_tmp;
+            eg.fwd(a->stream, c);
+            if (!a->comp_post_folded)
+                for (uint32_t i0 = 0; i0 < items; i0 += 65535u)
+                    a->comp->fwd_post(a->stream, eg.d_tmp + size_t(i0) * a->N, spectra + size_t(i0) * a->N,
+                                      items - i0 < 65535u ? items - i0 : 65535u, 1, a->d_order);
+        }
     } else if (a->lng) {
         if (a->K > 1)
             a->lng->fwd_sub_coh(a->stream, acq_coh_args(a, d_samples, fmt, a->d_tw_fwd, a->d_spectra, nullptr));
@@ -1037,30 +1095,36 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
     }
     if (t) HIPC(hipEventRecord(ev[1], a->stream));
     if (ah.side) HIPC(hipEventRecord(ah.ev_s, a->stream));
+    cf* const spectra = edge ? eg.d_spectra : a->d_spectra;
     if (a->lng) {
         if (a->n_workers) {
-            const size_t part = size_t(a->P) * a->D * a->Q;
+            const size_t part = size_t(a->P) * Dv * a->Q;
+            float* const lp = edge ? eg.d_long_part : a->d_long_part;
             gm::LongCorrArgs la{};
-            la.spectra = a->d_spectra; la.code_fft = a->d_long_code; la.tw_inv = a->d_tw_inv; la.Z = a->d_long_z;
-            la.pmax = a->d_long_part; la.parg = reinterpret_cast<uint32_t*>(a->d_long_part + part); la.psum = a->d_long_part + 2 * part;
+            la.spectra = spectra; la.code_fft = a->d_long_code; la.tw_inv = a->d_tw_inv; la.Z = a->d_long_z;
+            la.pmax = lp; la.parg = reinterpret_cast<uint32_t*>(lp + part); la.psum = lp + 2 * part;
             la.mmax = reinterpret_cast<float*>(met); la.margmax = met + PD; la.msum = reinterpret_cast<float*>(met + 2 * PD);
-            la.planes = a->d_planes; la.worker_list = a->d_worker_list;
-            la.n_workers = a->n_workers; la.n_bins = a->D; la.n_int = a->M; la.Q = a->Q; la.Nb = a->Nb; la.N = a->N;
+            la.planes = planes; la.worker_list = a->d_worker_list;
+            la.n_workers = a->n_workers; la.n_bins = Dv; la.n_int = a->M; la.Q = a->Q; la.Nb = a->Nb; la.N = a->N;
             la.slab_items = a->long_slab; la.scale = a->long_scale;
             gm::launch_long_corr(a->stream, a->lng, la);
-            if (a->d_planes)      // strict_sum_order: the plane sums once more, in is_good_satellite's own order (:229-235)
-                gm::launch_plane_strict_sum(a->stream, a->d_planes, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(a->D), uint32_t(a->N));
+            if (planes)      // strict_sum_order: the plane sums once more, in is_good_satellite's own order (:229-235)
+                gm::launch_plane_strict_sum(a->stream, planes, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), uint32_t(a->N));
         }
     } else if (a->Q == 1) {
-        a->plan->corr(a->stream, a->d_spectra, a->plan->code_paired ? a->d_code_fft_paired : a->d_code_fft, a->d_tw_inv, reinterpret_cast<float*>(met), met + PD,
-                      reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(a->D), int(a->M),
+        a->plan->corr(a->stream, spectra, a->plan->code_paired ? a->d_code_fft_paired : a->d_code_fft, a->d_tw_inv, reinterpret_cast<float*>(met), met + PD,
+                      reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), int(a->M),
                       a->d_split_scratch, a->split_planes, a->d_split_counter, a->cfg.strict_sum_order ? 1 : 0, tickets_cleared ? 1 : 0,
                       a->cfg.reference_products ? 1 : 0);
     } else if (a->n_workers) {
-        a->comp->corr(a->stream, a->d_spectra, a->d_code_comb, a->d_comp_twn, a->d_tw_inv, reinterpret_cast<float*>(met),
-                      met + PD, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(a->D), int(a->M), a->d_planes);
-        if (a->d_planes)      // strict_sum_order: the plane sums once more, in is_good_satellite's own order (:229-235)
-            gm::launch_plane_strict_sum(a->stream, a->d_planes, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(a->D), uint32_t(a->N));
+        a->comp->corr(a->stream, spectra, a->d_code_comb, a->d_comp_twn, a->d_tw_inv, reinterpret_cast<float*>(met),
+                      met + PD, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), int(a->M), planes);
+        if (planes)      // strict_sum_order: the plane sums once more, in is_good_satellite's own order (:229-235)
+            gm::launch_plane_strict_sum(a->stream, planes, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), uint32_t(a->N));
+    }
+    if (edge) {       // per (worker, bin) cell the hypothesis with the largest max (lowest h on ties): its words, and h into the choice plane
+        gm::launch_edge_reduce(a->stream, eg.d_full, met_out, eg.d_choice, a->d_worker_list, a->n_workers, a->P, eg.H, a->D);
+        met = met_out;
     }
     if (t) { HIPC(hipEventRecord(ev[2], a->stream)); a->tm.count++; a->tm.decide_valid = false; }
     HIPC(hipGetLastError());
@@ -1083,7 +1147,7 @@ int gm_acq_search_prepared_dev(gm_acq* a, uint64_t token, void* d_metrics) {
     if (!token || !ah.valid || ah.token != token)
         return set_err(GM_ERR_INVALID_ARG, "no such preparation (token stale, consumed, replaced or dropped)");
     if (int rc = ensure_device(a->device)) return rc;
-    if (!acq_fused(a)) {                    // composite and any-length sizes prepare nothing: the whole search runs now, from the samples named then,
+    if (!acq_fused(a) || a->edge.H) {       // composite and any-length sizes (and an edge search) prepare nothing: the whole search runs now, from the samples named then,
         ah.valid = false;                   // behind what `ready_stream` held at the time of gm_acq_prepare_dev
         if (ah.comp_wait) { HIPC(hipStreamWaitEvent(a->stream, ah.ev_in, 0)); ah.comp_wait = false; }
         return acq_search_common(a, ah.samples, ah.fmt, d_metrics, false);
@@ -1103,7 +1167,7 @@ int gm_acq_prepare_dev(gm_acq* a, const void* d_samples, int fmt, void* ready_st
     *token = 0;
     gm_acq::Ahead& ah = a->ahead;
     if (int rc = ensure_device(a->device)) return rc;
-    if (!acq_fused(a)) {                    // composite and any-length sizes: nothing is prepared, gm_acq_search_prepared_dev does all of it —
+    if (!acq_fused(a) || a->edge.H) {       // composite and any-length sizes, and every size while the edge search is on: nothing is prepared, gm_acq_search_prepared_dev does all of it —
         // but the ordering promise is the same: the samples are complete once the work queued on `ready_stream` so far has run, so
         // the event is recorded NOW and the search waits for it on the handle's stream (the token used to be handed
         // out before `ready_stream` was looked at)
@@ -1225,8 +1289,10 @@ int gm_acq_search(gm_acq* a, const void* samples, size_t n_samples, int fmt, uin
                   gm_acq_result* results, uint8_t* found) {
     if (!a || !samples || !results || !found) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (fmt < GM_FMT_C32 || fmt > GM_FMT_I8_REAL) return set_err(GM_ERR_INVALID_ARG, "bad sample format");
-    const size_t need = size_t(a->K) * a->M * a->N;
-    if (n_samples < need) return set_err(GM_ERR_OUT_OF_RANGE, "samples_chunk shorter than coherent_periods*num_integrations*fft_size");
+    const size_t need = acq_dwell_periods(a) * a->N;
+    if (n_samples < need)
+        return set_err(GM_ERR_OUT_OF_RANGE, a->edge.H ? "samples_chunk shorter than (coherent_periods*num_integrations + the last edge offset)*fft_size"
+                                                      : "samples_chunk shorter than coherent_periods*num_integrations*fft_size");
     if (int rc = ensure_device(a->device)) return rc;
     const size_t bps = fmt == GM_FMT_C32 ? 8 : (fmt == GM_FMT_I8_IQ ? 2 : 1);
     if (int rc = acq_set_mask(a, prn_mask)) return rc;
@@ -1243,7 +1309,7 @@ int gm_acq_search_ring(gm_acq* a, gm_ring* ring, uint64_t prn_mask, gm_acq_resul
                        uint64_t* local_tail_out) {
     if (!a || !ring || !results || !found) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (a->device != ring->device) return set_err(GM_ERR_INVALID_ARG, "ring lives on another device");
-    const size_t need = size_t(a->K) * a->M * a->N;
+    const size_t need = acq_dwell_periods(a) * a->N;     // (edge search: K*M + the last offset periods)
     if (need > ring->size) return set_err(GM_ERR_OUT_OF_RANGE, "ring smaller than coherent_periods*num_integrations*fft_size");
     if (int rc = ensure_device(ring->device)) return rc;
     ring_refresh_head(ring);
@@ -1307,9 +1373,21 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
         f.p1 = b1; f.p2 = b2; f.size_use = size_use;
     }
     const uint32_t N1 = uint32_t(f.p1->n), N2 = uint32_t(f.p2->n);
+    if (fft_size_out) *fft_size_out = uint64_t(N1) * N2;
+    // edge search: every found worker is refined on the K*M periods its winning hypothesis searched, i.e. from period o* on (whole
+    // periods do not move the code phase) — one pass per distinct offset among the found workers; without it one pass at offset 0
+    std::vector<uint32_t> off(n_prn, 0u);
+    if (a->edge.H)
+        if (int rc = gm_acq_result_offsets(a, results, found, n_prn, off.data())) return rc;
+    std::vector<uint32_t> passes;
+    for (uint32_t p = 0; p < n_prn; ++p)
+        if (found[p] && std::find(passes.begin(), passes.end(), off[p]) == passes.end()) passes.push_back(off[p]);
+    const size_t bps = a->last_fmt == GM_FMT_C32 ? 8 : (a->last_fmt == GM_FMT_I8_IQ ? 2 : 1);
+    for (const uint32_t o_star : passes) {
+    const void* const snap = static_cast<const char*>(a->last_samples) + size_t(o_star) * a->N * bps;
     std::vector<uint32_t> workers, cps, slot(n_prn, 0xFFFFFFFFu);
     for (uint32_t p = 0; p < n_prn; ++p) {
-        if (!found[p]) continue;
+        if (!found[p] || off[p] != o_star) continue;
         if (results[p].code_phase_samples + size_use > uint64_t(periods) * a->N)
             return set_err(GM_ERR_OUT_OF_RANGE, "code_phase + (K*M-1)*N exceeds the snapshot (:260 would panic)");
         slot[p] = uint32_t(workers.size());
@@ -1317,8 +1395,6 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
         cps.push_back(uint32_t(results[p].code_phase_samples));
     }
     const uint32_t S = uint32_t(workers.size());
-    if (fft_size_out) *fft_size_out = uint64_t(N1) * N2;
-    if (!S) return GM_OK;
     if (S > f.sats_cap) {
         hipFree(f.d_B); hipFree(f.d_rowmax); hipFree(f.d_rowarg); hipFree(f.d_sat_worker); hipFree(f.d_sat_cp);
         hipFree(f.d_peak_pow); hipFree(f.d_peak_idx);
@@ -1335,12 +1411,12 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
     HIPC(hipMemcpyAsync(f.d_sat_worker, workers.data(), S * 4, hipMemcpyHostToDevice, a->stream));
     HIPC(hipMemcpyAsync(f.d_sat_cp, cps.data(), S * 4, hipMemcpyHostToDevice, a->stream));
     gm::FineArgs fa{};
-    fa.samples = a->last_samples; fa.fmt = a->last_fmt; fa.mean = f.d_mean;
+    fa.samples = snap; fa.fmt = a->last_fmt; fa.mean = f.d_mean;
     fa.chips = f.d_chips; fa.code_len = a->code_len; fa.code_rate = a->code_rate; fa.fs = a->cfg.fs;
     fa.sat_worker = f.d_sat_worker; fa.sat_code_phase = f.d_sat_cp;
     fa.size_use = size_use; fa.N1 = N1; fa.N2 = N2; fa.B = f.d_B; fa.tw1 = f.d_tw1; fa.tw2 = f.d_tw2;
     fa.rowmax = f.d_rowmax; fa.rowarg = f.d_rowarg;
-    gm::launch_fine_mean(a->stream, a->last_samples, a->last_fmt, periods * a->N, f.d_mean);
+    gm::launch_fine_mean(a->stream, snap, a->last_fmt, periods * a->N, f.d_mean);
     f.p1->fine_cols(a->stream, fa, int(S));
     f.p2->fine_rows(a->stream, fa, int(S));
     gm::launch_fine_final(a->stream, f.d_rowmax, f.d_rowarg, N1 / uint32_t(f.p2->fine_rows_per_wg), int(S), f.d_peak_pow, f.d_peak_idx);
@@ -1361,6 +1437,7 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
             fine_freq_hz[p] = idx > one_side ? -((float(fft_size - idx) * a->cfg.fs) / float(fft_size))
                                              : (float(idx) * a->cfg.fs) / float(fft_size);
     }
+    }     // passes
     return GM_OK;
 }
 
@@ -1403,6 +1480,122 @@ int gm_acq_coherent_phasors(gm_acq* a, gm_c32* out) {
     if (!a || !out) return set_err(GM_ERR_INVALID_ARG, "null handle/out");
     if (int rc = ensure_device(a->device)) return rc;
     HIPC(hipMemcpy(out, a->d_rho, size_t(a->D) * a->K * 8, hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+// ---------------------------------------------------------------- edge search (additive entries, ABI 9)
+// the argument rules of gm_acq_edge_dwell_periods / gm_acq_set_edge_search; *neg: bit k set where secondary[k] = -1
+static int edge_check(uint32_t K, uint32_t n, const uint32_t* offsets, const int8_t* secondary, uint32_t* neg) {
+    if (K < 2) return set_err(GM_ERR_INVALID_ARG, "the edge search needs a coherent handle (coherent_periods >= 2)");
+    if (K > uint32_t(gm::GM_COHERENT_MAX)) return set_err(GM_ERR_INVALID_ARG, "coherent_periods > 32");
+    if (n > 32) return set_err(GM_ERR_INVALID_ARG, "more than 32 edge offsets");
+    if (!offsets) return set_err(GM_ERR_INVALID_ARG, "null offsets");
+    for (uint32_t h = 0; h < n; ++h) {
+        if (offsets[h] > 63) return set_err(GM_ERR_INVALID_ARG, "edge offset above 63 periods");
+        if (h && offsets[h] <= offsets[h - 1]) return set_err(GM_ERR_INVALID_ARG, "edge offsets must ascend strictly");
+    }
+    *neg = 0;
+    if (secondary)
+        for (uint32_t k = 0; k < K; ++k) {
+            if (secondary[k] != 1 && secondary[k] != -1) return set_err(GM_ERR_INVALID_ARG, "secondary row entries must be +1 or -1");
+            if (secondary[k] < 0) *neg |= 1u << k;
+        }
+    return GM_OK;
+}
+
+int gm_acq_edge_dwell_periods(uint32_t coherent_periods, uint32_t n_integrations, uint32_t n_offsets, const uint32_t* offsets,
+                              const int8_t* secondary, uint64_t* dwell_periods) {
+    if (!dwell_periods || !n_integrations) return set_err(GM_ERR_INVALID_ARG, "null dwell_periods / n_integrations == 0");
+    const uint32_t K = coherent_periods > 1 ? coherent_periods : 1;
+    if (!n_offsets) {                       // the edge search off: the handle's own dwell
+        if (K > uint32_t(gm::GM_COHERENT_MAX)) return set_err(GM_ERR_INVALID_ARG, "coherent_periods > 32");
+        *dwell_periods = uint64_t(K) * n_integrations;
+        return GM_OK;
+    }
+    uint32_t neg = 0;
+    if (int rc = edge_check(K, n_offsets, offsets, secondary, &neg)) return rc;
+    *dwell_periods = uint64_t(K) * n_integrations + offsets[n_offsets - 1];
+    return GM_OK;
+}
+
+int gm_acq_set_edge_search(gm_acq* a, uint32_t n_offsets, const uint32_t* offsets, const int8_t* secondary) {
+    if (!a) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    uint32_t neg = 0;
+    if (n_offsets)
+        if (int rc = edge_check(a->K, n_offsets, offsets, secondary, &neg)) return rc;
+    if (int rc = ensure_device(a->device)) return rc;
+    if (int rc = acq_flush_decision(a)) return rc;
+    a->ahead.valid = false;                 // an outstanding preparation is dropped: its token becomes stale
+    a->ahead.comp_wait = false;
+    HIPC(hipStreamSynchronize(a->stream));
+    if (!n_offsets) {
+        if (a->edge.H) a->last_samples = nullptr;
+        acq_edge_free(a->edge);
+        return GM_OK;
+    }
+    gm_acq::Edge e;
+    e.H = n_offsets; e.offsets.assign(offsets, offsets + n_offsets); e.o_max = offsets[n_offsets - 1]; e.neg = neg;
+    e.fwd = a->lng ? gm::find_edge_long_fwd_sub(a->lng->nb) : (a->Q == 1 ? gm::find_edge_mix_fft(a->plan->n) : gm::find_edge_comp_fwd_sub(a->comp->nb));
+    if (!e.fwd) return set_err(GM_ERR_UNSUPPORTED_N, "no edge-search stage F for this handle's base plan");
+    const size_t H = n_offsets, D = a->D, M = a->M, P = a->P, N = a->N, T = a->lng ? size_t(a->L) : N;
+    // everything new is allocated before anything old goes: a failure leaves the handle as it was
+    void* smp = nullptr;
+    const size_t smp_bytes = (size_t(a->K) * M + e.o_max) * N * 8;
+    bool ok = hipMalloc(&e.d_offsets, H * 4) == hipSuccess && hipMalloc(&e.d_spectra, H * D * M * T * 8) == hipSuccess &&
+              hipMalloc(&e.d_full, 3 * P * H * D * 4) == hipSuccess && hipMalloc(&e.d_choice, P * D * 4) == hipSuccess;
+    if (ok && a->Q > 1 && !a->lng && !a->comp_post_folded) ok = hipMalloc(&e.d_tmp, H * D * M * N * 8) == hipSuccess;
+    if (ok && a->lng) ok = hipMalloc(&e.d_long_part, 3 * P * H * D * a->Q * 4) == hipSuccess;
+    if (ok && a->d_planes) ok = hipMalloc(&e.d_planes, P * H * D * N * sizeof(float)) == hipSuccess;
+    if (ok && smp_bytes > a->samples_cap) ok = hipMalloc(&smp, smp_bytes) == hipSuccess;
+    if (ok) ok = hipMemset(e.d_full, 0, 3 * P * H * D * 4) == hipSuccess && hipMemset(e.d_choice, 0, P * D * 4) == hipSuccess &&
+                 hipMemcpy(e.d_offsets, e.offsets.data(), H * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        hipFree(smp);
+        acq_edge_free(e);
+        return set_err(GM_ERR_NOMEM, "the edge search's buffers do not fit (gnss_mi355x.h states the formula); the handle is as it was");
+    }
+    if (smp) { hipFree(a->d_samples); a->d_samples = smp; a->samples_cap = smp_bytes; }
+    acq_edge_free(a->edge);
+    a->edge = std::move(e);
+    a->last_samples = nullptr;              // (gm_acq_finer_doppler: the next search's snapshot)
+    return GM_OK;
+}
+
+int gm_acq_edge_metrics(gm_acq* a, float* mx, uint32_t* am, float* sm) {
+    if (!a) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!a->edge.H) return set_err(GM_ERR_INVALID_ARG, "the edge search is off (gm_acq_set_edge_search)");
+    if (int rc = ensure_device(a->device)) return rc;
+    HIPC(hipStreamSynchronize(a->stream));
+    const size_t n = size_t(a->P) * a->edge.H * a->D;
+    if (mx) HIPC(hipMemcpy(mx, a->edge.d_full, n * 4, hipMemcpyDeviceToHost));
+    if (am) HIPC(hipMemcpy(am, a->edge.d_full + n, n * 4, hipMemcpyDeviceToHost));
+    if (sm) HIPC(hipMemcpy(sm, a->edge.d_full + 2 * n, n * 4, hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+int gm_acq_edge_choice(gm_acq* a, uint32_t* hypothesis) {
+    if (!a || !hypothesis) return set_err(GM_ERR_INVALID_ARG, "null handle/out");
+    if (!a->edge.H) return set_err(GM_ERR_INVALID_ARG, "the edge search is off (gm_acq_set_edge_search)");
+    if (int rc = ensure_device(a->device)) return rc;
+    HIPC(hipStreamSynchronize(a->stream));
+    HIPC(hipMemcpy(hypothesis, a->edge.d_choice, size_t(a->P) * a->D * 4, hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+int gm_acq_result_offsets(gm_acq* a, const gm_acq_result* results, const uint8_t* found, uint32_t n_prn, uint32_t* offset_periods) {
+    if (!a || !results || !found || !offset_periods) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (!a->edge.H) return set_err(GM_ERR_INVALID_ARG, "the edge search is off (gm_acq_set_edge_search)");
+    if (n_prn > a->P) return set_err(GM_ERR_INVALID_ARG, "n_prn exceeds the handle's workers");
+    std::vector<uint32_t> choice(size_t(a->P) * a->D);
+    if (int rc = gm_acq_edge_choice(a, choice.data())) return rc;
+    for (uint32_t p = 0; p < n_prn; ++p) {
+        if (!found[p]) continue;
+        const int32_t d = results[p].doppler_bin;
+        if (d < 0 || uint32_t(d) >= a->D) return set_err(GM_ERR_OUT_OF_RANGE, "result.doppler_bin outside the handle's bins");
+        const uint32_t h = choice[size_t(p) * a->D + uint32_t(d)];
+        offset_periods[p] = a->edge.offsets[h < a->edge.H ? h : 0];
+    }
     return GM_OK;
 }
 

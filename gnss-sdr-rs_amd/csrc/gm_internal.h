@@ -42,6 +42,30 @@ template <class PL> void launch_mix_fft_coh(hipStream_t, const CohArgs&);
 template <class PL> void launch_comp_fwd_sub_coh(hipStream_t, const CohArgs&);
 template <class PL> void launch_long_fwd_sub_coh(hipStream_t, const CohArgs&);
 
+// Stage F of a coherent handle's edge search (gm_acq_set_edge_search, acq_edge.hip): H hypotheses, each the coherent stage F on the
+// samples from period offsets[h] on with the secondary row's signs in the fold; the output is laid out [H * n_bins][n_int][.], i.e.
+// what stage C takes with H * n_bins bins.  CohArgs' fields mean what they mean there (n_bins: the handle's own D).
+struct EdgeArgs {
+    const void* samples; int fmt;          // (K * M + offsets[H - 1]) * N samples
+    const cf* rho; uint32_t K;
+    const uint32_t* offsets; uint32_t H;   // device [H], ascending period offsets
+    uint32_t neg;                          // bit k set: secondary[k] = -1
+    const cf* tables; const cf* tw_fwd;
+    cf* out;
+    uint32_t n_bins, n_int;
+    uint32_t Q, N, lim;
+    uint32_t* clear_tickets;
+    const uint16_t* order;
+};
+// the launchers by base plan length (null: no such plan): in-LDS sizes, the composite bases, the long bases
+typedef void (*EdgeLaunch)(hipStream_t, const EdgeArgs&);
+EdgeLaunch find_edge_mix_fft(int n);
+EdgeLaunch find_edge_comp_fwd_sub(int nb);
+EdgeLaunch find_edge_long_fwd_sub(int nb);
+// full [3][P][H][D] -> met [3][P][D] + choice [P][D] for the listed workers: per cell the hypothesis with the largest max, lowest h on ties
+void launch_edge_reduce(hipStream_t, const uint32_t* full, uint32_t* met, uint32_t* choice, const uint32_t* worker_list,
+                        uint32_t n_workers, uint32_t P, uint32_t H, uint32_t D);
+
 // One entry per shipped transform size: launchers for the kernels instantiated on that plan.
 struct DecideArgs;
 struct PlanOps {

@@ -155,6 +155,22 @@ public:
               "finer_doppler");
         return freq;
     }
+    // The edge search of a coherent handle (gm_acq_set_edge_search): H ascending period offsets (each 0..63, H <= 32) and an optional
+    // secondary row of coherent_periods entries +-1 (empty: all +1); no offsets switch it off.  While it is on a dwell is
+    // (K * n_integrations + offsets.back()) * fft_size samples.
+    void set_edge_search(const std::vector<uint32_t>& offsets, const std::vector<int8_t>& secondary = {}) {
+        check(gm_acq_set_edge_search(h_, uint32_t(offsets.size()), offsets.empty() ? nullptr : offsets.data(),
+                                     secondary.empty() ? nullptr : secondary.data()), "set_edge_search");
+    }
+    // for every found result of the last search the offset, in periods, of the hypothesis its winning bin chose (others: 0)
+    std::vector<uint32_t> edge_offset_periods(const std::vector<std::optional<AcquisitionResult>>& results) {
+        std::vector<gm_acq_result> r(results.size());
+        std::vector<uint8_t> f(results.size(), 0);
+        for (size_t i = 0; i < results.size(); ++i) if (results[i]) { r[i] = *results[i]; f[i] = 1; }
+        std::vector<uint32_t> off(results.size(), 0u);
+        check(gm_acq_result_offsets(h_, r.data(), f.data(), uint32_t(results.size()), off.data()), "edge_offset_periods");
+        return off;
+    }
     std::vector<std::optional<AcquisitionResult>> search_i8(const std::vector<int8_t>& iq_interleaved, uint64_t local_tail,
                                                             uint64_t prn_mask = ~0ull) {
         std::vector<gm_acq_result> r(n_prn_);

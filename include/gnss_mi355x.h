@@ -35,7 +35,9 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 9   /* 9: gm_acq_cfg.coherent_periods, gm_acq_coherent_phasors;
+#define GM_ABI_VERSION 9   /* 9: gm_acq_cfg.coherent_periods, gm_acq_coherent_phasors; still 9, additive (no struct changed: a caller
+                              detects the feature by the symbol): the edge search — gm_acq_edge_dwell_periods,
+                              gm_acq_set_edge_search, gm_acq_edge_metrics, gm_acq_edge_choice, gm_acq_result_offsets;
                               8: gm_acq_cfg.any_length, gm_acq_plan_info;
                               7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
@@ -348,6 +350,53 @@ int gm_acq_tables(gm_acq *a, gm_c32 *tables, float *table_freq);
 /* The coherent fold's phasor words [n_bins][coherent_periods] exactly as the device uses them (gm_acq_cfg.coherent_periods);
  * at coherent_periods 0 or 1 the one word per bin is (1, 0).  (ABI 9) */
 int gm_acq_coherent_phasors(gm_acq *a, gm_c32 *out);
+/* ---- Edge search on a coherent handle (coherent_periods = K >= 2): a third search axis beside PRN and Doppler — H hypotheses
+ * about where the groups of K periods start, each with a secondary code's signs applied inside the group.  For GPS C/A with K = 20
+ * (one data bit) the hypothesis whose groups start on the bit edge keeps the whole bit; for a signal with a secondary code (BeiDou
+ * B1I's NH20, any tiered code of up to 32 periods) the aligned hypothesis wipes the code off, which is what makes K > 1 usable there.
+ *   offsets   : H period offsets, 1 <= H <= 32, each in [0, 63], strictly ascending
+ *   secondary : K entries of +1 / -1, or NULL (all +1)
+ * A dwell is (K*M + offsets[H-1]) * fft_size samples.  Hypothesis h is the coherent search on the samples from period offsets[h]
+ * on with secondary[k] * rho[d][k] in place of rho[d][k] in the fold,
+ *     y_{h,d,m}[n] = sum_k secondary[k] rho[d][k] x[(offsets[h] + m K + k) fft_size + n],
+ * in the fold's own arithmetic (k ascending, every product and sum rounded on its own; the multiplication by +-1 is exact).  Every
+ * hypothesis yields the usual three planes: the full block is [3][P][H][D] (gm_acq_edge_metrics).  A reduction then picks, for every
+ * (worker, bin) cell, the hypothesis with the largest max — on equal values the lowest h — and writes its three words into the
+ * ordinary [3][P][D] metrics block and h into a choice plane [P][D] (gm_acq_edge_choice).  From there on nothing changes:
+ * gm_acq_decide_dev / _host, both decision modes, the all-gather entries, gm_acq_metrics (the reduced planes) and
+ * gm_acq_fetch_results see today's layout, gm_acq_result keeps its meaning (whole periods do not move the code phase;
+ * sample_global_index = local_tail + code phase, relative to the dwell's first sample).  gm_acq_coherent_phasors is unchanged and does
+ * not show the row.
+ * While it is on: gm_acq_search*, gm_acq_search_dev, gm_acq_prepare_dev count (K*M + offsets[H-1]) * fft_size samples and
+ * gm_acq_search_ring reports local_tail = head - that; gm_acq_prepare_dev behaves as on composite sizes (a token, the ordering
+ * promise, the whole search at gm_acq_search_prepared_dev); gm_acq_set_deferred_decision is accepted and decides at once;
+ * gm_acq_finer_doppler strips the code from the winning hypothesis's offset o* on — (K*M-1) * fft_size samples from
+ * o* * fft_size + code_phase, the mean over the K*M periods from o* on.
+ * Stage F runs one grid over H * D * M transforms and stage C one launch over P * H * D items (acq_edge.hip).
+ * Device memory while it is on, beside the handle's own (T = gm_acq_plan_info's transform_len, N = fft_size):
+ *     8 H D M T  (spectra)  +  12 P H D + 4 P D + 4 H  (metric words, choice, offsets)  +  8 offsets[H-1] N  (the internal sample
+ *     buffer of the host / ring entries, when it has to grow)
+ *     + 8 H D M N  on composite sizes whose base plan has no storage-order table  + 12 P H D q  on any-length sizes
+ *     + 4 P H D N  with strict_sum_order on composite and any-length sizes (the stored power planes).
+ * gm_acq_set_edge_search allocates it; GM_ERR_NOMEM if that fails, with the handle (and an earlier edge search) as it was.
+ * GM_ERR_INVALID_ARG for K < 2, H > 32, an offset above 63, offsets that do not ascend strictly, a row entry other than +-1.  It runs
+ * a pending deferred decision and drops an outstanding preparation.  n_offsets = 0 switches the search off: the handle as it was,
+ * bit for bit.
+ * Thresholds: the reduction takes the largest of H cells, so the false-alarm count grows with the cells searched — take
+ * detection_threshold(M, n_cells * H, pfa) (acquisition.detection_threshold in the Python package) instead of (M, n_cells, pfa). */
+/* host only, no device: checks the arguments as gm_acq_set_edge_search does; *dwell_periods = K*M + offsets[n_offsets-1]
+ * (n_offsets = 0: K*M, coherent_periods 0 counting as 1) */
+int gm_acq_edge_dwell_periods(uint32_t coherent_periods, uint32_t n_integrations, uint32_t n_offsets,
+                              const uint32_t *offsets, const int8_t *secondary, uint64_t *dwell_periods);
+int gm_acq_set_edge_search(gm_acq *a, uint32_t n_offsets, const uint32_t *offsets, const int8_t *secondary);
+/* The planes of every hypothesis of the last search: [n_prn][H][n_bins] each, any pointer may be NULL.  Synchronises. */
+int gm_acq_edge_metrics(gm_acq *a, float *max, uint32_t *argmax, float *sum);
+/* The hypothesis index each (worker, bin) cell of the last search chose: [n_prn][n_bins]. */
+int gm_acq_edge_choice(gm_acq *a, uint32_t *hypothesis);
+/* For every found[p] the offset, in periods, of the hypothesis the winning bin (results[p].doppler_bin) of worker p chose in the
+ * last search; entries of not-found workers are left untouched.  n_prn <= the handle's workers. */
+int gm_acq_result_offsets(gm_acq *a, const gm_acq_result *results, const uint8_t *found, uint32_t n_prn,
+                          uint32_t *offset_periods);
 /* Kernel timing of the last gm_acq_search*_dev call, measured with HIP events on the handle's
  * stream: ms_mix_fft (stage F), ms_corr (stage C, the dominant kernel), ms_decide.  Enable first: on = 1 times every
  * search, on = k > 1 every k-th (an event record costs about 2 us of stream time; four per timed search), 0 disables. */

@@ -81,6 +81,15 @@ extern "C" {
     pub fn gm_acq_destroy(a: *mut GmAcq) -> c_int;
     // the coherent fold's phasor words [n_bins][coherent_periods] (gm_acq_cfg.coherent_periods, ABI 9)
     pub fn gm_acq_coherent_phasors(a: *mut GmAcq, out: *mut Complex32) -> c_int;
+    // the edge search of a coherent handle (additive entries, ABI stays 9: detect them by the symbol): H period offsets and an
+    // optional secondary row of +-1; a dwell is then (K * n_integrations + offsets[H-1]) periods
+    pub fn gm_acq_edge_dwell_periods(coherent_periods: u32, n_integrations: u32, n_offsets: u32, offsets: *const u32,
+                                     secondary: *const i8, dwell_periods: *mut u64) -> c_int;
+    pub fn gm_acq_set_edge_search(a: *mut GmAcq, n_offsets: u32, offsets: *const u32, secondary: *const i8) -> c_int;
+    pub fn gm_acq_edge_metrics(a: *mut GmAcq, max: *mut f32, argmax: *mut u32, sum: *mut f32) -> c_int;
+    pub fn gm_acq_edge_choice(a: *mut GmAcq, hypothesis: *mut u32) -> c_int;
+    pub fn gm_acq_result_offsets(a: *mut GmAcq, results: *const GmAcqResult, found: *const u8, n_prn: u32,
+                                 offset_periods: *mut u32) -> c_int;
     // do_acquisition.rs:302-313 + :158-226  (par_iter over workers / search_satellite)
     pub fn gm_acq_search_c32(a: *mut GmAcq, samples: *const Complex32, n: usize, local_tail: u64,
                              prn_mask: u64, results: *mut GmAcqResult, found: *mut u8) -> c_int;

@@ -124,6 +124,15 @@ impl AcquisitionEngine {
         if unsafe { gm_acq_create(&cfg, &mut h) } != 0 { return Err(AcqError); }
         Ok(Self { h, n_prn: prn_ids.len() })
     }
+    /// Not in the reference: on an engine built with coherent_periods >= 2, search `offsets` (ascending, in code periods) for where
+    /// the coherent groups start, with an optional secondary row of +-1 (e.g. BeiDou's NH20); a dwell then takes
+    /// (K * n_int + offsets.last()) * fft_size samples.  No offsets switch the search off.
+    pub fn set_edge_search(&mut self, offsets: &[u32], secondary: Option<&[i8]>) -> Result<(), AcqError> {
+        let sec = secondary.map_or(std::ptr::null(), |s| s.as_ptr());
+        let off = if offsets.is_empty() { std::ptr::null() } else { offsets.as_ptr() };
+        if unsafe { gm_acq_set_edge_search(self.h, offsets.len() as u32, off, sec) } != 0 { return Err(AcqError); }
+        Ok(())
+    }
     /// the body of `workers.par_iter_mut().enumerate().filter_map(..search_satellite..)` (:302-313)
     pub fn search(&mut self, chunk: &[Complex32], local_tail: usize, mask: u32) -> Vec<AcquisitionResult> {
         let mut raw = vec![GmAcqResult::default(); self.n_prn];
