@@ -128,6 +128,11 @@ SIGNATURES = {
     "gm_acq_edge_metrics": (_i, [_vp, _vp, _vp, _vp]),
     "gm_acq_edge_choice": (_i, [_vp, _vp]),
     "gm_acq_result_offsets": (_i, [_vp, _vp, _vp, _u32, _vp]),
+    "gm_acq_set_code_drift": (_i, [_vp, _u32, _vp]),
+    "gm_acq_code_drift_plan": (_i, [_u32, _u32, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "gm_acq_dwell_samples": (_i, [_vp, C.POINTER(_u64)]),
+    "gm_acq_code_drift_starts": (_i, [_vp, _vp]),
+    "gm_acq_code_drift_phasors": (_i, [_vp, _u32, _vp]),
     "gm_acq_enable_timing": (_i, [_vp, _i]),
     "gm_acq_last_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
     "gm_acq_timing_summary": (_i, [_vp, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f)]),

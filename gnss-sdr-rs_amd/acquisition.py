@@ -130,6 +130,26 @@ def edge_dwell_periods(coherent_periods, n_integrations, offsets, secondary=None
     return out.value
 
 
+def code_period_samples(fs, code_len, code_rate, doppler_hz=0.0, carrier_hz=None):
+    """The true code period in samples, fs * code_len / code_rate / (1 + doppler_hz / carrier_hz): what set_code_drift takes per bin.
+    carrier_hz None: without the Doppler factor (the geometry alone, e.g. 16367.6 at fs = 16.3676 MHz).  Scalars or arrays, float64."""
+    t = np.float64(fs) * np.float64(code_len) / np.float64(code_rate)
+    if carrier_hz is None:
+        return t + 0.0 * np.asarray(doppler_hz, np.float64)
+    return t / (1.0 + np.asarray(doppler_hz, np.float64) / np.float64(carrier_hz))
+
+
+def code_drift_plan(fft_size, n_periods, period_samples):
+    """gm_acq_code_drift_plan: (starts [D][n_periods] uint64, dwell_samples) with starts[d][p] = floor(p * T_d + 0.5) in float64 and
+    dwell_samples = max_d starts[d][-1] + fft_size, after the argument checks of set_code_drift (GmError INVALID_ARG).  Host only."""
+    t = np.ascontiguousarray(period_samples, np.float64).reshape(-1)
+    starts = np.zeros((t.size, int(n_periods)), np.uint64)
+    out = C.c_uint64(0)
+    check(lib().gm_acq_code_drift_plan(int(fft_size), int(n_periods), t.size, _p(t) if t.size else None, _p(starts), C.byref(out)),
+          "gm_acq_code_drift_plan")
+    return starts, out.value
+
+
 class AcquisitionEngine:
     """The batched replacement of `workers.par_iter_mut()` (do_acquisition.rs:268-271, 302-313):
     all AcquisitionWorkers of one stage in one handle."""
@@ -172,6 +192,7 @@ class AcquisitionEngine:
         h = C.c_void_p()
         check(lib().gm_acq_create(C.byref(cfg), C.byref(h)), "gm_acq_create")
         self._h = h
+        self.code_drift = None        # set_code_drift: the per-bin code periods while the compensation is on
         self.edge_offsets = None      # set_edge_search: the period offsets of the hypotheses while the edge search is on
         self.table_freq = np.zeros(self.D, np.float32)
         check(lib().gm_acq_tables(self._h, None, _p(self.table_freq)), "gm_acq_tables")
@@ -220,8 +241,43 @@ class AcquisitionEngine:
 
     @property
     def dwell_samples(self):
-        """Samples every entry that takes a dwell counts: K * M * N, plus the last offset's periods while the edge search is on."""
-        return (self.K * self.M + (int(self.edge_offsets[-1]) if self.edge_offsets is not None else 0)) * self.fft_size
+        """Samples every entry that takes a dwell counts (gm_acq_dwell_samples): K * M * N, plus the last offset's periods while the
+        edge search is on; up to the end of the last compensated period while the code drift is set."""
+        out = C.c_uint64(0)
+        check(lib().gm_acq_dwell_samples(self._h, C.byref(out)), "gm_acq_dwell_samples")
+        return out.value
+
+    @property
+    def dwell_periods(self):
+        """Code periods one dwell holds: K * M, plus the last offset while the edge search is on"""
+        return self.K * self.M + (int(self.edge_offsets[-1]) if self.edge_offsets is not None else 0)
+
+    # ---- code-drift compensation (gm_acq_set_code_drift): every period read from where it really starts
+    def set_code_drift(self, period_samples):
+        """The true code period in samples (code_period_samples), a scalar or one per Doppler bin, each within 8 of fft_size; None
+        switches the compensation off.  Period p of the dwell then starts at floor(p * T_d + 0.5) in bin d and a dwell is
+        `dwell_samples` long."""
+        if period_samples is None:
+            check(lib().gm_acq_set_code_drift(self._h, 0, None), "gm_acq_set_code_drift")
+            self.code_drift = None
+            return
+        t = np.ascontiguousarray(period_samples, np.float64).reshape(-1)
+        if t.size == 1:
+            t = np.full(self.D, t[0], np.float64)
+        check(lib().gm_acq_set_code_drift(self._h, t.size, _p(t)), "gm_acq_set_code_drift")
+        self.code_drift = t.copy()
+
+    def code_drift_starts(self):
+        """[D][R] uint64: the period starts in use (R = dwell_periods)"""
+        s = np.zeros((self.D, self.dwell_periods), np.uint64)
+        check(lib().gm_acq_code_drift_starts(self._h, _p(s)), "gm_acq_code_drift_starts")
+        return s
+
+    def code_drift_phasors(self, h=0):
+        """[D][M][K] complex64: hypothesis h's phasor words as they sit in device memory (without the secondary row's signs)"""
+        r = np.zeros((self.D, self.M, self.K), np.complex64)
+        check(lib().gm_acq_code_drift_phasors(self._h, int(h), _p(r)), "gm_acq_code_drift_phasors")
+        return r
 
     def edge_metrics(self):
         """(max, argmax, sum), each [P][H][D]: the planes of every hypothesis of the last search"""

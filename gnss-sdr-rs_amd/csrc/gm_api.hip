@@ -321,6 +321,19 @@ struct gm_acq {
         float* d_planes = nullptr;         // strict_sum_order on composite / any-length sizes: [P * H * D][N] power planes
         gm::EdgeLaunch fwd = nullptr;      // stage F of this handle's form
     } edge;
+    // gm_acq_set_code_drift: per-bin true code periods T_d; period p of the dwell starts at floor(p T_d + 0.5) in bin d and stage F
+    // reads it from there (acq_drift.hip) into the spectrum buffer the handle (or its edge search) has anyway.  Re-planned whenever
+    // the edge search changes (R = K M + the last offset).
+    struct Drift {
+        bool on = false;
+        std::vector<double> T;             // [D]
+        uint32_t R = 0;                    // periods of the dwell
+        std::vector<uint64_t> starts;      // [D][R]
+        uint64_t dwell = 0;                // max_d starts[d][R - 1] + N samples
+        uint64_t* d_starts = nullptr;      // [D][R]
+        cf* d_rho = nullptr;               // [max(H, 1)][D][M][K] phasor words continued to the real starts (no secondary signs)
+        gm::DriftLaunch fwd = nullptr;     // stage F of this handle's form
+    } drift;
     float code_rate = CA_RATE;
     std::vector<float> table_freq;
     std::vector<uint8_t> prn_ids, dev_prn_ids;
@@ -409,6 +422,12 @@ static void acq_edge_free(gm_acq::Edge& e) {
     hipFree(e.d_planes);
     e = gm_acq::Edge{};
 }
+static void acq_drift_free(gm_acq::Drift& d) {
+    hipFree(d.d_starts); hipFree(d.d_rho);
+    d = gm_acq::Drift{};
+}
+// samples one dwell holds (gm_acq_dwell_samples): the periods back to back, or up to the end of the last compensated period
+static size_t acq_dwell_samples(const gm_acq* a) { return a->drift.on ? size_t(a->drift.dwell) : acq_dwell_periods(a) * a->N; }
 
 static int acq_set_mask(gm_acq* a, uint64_t mask) {
     std::vector<uint32_t> wl;
@@ -708,6 +727,7 @@ int gm_acq_destroy(gm_acq* a) {
     if (!a) return GM_OK;
     if (a->device >= 0) hipSetDevice(a->device);
     acq_edge_free(a->edge);
+    acq_drift_free(a->drift);
     hipFree(a->d_planes);
     if (a->d_long_code != a->d_code_fft) hipFree(a->d_long_code);
     hipFree(a->d_long_z); hipFree(a->d_long_part);
@@ -1044,6 +1064,35 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
         std::swap(a->d_spectra, ah.d_spectra_alt);
         HIPC(hipStreamWaitEvent(a->stream, ah.ev_f, 0));
         tickets_cleared = false;
+    } else if (a->drift.on) {
+        // (never prepared either) every period from its own start (acq_drift.hip): one kernel per form for K = 1 and K >= 2, with the
+        // edge search's hypotheses or without; the spectra go where they would go without the compensation
+        const gm_acq::Drift& dr = a->drift;
+        gm::DriftArgs c{};
+        c.samples = d_samples; c.fmt = fmt; c.starts = dr.d_starts; c.R = dr.R; c.rho = dr.d_rho; c.K = a->K;
+        c.offsets = edge ? eg.d_offsets : nullptr; c.H = edge ? eg.H : 1u; c.neg = edge ? eg.neg : 0u;
+        c.tables = a->d_tables; c.n_bins = a->D; c.n_int = a->M; c.Q = a->Q; c.N = a->N; c.lim = a->long_lim;
+        c.order = a->lng ? nullptr : a->d_order;
+        const uint32_t items = Dv * a->M;
+        cf* const spectra = edge ? eg.d_spectra : a->d_spectra;
+        if (a->lng) {
+            c.tw_fwd = a->d_tw_fwd; c.out = spectra;
+            dr.fwd(a->stream, c);
+            for (uint32_t i0 = 0; i0 < items; i0 += 65535u)       // (grid rows: at most 65535 per launch)
+                gm::launch_long_fwd_post(a->stream, spectra + size_t(i0) * a->L, items - i0 < 65535u ? items - i0 : 65535u, a->Q, a->Nb);
+        } else if (a->Q == 1) {
+            c.tw_fwd = a->d_tw_mix; c.out = spectra; c.clear_tickets = a->d_split_counter;
+            dr.fwd(a->stream, c);
+            a->dec_deferred = false;
+        } else {
+            cf* const tmp = edge ? eg.d_tmp : a->d_comp_tmp;
+            c.tw_fwd = a->d_tw_mix; c.out = a->comp_post_folded ? spectra : tmp;
+            dr.fwd(a->stream, c);
+            if (!a->comp_post_folded)
+                for (uint32_t i0 = 0; i0 < items; i0 += 65535u)
+                    a->comp->fwd_post(a->stream, tmp + size_t(i0) * a->N, spectra + size_t(i0) * a->N,
+                                      items - i0 < 65535u ? items - i0 : 65535u, 1, a->d_order);
+        }
     } else if (edge) {
         // (never prepared: gm_acq_prepare_dev runs nothing ahead while the edge search is on)
         gm::EdgeArgs c{};
@@ -1147,7 +1196,7 @@ int gm_acq_search_prepared_dev(gm_acq* a, uint64_t token, void* d_metrics) {
     if (!token || !ah.valid || ah.token != token)
         return set_err(GM_ERR_INVALID_ARG, "no such preparation (token stale, consumed, replaced or dropped)");
     if (int rc = ensure_device(a->device)) return rc;
-    if (!acq_fused(a) || a->edge.H) {       // composite and any-length sizes (and an edge search) prepare nothing: the whole search runs now, from the samples named then,
+    if (!acq_fused(a) || a->edge.H || a->drift.on) {       // composite and any-length sizes (and an edge search, and a drift handle) prepare nothing: the whole search runs now, from the samples named then,
         ah.valid = false;                   // behind what `ready_stream` held at the time of gm_acq_prepare_dev
         if (ah.comp_wait) { HIPC(hipStreamWaitEvent(a->stream, ah.ev_in, 0)); ah.comp_wait = false; }
         return acq_search_common(a, ah.samples, ah.fmt, d_metrics, false);
@@ -1167,7 +1216,7 @@ int gm_acq_prepare_dev(gm_acq* a, const void* d_samples, int fmt, void* ready_st
     *token = 0;
     gm_acq::Ahead& ah = a->ahead;
     if (int rc = ensure_device(a->device)) return rc;
-    if (!acq_fused(a) || a->edge.H) {       // composite and any-length sizes, and every size while the edge search is on: nothing is prepared, gm_acq_search_prepared_dev does all of it —
+    if (!acq_fused(a) || a->edge.H || a->drift.on) {       // composite and any-length sizes, and every size while the edge search or the drift compensation is on: nothing is prepared, gm_acq_search_prepared_dev does all of it —
         // but the ordering promise is the same: the samples are complete once the work queued on `ready_stream` so far has run, so
         // the event is recorded NOW and the search waits for it on the handle's stream (the token used to be handed
         // out before `ready_stream` was looked at)
@@ -1244,7 +1293,7 @@ int gm_acq_decide_dev(gm_acq* a, const void* d_metrics, uint32_t n_prn, const ui
     da.best_bin_mode = a->cfg.decision_mode == GM_DECIDE_BEST_BIN ? 1 : 0;
     da.local_tail = local_tail;
     da.results = a->d_results; da.found = a->d_found;
-    if (a->defer_decisions && acq_fused(a) && a->K == 1 && !(a->tm.on && a->tm.this_call) && met == a->last_metrics && a->D <= 64) {
+    if (a->defer_decisions && acq_fused(a) && a->K == 1 && !a->drift.on && !(a->tm.on && a->tm.this_call) && met == a->last_metrics && a->D <= 64) {
         a->dec_args = da;          // runs with the next gm_acq_search_dev's stage F, or at the next flush point
         a->dec_deferred = true;
         return GM_OK;
@@ -1289,9 +1338,10 @@ int gm_acq_search(gm_acq* a, const void* samples, size_t n_samples, int fmt, uin
                   gm_acq_result* results, uint8_t* found) {
     if (!a || !samples || !results || !found) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (fmt < GM_FMT_C32 || fmt > GM_FMT_I8_REAL) return set_err(GM_ERR_INVALID_ARG, "bad sample format");
-    const size_t need = acq_dwell_periods(a) * a->N;
+    const size_t need = acq_dwell_samples(a);
     if (n_samples < need)
-        return set_err(GM_ERR_OUT_OF_RANGE, a->edge.H ? "samples_chunk shorter than (coherent_periods*num_integrations + the last edge offset)*fft_size"
+        return set_err(GM_ERR_OUT_OF_RANGE, a->drift.on ? "samples_chunk shorter than gm_acq_dwell_samples (code drift: up to the end of the last compensated period)"
+                                            : a->edge.H ? "samples_chunk shorter than (coherent_periods*num_integrations + the last edge offset)*fft_size"
                                                       : "samples_chunk shorter than coherent_periods*num_integrations*fft_size");
     if (int rc = ensure_device(a->device)) return rc;
     const size_t bps = fmt == GM_FMT_C32 ? 8 : (fmt == GM_FMT_I8_IQ ? 2 : 1);
@@ -1309,8 +1359,8 @@ int gm_acq_search_ring(gm_acq* a, gm_ring* ring, uint64_t prn_mask, gm_acq_resul
                        uint64_t* local_tail_out) {
     if (!a || !ring || !results || !found) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (a->device != ring->device) return set_err(GM_ERR_INVALID_ARG, "ring lives on another device");
-    const size_t need = acq_dwell_periods(a) * a->N;     // (edge search: K*M + the last offset periods)
-    if (need > ring->size) return set_err(GM_ERR_OUT_OF_RANGE, "ring smaller than coherent_periods*num_integrations*fft_size");
+    const size_t need = acq_dwell_samples(a);     // (edge search: K*M + the last offset periods; drift: to the end of the last period)
+    if (need > ring->size) return set_err(GM_ERR_OUT_OF_RANGE, "ring smaller than the dwell (coherent_periods*num_integrations*fft_size; gm_acq_dwell_samples)");
     if (int rc = ensure_device(ring->device)) return rc;
     ring_refresh_head(ring);
     const uint64_t head = ring->head.load(std::memory_order_acquire);
@@ -1383,6 +1433,11 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
     for (uint32_t p = 0; p < n_prn; ++p)
         if (found[p] && std::find(passes.begin(), passes.end(), off[p]) == passes.end()) passes.push_back(off[p]);
     const size_t bps = a->last_fmt == GM_FMT_C32 ? 8 : (a->last_fmt == GM_FMT_I8_IQ ? 2 : 1);
+    // (not compensated: the code is stripped over K*M contiguous periods from period o* on; a drift dwell of periods shorter than
+    //  fft_size ends before them — checked for the largest offset before any pass runs, so no output is half filled)
+    if (a->drift.on && !passes.empty() &&
+        (uint64_t(*std::max_element(passes.begin(), passes.end())) + periods) * a->N > a->drift.dwell)
+        return set_err(GM_ERR_OUT_OF_RANGE, "the code-drift dwell is shorter than the contiguous periods the fine Doppler reads (it is not compensated)");
     for (const uint32_t o_star : passes) {
     const void* const snap = static_cast<const char*>(a->last_samples) + size_t(o_star) * a->N * bps;
     std::vector<uint32_t> workers, cps, slot(n_prn, 0xFFFFFFFFu);
@@ -1483,6 +1538,8 @@ int gm_acq_coherent_phasors(gm_acq* a, gm_c32* out) {
     return GM_OK;
 }
 
+static int drift_build(const gm_acq* a, uint32_t n_offsets, const uint32_t* offsets, const double* T, gm_acq::Drift& out);
+
 // ---------------------------------------------------------------- edge search (additive entries, ABI 9)
 // the argument rules of gm_acq_edge_dwell_periods / gm_acq_set_edge_search; *neg: bit k set where secondary[k] = -1
 static int edge_check(uint32_t K, uint32_t n, const uint32_t* offsets, const int8_t* secondary, uint32_t* neg) {
@@ -1529,6 +1586,12 @@ int gm_acq_set_edge_search(gm_acq* a, uint32_t n_offsets, const uint32_t* offset
     a->ahead.comp_wait = false;
     HIPC(hipStreamSynchronize(a->stream));
     if (!n_offsets) {
+        if (a->drift.on && a->edge.H) {     // the compensation is planned again for the shorter dwell before the edge search goes
+            gm_acq::Drift nd;
+            if (int rc = drift_build(a, 0, nullptr, a->drift.T.data(), nd)) return rc;
+            acq_drift_free(a->drift);
+            a->drift = std::move(nd);
+        }
         if (a->edge.H) a->last_samples = nullptr;
         acq_edge_free(a->edge);
         return GM_OK;
@@ -1540,7 +1603,13 @@ int gm_acq_set_edge_search(gm_acq* a, uint32_t n_offsets, const uint32_t* offset
     const size_t H = n_offsets, D = a->D, M = a->M, P = a->P, N = a->N, T = a->lng ? size_t(a->L) : N;
     // everything new is allocated before anything old goes: a failure leaves the handle as it was
     void* smp = nullptr;
-    const size_t smp_bytes = (size_t(a->K) * M + e.o_max) * N * 8;
+    size_t smp_bytes = (size_t(a->K) * M + e.o_max) * N * 8;
+    gm_acq::Drift nd;                       // code-drift compensation on: planned again for the new hypotheses
+    if (a->drift.on) {
+        if (int rc = drift_build(a, n_offsets, offsets, a->drift.T.data(), nd)) return rc;
+        // (the larger of the two dwells: the compensation may be switched off later, and the buffer must then hold the plain dwell)
+        if (size_t(nd.dwell) * 8 > smp_bytes) smp_bytes = size_t(nd.dwell) * 8;
+    }
     bool ok = hipMalloc(&e.d_offsets, H * 4) == hipSuccess && hipMalloc(&e.d_spectra, H * D * M * T * 8) == hipSuccess &&
               hipMalloc(&e.d_full, 3 * P * H * D * 4) == hipSuccess && hipMalloc(&e.d_choice, P * D * 4) == hipSuccess;
     if (ok && a->Q > 1 && !a->lng && !a->comp_post_folded) ok = hipMalloc(&e.d_tmp, H * D * M * N * 8) == hipSuccess;
@@ -1553,11 +1622,13 @@ int gm_acq_set_edge_search(gm_acq* a, uint32_t n_offsets, const uint32_t* offset
         (void)hipGetLastError();
         hipFree(smp);
         acq_edge_free(e);
+        acq_drift_free(nd);
         return set_err(GM_ERR_NOMEM, "the edge search's buffers do not fit (gnss_mi355x.h states the formula); the handle is as it was");
     }
     if (smp) { hipFree(a->d_samples); a->d_samples = smp; a->samples_cap = smp_bytes; }
     acq_edge_free(a->edge);
     a->edge = std::move(e);
+    if (nd.on) { acq_drift_free(a->drift); a->drift = std::move(nd); }
     a->last_samples = nullptr;              // (gm_acq_finer_doppler: the next search's snapshot)
     return GM_OK;
 }
@@ -1596,6 +1667,132 @@ int gm_acq_result_offsets(gm_acq* a, const gm_acq_result* results, const uint8_t
         const uint32_t h = choice[size_t(p) * a->D + uint32_t(d)];
         offset_periods[p] = a->edge.offsets[h < a->edge.H ? h : 0];
     }
+    return GM_OK;
+}
+
+// ---------------------------------------------------------------- code-drift compensation (additive entries, ABI 9)
+// the argument rules of gm_acq_code_drift_plan / gm_acq_set_code_drift: every T finite and within 8 samples of fft_size
+static int drift_check(uint32_t N, uint32_t n_bins, const double* T) {
+    if (!N || N % 8) return set_err(GM_ERR_INVALID_ARG, "fft_size must be a positive multiple of 8");
+    if (!n_bins || !T) return set_err(GM_ERR_INVALID_ARG, "null period_samples / n_bins == 0");
+    for (uint32_t d = 0; d < n_bins; ++d)
+        if (!(::fabs(T[d] - double(N)) <= 8.0)) return set_err(GM_ERR_INVALID_ARG, "period_samples must be within 8 samples of fft_size");   // (NaN fails too)
+    return GM_OK;
+}
+// s[d][p] = floor(p T_d + 0.5), p < R, in f64; -> the dwell: max_d s[d][R - 1] + N
+static uint64_t drift_starts(uint32_t N, uint32_t R, uint32_t n_bins, const double* T, uint64_t* starts) {
+    uint64_t last = 0;
+    for (uint32_t d = 0; d < n_bins; ++d)
+        for (uint32_t p = 0; p < R; ++p) {
+            const uint64_t s = uint64_t(::floor(double(p) * T[d] + 0.5));
+            if (starts) starts[size_t(d) * R + p] = s;
+            if (p == R - 1 && s > last) last = s;
+        }
+    return last + N;
+}
+
+int gm_acq_code_drift_plan(uint32_t fft_size, uint32_t n_periods, uint32_t n_bins, const double* period_samples, uint64_t* starts,
+                           uint64_t* dwell_samples) {
+    if (!dwell_samples || !n_periods) return set_err(GM_ERR_INVALID_ARG, "null dwell_samples / n_periods == 0");
+    if (int rc = drift_check(fft_size, n_bins, period_samples)) return rc;
+    *dwell_samples = drift_starts(fft_size, n_periods, n_bins, period_samples, starts);
+    return GM_OK;
+}
+
+// plans the compensation of handle `a` for the periods T under the edge search (n_offsets, offsets) — 0: none — into `out`, device
+// memory included; nothing of the handle changes.  GM_ERR_NOMEM leaves `out` empty.
+static int drift_build(const gm_acq* a, uint32_t n_offsets, const uint32_t* offsets, const double* T, gm_acq::Drift& out) {
+    const size_t D = a->D, M = a->M, K = a->K, H = n_offsets ? n_offsets : 1;
+    gm_acq::Drift dr;
+    dr.on = true;
+    dr.T.assign(T, T + D);
+    dr.R = uint32_t(K * M) + (n_offsets ? offsets[n_offsets - 1] : 0u);
+    dr.starts.resize(D * dr.R);
+    dr.dwell = drift_starts(a->N, dr.R, a->D, dr.T.data(), dr.starts.data());
+    dr.fwd = a->lng ? gm::find_drift_long_fwd_sub(a->lng->nb) : (a->Q == 1 ? gm::find_drift_mix_fft(a->plan->n) : gm::find_drift_comp_fwd_sub(a->comp->nb));
+    if (!dr.fwd) return set_err(GM_ERR_UNSUPPORTED_N, "no code-drift stage F for this handle's base plan");
+    // the phasor words, as gm_acq_create forms the plain fold's: bin d's table phasor continued over the samples from the group's first
+    // period to period k's real start — f64, the phase reduced to one cycle, rounded to f32 (T = fft_size: the plain fold's words)
+    std::vector<gm_c32> rho(H * D * M * K);
+    for (size_t h = 0; h < H; ++h)
+        for (size_t d = 0; d < D; ++d)
+            for (size_t m = 0; m < M; ++m) {
+                const uint64_t* s = &dr.starts[d * dr.R + (n_offsets ? offsets[h] : 0u) + m * K];
+                for (size_t k = 0; k < K; ++k) {
+                    const double cyc = double(a->table_freq[d]) * double(s[k] - s[0]) / double(a->cfg.fs);
+                    const double ang = 2.0 * 3.14159265358979323846 * (cyc - ::floor(cyc));
+                    rho[((h * D + d) * M + m) * K + k] = gm_c32{float(::cos(ang)), float(0.0 - ::sin(ang))};
+                }
+            }
+    const bool ok = hipMalloc(&dr.d_starts, dr.starts.size() * 8) == hipSuccess && hipMalloc(&dr.d_rho, rho.size() * 8) == hipSuccess &&
+                    hipMemcpy(dr.d_starts, dr.starts.data(), dr.starts.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(dr.d_rho, rho.data(), rho.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        acq_drift_free(dr);
+        return set_err(GM_ERR_NOMEM, "the code-drift tables do not fit (gnss_mi355x.h states the formula); the handle is as it was");
+    }
+    out = std::move(dr);
+    return GM_OK;
+}
+
+int gm_acq_set_code_drift(gm_acq* a, uint32_t n_bins, const double* period_samples) {
+    if (!a) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    const bool off = !n_bins || !period_samples;
+    if (!off) {
+        if (n_bins != a->D) return set_err(GM_ERR_INVALID_ARG, "n_bins differs from the handle's");
+        if (int rc = drift_check(a->N, n_bins, period_samples)) return rc;
+    }
+    if (int rc = ensure_device(a->device)) return rc;
+    if (int rc = acq_flush_decision(a)) return rc;
+    a->ahead.valid = false;                 // an outstanding preparation is dropped: its token becomes stale
+    a->ahead.comp_wait = false;
+    HIPC(hipStreamSynchronize(a->stream));
+    if (off) {
+        if (a->drift.on) a->last_samples = nullptr;
+        acq_drift_free(a->drift);
+        return GM_OK;
+    }
+    // everything new is allocated before anything old goes: a failure leaves the handle as it was
+    gm_acq::Drift nd;
+    if (int rc = drift_build(a, a->edge.H, a->edge.H ? a->edge.offsets.data() : nullptr, period_samples, nd)) return rc;
+    void* smp = nullptr;
+    // (the buffer never holds less than the dwell without the compensation: switching it off releases tables only)
+    const size_t plain_bytes = acq_dwell_periods(a) * a->N * 8;
+    const size_t smp_bytes = size_t(nd.dwell) * 8 > plain_bytes ? size_t(nd.dwell) * 8 : plain_bytes;
+    if (smp_bytes > a->samples_cap && hipMalloc(&smp, smp_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        acq_drift_free(nd);
+        return set_err(GM_ERR_NOMEM, "the code-drift dwell's sample buffer does not fit (gnss_mi355x.h states the formula); the handle is as it was");
+    }
+    if (smp) { hipFree(a->d_samples); a->d_samples = smp; a->samples_cap = smp_bytes; }
+    acq_drift_free(a->drift);
+    a->drift = std::move(nd);
+    a->last_samples = nullptr;              // (gm_acq_finer_doppler: the next search's snapshot)
+    return GM_OK;
+}
+
+int gm_acq_dwell_samples(gm_acq* a, uint64_t* out) {
+    if (!a || !out) return set_err(GM_ERR_INVALID_ARG, "null handle/out");
+    *out = acq_dwell_samples(a);
+    return GM_OK;
+}
+
+int gm_acq_code_drift_starts(gm_acq* a, uint64_t* out) {
+    if (!a || !out) return set_err(GM_ERR_INVALID_ARG, "null handle/out");
+    if (!a->drift.on) return set_err(GM_ERR_INVALID_ARG, "the code-drift compensation is off (gm_acq_set_code_drift)");
+    if (int rc = ensure_device(a->device)) return rc;
+    HIPC(hipMemcpy(out, a->drift.d_starts, a->drift.starts.size() * 8, hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+int gm_acq_code_drift_phasors(gm_acq* a, uint32_t h, gm_c32* out) {
+    if (!a || !out) return set_err(GM_ERR_INVALID_ARG, "null handle/out");
+    if (!a->drift.on) return set_err(GM_ERR_INVALID_ARG, "the code-drift compensation is off (gm_acq_set_code_drift)");
+    if (h >= (a->edge.H ? a->edge.H : 1u)) return set_err(GM_ERR_INVALID_ARG, "no such hypothesis");
+    if (int rc = ensure_device(a->device)) return rc;
+    const size_t n = size_t(a->D) * a->M * a->K;
+    HIPC(hipMemcpy(out, a->drift.d_rho + size_t(h) * n, n * 8, hipMemcpyDeviceToHost));
     return GM_OK;
 }
 

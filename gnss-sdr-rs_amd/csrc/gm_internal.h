@@ -66,6 +66,28 @@ EdgeLaunch find_edge_long_fwd_sub(int nb);
 void launch_edge_reduce(hipStream_t, const uint32_t* full, uint32_t* met, uint32_t* choice, const uint32_t* worker_list,
                         uint32_t n_workers, uint32_t P, uint32_t H, uint32_t D);
 
+// Stage F of a handle with code-drift compensation (gm_acq_set_code_drift, acq_drift.hip): period k of group m of hypothesis h in bin
+// d is the N samples from starts[d][offsets[h] + m K + k] on, folded (K >= 2) with rho[h][d][m][k] and the secondary row's signs.
+// offsets == null: one hypothesis at offset 0 (H = 1), i.e. a handle without an edge search; K = 1: no fold, the samples themselves.
+// The other fields mean what they mean in EdgeArgs; the output is laid out [H * n_bins][n_int][.].
+struct DriftArgs {
+    const void* samples; int fmt;          // gm_acq_dwell_samples samples
+    const uint64_t* starts; uint32_t R;    // device [n_bins][R] period starts (64-bit element offsets)
+    const cf* rho; uint32_t K;             // device [H][n_bins][n_int][K] phasor words (gm_acq_code_drift_phasors)
+    const uint32_t* offsets; uint32_t H;
+    uint32_t neg;
+    const cf* tables; const cf* tw_fwd;
+    cf* out;
+    uint32_t n_bins, n_int;
+    uint32_t Q, N, lim;
+    uint32_t* clear_tickets;
+    const uint16_t* order;
+};
+typedef void (*DriftLaunch)(hipStream_t, const DriftArgs&);
+DriftLaunch find_drift_mix_fft(int n);
+DriftLaunch find_drift_comp_fwd_sub(int nb);
+DriftLaunch find_drift_long_fwd_sub(int nb);
+
 // One entry per shipped transform size: launchers for the kernels instantiated on that plan.
 struct DecideArgs;
 struct PlanOps {

@@ -162,6 +162,17 @@ public:
         check(gm_acq_set_edge_search(h_, uint32_t(offsets.size()), offsets.empty() ? nullptr : offsets.data(),
                                      secondary.empty() ? nullptr : secondary.data()), "set_edge_search");
     }
+    // Code-drift compensation (gm_acq_set_code_drift): the true code period in samples per Doppler bin (each within 8 of fft_size); period
+    // p of the dwell then starts at floor(p * T_d + 0.5) in bin d and a dwell is dwell_samples() long.  An empty vector switches it off.
+    void set_code_drift(const std::vector<double>& period_samples) {
+        check(gm_acq_set_code_drift(h_, uint32_t(period_samples.size()), period_samples.empty() ? nullptr : period_samples.data()), "set_code_drift");
+    }
+    // samples one dwell takes now, given coherent_periods, n_integrations, the edge search and the code drift (gm_acq_dwell_samples)
+    uint64_t dwell_samples() {
+        uint64_t n = 0;
+        check(gm_acq_dwell_samples(h_, &n), "dwell_samples");
+        return n;
+    }
     // for every found result of the last search the offset, in periods, of the hypothesis its winning bin chose (others: 0)
     std::vector<uint32_t> edge_offset_periods(const std::vector<std::optional<AcquisitionResult>>& results) {
         std::vector<gm_acq_result> r(results.size());

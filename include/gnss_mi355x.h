@@ -38,6 +38,8 @@ extern "C" {
 #define GM_ABI_VERSION 9   /* 9: gm_acq_cfg.coherent_periods, gm_acq_coherent_phasors; still 9, additive (no struct changed: a caller
                               detects the feature by the symbol): the edge search — gm_acq_edge_dwell_periods,
                               gm_acq_set_edge_search, gm_acq_edge_metrics, gm_acq_edge_choice, gm_acq_result_offsets;
+                              and the code-drift compensation — gm_acq_set_code_drift, gm_acq_code_drift_plan,
+                              gm_acq_dwell_samples, gm_acq_code_drift_starts, gm_acq_code_drift_phasors;
                               8: gm_acq_cfg.any_length, gm_acq_plan_info;
                               7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
@@ -397,6 +399,55 @@ int gm_acq_edge_choice(gm_acq *a, uint32_t *hypothesis);
  * last search; entries of not-found workers are left untouched.  n_prn <= the handle's workers. */
 int gm_acq_result_offsets(gm_acq *a, const gm_acq_result *results, const uint8_t *found, uint32_t n_prn,
                           uint32_t *offset_periods);
+/* ---- Code-drift compensation: every code period of the dwell read from where it really starts.  All of the above counts period p of
+ * a dwell from sample p * fft_size.  The true code period T is rarely fft_size samples: at fs = 16.3676 MHz a C/A period is 16367.6
+ * samples against fft_size = 16368 (0.4 samples per period), and a Doppler of f_d shortens every period by 1 / (1 + f_d / f_carrier)
+ * (3.2 chips per second at 5 kHz on L1).  Over a long dwell the code slides against the replica, the peak smears and moves.
+ *   period_samples[d] : the true code period in samples as Doppler bin d sees it, f64, |T_d - fft_size| <= 8 (the nearest multiple
+ *                       of 8 is within 4 of any period); n_bins must be the handle's.  n_bins = 0 or NULL: off, bit for bit.
+ * Let R = K*M + offsets[H-1] be the dwell's periods (K = coherent_periods, 0 counting as 1; no edge search: R = K*M).  On the host,
+ * in f64,
+ *     s[d][p] = (uint64) floor(p * T_d + 0.5),   p = 0 .. R-1,
+ * and period k of group m of hypothesis h in bin d is the fft_size samples from s[d][o_h + m K + k] on — the real samples at another
+ * place: no circular shift, no phase ramp.  A dwell is max_d s[d][R-1] + fft_size samples (gm_acq_dwell_samples), fewer or more than
+ * without the compensation, for every entry that takes one: gm_acq_search*, gm_acq_search_dev, gm_acq_prepare_dev, gm_acq_search_ring
+ * (local_tail = head - that).
+ * K >= 2: the fold's phasors run to where the period really starts,
+ *     rho[h][d][m][k] = exp(-j 2 pi f_d (s[d][o_h+mK+k] - s[d][o_h+mK]) / fs),   f_d: the bin's table_freq,
+ * formed as gm_acq_coherent_phasors' words are (f64, the phase reduced to one cycle, rounded to f32), the secondary row's sign applied
+ * to them as without the compensation, and the fold's arithmetic is unchanged (k ascending, every product and sum rounded on its own).
+ * K <= 1: no fold and no product — the words are those of a plain search of the gathered samples x'[m N + n] = x[s[d][m] + n].
+ * With every T_d = fft_size the starts, the dwell, the phasor words and every metric word are those of the handle without it.
+ * It works on every handle (every form gm_acq_plan_info reports, every sample format, code family, decision mode, strict_sum_order,
+ * reference_products where the handle accepts it, the edge search on or off); gm_acq_set_edge_search and gm_acq_set_code_drift may
+ * be called in either order, each plans the dwell again.  Stage C, the reduction over the hypotheses, the decision, the all-gather
+ * entries and every [D][M][.] buffer stay as they are (acq_drift.hip holds the three stage-F kernels).
+ * Results: s[d][0] = 0 and |s[d][o] - o T_d| <= 0.5, so code_phase_samples is the code phase at the dwell's first sample to within
+ * half a sample; sample_global_index keeps its definition.  gm_acq_coherent_phasors is unchanged.
+ * gm_acq_finer_doppler is unchanged and NOT compensated: it strips the code over contiguous samples (K*M periods of fft_size from
+ * the winning offset on); GM_ERR_OUT_OF_RANGE where the compensated dwell ends before them.
+ * While it is on gm_acq_prepare_dev behaves as on composite sizes (a token, the ordering promise, the whole search at
+ * gm_acq_search_prepared_dev) and gm_acq_set_deferred_decision is accepted and decides at once.
+ * Device memory while it is on, beside the handle's own and the edge search's:
+ *     8 D R  (the starts)  +  8 H D M K  (the phasor words; H = 1 without an edge search)
+ *     + 8 (dwell - what the internal sample buffer holds already)  when that buffer has to grow (it never holds less than the dwell
+ *       without the compensation, so switching the compensation off needs no memory).
+ * Everything new is allocated before anything old is released: GM_ERR_NOMEM leaves the handle (and an earlier compensation) as it
+ * was, GM_ERR_INVALID_ARG (a T_d off by more than 8 or not a number, a wrong n_bins) as well.  The setter runs a pending deferred
+ * decision and drops an outstanding preparation.  A handle on which it was never called, or was switched off, launches exactly the
+ * kernels it launched before.  (ABI 9, additive: a caller detects the feature by the symbol) */
+int gm_acq_set_code_drift(gm_acq *a, uint32_t n_bins, const double *period_samples);
+/* host only, no device: checks the arguments as gm_acq_set_code_drift does (fft_size a multiple of 8); starts [n_bins][n_periods]
+ * (may be NULL) and *dwell_samples = max_d starts[d][n_periods-1] + fft_size */
+int gm_acq_code_drift_plan(uint32_t fft_size, uint32_t n_periods, uint32_t n_bins, const double *period_samples,
+                           uint64_t *starts, uint64_t *dwell_samples);
+/* Samples one dwell of this handle takes now, given coherent_periods, n_integrations, the edge search and the code drift. */
+int gm_acq_dwell_samples(gm_acq *a, uint64_t *out);
+/* The period starts in use: [n_bins][R].  GM_ERR_INVALID_ARG while the compensation is off. */
+int gm_acq_code_drift_starts(gm_acq *a, uint64_t *out);
+/* Hypothesis h's phasor words [n_bins][n_integrations][K] as they sit in device memory (h = 0 without an edge search; the secondary
+ * row's signs are applied on the way into the fold and do not show here; (1, 0) throughout at K <= 1, where they are not used). */
+int gm_acq_code_drift_phasors(gm_acq *a, uint32_t h, gm_c32 *out);
 /* Kernel timing of the last gm_acq_search*_dev call, measured with HIP events on the handle's
  * stream: ms_mix_fft (stage F), ms_corr (stage C, the dominant kernel), ms_decide.  Enable first: on = 1 times every
  * search, on = k > 1 every k-th (an event record costs about 2 us of stream time; four per timed search), 0 disables. */

@@ -90,6 +90,14 @@ extern "C" {
     pub fn gm_acq_edge_choice(a: *mut GmAcq, hypothesis: *mut u32) -> c_int;
     pub fn gm_acq_result_offsets(a: *mut GmAcq, results: *const GmAcqResult, found: *const u8, n_prn: u32,
                                  offset_periods: *mut u32) -> c_int;
+    // code-drift compensation (additive entries, ABI stays 9): per-bin true code periods in samples; period p of the dwell starts at
+    // floor(p * T_d + 0.5) and a dwell is gm_acq_dwell_samples long
+    pub fn gm_acq_set_code_drift(a: *mut GmAcq, n_bins: u32, period_samples: *const f64) -> c_int;
+    pub fn gm_acq_code_drift_plan(fft_size: u32, n_periods: u32, n_bins: u32, period_samples: *const f64, starts: *mut u64,
+                                  dwell_samples: *mut u64) -> c_int;
+    pub fn gm_acq_dwell_samples(a: *mut GmAcq, out: *mut u64) -> c_int;
+    pub fn gm_acq_code_drift_starts(a: *mut GmAcq, out: *mut u64) -> c_int;
+    pub fn gm_acq_code_drift_phasors(a: *mut GmAcq, h: u32, out: *mut Complex32) -> c_int;
     // do_acquisition.rs:302-313 + :158-226  (par_iter over workers / search_satellite)
     pub fn gm_acq_search_c32(a: *mut GmAcq, samples: *const Complex32, n: usize, local_tail: u64,
                              prn_mask: u64, results: *mut GmAcqResult, found: *mut u8) -> c_int;

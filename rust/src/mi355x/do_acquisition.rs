@@ -133,6 +133,15 @@ impl AcquisitionEngine {
         if unsafe { gm_acq_set_edge_search(self.h, offsets.len() as u32, off, sec) } != 0 { return Err(AcqError); }
         Ok(())
     }
+    /// Not in the reference: read every code period of the dwell from where it really starts.  `period_samples`: the true code period
+    /// in samples per Doppler bin (each within 8 of fft_size); empty switches the compensation off.  -> the samples a dwell takes now.
+    pub fn set_code_drift(&mut self, period_samples: &[f64]) -> Result<u64, AcqError> {
+        let t = if period_samples.is_empty() { std::ptr::null() } else { period_samples.as_ptr() };
+        if unsafe { gm_acq_set_code_drift(self.h, period_samples.len() as u32, t) } != 0 { return Err(AcqError); }
+        let mut n = 0u64;
+        if unsafe { gm_acq_dwell_samples(self.h, &mut n) } != 0 { return Err(AcqError); }
+        Ok(n)
+    }
     /// the body of `workers.par_iter_mut().enumerate().filter_map(..search_satellite..)` (:302-313)
     pub fn search(&mut self, chunk: &[Complex32], local_tail: usize, mask: u32) -> Vec<AcquisitionResult> {
         let mut raw = vec![GmAcqResult::default(); self.n_prn];
