@@ -371,8 +371,7 @@ template <class PL, uint32_t Q> struct CompLaunch {
     static void fold_post(hipStream_t st, const cf* comb_in, const uint16_t* order, cf* comb2, uint32_t n_codes) {
         hipLaunchKernelGGL((comp_fold_post_kernel<PL, Q>), dim3((PL::N + 255) / 256, n_codes * Q), dim3(256), 0, st, comb_in, order, comb2);
     }
-    static constexpr CompOps ops() { return CompOps{PL::N, int(Q), &fwd_sub, &fwd_post, &corr, &fill_twn, &comb, &fill_order, &relayout, &fold_post,
-                                                     &launch_comp_fwd_sub_coh<PL>}; }
+    static constexpr CompOps ops() { return CompOps{PL::N, int(Q), &fwd_sub, &fwd_post, &corr, &fill_twn, &comb, &fill_order, &relayout, &fold_post}; }
 };
 }  // namespace
 

@@ -201,42 +201,6 @@ __device__ __forceinline__ cf load_sample(const void* samples, int fmt, size_t i
     return cf_make(float(reinterpret_cast<const int8_t*>(samples)[idx]), 0.0f);
 }
 
-// Stage F's pass-0 sample loaders: element n of the M-th input sequence of a dwell made of periods of N samples.
-// PlainLoad: period m itself (today's search).
-struct PlainLoad {
-    const void* samples; int fmt;
-    __device__ __forceinline__ void stage(uint32_t, int) const {}
-    __device__ __forceinline__ cf operator()(size_t m, size_t N, size_t n) const { return load_sample(samples, fmt, m * N + n); }
-};
-
-// Coherent fold (gm_acq_cfg.coherent_periods = K): group m of K consecutive periods, y[n] = sum_k rho[k] x[(m K + k) N + n] with
-// rho[k] the bin's phasor words (gm_acq_coherent_phasors).  k ascends, and every product and every sum is rounded on its own as
-// num-complex forms them (the sources build with -ffp-contract=off: no fma here), so the host restates the fold exactly.
-// 64-bit element offsets: K M N samples of 8 bytes can pass 4 GiB.
-__device__ __forceinline__ cf fold_sample(const void* samples, int fmt, size_t idx, size_t stride, uint32_t K, const cf* rho) {
-    cf s = load_sample(samples, fmt, idx), r = rho[0];
-    cf acc = cf_make(r.x * s.x - r.y * s.y, r.x * s.y + r.y * s.x);
-    for (uint32_t k = 1; k < K; ++k) {
-        s = load_sample(samples, fmt, idx + size_t(k) * stride);
-        r = rho[k];
-        acc = cf_make(acc.x + (r.x * s.x - r.y * s.y), acc.y + (r.x * s.y + r.y * s.x));
-    }
-    return acc;
-}
-// rho_g: [n_bins][K] phasor words in HBM; rho_s: GM_COHERENT_MAX words of the workgroup's LDS.  stage(d, tid) copies bin d's K words
-// once per workgroup (uniform over it) and orders them before the first pass-0 load by a barrier of its own.
-struct CohLoad {
-    const void* samples; int fmt;
-    const cf* rho_g; uint32_t K; cf* rho_s;
-    __device__ __forceinline__ void stage(uint32_t d, int tid) const {
-        if (uint32_t(tid) < K) rho_s[tid] = rho_g[size_t(d) * K + tid];
-        __syncthreads();
-    }
-    __device__ __forceinline__ cf operator()(size_t m, size_t N, size_t n) const {
-        return fold_sample(samples, fmt, m * K * N + n, N, K, rho_s);
-    }
-};
-
 // (value, index) reduction: larger value wins, equal values -> lower index (first strict maximum)
 __device__ __forceinline__ void take_better(float& bv, uint32_t& bi, float v, uint32_t i) {
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }

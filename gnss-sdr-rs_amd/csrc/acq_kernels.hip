@@ -992,8 +992,7 @@ template <class PL> struct Launch {
                        CorrLayout<CP>::RELAYOUT ? 1 : 0,
                        &fill_tw, &fill_order, &mix_fft, &corr, &code_fft, &pair_codes, &fft_batch,
                        POW2 ? &fine_cols : nullptr, POW2 ? &fine_rows : nullptr, FineRows<PL>::RT,
-                       POW2 ? &big_cols : nullptr, POW2 ? &big_rows : nullptr, MP::TW_TOTAL, &fill_tw_mix, corr_tw_total(), &fill_tw_corr,
-                       &launch_mix_fft_coh<PL>};
+                       POW2 ? &big_cols : nullptr, POW2 ? &big_rows : nullptr, MP::TW_TOTAL, &fill_tw_mix, corr_tw_total(), &fill_tw_corr};
     }
 };
 

@@ -232,7 +232,7 @@ template <class PL> struct LongLaunch {
         hipLaunchKernelGGL(long_corr_inv_kernel<PL>, dim3(n_slab * Q), dim3(PL::T), 0, st, Z, tw_inv, pmax, parg, psum, planes,
                            worker_list, n_workers, n_bins, item0, Q, N, n_int, scale);
     }
-    static constexpr LongOps ops() { return LongOps{PL::N, &fwd_sub, &corr_inv, &launch_long_fwd_sub_coh<PL>}; }
+    static constexpr LongOps ops() { return LongOps{PL::N, &fwd_sub, &corr_inv}; }
 };
 }  // namespace
 

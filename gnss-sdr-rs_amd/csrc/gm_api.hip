@@ -304,10 +304,11 @@ struct gm_acq {
     uint32_t N = 0, D = 0, M = 0, P = 0;
     uint32_t K = 1;                        // gm_acq_cfg.coherent_periods (0 -> 1): a dwell is K * M periods, M groups of K folded coherently
     cf* d_rho = nullptr;                   // [D][K] the fold's phasor words (gm_acq_coherent_phasors)
+    gm::StageFLaunch coh_fwd = nullptr;    // K >= 2: stage F of this handle's form (acq_stage_f_variants.h)
     // gm_acq_set_edge_search (K >= 2): H hypotheses about where the groups start, each with the secondary row's signs in the fold
-    // (acq_edge.hip).  Stage F writes the spectra [H * D][M][.], stage C runs with H * D bins into `d_full`, the reduction picks a
-    // hypothesis per (worker, bin) cell into the ordinary metrics block and `d_choice`.  All buffers are the edge search's own: the
-    // handle's are untouched, so switching it off (H = 0) is the handle as it was.
+    // (EdgeLoad, acq_stage_f_variants.h).  Stage F writes the spectra [H * D][M][.], stage C runs with H * D bins into `d_full`, the
+    // reduction picks a hypothesis per (worker, bin) cell into the ordinary metrics block and `d_choice`.  All buffers are the edge
+    // search's own: the handle's are untouched, so switching it off (H = 0) is the handle as it was.
     struct Edge {
         uint32_t H = 0;                    // 0: off
         std::vector<uint32_t> offsets;     // [H] ascending period offsets
@@ -319,11 +320,11 @@ struct gm_acq {
         uint32_t* d_choice = nullptr;      // [P][D] the hypothesis each cell of the last search chose (gm_acq_edge_choice)
         float* d_long_part = nullptr;      // any-length sizes: [3][P * H * D][Q] partials
         float* d_planes = nullptr;         // strict_sum_order on composite / any-length sizes: [P * H * D][N] power planes
-        gm::EdgeLaunch fwd = nullptr;      // stage F of this handle's form
+        gm::StageFLaunch fwd = nullptr;    // stage F of this handle's form
     } edge;
     // gm_acq_set_code_drift: per-bin true code periods T_d; period p of the dwell starts at floor(p T_d + 0.5) in bin d and stage F
-    // reads it from there (acq_drift.hip) into the spectrum buffer the handle (or its edge search) has anyway.  Re-planned whenever
-    // the edge search changes (R = K M + the last offset).
+    // reads it from there (DriftLoad, acq_stage_f_variants.h) into the spectrum buffer the handle (or its edge search) has anyway.
+    // Re-planned whenever the edge search changes (R = K M + the last offset).
     struct Drift {
         bool on = false;
         std::vector<double> T;             // [D]
@@ -332,7 +333,7 @@ struct gm_acq {
         uint64_t dwell = 0;                // max_d starts[d][R - 1] + N samples
         uint64_t* d_starts = nullptr;      // [D][R]
         cf* d_rho = nullptr;               // [max(H, 1)][D][M][K] phasor words continued to the real starts (no secondary signs)
-        gm::DriftLaunch fwd = nullptr;     // stage F of this handle's form
+        gm::StageFLaunch fwd = nullptr;    // stage F of this handle's form
     } drift;
     float code_rate = CA_RATE;
     std::vector<float> table_freq;
@@ -415,6 +416,11 @@ struct gm_acq {
 // the fused single-LDS-buffer kernels (acq_kernels.hip): neither a composite nor an any-length size
 static bool acq_fused(const gm_acq* a) { return a->Q == 1 && !a->lng; }
 
+// stage F of one of the three variant families (Load: gm::CohLoad, gm::EdgeLoad, gm::DriftLoad) for this handle's form; null: no such plan
+template <class Load> static gm::StageFLaunch acq_find_stage_f(const gm_acq* a) {
+    return a->lng ? gm::find_stage_f<Load>(gm::STAGE_F_LONG, a->lng->nb)
+                  : (a->Q == 1 ? gm::find_stage_f<Load>(gm::STAGE_F_MIX, a->plan->n) : gm::find_stage_f<Load>(gm::STAGE_F_COMP, a->comp->nb));
+}
 // code periods one dwell holds: K * M, plus the last offset while the edge search is on
 static size_t acq_dwell_periods(const gm_acq* a) { return size_t(a->K) * a->M + (a->edge.H ? a->edge.o_max : 0u); }
 static void acq_edge_free(gm_acq::Edge& e) {
@@ -848,6 +854,8 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     const size_t N = a->N, D = a->D, M = a->M, P = a->P, K = a->K;
     int rc = GM_OK;
     auto fail = [&](int code) { gm_acq_destroy(a); return code; };
+    if (K > 1 && !(a->coh_fwd = acq_find_stage_f<gm::CohLoad>(a)))
+        return fail(set_err(GM_ERR_UNSUPPORTED_N, "no coherent stage F for this handle's base plan"));
 
     // Doppler tables (do_acquisition.rs:252-262) — host glibc cosf/sinf like the reference
     std::vector<gm_c32> tables(D * N);
@@ -1028,13 +1036,40 @@ int gm_acq_set_prn_mask(gm_acq* a, uint64_t mask) {
     return acq_set_mask(a, mask);
 }
 
-// stage F's arguments on a coherent handle (gm_acq_cfg.coherent_periods = K >= 2)
-static gm::CohArgs acq_coh_args(const gm_acq* a, const void* d_samples, int fmt, const cf* tw_fwd, cf* out, uint32_t* clear_tickets) {
-    gm::CohArgs c{};
-    c.samples = d_samples; c.fmt = fmt; c.rho = a->d_rho; c.K = a->K; c.tables = a->d_tables; c.tw_fwd = tw_fwd; c.out = out;
-    c.n_bins = a->D; c.n_int = a->M; c.Q = a->Q; c.N = a->N; c.lim = a->long_lim; c.clear_tickets = clear_tickets;
+// Stage F of a coherent handle (K >= 2), of its edge search and of a handle with code-drift compensation (K = 1 included), on stream
+// `st` into `spectra` (acq_stage_f_variants.h): the family's kernel of the handle's form — with the drift compensation every period
+// from its own start, with the edge search H hypotheses, [H * D][M][.] — and then the post pass of the form in chunks of at most 65535
+// items (grid rows).  clear_tickets: the tail split's tickets for the in-LDS form to clear on its way, or null.
+static void acq_stage_f_variant(const gm_acq* a, hipStream_t st, const void* d_samples, int fmt, cf* spectra, uint32_t* clear_tickets) {
+    const gm_acq::Edge& eg = a->edge;
+    const gm_acq::Drift& dr = a->drift;
+    const bool edge = eg.H > 0;
+    gm::StageFArgs c{};
+    c.samples = d_samples; c.fmt = fmt; c.K = a->K; c.rho = a->d_rho; c.H = 1;
+    if (dr.on) { c.starts = dr.d_starts; c.R = dr.R; c.rho = dr.d_rho; }
+    if (edge) { c.offsets = eg.d_offsets; c.H = eg.H; c.neg = eg.neg; }
+    c.tables = a->d_tables; c.n_bins = a->D; c.n_int = a->M; c.Q = a->Q; c.N = a->N; c.lim = a->long_lim;
     c.order = a->lng ? nullptr : a->d_order;
-    return c;
+    c.clear_tickets = clear_tickets;
+    const gm::StageFLaunch fwd = dr.on ? dr.fwd : (edge ? eg.fwd : a->coh_fwd);
+    const uint32_t items = c.H * a->D * a->M;
+    if (a->lng) {
+        c.tw_fwd = a->d_tw_fwd; c.out = spectra;
+        fwd(st, c);
+        for (uint32_t i0 = 0; i0 < items; i0 += 65535u)
+            gm::launch_long_fwd_post(st, spectra + size_t(i0) * a->L, items - i0 < 65535u ? items - i0 : 65535u, a->Q, a->Nb);
+    } else if (a->Q == 1) {
+        c.tw_fwd = a->d_tw_mix; c.out = spectra;
+        fwd(st, c);
+    } else {
+        // the sub-transforms ARE what the correlation kernel reads (comp_post_folded), else forward step 2 follows
+        cf* const tmp = edge ? eg.d_tmp : a->d_comp_tmp;
+        c.tw_fwd = a->d_tw_mix; c.out = a->comp_post_folded ? spectra : tmp;
+        fwd(st, c);
+        if (!a->comp_post_folded)
+            for (uint32_t i0 = 0; i0 < items; i0 += 65535u)
+                a->comp->fwd_post(st, tmp + size_t(i0) * a->N, spectra + size_t(i0) * a->N, items - i0 < 65535u ? items - i0 : 65535u, 1, a->d_order);
+    }
 }
 
 // stage F (unless `prepared`: then the spectra wait in the second buffer) + stage C of one dwell on the handle's stream
@@ -1064,80 +1099,22 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
         std::swap(a->d_spectra, ah.d_spectra_alt);
         HIPC(hipStreamWaitEvent(a->stream, ah.ev_f, 0));
         tickets_cleared = false;
-    } else if (a->drift.on) {
-        // (never prepared either) every period from its own start (acq_drift.hip): one kernel per form for K = 1 and K >= 2, with the
-        // edge search's hypotheses or without; the spectra go where they would go without the compensation
-        const gm_acq::Drift& dr = a->drift;
-        gm::DriftArgs c{};
-        c.samples = d_samples; c.fmt = fmt; c.starts = dr.d_starts; c.R = dr.R; c.rho = dr.d_rho; c.K = a->K;
-        c.offsets = edge ? eg.d_offsets : nullptr; c.H = edge ? eg.H : 1u; c.neg = edge ? eg.neg : 0u;
-        c.tables = a->d_tables; c.n_bins = a->D; c.n_int = a->M; c.Q = a->Q; c.N = a->N; c.lim = a->long_lim;
-        c.order = a->lng ? nullptr : a->d_order;
-        const uint32_t items = Dv * a->M;
-        cf* const spectra = edge ? eg.d_spectra : a->d_spectra;
-        if (a->lng) {
-            c.tw_fwd = a->d_tw_fwd; c.out = spectra;
-            dr.fwd(a->stream, c);
-            for (uint32_t i0 = 0; i0 < items; i0 += 65535u)       // (grid rows: at most 65535 per launch)
-                gm::launch_long_fwd_post(a->stream, spectra + size_t(i0) * a->L, items - i0 < 65535u ? items - i0 : 65535u, a->Q, a->Nb);
-        } else if (a->Q == 1) {
-            c.tw_fwd = a->d_tw_mix; c.out = spectra; c.clear_tickets = a->d_split_counter;
-            dr.fwd(a->stream, c);
-            a->dec_deferred = false;
-        } else {
-            cf* const tmp = edge ? eg.d_tmp : a->d_comp_tmp;
-            c.tw_fwd = a->d_tw_mix; c.out = a->comp_post_folded ? spectra : tmp;
-            dr.fwd(a->stream, c);
-            if (!a->comp_post_folded)
-                for (uint32_t i0 = 0; i0 < items; i0 += 65535u)
-                    a->comp->fwd_post(a->stream, tmp + size_t(i0) * a->N, spectra + size_t(i0) * a->N,
-                                      items - i0 < 65535u ? items - i0 : 65535u, 1, a->d_order);
-        }
-    } else if (edge) {
-        // (never prepared: gm_acq_prepare_dev runs nothing ahead while the edge search is on)
-        gm::EdgeArgs c{};
-        c.samples = d_samples; c.fmt = fmt; c.rho = a->d_rho; c.K = a->K; c.offsets = eg.d_offsets; c.H = eg.H; c.neg = eg.neg;
-        c.tables = a->d_tables; c.n_bins = a->D; c.n_int = a->M; c.Q = a->Q; c.N = a->N; c.lim = a->long_lim;
-        c.order = a->lng ? nullptr : a->d_order;
-        const uint32_t items = Dv * a->M;
-        cf* const spectra = eg.d_spectra;
-        if (a->lng) {
-            c.tw_fwd = a->d_tw_fwd; c.out = spectra;
-            eg.fwd(a->stream, c);
-            for (uint32_t i0 = 0; i0 < items; i0 += 65535u)       // (grid rows: at most 65535 per launch)
-                gm::launch_long_fwd_post(a->stream, spectra + size_t(i0) * a->L, items - i0 < 65535u ? items - i0 : 65535u, a->Q, a->Nb);
-        } else if (a->Q == 1) {
-            c.tw_fwd = a->d_tw_mix; c.out = spectra; c.clear_tickets = a->d_split_counter;
-            eg.fwd(a->stream, c);
-            a->dec_deferred = false;
-        } else {
-            c.tw_fwd = a->d_tw_mix; c.out = a->comp_post_folded ? spectra : eg.d_tmp;
-            eg.fwd(a->stream, c);
-            if (!a->comp_post_folded)
-                for (uint32_t i0 = 0; i0 < items; i0 += 65535u)
-                    a->comp->fwd_post(a->stream, eg.d_tmp + size_t(i0) * a->N, spectra + size_t(i0) * a->N,
-                                      items - i0 < 65535u ? items - i0 : 65535u, 1, a->d_order);
-        }
+    } else if (a->drift.on || edge || a->K > 1) {
+        // (with the drift compensation or the edge search on, never prepared: gm_acq_prepare_dev runs nothing ahead then; none of
+        // these handles defers its decision)
+        acq_stage_f_variant(a, a->stream, d_samples, fmt, edge ? eg.d_spectra : a->d_spectra, a->d_split_counter);
+        a->dec_deferred = false;
     } else if (a->lng) {
-        if (a->K > 1)
-            a->lng->fwd_sub_coh(a->stream, acq_coh_args(a, d_samples, fmt, a->d_tw_fwd, a->d_spectra, nullptr));
-        else
-            a->lng->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_fwd, a->d_spectra, a->D * a->M, a->Q, a->N, a->long_lim, a->M);
+        a->lng->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_fwd, a->d_spectra, a->D * a->M, a->Q, a->N, a->long_lim, a->M);
         gm::launch_long_fwd_post(a->stream, a->d_spectra, a->D * a->M, a->Q, a->Nb);
     } else if (a->Q == 1) {
-        if (a->K > 1)       // (a coherent handle never defers its decision: dec_deferred is false here)
-            a->plan->mix_fft_coh(a->stream, acq_coh_args(a, d_samples, fmt, a->d_tw_mix, a->d_spectra, a->d_split_counter));
-        else
-            a->plan->mix_fft(a->stream, d_samples, fmt, a->d_tables, a->d_tw_mix, a->d_spectra, int(a->D), int(a->M), a->d_split_counter, a->d_order,
-                             a->dec_deferred ? &a->dec_args : nullptr);
+        a->plan->mix_fft(a->stream, d_samples, fmt, a->d_tables, a->d_tw_mix, a->d_spectra, int(a->D), int(a->M), a->d_split_counter, a->d_order,
+                         a->dec_deferred ? &a->dec_args : nullptr);
         a->dec_deferred = false;
     } else {
         // the sub-transforms ARE what the correlation kernel reads (comp_post_folded), else forward step 2 follows
         cf* sub = a->comp_post_folded ? a->d_spectra : a->d_comp_tmp;
-        if (a->K > 1)
-            a->comp->fwd_sub_coh(a->stream, acq_coh_args(a, d_samples, fmt, a->d_tw_mix, sub, nullptr));
-        else
-            a->comp->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_mix, sub, a->D * a->M, a->M, a->d_order);
+        a->comp->fwd_sub(a->stream, d_samples, fmt, a->d_tables, nullptr, a->d_tw_mix, sub, a->D * a->M, a->M, a->d_order);
         if (!a->comp_post_folded) {
             a->comp->fwd_post(a->stream, a->d_comp_tmp, a->d_spectra, a->D * a->M, 1, a->d_order);
         }
@@ -1258,7 +1235,7 @@ int gm_acq_prepare_dev(gm_acq* a, const void* d_samples, int fmt, void* ready_st
     }
     ah.valid = false;
     if (a->K > 1)
-        a->plan->mix_fft_coh(ah.side, acq_coh_args(a, d_samples, fmt, a->d_tw_mix, ah.d_spectra_alt, nullptr));
+        acq_stage_f_variant(a, ah.side, d_samples, fmt, ah.d_spectra_alt, nullptr);
     else
         a->plan->mix_fft(ah.side, d_samples, fmt, a->d_tables, a->d_tw_mix, ah.d_spectra_alt, int(a->D), int(a->M), nullptr, a->d_order, nullptr);
     HIPC(hipEventRecord(ah.ev_f, ah.side));
@@ -1598,7 +1575,7 @@ int gm_acq_set_edge_search(gm_acq* a, uint32_t n_offsets, const uint32_t* offset
     }
     gm_acq::Edge e;
     e.H = n_offsets; e.offsets.assign(offsets, offsets + n_offsets); e.o_max = offsets[n_offsets - 1]; e.neg = neg;
-    e.fwd = a->lng ? gm::find_edge_long_fwd_sub(a->lng->nb) : (a->Q == 1 ? gm::find_edge_mix_fft(a->plan->n) : gm::find_edge_comp_fwd_sub(a->comp->nb));
+    e.fwd = acq_find_stage_f<gm::EdgeLoad>(a);
     if (!e.fwd) return set_err(GM_ERR_UNSUPPORTED_N, "no edge-search stage F for this handle's base plan");
     const size_t H = n_offsets, D = a->D, M = a->M, P = a->P, N = a->N, T = a->lng ? size_t(a->L) : N;
     // everything new is allocated before anything old goes: a failure leaves the handle as it was
@@ -1709,7 +1686,7 @@ static int drift_build(const gm_acq* a, uint32_t n_offsets, const uint32_t* offs
     dr.R = uint32_t(K * M) + (n_offsets ? offsets[n_offsets - 1] : 0u);
     dr.starts.resize(D * dr.R);
     dr.dwell = drift_starts(a->N, dr.R, a->D, dr.T.data(), dr.starts.data());
-    dr.fwd = a->lng ? gm::find_drift_long_fwd_sub(a->lng->nb) : (a->Q == 1 ? gm::find_drift_mix_fft(a->plan->n) : gm::find_drift_comp_fwd_sub(a->comp->nb));
+    dr.fwd = acq_find_stage_f<gm::DriftLoad>(a);
     if (!dr.fwd) return set_err(GM_ERR_UNSUPPORTED_N, "no code-drift stage F for this handle's base plan");
     // the phasor words, as gm_acq_create forms the plain fold's: bin d's table phasor continued over the samples from the group's first
     // period to period k's real start — f64, the phase reduced to one cycle, rounded to f32 (T = fft_size: the plain fold's words)

@@ -26,67 +26,36 @@ struct FineArgs {
 // gm_acq_cfg.coherent_periods: the most code periods one coherent group folds (gm_acq_create refuses more; stage F's LDS holds the phasors)
 constexpr int GM_COHERENT_MAX = 32;
 
-// Stage F of a coherent handle (acq_coherent.hip): the M groups of K consecutive periods of the dwell, each folded with its Doppler
-// bin's phasor words before the carrier mix (CohLoad, acq_device.h).  One argument block for the three forms.
-struct CohArgs {
-    const void* samples; int fmt;          // K * M * N samples
-    const cf* rho; uint32_t K;             // [n_bins][K] phasor words (gm_acq_coherent_phasors)
+// Stage F of a coherent handle (gm_acq_cfg.coherent_periods = K >= 2), of its edge search (gm_acq_set_edge_search) and of a handle with
+// code-drift compensation (gm_acq_set_code_drift): one argument block for the three families and the three forms
+// (acq_stage_f_variants.h).  The dwell's M groups of K periods are folded with phasor words before the carrier mix; the output is laid
+// out [H * n_bins][n_int][.], i.e. what stage C takes with H * n_bins bins.
+//   coherent: group m is periods m K .. m K + K - 1 of N samples, rho is [n_bins][K] (gm_acq_coherent_phasors); H = 1, the rest null / 0
+//   edge:     H hypotheses, each the coherent stage F on the samples from period offsets[h] on, the secondary row's signs in the fold
+//   drift:    period k of group m of hypothesis h in bin d is the N samples from starts[d][offsets[h] + m K + k] on, rho is
+//             [H][n_bins][n_int][K] (gm_acq_code_drift_phasors); offsets == null: one hypothesis at offset 0 (H = 1); K = 1: no fold
+struct StageFArgs {
+    const void* samples; int fmt;          // the dwell (coherent: K * M * N samples; edge: + offsets[H - 1] * N; drift: gm_acq_dwell_samples)
+    const uint64_t* starts; uint32_t R;    // drift: device [n_bins][R] period starts (64-bit element offsets)
+    const cf* rho; uint32_t K;             // device phasor words
+    const uint32_t* offsets; uint32_t H;   // device [H], ascending period offsets
+    uint32_t neg;                          // bit k set: secondary[k] = -1
     const cf* tables; const cf* tw_fwd;    // the Doppler tables [n_bins][N]; the forward plan's base twiddles
     cf* out;                               // in-LDS: the spectra; composite / long: the forward sub-transforms A
-    uint32_t n_bins, n_int;                // items = n_bins * n_int
+    uint32_t n_bins, n_int;                // the handle's own D and M: items = H * n_bins * n_int
     uint32_t Q, N, lim;                    // composite / long: Q; long: N and the signal's extension (N native, 2N padded)
     uint32_t* clear_tickets;               // in-LDS: the tail split's tickets, cleared on the way (PlanOps::mix_fft)
     const uint16_t* order;                 // in-LDS / composite: the storage order table (PlanOps::fill_order), may be null
 };
-template <class PL> void launch_mix_fft_coh(hipStream_t, const CohArgs&);
-template <class PL> void launch_comp_fwd_sub_coh(hipStream_t, const CohArgs&);
-template <class PL> void launch_long_fwd_sub_coh(hipStream_t, const CohArgs&);
-
-// Stage F of a coherent handle's edge search (gm_acq_set_edge_search, acq_edge.hip): H hypotheses, each the coherent stage F on the
-// samples from period offsets[h] on with the secondary row's signs in the fold; the output is laid out [H * n_bins][n_int][.], i.e.
-// what stage C takes with H * n_bins bins.  CohArgs' fields mean what they mean there (n_bins: the handle's own D).
-struct EdgeArgs {
-    const void* samples; int fmt;          // (K * M + offsets[H - 1]) * N samples
-    const cf* rho; uint32_t K;
-    const uint32_t* offsets; uint32_t H;   // device [H], ascending period offsets
-    uint32_t neg;                          // bit k set: secondary[k] = -1
-    const cf* tables; const cf* tw_fwd;
-    cf* out;
-    uint32_t n_bins, n_int;
-    uint32_t Q, N, lim;
-    uint32_t* clear_tickets;
-    const uint16_t* order;
-};
-// the launchers by base plan length (null: no such plan): in-LDS sizes, the composite bases, the long bases
-typedef void (*EdgeLaunch)(hipStream_t, const EdgeArgs&);
-EdgeLaunch find_edge_mix_fft(int n);
-EdgeLaunch find_edge_comp_fwd_sub(int nb);
-EdgeLaunch find_edge_long_fwd_sub(int nb);
+// the launcher of a family (its loader: CohLoad, EdgeLoad, DriftLoad) for a form and its base plan length — in-LDS sizes: the size
+// itself; composite and long: the base — or null: no such plan
+typedef void (*StageFLaunch)(hipStream_t, const StageFArgs&);
+enum { STAGE_F_MIX, STAGE_F_COMP, STAGE_F_LONG };
+struct CohLoad; struct EdgeLoad; struct DriftLoad;
+template <class Load> StageFLaunch find_stage_f(int form, int n);
 // full [3][P][H][D] -> met [3][P][D] + choice [P][D] for the listed workers: per cell the hypothesis with the largest max, lowest h on ties
 void launch_edge_reduce(hipStream_t, const uint32_t* full, uint32_t* met, uint32_t* choice, const uint32_t* worker_list,
                         uint32_t n_workers, uint32_t P, uint32_t H, uint32_t D);
-
-// Stage F of a handle with code-drift compensation (gm_acq_set_code_drift, acq_drift.hip): period k of group m of hypothesis h in bin
-// d is the N samples from starts[d][offsets[h] + m K + k] on, folded (K >= 2) with rho[h][d][m][k] and the secondary row's signs.
-// offsets == null: one hypothesis at offset 0 (H = 1), i.e. a handle without an edge search; K = 1: no fold, the samples themselves.
-// The other fields mean what they mean in EdgeArgs; the output is laid out [H * n_bins][n_int][.].
-struct DriftArgs {
-    const void* samples; int fmt;          // gm_acq_dwell_samples samples
-    const uint64_t* starts; uint32_t R;    // device [n_bins][R] period starts (64-bit element offsets)
-    const cf* rho; uint32_t K;             // device [H][n_bins][n_int][K] phasor words (gm_acq_code_drift_phasors)
-    const uint32_t* offsets; uint32_t H;
-    uint32_t neg;
-    const cf* tables; const cf* tw_fwd;
-    cf* out;
-    uint32_t n_bins, n_int;
-    uint32_t Q, N, lim;
-    uint32_t* clear_tickets;
-    const uint16_t* order;
-};
-typedef void (*DriftLaunch)(hipStream_t, const DriftArgs&);
-DriftLaunch find_drift_mix_fft(int n);
-DriftLaunch find_drift_comp_fwd_sub(int nb);
-DriftLaunch find_drift_long_fwd_sub(int nb);
 
 // One entry per shipped transform size: launchers for the kernels instantiated on that plan.
 struct DecideArgs;
@@ -136,9 +105,6 @@ struct PlanOps {
     // than the registered one since round 6, e.g. N = 8192; empty for prime-factor and hybrid correlation plans)
     int tw_total_corr;
     void (*fill_tw_corr)(cf* tw);
-    // stage F of a coherent handle (gm_acq_cfg.coherent_periods = K >= 2, acq_coherent.hip): mix_fft on the dwell's M groups of K
-    // periods, each folded with its bin's phasor words before the carrier mix; the same spectra, no trailing decision
-    void (*mix_fft_coh)(hipStream_t, const CohArgs&);
 };
 // mean of the snapshot (finer_doppler :236) and the final per-satellite reduction over the rows
 void launch_fine_mean(hipStream_t, const void* samples, int fmt, uint32_t n, float* d_mean);
@@ -186,8 +152,6 @@ struct CompOps {
     // base plans with an order table: forward step 2 folded into the table — comb2[p][n1][n1'][pos] such that a sub-transform's input is
     // sum_n1' A[n1'][pos] * comb2[n1][n1'][pos] on the forward sub-transforms A as fwd_sub leaves them (no fwd_post per dwell)
     void (*fold_post)(hipStream_t, const cf* comb, const uint16_t* order, cf* comb2, uint32_t n_codes);
-    // forward step 1 of a coherent handle's signal (acq_coherent.hip): the M groups folded over K periods; the replicas keep fwd_sub
-    void (*fwd_sub_coh)(hipStream_t, const CohArgs&);
 };
 const CompOps* find_comp(uint32_t n);
 // strict_sum_order on the composite path: msum[o] = is_good_satellite's eight-lane ordered sum (do_acquisition.rs:229-235) of plane o,
@@ -205,8 +169,6 @@ struct LongOps {
     void (*corr_inv)(hipStream_t, const cf* Z, const cf* tw_inv, float* pmax, uint32_t* parg, float* psum, float* planes,
                      const uint32_t* worker_list, uint32_t n_workers, uint32_t n_bins, uint32_t item0, uint32_t n_slab, uint32_t Q,
                      uint32_t N, uint32_t n_int, float scale);
-    // F1 of a coherent handle's signal (acq_coherent.hip): element i of group m is the fold over its K periods; the replicas keep fwd_sub
-    void (*fwd_sub_coh)(hipStream_t, const CohArgs&);
 };
 // the base plans, largest first
 const LongOps* long_bases(int* n);

@@ -374,7 +374,7 @@ int gm_acq_coherent_phasors(gm_acq *a, gm_c32 *out);
  * promise, the whole search at gm_acq_search_prepared_dev); gm_acq_set_deferred_decision is accepted and decides at once;
  * gm_acq_finer_doppler strips the code from the winning hypothesis's offset o* on — (K*M-1) * fft_size samples from
  * o* * fft_size + code_phase, the mean over the K*M periods from o* on.
- * Stage F runs one grid over H * D * M transforms and stage C one launch over P * H * D items (acq_edge.hip).
+ * Stage F runs one grid over H * D * M transforms and stage C one launch over P * H * D items (acq_stage_f_variants.h).
  * Device memory while it is on, beside the handle's own (T = gm_acq_plan_info's transform_len, N = fft_size):
  *     8 H D M T  (spectra)  +  12 P H D + 4 P D + 4 H  (metric words, choice, offsets)  +  8 offsets[H-1] N  (the internal sample
  *     buffer of the host / ring entries, when it has to grow)
@@ -421,7 +421,7 @@ int gm_acq_result_offsets(gm_acq *a, const gm_acq_result *results, const uint8_t
  * It works on every handle (every form gm_acq_plan_info reports, every sample format, code family, decision mode, strict_sum_order,
  * reference_products where the handle accepts it, the edge search on or off); gm_acq_set_edge_search and gm_acq_set_code_drift may
  * be called in either order, each plans the dwell again.  Stage C, the reduction over the hypotheses, the decision, the all-gather
- * entries and every [D][M][.] buffer stay as they are (acq_drift.hip holds the three stage-F kernels).
+ * entries and every [D][M][.] buffer stay as they are (acq_stage_f_variants.h holds the three stage-F kernels).
  * Results: s[d][0] = 0 and |s[d][o] - o T_d| <= 0.5, so code_phase_samples is the code phase at the dwell's first sample to within
  * half a sample; sample_global_index keeps its definition.  gm_acq_coherent_phasors is unchanged.
  * gm_acq_finer_doppler is unchanged and NOT compensated: it strips the code over contiguous samples (K*M periods of fft_size from

@@ -43,7 +43,7 @@ def test_the_entries_are_in_every_layer(gm):
     assert "set_code_drift" in _read("rust", "src", "mi355x", "do_acquisition.rs")
     hpp = _read("gnss-sdr-rs_amd", "host", "gnss_sdr.hpp")
     assert "set_code_drift" in hpp and "gm_acq_dwell_samples" in hpp
-    assert "acq_drift.hip" in _read("gnss-sdr-rs_amd", "build.py")
+    assert "acq_stage_f_drift.hip" in _read("gnss-sdr-rs_amd", "build.py")
     assert "NOT compensated" in header      # gm_acq_finer_doppler says so
 
 

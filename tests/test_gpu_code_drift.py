@@ -1,4 +1,4 @@
-"""Code-drift compensation of acquisition (gm_acq_set_code_drift, acq_drift.hip) on the GPU.
+"""Code-drift compensation of acquisition (gm_acq_set_code_drift, DriftLoad in acq_stage_f_variants.h) on the GPU.
 
 Period p of the dwell starts at s[d][p] = floor(p T_d + 0.5) in bin d.  Off, and T = fft_size, are the handle as it was, word for
 word.  At K = 1 bin d's words are those of a plain search of the gathered samples x'[m N + n] = x[s[d][m] + n].  At K >= 2 (with

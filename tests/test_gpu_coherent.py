@@ -1,4 +1,4 @@
-"""Coherent integration over K code periods (gm_acq_cfg.coherent_periods, acq_coherent.hip) on the GPU.
+"""Coherent integration over K code periods (gm_acq_cfg.coherent_periods, CohLoad in acq_stage_f_variants.h) on the GPU.
 
 The fold y_{d,m}[n] = sum_k rho_{d,k} x[(m K + k) N + n] is restated on the host in float32 with the handle's own phasor words and the
 same arithmetic (every product and sum rounded on its own, k ascending); the folded groups then go through the unchanged oracle, one

@@ -1,4 +1,4 @@
-"""The edge search of a coherent handle (gm_acq_set_edge_search, acq_edge.hip) on the GPU.
+"""The edge search of a coherent handle (gm_acq_set_edge_search, EdgeLoad in acq_stage_f_variants.h) on the GPU.
 
 Hypothesis h is the coherent search on the samples from period o_h on with s[k] * rho[d][k] in the fold.  The host restates that fold
 in float32 with the handle's own phasor words (every product and sum rounded on its own, k ascending; the multiplication by +-1 is

@@ -1,5 +1,5 @@
-"""Every stage-F copy of the coherent, edge and drift handles (acq_coherent.hip, acq_edge.hip, acq_drift.hip) on every plan it is built
-for: the 18 in-LDS plans, the eight composite bases find_comp can reach and the seven long-path bases, native and padded — one row
+"""Every stage-F kernel of the coherent, edge and drift handles (acq_stage_f_variants.h: one body per form, a loader per family) on every
+plan it is built for: the 18 in-LDS plans, the eight composite bases find_comp can reach and the seven long-path bases, native and padded — one row
 of acq_model.CASES per (form, base) pair gm_acq_plan_info can return (tests/test_acq_model_host.py holds the table to the planner).
 
 Every row runs P = 2 codes, D = 3 bins, fs = 1000 N, f_if = 0 under four variants, the sample formats rotating over the rows:
@@ -14,9 +14,9 @@ scene check on the CPU shows every cell's second lag at least 1e-3 below its pea
 reduced block and the choice against numpy's reduction of the device's block.  Identity: the host forms the fold in float32 with the
 handle's own phasor words and starts (acq_model.fold) and a plain handle (coherent_periods = 1, same size, bins, codes and
 n_integrations) searches the M folded groups, one call per (h, d); column d of its three words equals the variant's [., h, d] words
-as uint32 — "the host restates the fold exactly" (acq_device.h) and "a cell's words do not depend on what shares the launch".  The
+as uint32 — "the host restates the fold exactly" (acq_stage_f_variants.h) and "a cell's words do not depend on what shares the launch".  The
 composite bases are no exception: the wave-specialised kernel of base 16000 (acq_comp_ws.h) is stage C's, which the variants and the
-plain handle share; stage F there is comp_fwd_sub_kernel and its three copies like everywhere else.
+plain handle share; stage F there is comp_fwd_sub_kernel and comp_fwd_sub_fold_kernel like everywhere else.
 
 Then the two cases of acq_edge_reduce_kernel no other test reaches: ties between the hypotheses, and a PRN mask."""
 import numpy as np
