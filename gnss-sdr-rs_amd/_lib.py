@@ -38,6 +38,22 @@ class AcqPlan(C.Structure):
     _fields_ = [("form", C.c_int32), ("base", C.c_uint32), ("q", C.c_uint32), ("transform_len", C.c_uint32)]
 
 
+class AcqRefineCfg(C.Structure):
+    """gm_acq_refine_cfg: zeros are the defaults"""
+    _fields_ = [("span_periods", C.c_uint32), ("n_freq", C.c_uint32), ("half_span_hz", C.c_float)]
+
+
+class AcqRefineOut(C.Structure):
+    """gm_acq_refine_out"""
+    _fields_ = [("carrier_hz", C.c_double), ("delta_hz", C.c_float), ("step_hz", C.c_float), ("half_span_hz", C.c_float),
+                ("peak_power", C.c_float), ("center_power", C.c_float), ("peak_index", C.c_uint32), ("at_edge", C.c_uint32),
+                ("doppler_bin", C.c_uint32), ("offset_periods", C.c_uint32), ("span_periods", C.c_uint32),
+                ("n_groups", C.c_uint32), ("n_freq", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 ACQ_FORM_LDS, ACQ_FORM_COMPOSITE, ACQ_FORM_LONG, ACQ_FORM_LONG_PADDED = 0, 1, 2, 3   # gm_acq_form
 
 
@@ -133,6 +149,9 @@ SIGNATURES = {
     "gm_acq_dwell_samples": (_i, [_vp, C.POINTER(_u64)]),
     "gm_acq_code_drift_starts": (_i, [_vp, _vp]),
     "gm_acq_code_drift_phasors": (_i, [_vp, _u32, _vp]),
+    "gm_acq_refine_doppler": (_i, [_vp, _vp, _vp, _u32, C.POINTER(AcqRefineCfg), _vp, _vp, _vp]),
+    "gm_acq_refine_plan": (_i, [_u32, _u32, C.POINTER(AcqRefineCfg), _f, _u32, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32),
+                            C.POINTER(_u32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gm_acq_enable_timing": (_i, [_vp, _i]),
     "gm_acq_last_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
     "gm_acq_timing_summary": (_i, [_vp, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f)]),

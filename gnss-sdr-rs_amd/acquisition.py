@@ -6,7 +6,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import AcqCfg, AcqPlan, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
+from ._lib import AcqCfg, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
 
 PRN_SEARCH_ACQUISITION_TOTAL = 32      # do_acquisition.rs:22
 FREQ_SEARCH_ACQUISITION_HZ = 14e3      # :20
@@ -148,6 +148,20 @@ def code_drift_plan(fft_size, n_periods, period_samples):
     check(lib().gm_acq_code_drift_plan(int(fft_size), int(n_periods), t.size, _p(t) if t.size else None, _p(starts), C.byref(out)),
           "gm_acq_code_drift_plan")
     return starts, out.value
+
+
+def refine_plan(coherent_periods, n_integrations, fs, fft_size, table_freq, bin=0, span_periods=0, n_freq=0, half_span_hz=0.0):
+    """gm_acq_refine_plan: what refine_doppler would use for Doppler bin `bin` of a handle with these settings, after its argument
+    checks (GmError INVALID_ARG) -> dict(span_periods, n_groups, n_freq, half_span_hz, step_hz); a dwell yields span_periods * n_groups
+    prompts per satellite.  Host only."""
+    tf = np.ascontiguousarray(table_freq, np.float32).reshape(-1)
+    cfg = AcqRefineCfg(int(span_periods), int(n_freq), float(half_span_hz))
+    j, g, z = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    hs, st = C.c_double(0), C.c_double(0)
+    check(lib().gm_acq_refine_plan(int(coherent_periods), int(n_integrations), C.byref(cfg), float(fs), int(fft_size), tf.size,
+                                   _p(tf) if tf.size else None, int(bin), C.byref(j), C.byref(g), C.byref(z), C.byref(hs),
+                                   C.byref(st)), "gm_acq_refine_plan")
+    return dict(span_periods=j.value, n_groups=g.value, n_freq=z.value, half_span_hz=hs.value, step_hz=st.value)
 
 
 class AcquisitionEngine:
@@ -346,6 +360,50 @@ class AcquisitionEngine:
                                          C.byref(size)), "gm_acq_finer_doppler")
         return [dict(freq_hz=float(f[i]), peak_index=int(idx[i]), peak_mag=float(mag[i]), fft_size=size.value)
                 if found[i] else None for i in range(n)]
+
+    def _results_array(self, results):
+        n = len(results)
+        res = (AcqResult * n)()
+        found = np.zeros(n, np.uint8)
+        for i, r in enumerate(results):
+            if r:
+                found[i] = 1
+                for k, _ in AcqResult._fields_:
+                    setattr(res[i], k, r.get(k, 0))
+        return res, found, n
+
+    def refine_doppler(self, results, span_periods=0, n_freq=0, half_span_hz=0.0, want_prompts=False, want_spectrum=False):
+        """Fine Doppler from per-period prompts (gm_acq_refine_doppler) for the found results of the LAST search, on that search's
+        snapshot: the search's own statistic on n_freq grid points within +-half_span_hz of the winning bin's table frequency — with
+        the handle's coherent groups, the edge search's offset and secondary row and the code-drift starts.  A result needs
+        `doppler_bin` and `code_phase_samples` only.  -> list (per entry) of dict(carrier_hz, delta_hz, step_hz, half_span_hz,
+        peak_power, center_power, peak_index, at_edge, doppler_bin, offset_periods, span_periods, n_groups, n_freq) or None; with
+        want_prompts `prompts` (complex64 [span_periods * n_groups]), with want_spectrum `spectrum` (float32 [n_freq])."""
+        res, found, n = self._results_array(results)
+        cfg = AcqRefineCfg(int(span_periods), int(n_freq), float(half_span_hz))
+        out = (AcqRefineOut * max(n, 1))()
+        z = s = None
+        if want_prompts or want_spectrum:
+            plan = refine_plan(self.K, self.M, self.fs, self.fft_size, self.table_freq, 0, span_periods, n_freq, half_span_hz)
+            if want_prompts:
+                z = np.zeros((n, plan["span_periods"] * plan["n_groups"]), np.complex64)
+            if want_spectrum:
+                s = np.zeros((n, plan["n_freq"]), np.float32)
+        check(lib().gm_acq_refine_doppler(self._h, C.cast(res, C.c_void_p), _p(found), n, C.byref(cfg), C.cast(out, C.c_void_p),
+                                          _p(z) if z is not None else None, _p(s) if s is not None else None),
+              "gm_acq_refine_doppler")
+        ret = []
+        for i in range(n):
+            if not found[i]:
+                ret.append(None)
+                continue
+            d = out[i].as_dict()
+            if z is not None:
+                d["prompts"] = z[i].copy()
+            if s is not None:
+                d["spectrum"] = s[i].copy()
+            ret.append(d)
+        return ret
 
     def metrics(self):
         mx = np.zeros((self.P, self.D), np.float32)

@@ -411,6 +411,12 @@ struct gm_acq {
         float *d_mean = nullptr, *d_rowmax = nullptr, *d_peak_pow = nullptr;
         uint32_t *d_rowarg = nullptr, *d_sat_worker = nullptr, *d_sat_cp = nullptr, *d_peak_idx = nullptr;
     } fine;
+    // fine Doppler from per-period prompts (gm_acq_refine_doppler): one lazily built device block, carved per call into the satellite
+    // list, the prompts, the period times, the per-satellite centre and step, the spectra and the peaks; grown when a call needs more
+    struct Refine {
+        void* d_block = nullptr;
+        size_t bytes = 0;
+    } refine;
 };
 
 // the fused single-LDS-buffer kernels (acq_kernels.hip): neither a composite nor an any-length size
@@ -741,6 +747,7 @@ int gm_acq_destroy(gm_acq* a) {
     hipFree(a->fine.d_chips); hipFree(a->fine.d_tw1); hipFree(a->fine.d_tw2); hipFree(a->fine.d_B); hipFree(a->fine.d_mean);
     hipFree(a->fine.d_rowmax); hipFree(a->fine.d_rowarg); hipFree(a->fine.d_sat_worker); hipFree(a->fine.d_sat_cp);
     hipFree(a->fine.d_peak_pow); hipFree(a->fine.d_peak_idx);
+    hipFree(a->refine.d_block);
     if (a->device >= 0) hipSetDevice(a->device);
     hipFree(a->d_tw_mix);
     hipFree(a->d_tables); hipFree(a->d_tw_fwd); hipFree(a->d_tw_inv); hipFree(a->d_code_fft); hipFree(a->d_code_fft_paired); hipFree(a->d_order);
@@ -1770,6 +1777,169 @@ int gm_acq_code_drift_phasors(gm_acq* a, uint32_t h, gm_c32* out) {
     if (int rc = ensure_device(a->device)) return rc;
     const size_t n = size_t(a->D) * a->M * a->K;
     HIPC(hipMemcpy(out, a->drift.d_rho + size_t(h) * n, n * 8, hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+// ---------------------------------------------------------------- fine Doppler from per-period prompts (additive entries, ABI 9)
+namespace {
+struct RefinePlan { uint32_t J = 0, G = 0, Z = 0; double half_span = 0.0, step = 0.0; };
+}
+// the argument rules of gm_acq_refine_plan / gm_acq_refine_doppler and what a call uses for `bin` (gnss_mi355x.h states them)
+static int refine_rules(uint32_t coherent_periods, uint32_t M, const gm_acq_refine_cfg* cfg, double fs, uint32_t N, uint32_t D,
+                        const float* table_freq, uint32_t bin, RefinePlan& o) {
+    const gm_acq_refine_cfg c = cfg ? *cfg : gm_acq_refine_cfg{0u, 0u, 0.0f};
+    const uint32_t K = coherent_periods > 1 ? coherent_periods : 1;
+    if (K > uint32_t(gm::GM_COHERENT_MAX)) return set_err(GM_ERR_INVALID_ARG, "coherent_periods > 32");
+    if (!M || !N || !D || !table_freq || !(fs > 0.0)) return set_err(GM_ERR_INVALID_ARG, "n_integrations, fft_size, n_bins, table_freq and fs are required");
+    if (bin >= D) return set_err(GM_ERR_INVALID_ARG, "doppler bin outside the handle's bins");
+    if (K >= 2) {
+        if (c.span_periods && c.span_periods != K) return set_err(GM_ERR_INVALID_ARG, "span_periods must be 0 or coherent_periods on a coherent handle");
+        o.J = K; o.G = M;
+    } else {
+        o.J = c.span_periods ? c.span_periods : M;
+        o.G = M / o.J;
+    }
+    if (o.J < 2) return set_err(GM_ERR_INVALID_ARG, "the fine Doppler needs at least 2 periods per group (one period carries no frequency information)");
+    if (o.G < 1) return set_err(GM_ERR_INVALID_ARG, "span_periods exceeds n_integrations");
+    o.Z = c.n_freq ? c.n_freq : 257u;
+    if (o.Z < 3 || o.Z > 4097 || !(o.Z & 1u)) return set_err(GM_ERR_INVALID_ARG, "n_freq must be odd, 3 .. 4097");
+    const double limit = fs / (2.0 * double(N));          // per-period prompts alias beyond it
+    double hs = double(c.half_span_hz);
+    if (c.half_span_hz == 0.0f) {
+        if (D == 1) hs = fs / (2.0 * double(N) * double(K));
+        else {
+            const double f = double(table_freq[bin]);
+            const double lo = bin > 0 ? ::fabs(f - double(table_freq[bin - 1])) : 0.0;
+            const double hi = bin + 1 < D ? ::fabs(double(table_freq[bin + 1]) - f) : 0.0;
+            hs = 0.5 * (lo > hi ? lo : hi);
+        }
+        if (hs > limit) hs = limit;
+    }
+    if (!(hs > 0.0) || !(hs <= limit)) return set_err(GM_ERR_INVALID_ARG, "half_span_hz must lie in (0, fs / (2 fft_size)]");   // (NaN fails too)
+    o.half_span = hs;
+    o.step = hs / double((o.Z - 1) / 2);
+    return GM_OK;
+}
+
+int gm_acq_refine_plan(uint32_t coherent_periods, uint32_t n_integrations, const gm_acq_refine_cfg* cfg, float fs, uint32_t fft_size,
+                       uint32_t n_bins, const float* table_freq, uint32_t bin, uint32_t* span_periods, uint32_t* n_groups,
+                       uint32_t* n_freq, double* half_span_hz, double* step_hz) {
+    RefinePlan o;
+    if (int rc = refine_rules(coherent_periods, n_integrations, cfg, double(fs), fft_size, n_bins, table_freq, bin, o)) return rc;
+    if (span_periods) *span_periods = o.J;
+    if (n_groups) *n_groups = o.G;
+    if (n_freq) *n_freq = o.Z;
+    if (half_span_hz) *half_span_hz = o.half_span;
+    if (step_hz) *step_hz = o.step;
+    return GM_OK;
+}
+
+int gm_acq_refine_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t* found, uint32_t n_prn, const gm_acq_refine_cfg* cfg,
+                          gm_acq_refine_out* out, gm_c32* prompts, float* spectrum) {
+    if (!a || !results || !found || !out) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (n_prn > a->P) return set_err(GM_ERR_INVALID_ARG, "n_prn exceeds the handle's workers");
+    if (!a->last_samples) return set_err(GM_ERR_INVALID_ARG, "no search has run on this handle yet");
+    const uint32_t N = a->N, D = a->D;
+    const double fs = double(a->cfg.fs);
+    // every argument is checked before anything runs or is written
+    std::vector<RefinePlan> plans(n_prn);
+    std::vector<uint32_t> list;
+    RefinePlan common;
+    if (int rc = refine_rules(a->cfg.coherent_periods, a->M, cfg, fs, N, D, a->table_freq.data(), 0, common)) return rc;
+    for (uint32_t p = 0; p < n_prn; ++p) {
+        if (!found[p]) continue;
+        const int32_t d = results[p].doppler_bin;
+        if (d < 0 || uint32_t(d) >= D) return set_err(GM_ERR_INVALID_ARG, "result.doppler_bin outside the handle's bins");
+        if (results[p].code_phase_samples >= N) return set_err(GM_ERR_INVALID_ARG, "result.code_phase_samples >= fft_size");
+        if (int rc = refine_rules(a->cfg.coherent_periods, a->M, cfg, fs, N, D, a->table_freq.data(), uint32_t(d), plans[p])) return rc;
+        list.push_back(p);
+    }
+    if (list.empty()) return GM_OK;
+    if (int rc = ensure_device(a->device)) return rc;
+    if (int rc = acq_flush_decision(a)) return rc;
+    const uint32_t S = uint32_t(list.size()), J = common.J, G = common.G, Z = common.Z, R_u = J * G;
+    std::vector<uint32_t> off(n_prn, 0u);
+    if (a->edge.H)
+        if (int rc = gm_acq_result_offsets(a, results, found, n_prn, off.data())) return rc;
+    // the block: [sats | z | t | fc | step | spectrum | peak values | peak indices], every part 256-byte aligned
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_sat = 0, o_z = o_sat + up(size_t(S) * sizeof(gm::RefineSat)), o_t = o_z + up(size_t(S) * R_u * 8),
+                 o_fc = o_t + up(size_t(S) * R_u * 8), o_step = o_fc + up(size_t(S) * 8), o_spec = o_step + up(size_t(S) * 8),
+                 o_pv = o_spec + up(size_t(S) * Z * 4), o_pi = o_pv + up(size_t(S) * 4), total = o_pi + up(size_t(S) * 4);
+    gm_acq::Refine& rf = a->refine;
+    if (total > rf.bytes) {                 // the new block before the old one goes: a failure leaves the handle as it was
+        void* blk = nullptr;
+        if (hipMalloc(&blk, total) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(GM_ERR_NOMEM, "the fine-Doppler block does not fit (gnss_mi355x.h states the formula); the handle is as it was");
+        }
+        if (hipError_t e = hipStreamSynchronize(a->stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
+        hipFree(rf.d_block);
+        rf.d_block = blk; rf.bytes = total;
+    }
+    char* const base = static_cast<char*>(rf.d_block);
+    // host side of the block's inputs: the satellite list, the period times of every group (f64, relative to the group's first
+    // period: whole samples over fs), the centre frequency and the grid step
+    std::vector<gm::RefineSat> sats(S);
+    std::vector<double> t(size_t(S) * R_u), fc(S), step(S);
+    for (uint32_t i = 0; i < S; ++i) {
+        const uint32_t p = list[i], d = uint32_t(results[p].doppler_bin), o = off[p];
+        sats[i] = gm::RefineSat{p, uint32_t(results[p].code_phase_samples), d, o};
+        fc[i] = double(a->table_freq[d]);
+        step[i] = plans[p].step;
+        for (uint32_t g = 0; g < G; ++g)
+            for (uint32_t k = 0; k < J; ++k) {
+                const uint32_t q0 = o + g * J, q = q0 + k;
+                const uint64_t s0 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q0] : uint64_t(q0) * N;
+                const uint64_t s1 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q] : uint64_t(q) * N;
+                t[size_t(i) * R_u + g * J + k] = double(s1 - s0) / fs;
+            }
+    }
+    HIPC(hipMemcpyAsync(base + o_sat, sats.data(), size_t(S) * sizeof(gm::RefineSat), hipMemcpyHostToDevice, a->stream));
+    HIPC(hipMemcpyAsync(base + o_t, t.data(), t.size() * 8, hipMemcpyHostToDevice, a->stream));
+    HIPC(hipMemcpyAsync(base + o_fc, fc.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
+    HIPC(hipMemcpyAsync(base + o_step, step.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
+    gm::RefineArgs ra{};
+    ra.samples = a->last_samples; ra.fmt = a->last_fmt;
+    ra.starts = a->drift.on ? a->drift.d_starts : nullptr; ra.R = a->drift.on ? a->drift.R : 0u;
+    ra.tables = a->d_tables; ra.code_samples = a->d_code_samples;
+    ra.sats = reinterpret_cast<const gm::RefineSat*>(base + o_sat); ra.n_sats = S;
+    ra.N = N; ra.R_u = R_u; ra.J = J; ra.G = G; ra.Z = Z;
+    ra.neg = (a->K >= 2 && a->edge.H) ? a->edge.neg : 0u;
+    ra.z = reinterpret_cast<cf*>(base + o_z); ra.t = reinterpret_cast<const double*>(base + o_t);
+    ra.fc = reinterpret_cast<const double*>(base + o_fc); ra.step = reinterpret_cast<const double*>(base + o_step);
+    ra.spectrum = reinterpret_cast<float*>(base + o_spec);
+    ra.peak_val = reinterpret_cast<float*>(base + o_pv); ra.peak_idx = reinterpret_cast<uint32_t*>(base + o_pi);
+    gm::launch_refine(a->stream, ra);
+    HIPC(hipGetLastError());
+    std::vector<float> spec(size_t(S) * Z);
+    std::vector<uint32_t> pi(S);
+    std::vector<gm_c32> zh(prompts ? size_t(S) * R_u : 0);
+    HIPC(hipMemcpyAsync(spec.data(), base + o_spec, spec.size() * 4, hipMemcpyDeviceToHost, a->stream));
+    HIPC(hipMemcpyAsync(pi.data(), base + o_pi, size_t(S) * 4, hipMemcpyDeviceToHost, a->stream));
+    if (prompts) HIPC(hipMemcpyAsync(zh.data(), base + o_z, zh.size() * 8, hipMemcpyDeviceToHost, a->stream));
+    HIPC(hipStreamSynchronize(a->stream));
+    for (uint32_t i = 0; i < S; ++i) {
+        const uint32_t p = list[i];
+        const float* sp = &spec[size_t(i) * Z];
+        const uint32_t pk = pi[i] < Z ? pi[i] : (Z - 1) / 2;      // (no comparable value at all, e.g. samples that are not numbers: the centre)
+        gm_acq_refine_out& r = out[p];
+        r.at_edge = (pk == 0 || pk == Z - 1) ? 1u : 0u;
+        double delta = (double(pk) - double((Z - 1) / 2)) * step[i];
+        if (!r.at_edge) {                   // three-point parabola through the peak and its neighbours, f64
+            const double y0 = sp[pk - 1], y1 = sp[pk], y2 = sp[pk + 1], den = y0 - 2.0 * y1 + y2;
+            double x = den < 0.0 ? 0.5 * (y0 - y2) / den : 0.0;
+            x = x > 0.5 ? 0.5 : (x < -0.5 ? -0.5 : x);
+            delta += x * step[i];
+        }
+        r.carrier_hz = fc[i] + delta;
+        r.delta_hz = float(delta); r.step_hz = float(step[i]); r.half_span_hz = float(plans[p].half_span);
+        r.peak_power = sp[pk]; r.center_power = sp[(Z - 1) / 2];
+        r.peak_index = pk;
+        r.doppler_bin = sats[i].bin; r.offset_periods = sats[i].offset; r.span_periods = J; r.n_groups = G; r.n_freq = Z;
+        if (prompts) memcpy(prompts + size_t(p) * R_u, &zh[size_t(i) * R_u], size_t(R_u) * 8);
+        if (spectrum) memcpy(spectrum + size_t(p) * Z, sp, size_t(Z) * 4);
+    }
     return GM_OK;
 }
 

@@ -57,6 +57,25 @@ template <class Load> StageFLaunch find_stage_f(int form, int n);
 void launch_edge_reduce(hipStream_t, const uint32_t* full, uint32_t* met, uint32_t* choice, const uint32_t* worker_list,
                         uint32_t n_workers, uint32_t P, uint32_t H, uint32_t D);
 
+// Fine Doppler from per-period prompts (gm_acq_refine_doppler, acq_refine.hip): the despreading kernel on grid (R_u, n_sats), then
+// the scan over the Z grid points per satellite.  Nothing here depends on the handle's stage-C form.
+struct RefineSat { uint32_t worker, code_phase, bin, offset; };   // offset: the periods the satellite's cell chose (0 without an edge search)
+struct RefineArgs {
+    const void* samples; int fmt;          // the snapshot of the last search
+    const uint64_t* starts; uint32_t R;    // device [n_bins][R] period starts, or null: period p starts at p N
+    const cf* tables;                      // the mix tables [n_bins][N]
+    const int8_t* code_samples;            // the resampled replicas [P][N], natural order
+    const RefineSat* sats; uint32_t n_sats;
+    uint32_t N, R_u, J, G, Z;              // R_u = G * J prompts per satellite; Z grid points
+    uint32_t neg;                          // bit k set: sigma_k = -1
+    cf* z;                                 // [n_sats][R_u] prompts
+    const double* t;                       // [n_sats][R_u] (s[o + g J + k] - s[o + g J]) / fs, seconds
+    const double *fc, *step;               // [n_sats] table_freq of the bin; grid step in Hz
+    float* spectrum;                       // [n_sats][Z]
+    float* peak_val; uint32_t* peak_idx;   // [n_sats] first index of the maximum
+};
+void launch_refine(hipStream_t, const RefineArgs&);
+
 // One entry per shipped transform size: launchers for the kernels instantiated on that plan.
 struct DecideArgs;
 struct PlanOps {

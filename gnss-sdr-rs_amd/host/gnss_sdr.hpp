@@ -155,6 +155,20 @@ public:
               "finer_doppler");
         return freq;
     }
+    // Fine Doppler from per-period prompts (gm_acq_refine_doppler) on the snapshot of the last search: the search's own statistic on a
+    // fine grid around every found result's bin — valid with coherent groups, the edge search and the code drift, where finer_doppler
+    // is not.  cfg zeros are the defaults.  Entries of not-found workers are nullopt; carrier_hz is the refined IF + Doppler.
+    std::vector<std::optional<gm_acq_refine_out>> refine_doppler(const std::vector<std::optional<AcquisitionResult>>& results,
+                                                                 const gm_acq_refine_cfg& cfg = {}) {
+        std::vector<gm_acq_result> r(results.size());
+        std::vector<uint8_t> f(results.size(), 0);
+        for (size_t i = 0; i < results.size(); ++i) if (results[i]) { r[i] = *results[i]; f[i] = 1; }
+        std::vector<gm_acq_refine_out> o(results.size());
+        check(gm_acq_refine_doppler(h_, r.data(), f.data(), uint32_t(results.size()), &cfg, o.data(), nullptr, nullptr), "refine_doppler");
+        std::vector<std::optional<gm_acq_refine_out>> out(results.size());
+        for (size_t i = 0; i < results.size(); ++i) if (f[i]) out[i] = o[i];
+        return out;
+    }
     // The edge search of a coherent handle (gm_acq_set_edge_search): H ascending period offsets (each 0..63, H <= 32) and an optional
     // secondary row of coherent_periods entries +-1 (empty: all +1); no offsets switch it off.  While it is on a dwell is
     // (K * n_integrations + offsets.back()) * fft_size samples.
@@ -416,6 +430,9 @@ struct AcquisitionRunOptions {            // the reference's compile-time consta
     double first_round_signal_ms = -1.0;
     // refine every hit's carrier (finer_doppler, acquisition_bk.rs:215-302) before it goes to tracking
     bool fine_doppler = false;
+    // the same hand-over through gm_acq_refine_doppler (per-period prompts: follows coherent_periods, an edge search and a code-drift
+    // compensation set on the engine); when set it replaces fine_doppler's carrier with carrier_hz
+    bool refine_doppler = false;
     // gm_acq_cfg.coherent_periods: K code periods integrated coherently; a round then searches K * long_samples_length periods
     uint32_t coherent_periods = 1;
     std::function<void(uint64_t head, const std::vector<std::optional<AcquisitionResult>>&)> on_round;   // after every round (may be empty)
@@ -467,16 +484,22 @@ inline void run_acquisition(MulticastRingBuffer& multi_buffer, float freq_sampli
         if (!results) { std::this_thread::sleep_for(std::chrono::milliseconds(1)); continue; }              // :324-326
         const uint64_t head_of_round = local_tail + uint64_t(opt.coherent_periods > 1 ? opt.coherent_periods : 1) *
                                                     uint64_t(opt.long_samples_length) * fft_size;
-        if (opt.fine_doppler) {
+        if (opt.fine_doppler || opt.refine_doppler) {
             // hits on satellites that are tracked already go nowhere (:315-320 would hand them over again; the mask
             // normally excludes them) — refine only what is about to start a channel
             bool any = false;
             for (auto& r : *results) { if (r && active_prns.count(r->prn)) r.reset(); any = any || bool(r); }
             if (any) {
                 t0 = std::chrono::steady_clock::now();
-                const std::vector<float> fine = workers.finer_doppler(*results);
-                for (size_t i = 0; i < results->size(); ++i)
-                    if ((*results)[i] && std::isfinite(fine[i])) (*results)[i]->carrier_freq = fine[i];
+                if (opt.refine_doppler) {
+                    const auto fine = workers.refine_doppler(*results);
+                    for (size_t i = 0; i < results->size(); ++i)
+                        if ((*results)[i] && fine[i] && std::isfinite(fine[i]->carrier_hz)) (*results)[i]->carrier_freq = float(fine[i]->carrier_hz);
+                } else {
+                    const std::vector<float> fine = workers.finer_doppler(*results);
+                    for (size_t i = 0; i < results->size(); ++i)
+                        if ((*results)[i] && std::isfinite(fine[i])) (*results)[i]->carrier_freq = fine[i];
+                }
                 ctl.fine_ns += stage_ns(t0);
             }
         }

@@ -40,6 +40,7 @@ extern "C" {
                               gm_acq_set_edge_search, gm_acq_edge_metrics, gm_acq_edge_choice, gm_acq_result_offsets;
                               and the code-drift compensation — gm_acq_set_code_drift, gm_acq_code_drift_plan,
                               gm_acq_dwell_samples, gm_acq_code_drift_starts, gm_acq_code_drift_phasors;
+                              and the fine Doppler from per-period prompts — gm_acq_refine_doppler, gm_acq_refine_plan;
                               8: gm_acq_cfg.any_length, gm_acq_plan_info;
                               7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
@@ -240,7 +241,8 @@ int gm_acq_search_ring(gm_acq *a, gm_ring *ring, uint64_t prn_mask, gm_acq_resul
  * gives fine_freq_hz[p] = (idx*fs)/fft_size (:251-253), i.e. IF + Doppler to fs/fft_size (7.6 Hz at 8 Msps, 10 ms).
  * Indices above fft_size/2 are reported as negative frequencies (the legacy indexes out of bounds there, :285-288, and
  * multiplies by (-1)^is_complex, :298-299: neither is reproduced).  Entries of not-found PRNs are left untouched.
- * Any output pointer may be NULL.  Synchronous.  GM_ERR_UNSUPPORTED_N if the long FFT does not factor into two in-LDS plans. */
+ * Any output pointer may be NULL.  Synchronous.  GM_ERR_UNSUPPORTED_N if the long FFT does not factor into two in-LDS plans.
+ * gm_acq_refine_doppler (below, after the code-drift entries) is the estimator that follows the coherent, edge and drift handles. */
 int gm_acq_finer_doppler(gm_acq *a, const gm_acq_result *results, const uint8_t *found, uint32_t n_prn,
                          float *fine_freq_hz, uint64_t *peak_index, float *peak_mag, uint64_t *fft_size);
 
@@ -448,6 +450,56 @@ int gm_acq_code_drift_starts(gm_acq *a, uint64_t *out);
 /* Hypothesis h's phasor words [n_bins][n_integrations][K] as they sit in device memory (h = 0 without an edge search; the secondary
  * row's signs are applied on the way into the fold and do not show here; (1, 0) throughout at K <= 1, where they are not used). */
 int gm_acq_code_drift_phasors(gm_acq *a, uint32_t h, gm_c32 *out);
+/* ---- Fine Doppler from per-period prompts: the search's own detection statistic on a fine frequency grid around the winning bin, built
+ * from the pieces the search used — valid wherever the search is (coherent_periods 0 .. 32, the edge search and its secondary row, the
+ * code-drift compensation, every form gm_acq_plan_info reports, every sample format).  For a found worker w with d =
+ * results[w].doppler_bin and cp = results[w].code_phase_samples let o be the offset in periods its cell chose (gm_acq_result_offsets; 0
+ * without an edge search), s[d][.] the period starts in use (p * fft_size without the compensation), tab[d] the handle's mix table,
+ * c_w the handle's resampled replica, f_c = table_freq[d], N = fft_size.
+ *   Prompts, i = 0 .. R_u-1:   z[i] = sum_{n<N} x[s[d][o+i] + n] * tab[d][n] * c_w[(n - cp) mod N]
+ *     the circular correlation value at lag cp of period o+i alone: only samples the search read.  f32; the sample-table product is
+ *     formed as in stage F; the N terms are added in a fixed order (no floating-point atomics): two calls give the same words.
+ *   Groups.  K >= 2: the search's own — J = K, G = n_integrations, R_u = K*G, signs sigma_k = the edge search's secondary row (all +1
+ *     without one); span_periods must be 0 or K.  K <= 1: J = span_periods (0 -> n_integrations), G = floor(n_integrations / J),
+ *     R_u = G*J, sigma = +1.  An effective J < 2 (one period carries no frequency information) or G < 1: GM_ERR_INVALID_ARG.
+ *   Grid.  Z = n_freq points, odd, 3 .. 4097 (0 -> 257); delta_j = (j - (Z-1)/2) * step, step = half_span / ((Z-1)/2).  half_span_hz
+ *     0 -> half the distance from f_c to the farther neighbouring bin's table_freq, at most fs / (2N); a one-bin handle:
+ *     fs / (2 N max(K,1)).  A given value above fs / (2N) (per-period prompts alias there), negative or not a number:
+ *     GM_ERR_INVALID_ARG.
+ *   Statistic.   S[j] = N^2 * sum_{g<G} | sum_{k<J} sigma_k * w_{g,k}(delta_j) * z[gJ+k] |^2,
+ *                w_{g,k}(delta) = exp(-j 2 pi frac((f_c + delta) * (s[d][o+gJ+k] - s[d][o+gJ]) / fs))
+ *     the cycles formed and reduced to one cycle in f64 (as the coherent and drift phasor words are), f32 sine / cosine after that.
+ *     The N^2 puts S in gm_acq_metrics' units: at K >= 2 S at delta = 0 is the accumulated peak power of cell (w, d), FFT rounding
+ *     aside (at K <= 1 that power is N^2 * sum_i |z[i]|^2 over the n_integrations periods).
+ *   Peak.  peak_index = the first index of the maximum; delta_hz = delta_peak plus a three-point parabolic offset (host, f64);
+ *     at_edge = 1 when the peak is at j = 0 or Z-1: no interpolation then, and the caller should widen the span.
+ * Cost: R_u * N sample, table and replica reads per satellite (one 256-lane workgroup per (period, satellite)), no long FFT. */
+typedef struct { uint32_t span_periods; uint32_t n_freq; float half_span_hz; } gm_acq_refine_cfg;   /* zeros: defaults */
+typedef struct {
+    double   carrier_hz;      /* table_freq[d] + delta_hz, f64: an f32 resolves 0.5 Hz at 4 MHz */
+    float    delta_hz, step_hz, half_span_hz;
+    float    peak_power, center_power;          /* S[peak_index], S[(Z-1)/2] */
+    uint32_t peak_index, at_edge;
+    uint32_t doppler_bin, offset_periods, span_periods, n_groups, n_freq;
+} gm_acq_refine_out;
+/* Works like gm_acq_finer_doppler: on the snapshot of the LAST search on this handle (gm_acq_search, _search_dev,
+ * _search_prepared_dev, _search_ring), on the handle's stream, synchronous; entries of not-found workers are left untouched (out,
+ * prompts and spectrum alike).  It runs a pending deferred decision first and changes no metric, choice or result word.
+ *   out      : [n_prn]
+ *   prompts  : [n_prn][R_u] or NULL;  spectrum : [n_prn][Z] or NULL  (R_u and Z: gm_acq_refine_plan)
+ * GM_ERR_INVALID_ARG: a null handle (no device is touched), results, found or out; no search yet on this handle (or none since the last
+ * gm_acq_set_edge_search / gm_acq_set_code_drift); n_prn above the handle's workers; a found entry's doppler_bin outside the bins or
+ * code phase >= fft_size; the span / n_freq / half-span rules above.  All found flags zero: GM_OK, nothing written.
+ * Device memory: one block of about n_found * (16 R_u + 4 Z + 40) bytes, built at the first call and grown when a call needs more — the new
+ * block is allocated before the old one goes (GM_ERR_NOMEM leaves the handle as it was); gm_acq_destroy releases it.
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+int gm_acq_refine_doppler(gm_acq *a, const gm_acq_result *results, const uint8_t *found, uint32_t n_prn,
+                          const gm_acq_refine_cfg *cfg /* NULL: defaults */, gm_acq_refine_out *out /* [n_prn] */,
+                          gm_c32 *prompts /* [n_prn][R_u] or NULL */, float *spectrum /* [n_prn][Z] or NULL */);
+/* host only, no device: the argument rules and what a call would use for `bin` (any output pointer may be NULL) */
+int gm_acq_refine_plan(uint32_t coherent_periods, uint32_t n_integrations, const gm_acq_refine_cfg *cfg, float fs,
+                       uint32_t fft_size, uint32_t n_bins, const float *table_freq, uint32_t bin,
+                       uint32_t *span_periods, uint32_t *n_groups, uint32_t *n_freq, double *half_span_hz, double *step_hz);
 /* Kernel timing of the last gm_acq_search*_dev call, measured with HIP events on the handle's
  * stream: ms_mix_fft (stage F), ms_corr (stage C, the dominant kernel), ms_decide.  Enable first: on = 1 times every
  * search, on = k > 1 every k-th (an event record costs about 2 us of stream time; four per timed search), 0 disables. */

@@ -71,6 +71,18 @@ pub struct GmTrkCfg {               // gm_trk_cfg (zero = reference default)
     pub strict_sum_order: i32,      // 1 = the correlator sums added sample by sample like do_tracking.rs:256-262 (with strict_libm: bit-identical state)
     pub share_device: i32,          // 1 = a receiver: the tracking kernel leaves room for the front-end's and the acquisition's kernels beside it (ABI 6)
 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmAcqRefineCfg {         // gm_acq_refine_cfg (zeros: the defaults)
+    pub span_periods: u32, pub n_freq: u32, pub half_span_hz: f32,
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmAcqRefineOut {         // gm_acq_refine_out
+    pub carrier_hz: f64,             // table_freq[doppler_bin] + delta_hz
+    pub delta_hz: f32, pub step_hz: f32, pub half_span_hz: f32,
+    pub peak_power: f32, pub center_power: f32,
+    pub peak_index: u32, pub at_edge: u32,
+    pub doppler_bin: u32, pub offset_periods: u32, pub span_periods: u32, pub n_groups: u32, pub n_freq: u32,
+}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {}
 
 extern "C" {
@@ -98,6 +110,13 @@ extern "C" {
     pub fn gm_acq_dwell_samples(a: *mut GmAcq, out: *mut u64) -> c_int;
     pub fn gm_acq_code_drift_starts(a: *mut GmAcq, out: *mut u64) -> c_int;
     pub fn gm_acq_code_drift_phasors(a: *mut GmAcq, h: u32, out: *mut Complex32) -> c_int;
+    // fine Doppler from per-period prompts (additive entries, ABI stays 9): the search's own statistic on a fine frequency grid around
+    // the winning bin, with the handle's coherent groups, edge offset, secondary row and code-drift starts
+    pub fn gm_acq_refine_doppler(a: *mut GmAcq, results: *const GmAcqResult, found: *const u8, n_prn: u32, cfg: *const GmAcqRefineCfg,
+                                 out: *mut GmAcqRefineOut, prompts: *mut Complex32, spectrum: *mut f32) -> c_int;
+    pub fn gm_acq_refine_plan(coherent_periods: u32, n_integrations: u32, cfg: *const GmAcqRefineCfg, fs: f32, fft_size: u32,
+                              n_bins: u32, table_freq: *const f32, bin: u32, span_periods: *mut u32, n_groups: *mut u32,
+                              n_freq: *mut u32, half_span_hz: *mut f64, step_hz: *mut f64) -> c_int;
     // do_acquisition.rs:302-313 + :158-226  (par_iter over workers / search_satellite)
     pub fn gm_acq_search_c32(a: *mut GmAcq, samples: *const Complex32, n: usize, local_tail: u64,
                              prn_mask: u64, results: *mut GmAcqResult, found: *mut u8) -> c_int;

@@ -142,6 +142,16 @@ impl AcquisitionEngine {
         if unsafe { gm_acq_dwell_samples(self.h, &mut n) } != 0 { return Err(AcqError); }
         Ok(n)
     }
+    /// Not in the reference: the fine Doppler of the found entries of `raw` (the results of the LAST search on this engine, one per
+    /// worker, with their `doppler_bin`) from per-period prompts — valid with coherent groups, the edge search and the code drift.
+    /// `cfg` zeros are the defaults.  -> per entry Some(out) where found, out.carrier_hz being the refined IF + Doppler.
+    pub fn refine_doppler(&mut self, raw: &[GmAcqResult], found: &[u8], cfg: &GmAcqRefineCfg) -> Result<Vec<Option<GmAcqRefineOut>>, AcqError> {
+        if raw.len() != found.len() { return Err(AcqError); }
+        let mut out = vec![GmAcqRefineOut::default(); raw.len()];
+        if unsafe { gm_acq_refine_doppler(self.h, raw.as_ptr(), found.as_ptr(), raw.len() as u32, cfg, out.as_mut_ptr(),
+                                          std::ptr::null_mut(), std::ptr::null_mut()) } != 0 { return Err(AcqError); }
+        Ok(out.into_iter().zip(found).map(|(o, f)| if *f != 0 { Some(o) } else { None }).collect())
+    }
     /// the body of `workers.par_iter_mut().enumerate().filter_map(..search_satellite..)` (:302-313)
     pub fn search(&mut self, chunk: &[Complex32], local_tail: usize, mask: u32) -> Vec<AcquisitionResult> {
         let mut raw = vec![GmAcqResult::default(); self.n_prn];
