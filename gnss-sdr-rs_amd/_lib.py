@@ -54,6 +54,28 @@ class AcqRefineOut(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AcqCand(C.Structure):
+    """gm_acq_cand: a known (worker, bin, code phase, offset) cell for gm_acq_local_search"""
+    _fields_ = [("worker", C.c_uint32), ("doppler_bin", C.c_int32), ("code_phase_samples", C.c_uint32), ("offset_periods", C.c_uint32)]
+
+
+class AcqLocalCfg(C.Structure):
+    """gm_acq_local_cfg: zeros are the defaults"""
+    _fields_ = [("lag_half_window", C.c_uint32), ("span_periods", C.c_uint32), ("n_freq", C.c_uint32), ("half_span_hz", C.c_float)]
+
+
+class AcqLocalOut(C.Structure):
+    """gm_acq_local_out (88 bytes)"""
+    _fields_ = [("carrier_hz", C.c_double), ("code_phase_fine", C.c_double), ("delta_hz", C.c_float), ("step_hz", C.c_float),
+                ("half_span_hz", C.c_float), ("peak_power", C.c_float), ("floor_power", C.c_float), ("peak_lag_index", C.c_uint32),
+                ("peak_freq_index", C.c_uint32), ("code_phase_samples", C.c_uint32), ("lag_at_edge", C.c_uint32),
+                ("freq_at_edge", C.c_uint32), ("n_floor", C.c_uint32), ("doppler_bin", C.c_uint32), ("offset_periods", C.c_uint32),
+                ("span_periods", C.c_uint32), ("n_groups", C.c_uint32), ("n_freq", C.c_uint32), ("n_lags", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 ACQ_FORM_LDS, ACQ_FORM_COMPOSITE, ACQ_FORM_LONG, ACQ_FORM_LONG_PADDED = 0, 1, 2, 3   # gm_acq_form
 
 
@@ -152,6 +174,9 @@ SIGNATURES = {
     "gm_acq_refine_doppler": (_i, [_vp, _vp, _vp, _u32, C.POINTER(AcqRefineCfg), _vp, _vp, _vp]),
     "gm_acq_refine_plan": (_i, [_u32, _u32, C.POINTER(AcqRefineCfg), _f, _u32, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32),
                             C.POINTER(_u32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gm_acq_local_search": (_i, [_vp, _vp, _i, _vp, _u32, C.POINTER(AcqLocalCfg), _vp, _vp, _vp]),
+    "gm_acq_local_plan": (_i, [_u32, _u32, C.POINTER(AcqLocalCfg), _f, _u32, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32),
+                           C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gm_acq_enable_timing": (_i, [_vp, _i]),
     "gm_acq_last_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
     "gm_acq_timing_summary": (_i, [_vp, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f)]),

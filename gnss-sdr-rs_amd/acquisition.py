@@ -6,7 +6,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import AcqCfg, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
+from ._lib import AcqCand, AcqCfg, AcqLocalCfg, AcqLocalOut, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
 
 PRN_SEARCH_ACQUISITION_TOTAL = 32      # do_acquisition.rs:22
 FREQ_SEARCH_ACQUISITION_HZ = 14e3      # :20
@@ -162,6 +162,21 @@ def refine_plan(coherent_periods, n_integrations, fs, fft_size, table_freq, bin=
                                    _p(tf) if tf.size else None, int(bin), C.byref(j), C.byref(g), C.byref(z), C.byref(hs),
                                    C.byref(st)), "gm_acq_refine_plan")
     return dict(span_periods=j.value, n_groups=g.value, n_freq=z.value, half_span_hz=hs.value, step_hz=st.value)
+
+
+def local_plan(coherent_periods, n_integrations, fs, fft_size, table_freq, bin=0, lag_half_window=0, span_periods=0, n_freq=0,
+               half_span_hz=0.0):
+    """gm_acq_local_plan: what local_search would use for Doppler bin `bin` of a handle with these settings, after its argument checks
+    (GmError INVALID_ARG) -> dict(n_lags, span_periods, n_groups, n_freq, half_span_hz, step_hz): refine_plan's rules plus the lag
+    window's (lag_half_window 0 .. 64, 2 lag_half_window + 1 <= fft_size).  Host only."""
+    tf = np.ascontiguousarray(table_freq, np.float32).reshape(-1)
+    cfg = AcqLocalCfg(int(lag_half_window), int(span_periods), int(n_freq), float(half_span_hz))
+    w, j, g, z = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    hs, st = C.c_double(0), C.c_double(0)
+    check(lib().gm_acq_local_plan(int(coherent_periods), int(n_integrations), C.byref(cfg), float(fs), int(fft_size), tf.size,
+                                  _p(tf) if tf.size else None, int(bin), C.byref(w), C.byref(j), C.byref(g), C.byref(z), C.byref(hs),
+                                  C.byref(st)), "gm_acq_local_plan")
+    return dict(n_lags=w.value, span_periods=j.value, n_groups=g.value, n_freq=z.value, half_span_hz=hs.value, step_hz=st.value)
 
 
 class AcquisitionEngine:
@@ -402,6 +417,43 @@ class AcquisitionEngine:
                 d["prompts"] = z[i].copy()
             if s is not None:
                 d["spectrum"] = s[i].copy()
+            ret.append(d)
+        return ret
+
+    def local_search(self, cands, samples=None, lag_half_window=0, span_periods=0, n_freq=0, half_span_hz=0.0, want_prompts=False,
+                     want_surface=False, fmt=FMT_C32):
+        """Lag window x fine Doppler at known cells (gm_acq_local_search): refine_doppler's statistic on the 2 lag_half_window + 1 code
+        phases around each candidate's, all lags from one pass over the samples.  A candidate is a dict with `worker`, `doppler_bin`,
+        `code_phase_samples` (the window's centre) and `offset_periods`.  samples None: the snapshot of the last search; else a device
+        pointer to dwell_samples samples in format `fmt` (as search_dev takes them) — any dwell, read only, not made the snapshot.
+        -> list of dict(carrier_hz, code_phase_fine, delta_hz, step_hz, half_span_hz, peak_power, floor_power, peak_lag_index,
+        peak_freq_index, code_phase_samples, lag_at_edge, freq_at_edge, n_floor, doppler_bin, offset_periods, span_periods, n_groups,
+        n_freq, n_lags); with want_prompts `prompts` (complex64 [n_lags][span_periods * n_groups]), with want_surface `surface`
+        (float32 [n_lags][n_freq]).  The library makes no detection decision."""
+        n = len(cands)
+        cs = (AcqCand * max(n, 1))()
+        for i, c in enumerate(cands):
+            cs[i] = AcqCand(int(c["worker"]), int(c["doppler_bin"]), int(c["code_phase_samples"]), int(c.get("offset_periods", 0)))
+        cfg = AcqLocalCfg(int(lag_half_window), int(span_periods), int(n_freq), float(half_span_hz))
+        out = (AcqLocalOut * max(n, 1))()
+        z = s = None
+        if n and (want_prompts or want_surface):
+            plan = local_plan(self.K, self.M, self.fs, self.fft_size, self.table_freq, 0, lag_half_window, span_periods, n_freq,
+                              half_span_hz)
+            if want_prompts:
+                z = np.zeros((n, plan["n_lags"], plan["span_periods"] * plan["n_groups"]), np.complex64)
+            if want_surface:
+                s = np.zeros((n, plan["n_lags"], plan["n_freq"]), np.float32)
+        check(lib().gm_acq_local_search(self._h, C.c_void_p(samples) if samples else None, int(fmt), C.cast(cs, C.c_void_p), n,
+                                        C.byref(cfg), C.cast(out, C.c_void_p), _p(z) if z is not None else None,
+                                        _p(s) if s is not None else None), "gm_acq_local_search")
+        ret = []
+        for i in range(n):
+            d = out[i].as_dict()
+            if z is not None:
+                d["prompts"] = z[i].copy()
+            if s is not None:
+                d["surface"] = s[i].copy()
             ret.append(d)
         return ret
 

@@ -417,6 +417,11 @@ struct gm_acq {
         void* d_block = nullptr;
         size_t bytes = 0;
     } refine;
+    // lag window x fine Doppler at known cells (gm_acq_local_search): one device block of its own, carved per call and grown like refine's
+    struct Local {
+        void* d_block = nullptr;
+        size_t bytes = 0;
+    } local;
 };
 
 // the fused single-LDS-buffer kernels (acq_kernels.hip): neither a composite nor an any-length size
@@ -748,6 +753,7 @@ int gm_acq_destroy(gm_acq* a) {
     hipFree(a->fine.d_rowmax); hipFree(a->fine.d_rowarg); hipFree(a->fine.d_sat_worker); hipFree(a->fine.d_sat_cp);
     hipFree(a->fine.d_peak_pow); hipFree(a->fine.d_peak_idx);
     hipFree(a->refine.d_block);
+    hipFree(a->local.d_block);
     if (a->device >= 0) hipSetDevice(a->device);
     hipFree(a->d_tw_mix);
     hipFree(a->d_tables); hipFree(a->d_tw_fwd); hipFree(a->d_tw_inv); hipFree(a->d_code_fft); hipFree(a->d_code_fft_paired); hipFree(a->d_order);
@@ -1939,6 +1945,168 @@ int gm_acq_refine_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t
         r.doppler_bin = sats[i].bin; r.offset_periods = sats[i].offset; r.span_periods = J; r.n_groups = G; r.n_freq = Z;
         if (prompts) memcpy(prompts + size_t(p) * R_u, &zh[size_t(i) * R_u], size_t(R_u) * 8);
         if (spectrum) memcpy(spectrum + size_t(p) * Z, sp, size_t(Z) * 4);
+    }
+    return GM_OK;
+}
+
+// ---------------------------------------------------------------- lag window x fine Doppler at known cells (additive entries, ABI 9)
+static int local_rules(uint32_t coherent_periods, uint32_t M, const gm_acq_local_cfg* cfg, double fs, uint32_t N, uint32_t D,
+                       const float* table_freq, uint32_t bin, RefinePlan& o, uint32_t& L) {
+    const gm_acq_local_cfg c = cfg ? *cfg : gm_acq_local_cfg{0u, 0u, 0u, 0.0f};
+    const gm_acq_refine_cfg rc{c.span_periods, c.n_freq, c.half_span_hz};
+    if (int rv = refine_rules(coherent_periods, M, &rc, fs, N, D, table_freq, bin, o)) return rv;
+    if (c.lag_half_window > 64u) return set_err(GM_ERR_INVALID_ARG, "lag_half_window > 64");
+    if (2u * c.lag_half_window + 1u > N) return set_err(GM_ERR_INVALID_ARG, "the lag window (2 lag_half_window + 1) exceeds fft_size");
+    L = c.lag_half_window;
+    return GM_OK;
+}
+
+int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const gm_acq_local_cfg* cfg, float fs, uint32_t fft_size,
+                      uint32_t n_bins, const float* table_freq, uint32_t bin, uint32_t* n_lags, uint32_t* span_periods,
+                      uint32_t* n_groups, uint32_t* n_freq, double* half_span_hz, double* step_hz) {
+    RefinePlan o;
+    uint32_t L = 0;
+    if (int rc = local_rules(coherent_periods, n_integrations, cfg, double(fs), fft_size, n_bins, table_freq, bin, o, L)) return rc;
+    if (n_lags) *n_lags = 2 * L + 1;
+    if (span_periods) *span_periods = o.J;
+    if (n_groups) *n_groups = o.G;
+    if (n_freq) *n_freq = o.Z;
+    if (half_span_hz) *half_span_hz = o.half_span;
+    if (step_hz) *step_hz = o.step;
+    return GM_OK;
+}
+
+int gm_acq_local_search(gm_acq* a, const void* d_samples, int fmt, const gm_acq_cand* cands, uint32_t n_cands,
+                        const gm_acq_local_cfg* cfg, gm_acq_local_out* out, gm_c32* prompts, float* surface) {
+    if (!a || !cands || !out) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (d_samples) {
+        if (fmt < GM_FMT_C32 || fmt > GM_FMT_I8_REAL) return set_err(GM_ERR_INVALID_ARG, "bad sample format");
+    } else if (!a->last_samples) return set_err(GM_ERR_INVALID_ARG, "no search has run on this handle yet");
+    const uint32_t N = a->N, D = a->D;
+    const double fs = double(a->cfg.fs);
+    // every argument is checked before anything runs or is written
+    RefinePlan common;
+    uint32_t L = 0;
+    if (int rc = local_rules(a->cfg.coherent_periods, a->M, cfg, fs, N, D, a->table_freq.data(), 0, common, L)) return rc;
+    std::vector<RefinePlan> plans(n_cands);
+    for (uint32_t c = 0; c < n_cands; ++c) {
+        if (cands[c].worker >= a->P) return set_err(GM_ERR_INVALID_ARG, "candidate.worker outside the handle's workers");
+        const int32_t d = cands[c].doppler_bin;
+        if (d < 0 || uint32_t(d) >= D) return set_err(GM_ERR_INVALID_ARG, "candidate.doppler_bin outside the handle's bins");
+        if (cands[c].code_phase_samples >= N) return set_err(GM_ERR_INVALID_ARG, "candidate.code_phase_samples >= fft_size");
+        if (cands[c].offset_periods > (a->edge.H ? a->edge.o_max : 0u))
+            return set_err(GM_ERR_INVALID_ARG, "candidate.offset_periods above the edge search's last offset (0 without an edge search)");
+        uint32_t l = 0;
+        if (int rc = local_rules(a->cfg.coherent_periods, a->M, cfg, fs, N, D, a->table_freq.data(), uint32_t(d), plans[c], l)) return rc;
+    }
+    if (!n_cands) return GM_OK;
+    if (int rc = ensure_device(a->device)) return rc;
+    if (int rc = acq_flush_decision(a)) return rc;
+    const uint32_t S = n_cands, W = 2 * L + 1, J = common.J, G = common.G, Z = common.Z, R_u = J * G;
+    const size_t rows = size_t(S) * W;
+    // the block: [cands | z | t | fc | step | surface | row maxima | row indices | row sums | picks], every part 256-byte aligned
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_cand = 0, o_z = o_cand + up(size_t(S) * sizeof(gm::RefineSat)), o_t = o_z + up(rows * R_u * 8),
+                 o_fc = o_t + up(size_t(S) * R_u * 8), o_step = o_fc + up(size_t(S) * 8), o_surf = o_step + up(size_t(S) * 8),
+                 o_rv = o_surf + up(rows * Z * 4), o_ri = o_rv + up(rows * 4), o_rs = o_ri + up(rows * 4), o_pk = o_rs + up(rows * 8),
+                 total = o_pk + up(size_t(S) * sizeof(gm::LocalPick));
+    gm_acq::Local& lc = a->local;
+    if (total > lc.bytes) {                 // the new block before the old one goes: a failure leaves the handle as it was
+        void* blk = nullptr;
+        if (hipMalloc(&blk, total) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(GM_ERR_NOMEM, "the local-search block does not fit (gnss_mi355x.h states the formula); the handle is as it was");
+        }
+        if (hipError_t e = hipStreamSynchronize(a->stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
+        hipFree(lc.d_block);
+        lc.d_block = blk; lc.bytes = total;
+    }
+    char* const base = static_cast<char*>(lc.d_block);
+    // host side of the block's inputs, as gm_acq_refine_doppler forms them: the period times of every group (f64, relative to the
+    // group's first period: whole samples over fs), the centre frequency and the grid step
+    std::vector<gm::RefineSat> cs(S);
+    std::vector<double> t(size_t(S) * R_u), fc(S), step(S);
+    for (uint32_t c = 0; c < S; ++c) {
+        const uint32_t d = uint32_t(cands[c].doppler_bin), o = cands[c].offset_periods;
+        cs[c] = gm::RefineSat{cands[c].worker, cands[c].code_phase_samples, d, o};
+        fc[c] = double(a->table_freq[d]);
+        step[c] = plans[c].step;
+        for (uint32_t g = 0; g < G; ++g)
+            for (uint32_t k = 0; k < J; ++k) {
+                const uint32_t q0 = o + g * J, q = q0 + k;
+                const uint64_t s0 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q0] : uint64_t(q0) * N;
+                const uint64_t s1 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q] : uint64_t(q) * N;
+                t[size_t(c) * R_u + g * J + k] = double(s1 - s0) / fs;
+            }
+    }
+    HIPC(hipMemcpyAsync(base + o_cand, cs.data(), size_t(S) * sizeof(gm::RefineSat), hipMemcpyHostToDevice, a->stream));
+    HIPC(hipMemcpyAsync(base + o_t, t.data(), t.size() * 8, hipMemcpyHostToDevice, a->stream));
+    HIPC(hipMemcpyAsync(base + o_fc, fc.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
+    HIPC(hipMemcpyAsync(base + o_step, step.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
+    gm::LocalArgs la{};
+    la.samples = d_samples ? d_samples : a->last_samples; la.fmt = d_samples ? fmt : a->last_fmt;
+    la.starts = a->drift.on ? a->drift.d_starts : nullptr; la.R = a->drift.on ? a->drift.R : 0u;
+    la.tables = a->d_tables; la.code_samples = a->d_code_samples;
+    la.cands = reinterpret_cast<const gm::RefineSat*>(base + o_cand); la.n_cands = S;
+    la.N = N; la.R_u = R_u; la.J = J; la.G = G; la.Z = Z; la.L = L;
+    la.neg = (a->K >= 2 && a->edge.H) ? a->edge.neg : 0u;
+    la.guard = uint32_t(::ceil(fs / double(a->code_rate))) + 1u;
+    la.z = reinterpret_cast<cf*>(base + o_z); la.t = reinterpret_cast<const double*>(base + o_t);
+    la.fc = reinterpret_cast<const double*>(base + o_fc); la.step = reinterpret_cast<const double*>(base + o_step);
+    la.surface = reinterpret_cast<float*>(base + o_surf);
+    la.row_val = reinterpret_cast<float*>(base + o_rv); la.row_idx = reinterpret_cast<uint32_t*>(base + o_ri);
+    la.row_sum = reinterpret_cast<double*>(base + o_rs); la.picks = reinterpret_cast<gm::LocalPick*>(base + o_pk);
+    gm::launch_local(a->stream, la);
+    HIPC(hipGetLastError());
+    std::vector<gm::LocalPick> pk(S);
+    HIPC(hipMemcpyAsync(pk.data(), base + o_pk, size_t(S) * sizeof(gm::LocalPick), hipMemcpyDeviceToHost, a->stream));
+    // the caller's arrays have the block's layout: filled directly, after every check and launch has passed
+    if (prompts) HIPC(hipMemcpyAsync(prompts, base + o_z, rows * R_u * 8, hipMemcpyDeviceToHost, a->stream));
+    if (surface) HIPC(hipMemcpyAsync(surface, base + o_surf, rows * Z * 4, hipMemcpyDeviceToHost, a->stream));
+    HIPC(hipStreamSynchronize(a->stream));
+    for (uint32_t c = 0; c < S; ++c) {
+        const gm::LocalPick& p = pk[c];
+        const uint32_t d = cs[c].bin, o = cs[c].offset, ls = p.l < W ? p.l : L, js = p.j < Z ? p.j : (Z - 1) / 2;
+        gm_acq_local_out& r = out[c];
+        r.freq_at_edge = (js == 0 || js == Z - 1) ? 1u : 0u;
+        double delta = (double(js) - double((Z - 1) / 2)) * step[c];
+        if (!r.freq_at_edge) {              // gm_acq_refine_doppler's three-point parabola along j, f64
+            const double y0 = p.s_jm, y1 = p.s0, y2 = p.s_jp, den = y0 - 2.0 * y1 + y2;
+            double x = den < 0.0 ? 0.5 * (y0 - y2) / den : 0.0;
+            x = x > 0.5 ? 0.5 : (x < -0.5 ? -0.5 : x);
+            delta += x * step[c];
+        }
+        r.carrier_hz = fc[c] + delta;
+        r.delta_hz = float(delta); r.step_hz = float(step[c]); r.half_span_hz = float(plans[c].half_span);
+        r.peak_power = p.s0;
+        r.floor_power = p.n_floor ? float(p.floor_sum / (double(p.n_floor) * double(Z))) : 0.0f;
+        r.n_floor = p.n_floor;
+        r.peak_lag_index = ls; r.peak_freq_index = js;
+        const uint32_t lam = (cs[c].code_phase + N - L + ls) % N;          // lambda_{l*}: cp < N, L < N
+        r.code_phase_samples = lam;
+        r.lag_at_edge = (ls == 0 || ls == W - 1) ? 1u : 0u;
+        r.code_phase_fine = double(lam);
+        if (!r.lag_at_edge) {
+            // the vertex of a symmetric triangle through the three amplitudes
+            const double am = ::sqrt(double(p.s_lm)), a0 = ::sqrt(double(p.s0)), ap = ::sqrt(double(p.s_lp));
+            const double den = 2.0 * (a0 - (am < ap ? am : ap));
+            double frac = den > 0.0 ? (ap - am) / den : 0.0;
+            frac = frac > 0.5 ? 0.5 : (frac < -0.5 ? -0.5 : frac);
+            const double lambda = double(lam) + frac;
+            double fine = lambda;
+            if (a->drift.on) {
+                // the starts' roundings, and the samples in front of the lag, which belong to the previous (shorter or longer) period
+                const double T = a->drift.T[d];
+                double e = 0.0;
+                for (uint32_t i = 0; i < R_u; ++i) e += double(a->drift.starts[size_t(d) * a->drift.R + o + i]) - double(o + i) * T;
+                fine = lambda + e / double(R_u) - (lambda / double(N)) * (double(N) - T);
+            }
+            fine = ::fmod(fine, double(N));
+            if (fine < 0.0) fine += double(N);
+            if (fine >= double(N)) fine -= double(N);
+            r.code_phase_fine = fine;
+        }
+        r.doppler_bin = d; r.offset_periods = o; r.span_periods = J; r.n_groups = G; r.n_freq = Z; r.n_lags = W;
     }
     return GM_OK;
 }

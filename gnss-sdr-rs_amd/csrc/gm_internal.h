@@ -76,6 +76,31 @@ struct RefineArgs {
 };
 void launch_refine(hipStream_t, const RefineArgs&);
 
+// Lag window x fine Doppler at known cells (gm_acq_local_search, acq_local.hip): the despreading kernel on grid (R_u, n_cands) serves
+// all W = 2L + 1 lags of a (period, candidate) from one pass over the samples, the scan runs on grid (W, n_cands), the pick per
+// candidate.  A candidate is a RefineSat whose code_phase is the window's centre.
+struct LocalPick {
+    double floor_sum;                      // sum of S over all j of the n_floor rows at least `guard` lags from the peak
+    float s0, s_jm, s_jp, s_lm, s_lp, s_c; // S at the peak, its neighbours along j and along l (0 past a rim), S[l*][(Z-1)/2]
+    uint32_t l, j, n_floor;                // the first maximum in (l, j) order
+};
+struct LocalArgs {
+    const void* samples; int fmt;          // the snapshot of the last search, or the caller's dwell
+    const uint64_t* starts; uint32_t R;    // as RefineArgs
+    const cf* tables;
+    const int8_t* code_samples;
+    const RefineSat* cands; uint32_t n_cands;
+    uint32_t N, R_u, J, G, Z, L;           // L = lag_half_window (<= 64, 2L + 1 <= N)
+    uint32_t neg, guard;                   // bit k set: sigma_k = -1; the floor's least circular distance in lags
+    cf* z;                                 // [n_cands][W][R_u] prompts
+    const double* t;                       // [n_cands][R_u]
+    const double *fc, *step;               // [n_cands]
+    float* surface;                        // [n_cands][W][Z]
+    float* row_val; uint32_t* row_idx; double* row_sum;   // [n_cands][W] first maximum and sum of every row
+    LocalPick* picks;                      // [n_cands]
+};
+void launch_local(hipStream_t, const LocalArgs&);
+
 // One entry per shipped transform size: launchers for the kernels instantiated on that plan.
 struct DecideArgs;
 struct PlanOps {

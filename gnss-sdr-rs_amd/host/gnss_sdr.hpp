@@ -169,6 +169,15 @@ public:
         for (size_t i = 0; i < results.size(); ++i) if (f[i]) out[i] = o[i];
         return out;
     }
+    // Lag window x fine Doppler at known cells (gm_acq_local_search): refine_doppler's statistic on 2 * cfg.lag_half_window + 1 code
+    // phases around every candidate's, from one pass over the samples — on the snapshot of the last search (d_samples null) or on any
+    // dwell of dwell_samples() samples in device memory (read only; it does not become the snapshot).  No detection decision is made.
+    std::vector<gm_acq_local_out> local_search(const std::vector<gm_acq_cand>& cands, const gm_acq_local_cfg& cfg = {},
+                                               const void* d_samples = nullptr, int fmt = GM_FMT_C32) {
+        std::vector<gm_acq_local_out> out(cands.size());
+        check(gm_acq_local_search(h_, d_samples, fmt, cands.data(), uint32_t(cands.size()), &cfg, out.data(), nullptr, nullptr), "local_search");
+        return out;
+    }
     // The edge search of a coherent handle (gm_acq_set_edge_search): H ascending period offsets (each 0..63, H <= 32) and an optional
     // secondary row of coherent_periods entries +-1 (empty: all +1); no offsets switch it off.  While it is on a dwell is
     // (K * n_integrations + offsets.back()) * fft_size samples.

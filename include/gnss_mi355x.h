@@ -41,6 +41,7 @@ extern "C" {
                               and the code-drift compensation — gm_acq_set_code_drift, gm_acq_code_drift_plan,
                               gm_acq_dwell_samples, gm_acq_code_drift_starts, gm_acq_code_drift_phasors;
                               and the fine Doppler from per-period prompts — gm_acq_refine_doppler, gm_acq_refine_plan;
+                              and the lag window x fine Doppler at known cells — gm_acq_local_search, gm_acq_local_plan;
                               8: gm_acq_cfg.any_length, gm_acq_plan_info;
                               7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
@@ -500,6 +501,70 @@ int gm_acq_refine_doppler(gm_acq *a, const gm_acq_result *results, const uint8_t
 int gm_acq_refine_plan(uint32_t coherent_periods, uint32_t n_integrations, const gm_acq_refine_cfg *cfg, float fs,
                        uint32_t fft_size, uint32_t n_bins, const float *table_freq, uint32_t bin,
                        uint32_t *span_periods, uint32_t *n_groups, uint32_t *n_freq, double *half_span_hz, double *step_hz);
+/* ---- Lag window x fine Doppler at known cells: gm_acq_refine_doppler's statistic on W = 2L + 1 code phases around a predicted one, for
+ * a receiver that already knows roughly where a satellite is (reacquisition after a loss of lock; probing found cells again on the next
+ * dwell; a code phase finer than one sample for the hand-over) — without the P x H x D transforms of a search.
+ * A candidate c names worker w, bin d, the window's centre cp and an offset o in periods: with an edge search any o <= the last offset
+ * (it need not be one of the searched offsets: a predicted edge is fine), without one o = 0.  L = lag_half_window, 0 .. 64, W <= N.
+ *   Lags, l = 0 .. W-1:        lambda_l = (cp + l - L) mod N
+ *   Prompts, i = 0 .. R_u-1:   z[l][i] = sum_{n<N} x[s[d][o+i] + n] * tab[d][n] * c_w[(n - lambda_l) mod N]
+ *     gm_acq_refine_doppler's prompts at lag lambda_l.  All W lags of a (period, candidate) come from ONE pass over the samples: every
+ *     sample and table word is read once and the sample-table product is formed once, as stage F forms it.  Sums are added in a fixed
+ *     order (no floating-point atomics): a candidate's words depend on the candidate, the samples and cfg alone, not on what else is
+ *     in the call and not on repetition.
+ *   Groups, signs, grid and statistic: gm_acq_refine_doppler's (above), unchanged and per lag,
+ *     S[l][j] = N^2 * sum_{g<G} | sum_{k<J} sigma_k * w_{g,k}(delta_j) * z[l][gJ+k] |^2;  J, G, Z, half_span: gm_acq_refine_plan's rules.
+ *   Peak.  (l*, j*) = the first index of the maximum of S in (l, j) order; code_phase_samples = lambda_{l*}; delta_hz and carrier_hz by
+ *     gm_acq_refine_doppler's three-point parabola along j in row l*; freq_at_edge = 1 when j* is 0 or Z-1 (no interpolation then).
+ *   Fine code phase (host, f64), defined when 0 < l* < W-1; otherwise lag_at_edge = 1 and code_phase_fine = code_phase_samples.  With
+ *     a-, a0, a+ = sqrt(S[l*-1][j*]), sqrt(S[l*][j*]), sqrt(S[l*+1][j*]):  frac = (a+ - a-) / (2 (a0 - min(a-, a+))), the exact vertex of
+ *     a symmetric triangle through three samples, clamped to +-0.5, 0 where the denominator is not positive; lambda = lambda_{l*} + frac.
+ *     Without the code-drift compensation code_phase_fine = lambda mod N.  With it the period starts are known, so the rounding of the
+ *     starts and the blend of two signal periods inside one read are both taken out:
+ *       ebar = mean_i (s[d][o+i] - (o+i) T_d) over the R_u periods used;
+ *       the lambda samples in front of the lag belong to the previous signal period, which ends N - T_d samples before the replica
+ *       says it does: subtract (lambda / N)(N - T_d);
+ *       code_phase_fine = (lambda + ebar - (lambda / N)(N - T_d)) mod N      (samples into the dwell, of the code's start)
+ *     The estimate needs the chip edges to fall on varying sample phases: at an integer number of samples per chip with no drift the
+ *     correlation is flat within a sample and the sub-sample part is unobservable (frac then only reflects noise).
+ *   Floor.  floor_power = the mean of S[l][j] over all j and over the n_floor lags whose circular distance (mod N) from l* is at least
+ *     ceil(fs / code_rate) + 1 samples (one chip and a sample: outside the correlation triangle); n_floor = 0 -> floor_power = 0.
+ *     The library makes NO detection decision.  A caller can compare peak_power / floor_power, or peak_power against the last
+ *     search's sum / N of the cell (gm_acq_metrics: the plane's mean); the W * Z values are strongly correlated along j (the grid
+ *     oversamples the dwell's frequency resolution), so they are far fewer than W * Z independent trials.
+ * Samples.  d_samples NULL: the snapshot of the LAST search on the handle — gm_acq_refine_doppler's rules (no search yet, or none since
+ * the last gm_acq_set_edge_search / gm_acq_set_code_drift: GM_ERR_INVALID_ARG); fmt is ignored.  Non-NULL: a device pointer to
+ * gm_acq_dwell_samples samples in format fmt, ready on the handle's stream — any dwell, for instance a later one; it is only read and
+ * does NOT become the snapshot (a following gm_acq_refine_doppler / gm_acq_finer_doppler still sees the last search's samples).
+ * Synchronous, on the handle's stream; runs a pending deferred decision first; changes no metric, choice or result word.
+ *   out : [n_cands];  prompts : [n_cands][W][R_u] or NULL;  surface : [n_cands][W][Z] or NULL   (gm_acq_local_plan gives W, R_u, Z)
+ * GM_ERR_INVALID_ARG, all checked before anything runs or is written: a null handle (no device is touched), cands or out; worker >=
+ * the handle's workers; doppler_bin outside the bins; code_phase_samples >= fft_size; an offset outside the rule above;
+ * lag_half_window > 64 or 2 * lag_half_window + 1 > fft_size; the span / n_freq / half-span rules of gm_acq_refine_plan; fmt not a
+ * format (d_samples non-NULL).  n_cands = 0: GM_OK, nothing is written.
+ * Device memory: one block of about n_cands * (W * (8 R_u + 4 Z + 16) + 8 R_u + 80) bytes, built at the first call and grown when a call
+ * needs more — the new block is allocated before the old one goes (GM_ERR_NOMEM leaves the handle as it was); gm_acq_destroy releases it.
+ * Cost: R_u * N sample and table reads and R_u * N * W multiply-adds per candidate (one 256-lane workgroup per (period, candidate)).
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct { uint32_t worker; int32_t doppler_bin; uint32_t code_phase_samples; uint32_t offset_periods; } gm_acq_cand;
+typedef struct { uint32_t lag_half_window; uint32_t span_periods; uint32_t n_freq; float half_span_hz; } gm_acq_local_cfg; /* zeros: defaults */
+typedef struct {                      /* 88 bytes (84 and the padding to the doubles' alignment) */
+    double   carrier_hz;              /* table_freq[d] + delta_hz */
+    double   code_phase_fine;         /* samples, [0, fft_size) */
+    float    delta_hz, step_hz, half_span_hz;
+    float    peak_power, floor_power; /* S[l*][j*]; the mean over the far lags */
+    uint32_t peak_lag_index, peak_freq_index;   /* l*, j* */
+    uint32_t code_phase_samples;      /* lambda_{l*} */
+    uint32_t lag_at_edge, freq_at_edge, n_floor;
+    uint32_t doppler_bin, offset_periods, span_periods, n_groups, n_freq, n_lags;
+} gm_acq_local_out;
+int gm_acq_local_search(gm_acq *a, const void *d_samples /* NULL: the last search's snapshot */, int fmt, const gm_acq_cand *cands,
+                        uint32_t n_cands, const gm_acq_local_cfg *cfg /* NULL: defaults */, gm_acq_local_out *out /* [n_cands] */,
+                        gm_c32 *prompts /* [n_cands][W][R_u] or NULL */, float *surface /* [n_cands][W][Z] or NULL */);
+/* host only, no device: gm_acq_refine_plan's rules (the same host code) plus the lag rules; n_lags = W (any output pointer may be NULL) */
+int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const gm_acq_local_cfg *cfg, float fs, uint32_t fft_size,
+                      uint32_t n_bins, const float *table_freq, uint32_t bin, uint32_t *n_lags, uint32_t *span_periods,
+                      uint32_t *n_groups, uint32_t *n_freq, double *half_span_hz, double *step_hz);
 /* Kernel timing of the last gm_acq_search*_dev call, measured with HIP events on the handle's
  * stream: ms_mix_fft (stage F), ms_corr (stage C, the dominant kernel), ms_decide.  Enable first: on = 1 times every
  * search, on = k > 1 every k-th (an event record costs about 2 us of stream time; four per timed search), 0 disables. */

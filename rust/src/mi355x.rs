@@ -83,6 +83,24 @@ pub struct GmAcqRefineOut {         // gm_acq_refine_out
     pub peak_index: u32, pub at_edge: u32,
     pub doppler_bin: u32, pub offset_periods: u32, pub span_periods: u32, pub n_groups: u32, pub n_freq: u32,
 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmAcqCand {              // gm_acq_cand: a known cell for gm_acq_local_search
+    pub worker: u32, pub doppler_bin: i32, pub code_phase_samples: u32, pub offset_periods: u32,
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmAcqLocalCfg {          // gm_acq_local_cfg (zeros: the defaults)
+    pub lag_half_window: u32, pub span_periods: u32, pub n_freq: u32, pub half_span_hz: f32,
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmAcqLocalOut {          // gm_acq_local_out (88 bytes)
+    pub carrier_hz: f64,             // table_freq[doppler_bin] + delta_hz
+    pub code_phase_fine: f64,        // samples, [0, fft_size)
+    pub delta_hz: f32, pub step_hz: f32, pub half_span_hz: f32,
+    pub peak_power: f32, pub floor_power: f32,
+    pub peak_lag_index: u32, pub peak_freq_index: u32, pub code_phase_samples: u32,
+    pub lag_at_edge: u32, pub freq_at_edge: u32, pub n_floor: u32,
+    pub doppler_bin: u32, pub offset_periods: u32, pub span_periods: u32, pub n_groups: u32, pub n_freq: u32, pub n_lags: u32,
+}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {}
 
 extern "C" {
@@ -117,6 +135,13 @@ extern "C" {
     pub fn gm_acq_refine_plan(coherent_periods: u32, n_integrations: u32, cfg: *const GmAcqRefineCfg, fs: f32, fft_size: u32,
                               n_bins: u32, table_freq: *const f32, bin: u32, span_periods: *mut u32, n_groups: *mut u32,
                               n_freq: *mut u32, half_span_hz: *mut f64, step_hz: *mut f64) -> c_int;
+    // lag window x fine Doppler at known cells (additive entries, ABI stays 9): gm_acq_refine_doppler's statistic on 2 L + 1 code
+    // phases around a predicted one, from one pass over the samples; d_samples null: the snapshot of the last search
+    pub fn gm_acq_local_search(a: *mut GmAcq, d_samples: *const c_void, fmt: c_int, cands: *const GmAcqCand, n_cands: u32,
+                               cfg: *const GmAcqLocalCfg, out: *mut GmAcqLocalOut, prompts: *mut Complex32, surface: *mut f32) -> c_int;
+    pub fn gm_acq_local_plan(coherent_periods: u32, n_integrations: u32, cfg: *const GmAcqLocalCfg, fs: f32, fft_size: u32,
+                             n_bins: u32, table_freq: *const f32, bin: u32, n_lags: *mut u32, span_periods: *mut u32,
+                             n_groups: *mut u32, n_freq: *mut u32, half_span_hz: *mut f64, step_hz: *mut f64) -> c_int;
     // do_acquisition.rs:302-313 + :158-226  (par_iter over workers / search_satellite)
     pub fn gm_acq_search_c32(a: *mut GmAcq, samples: *const Complex32, n: usize, local_tail: u64,
                              prn_mask: u64, results: *mut GmAcqResult, found: *mut u8) -> c_int;

@@ -152,6 +152,16 @@ impl AcquisitionEngine {
                                           std::ptr::null_mut(), std::ptr::null_mut()) } != 0 { return Err(AcqError); }
         Ok(out.into_iter().zip(found).map(|(o, f)| if *f != 0 { Some(o) } else { None }).collect())
     }
+    /// Not in the reference: a local evaluation around known cells (reacquisition, verification, a sub-sample code phase) — the fine
+    /// Doppler statistic on 2 * cfg.lag_half_window + 1 code phases around every candidate's, on the snapshot of the LAST search
+    /// (`d_samples` None) or on any dwell in device memory (`Some((pointer, format))`, read only).  No detection decision is made.
+    pub fn local_search(&mut self, cands: &[GmAcqCand], d_samples: Option<(*const std::os::raw::c_void, i32)>, cfg: &GmAcqLocalCfg) -> Result<Vec<GmAcqLocalOut>, AcqError> {
+        let mut out = vec![GmAcqLocalOut::default(); cands.len()];
+        let (ptr, fmt) = d_samples.unwrap_or((std::ptr::null(), 0));
+        if unsafe { gm_acq_local_search(self.h, ptr, fmt, cands.as_ptr(), cands.len() as u32, cfg, out.as_mut_ptr(),
+                                        std::ptr::null_mut(), std::ptr::null_mut()) } != 0 { return Err(AcqError); }
+        Ok(out)
+    }
     /// the body of `workers.par_iter_mut().enumerate().filter_map(..search_satellite..)` (:302-313)
     pub fn search(&mut self, chunk: &[Complex32], local_tail: usize, mask: u32) -> Vec<AcquisitionResult> {
         let mut raw = vec![GmAcqResult::default(); self.n_prn];
