@@ -76,6 +76,21 @@ class AcqLocalOut(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AcqCancelCand(C.Structure):
+    """gm_acq_cancel_cand (32 bytes): a found satellite for gm_acq_cancel"""
+    _fields_ = [("worker", C.c_uint32), ("reserved", C.c_uint32), ("carrier_hz", C.c_double), ("code_phase", C.c_double),
+                ("period_samples", C.c_double)]
+
+
+class AcqCancelOut(C.Structure):
+    """gm_acq_cancel_out (32 bytes)"""
+    _fields_ = [("removed_energy", C.c_double), ("amp_rms", C.c_float), ("n_segments", C.c_uint32), ("first_samples", C.c_uint32),
+                ("last_samples", C.c_uint32), ("worker", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 ACQ_FORM_LDS, ACQ_FORM_COMPOSITE, ACQ_FORM_LONG, ACQ_FORM_LONG_PADDED = 0, 1, 2, 3   # gm_acq_form
 
 
@@ -177,6 +192,8 @@ SIGNATURES = {
     "gm_acq_local_search": (_i, [_vp, _vp, _i, _vp, _u32, C.POINTER(AcqLocalCfg), _vp, _vp, _vp]),
     "gm_acq_local_plan": (_i, [_u32, _u32, C.POINTER(AcqLocalCfg), _f, _u32, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32),
                            C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gm_acq_cancel": (_i, [_vp, _vp, _i, _vp, _u32, _vp, _vp, _vp, _u32]),
+    "gm_acq_cancel_plan": (_i, [C.c_uint64, _u32, C.c_double, C.c_double, C.POINTER(_u32), _vp, _u32]),
     "gm_acq_enable_timing": (_i, [_vp, _i]),
     "gm_acq_last_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
     "gm_acq_timing_summary": (_i, [_vp, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f)]),

@@ -6,7 +6,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import AcqCand, AcqCfg, AcqLocalCfg, AcqLocalOut, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
+from ._lib import AcqCancelCand, AcqCancelOut, AcqCand, AcqCfg, AcqLocalCfg, AcqLocalOut, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
 
 PRN_SEARCH_ACQUISITION_TOTAL = 32      # do_acquisition.rs:22
 FREQ_SEARCH_ACQUISITION_HZ = 14e3      # :20
@@ -177,6 +177,20 @@ def local_plan(coherent_periods, n_integrations, fs, fft_size, table_freq, bin=0
                                   _p(tf) if tf.size else None, int(bin), C.byref(w), C.byref(j), C.byref(g), C.byref(z), C.byref(hs),
                                   C.byref(st)), "gm_acq_local_plan")
     return dict(n_lags=w.value, span_periods=j.value, n_groups=g.value, n_freq=z.value, half_span_hz=hs.value, step_hz=st.value)
+
+
+def cancel_plan(dwell_samples, fft_size, code_phase, period_samples=0.0):
+    """gm_acq_cancel_plan: the signal code periods ("segments") gm_acq_cancel cuts a dwell of dwell_samples samples into for a
+    satellite whose code starts code_phase samples into the dwell and repeats every period_samples samples (0: fft_size), after its
+    argument checks (GmError INVALID_ARG) -> dict(n_segments = Q, bounds = uint64 [Q + 1]: segment k is bounds[k] <= n < bounds[k + 1]).
+    Host only."""
+    q = C.c_uint32(0)
+    check(lib().gm_acq_cancel_plan(int(dwell_samples), int(fft_size), float(code_phase), float(period_samples), C.byref(q), None, 0),
+          "gm_acq_cancel_plan")
+    b = np.zeros(q.value + 1, np.uint64)
+    check(lib().gm_acq_cancel_plan(int(dwell_samples), int(fft_size), float(code_phase), float(period_samples), C.byref(q), _p(b),
+                                   b.size), "gm_acq_cancel_plan")
+    return dict(n_segments=q.value, bounds=b)
 
 
 class AcquisitionEngine:
@@ -456,6 +470,44 @@ class AcquisitionEngine:
                 d["surface"] = s[i].copy()
             ret.append(d)
         return ret
+
+    def cancel(self, cands, out_ptr, samples=None, fmt=FMT_C32, want_amps=False):
+        """Subtract found satellites from a dwell (gm_acq_cancel): one complex amplitude per signal code period and satellite is
+        estimated from the input and the replica times it is subtracted; the result is written as c32 to the device pointer out_ptr
+        (dwell_samples samples), which search_dev takes as a dwell.  A candidate is a dict with `worker`, `carrier_hz`, `code_phase`
+        (what local_search returns as carrier_hz and code_phase_fine) and `period_samples` (the signal's true code period; 0 or
+        missing: fft_size) — cancel_cands_from_local builds them.  samples None: the snapshot of the last search; else a device
+        pointer to dwell_samples samples in format `fmt`, read only (out_ptr may be that pointer itself when fmt is FMT_C32: in place).
+        -> list of dict(removed_energy, amp_rms, n_segments, first_samples, last_samples, worker); with want_amps `amps` (complex64
+        [n_segments]).  The library makes no detection decision."""
+        n = len(cands)
+        cs = (AcqCancelCand * max(n, 1))()
+        for i, c in enumerate(cands):
+            cs[i] = AcqCancelCand(int(c["worker"]), 0, float(c["carrier_hz"]), float(c["code_phase"]), float(c.get("period_samples", 0.0)))
+        out = (AcqCancelOut * max(n, 1))()
+        amps, stride = None, 0
+        if n and want_amps:
+            D = self.dwell_samples
+            stride = max(cancel_plan(D, self.fft_size, cs[i].code_phase, cs[i].period_samples)["n_segments"] for i in range(n))
+            amps = np.zeros((n, stride), np.complex64)
+        check(lib().gm_acq_cancel(self._h, C.c_void_p(samples) if samples else None, int(fmt), C.cast(cs, C.c_void_p), n,
+                                  C.c_void_p(out_ptr) if out_ptr else None, C.cast(out, C.c_void_p),
+                                  _p(amps) if amps is not None else None, stride), "gm_acq_cancel")
+        ret = []
+        for i in range(n):
+            d = out[i].as_dict()
+            if amps is not None:
+                d["amps"] = amps[i, :d["n_segments"]].copy()
+            ret.append(d)
+        return ret
+
+    def cancel_cands_from_local(self, local_outs, workers):
+        """The candidates of cancel() from local_search's dicts and the workers they belong to: carrier_hz, code_phase =
+        code_phase_fine and period_samples = the handle's code-drift period of the dict's doppler_bin (0, i.e. fft_size, while the
+        compensation is off)."""
+        return [dict(worker=int(w), carrier_hz=float(o["carrier_hz"]), code_phase=float(o["code_phase_fine"]),
+                     period_samples=float(self.code_drift[int(o["doppler_bin"])]) if self.code_drift is not None else 0.0)
+                for o, w in zip(local_outs, workers)]
 
     def metrics(self):
         mx = np.zeros((self.P, self.D), np.float32)

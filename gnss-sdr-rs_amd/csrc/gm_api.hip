@@ -422,6 +422,13 @@ struct gm_acq {
         void* d_block = nullptr;
         size_t bytes = 0;
     } local;
+    // subtracting found satellites from a dwell (gm_acq_cancel): one device block (candidate constants, the segment tables o and b, the
+    // amplitudes), grown like local's, and a device copy of the raw chip rows [P][code_len], uploaded at the first call
+    struct Cancel {
+        void* d_block = nullptr;
+        size_t bytes = 0;
+        int8_t* d_chips = nullptr;
+    } cancel;
 };
 
 // the fused single-LDS-buffer kernels (acq_kernels.hip): neither a composite nor an any-length size
@@ -754,6 +761,7 @@ int gm_acq_destroy(gm_acq* a) {
     hipFree(a->fine.d_peak_pow); hipFree(a->fine.d_peak_idx);
     hipFree(a->refine.d_block);
     hipFree(a->local.d_block);
+    hipFree(a->cancel.d_block); hipFree(a->cancel.d_chips);
     if (a->device >= 0) hipSetDevice(a->device);
     hipFree(a->d_tw_mix);
     hipFree(a->d_tables); hipFree(a->d_tw_fwd); hipFree(a->d_tw_inv); hipFree(a->d_code_fft); hipFree(a->d_code_fft_paired); hipFree(a->d_order);
@@ -2107,6 +2115,157 @@ int gm_acq_local_search(gm_acq* a, const void* d_samples, int fmt, const gm_acq_
             r.code_phase_fine = fine;
         }
         r.doppler_bin = d; r.offset_periods = o; r.span_periods = J; r.n_groups = G; r.n_freq = Z; r.n_lags = W;
+    }
+    return GM_OK;
+}
+
+// ---------------------------------------------------------------- subtracting found satellites from a dwell (additive entries, ABI 9)
+// the segments of one candidate on a dwell of D samples (gnss_mi355x.h states the rule; tests/acq_cancel_model.py restates it): host f64
+struct CancelPlan {
+    double T = 0.0;                         // the period in use (period_samples, or fft_size where that is 0)
+    int64_t q0 = 0;
+    std::vector<double> o;                  // [Q + 1]
+    std::vector<uint64_t> b;                // [Q + 1], b[0] = 0, b[Q] = D
+    uint32_t Q = 0;
+};
+constexpr uint64_t CANCEL_MAX_DWELL = 1ull << 40;      // (a dwell is K * M + o_max periods of at most 2^18 samples)
+static int cancel_rules(uint64_t D, uint32_t N, double cp, double period, CancelPlan& p) {
+    if (N < 16) return set_err(GM_ERR_INVALID_ARG, "fft_size below 16");
+    if (!D || D > CANCEL_MAX_DWELL) return set_err(GM_ERR_INVALID_ARG, "dwell_samples is 0 or above 2^40");
+    if (double(D) / (double(N) - 8.0) > double(1u << 24)) return set_err(GM_ERR_INVALID_ARG, "dwell_samples holds more than 2^24 code periods");
+    if (!(cp >= 0.0 && cp < double(N))) return set_err(GM_ERR_INVALID_ARG, "code_phase outside [0, fft_size)");
+    if (period != 0.0 && !(::fabs(period - double(N)) <= 8.0))
+        return set_err(GM_ERR_INVALID_ARG, "period_samples not within 8 of fft_size (0: fft_size)");
+    const double T = period != 0.0 ? period : double(N);
+    p.T = T;
+    p.q0 = -int64_t(::ceil(cp / T));
+    p.o.clear(); p.b.clear();
+    for (uint64_t k = 0;; ++k) {
+        const double o = cp + double(p.q0 + int64_t(k)) * T;
+        p.o.push_back(o);
+        if (o >= double(D)) { p.b.push_back(D); break; }
+        const double c = ::ceil(o);
+        p.b.push_back(c <= 0.0 ? 0ull : uint64_t(c));          // (o < D: ceil(o) <= D)
+    }
+    p.Q = uint32_t(p.o.size() - 1);
+    return GM_OK;
+}
+
+int gm_acq_cancel_plan(uint64_t dwell_samples, uint32_t fft_size, double code_phase, double period_samples, uint32_t* n_segments,
+                       uint64_t* bounds, uint32_t bounds_cap) {
+    CancelPlan p;
+    if (int rc = cancel_rules(dwell_samples, fft_size, code_phase, period_samples, p)) return rc;
+    if (bounds && bounds_cap < p.Q + 1) return set_err(GM_ERR_INVALID_ARG, "bounds_cap below n_segments + 1");
+    if (n_segments) *n_segments = p.Q;
+    if (bounds) memcpy(bounds, p.b.data(), size_t(p.Q + 1) * sizeof(uint64_t));
+    return GM_OK;
+}
+
+int gm_acq_cancel(gm_acq* a, const void* d_samples, int fmt, const gm_acq_cancel_cand* cands, uint32_t n_cands, void* d_out,
+                  gm_acq_cancel_out* out, gm_c32* amps, uint32_t amps_stride) {
+    if (!a || (!cands && n_cands) || !d_out) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (n_cands > 64) return set_err(GM_ERR_INVALID_ARG, "more than 64 candidates");
+    if (d_samples) {
+        if (fmt < GM_FMT_C32 || fmt > GM_FMT_I8_REAL) return set_err(GM_ERR_INVALID_ARG, "bad sample format");
+    } else if (!a->last_samples) return set_err(GM_ERR_INVALID_ARG, "no search has run on this handle yet");
+    const void* const in = d_samples ? d_samples : a->last_samples;
+    const int in_fmt = d_samples ? fmt : a->last_fmt;
+    const uint32_t N = a->N;
+    const uint64_t D = acq_dwell_samples(a);
+    const double fs = double(a->cfg.fs);
+    // every argument is checked before anything runs or is written
+    {   // the output may be the c32 input itself (in place); any other overlap of the two ranges is refused
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + D * (in_fmt == GM_FMT_C32 ? 8u : (in_fmt == GM_FMT_I8_IQ ? 2u : 1u));
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + D * 8u;
+        if (!(o0 == i0 && in_fmt == GM_FMT_C32) && o0 < i1 && i0 < o1)
+            return set_err(GM_ERR_INVALID_ARG, "d_out overlaps the input (only d_out == the c32 input itself is allowed)");
+        if (o0 & 7u) return set_err(GM_ERR_INVALID_ARG, "d_out is not aligned to a c32 sample");
+    }
+    std::vector<CancelPlan> plans(n_cands);
+    uint32_t q_max = 0;
+    for (uint32_t c = 0; c < n_cands; ++c) {
+        const gm_acq_cancel_cand& cd = cands[c];
+        if (cd.worker >= a->P) return set_err(GM_ERR_INVALID_ARG, "candidate.worker outside the handle's workers");
+        if (cd.reserved) return set_err(GM_ERR_INVALID_ARG, "candidate.reserved must be 0");
+        if (!(::fabs(cd.carrier_hz) < fs)) return set_err(GM_ERR_INVALID_ARG, "candidate.carrier_hz is not a number or |carrier_hz| >= fs");
+        if (int rc = cancel_rules(D, N, cd.code_phase, cd.period_samples, plans[c])) return rc;
+        q_max = plans[c].Q > q_max ? plans[c].Q : q_max;
+    }
+    if (amps && amps_stride < q_max) return set_err(GM_ERR_INVALID_ARG, "amps_stride below the largest n_segments");
+    if (int rc = ensure_device(a->device)) return rc;
+    if (int rc = acq_flush_decision(a)) return rc;
+    gm_acq::Cancel& cn = a->cancel;
+    if (!cn.d_chips) {
+        int8_t* chips = nullptr;
+        if (hipMalloc(&chips, a->chips.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(GM_ERR_NOMEM, "the chip rows of gm_acq_cancel do not fit; the handle is as it was");
+        }
+        if (hipError_t e = hipMemcpy(chips, a->chips.data(), a->chips.size(), hipMemcpyHostToDevice); e != hipSuccess) {
+            hipFree(chips);
+            return hip_fail(e, "hipMemcpy");
+        }
+        cn.d_chips = chips;
+    }
+    // the block: [candidate constants | o | b | amplitudes], every part 256-byte aligned; the tables are [n_cands][stride]
+    const uint32_t S = n_cands, stride = q_max + 1;
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t cells = size_t(S) * stride;
+    const size_t o_cand = 0, o_o = o_cand + up(size_t(S) * sizeof(gm::CancelCand)), o_b = o_o + up(cells * 8), o_a = o_b + up(cells * 8),
+                 total = o_a + up(cells * 8) + 256;
+    if (total > cn.bytes) {                 // the new block before the old one goes: a failure leaves the handle as it was
+        void* blk = nullptr;
+        if (hipMalloc(&blk, total) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(GM_ERR_NOMEM, "the cancellation block does not fit (gnss_mi355x.h states the formula); the handle is as it was");
+        }
+        if (hipError_t e = hipStreamSynchronize(a->stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
+        hipFree(cn.d_block);
+        cn.d_block = blk; cn.bytes = total;
+    }
+    char* const base = static_cast<char*>(cn.d_block);
+    std::vector<gm::CancelCand> cs(S);
+    std::vector<double> o(cells, 0.0);
+    std::vector<uint64_t> b(cells, D);
+    for (uint32_t c = 0; c < S; ++c) {
+        const CancelPlan& p = plans[c];
+        cs[c] = gm::CancelCand{double(a->code_len) / p.T, cands[c].carrier_hz / fs, cands[c].code_phase, 1.0 / p.T,
+                               cands[c].worker, a->code_len, p.Q, int32_t(p.q0)};
+        std::copy(p.o.begin(), p.o.end(), o.begin() + size_t(c) * stride);
+        std::copy(p.b.begin(), p.b.end(), b.begin() + size_t(c) * stride);
+    }
+    if (S) {
+        HIPC(hipMemcpyAsync(base + o_cand, cs.data(), size_t(S) * sizeof(gm::CancelCand), hipMemcpyHostToDevice, a->stream));
+        HIPC(hipMemcpyAsync(base + o_o, o.data(), cells * 8, hipMemcpyHostToDevice, a->stream));
+        HIPC(hipMemcpyAsync(base + o_b, b.data(), cells * 8, hipMemcpyHostToDevice, a->stream));
+    }
+    gm::CancelArgs ca{};
+    ca.samples = in; ca.fmt = in_fmt; ca.D = D;
+    ca.cands = reinterpret_cast<const gm::CancelCand*>(base + o_cand); ca.n_cands = S; ca.q_max = q_max; ca.stride = stride;
+    ca.o = reinterpret_cast<const double*>(base + o_o); ca.b = reinterpret_cast<const uint64_t*>(base + o_b);
+    ca.chips = cn.d_chips;
+    ca.amps = reinterpret_cast<cf*>(base + o_a); ca.out = static_cast<cf*>(d_out);
+    gm::launch_cancel(a->stream, ca);
+    HIPC(hipGetLastError());
+    std::vector<cf> am(cells);
+    if (S) HIPC(hipMemcpyAsync(am.data(), base + o_a, cells * 8, hipMemcpyDeviceToHost, a->stream));
+    HIPC(hipStreamSynchronize(a->stream));  // (the host vectors above live until here)
+    for (uint32_t c = 0; c < S; ++c) {
+        const CancelPlan& p = plans[c];
+        const cf* row = &am[size_t(c) * stride];
+        if (amps) memcpy(amps + size_t(c) * amps_stride, row, size_t(p.Q) * sizeof(cf));
+        if (!out) continue;
+        double energy = 0.0;
+        for (uint32_t k = 0; k < p.Q; ++k)
+            energy += double(p.b[k + 1] - p.b[k]) * (double(row[k].x) * double(row[k].x) + double(row[k].y) * double(row[k].y));
+        gm_acq_cancel_out& r = out[c];
+        r.removed_energy = energy;
+        r.amp_rms = float(::sqrt(energy / double(D)));
+        r.n_segments = p.Q;
+        r.first_samples = uint32_t(p.b[1] - p.b[0]);
+        r.last_samples = uint32_t(p.b[p.Q] - p.b[p.Q - 1]);
+        r.worker = cands[c].worker;
+        r.reserved = 0;
     }
     return GM_OK;
 }

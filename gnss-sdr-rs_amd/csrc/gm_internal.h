@@ -101,6 +101,27 @@ struct LocalArgs {
 };
 void launch_local(hipStream_t, const LocalArgs&);
 
+// Subtracting found satellites from a dwell (gm_acq_cancel, acq_cancel.hip): the amplitude kernel on grid (q_max, n_cands) sums one
+// signal code period of one candidate per workgroup, the subtraction is one pass over the dwell.  The tables are [n_cands][stride],
+// stride >= q_max + 1: o and b hold Q + 1 entries of a candidate, amps Q.
+struct CancelCand {
+    double cpl, fq;                        // L / T chips per sample; f / fs cycles per sample
+    double cp, inv_T;                      // for the segment guess floor((n - cp) / T) - q0 only: the b table decides
+    uint32_t worker, L, Q;                 // L = code_len
+    int32_t q0;                            // -ceil(cp / T)
+};
+struct CancelArgs {
+    const void* samples; int fmt;          // the snapshot of the last search, or the caller's dwell
+    uint64_t D;                            // samples of the dwell
+    const CancelCand* cands; uint32_t n_cands, q_max, stride;
+    const double* o;                       // [n_cands][stride] segment origins o_k
+    const uint64_t* b;                     // [n_cands][stride] segment bounds b_k (b_0 = 0, b_Q = D)
+    const int8_t* chips;                   // [P][L] raw chips
+    cf* amps;                              // [n_cands][stride]
+    cf* out;                               // [D]; may be `samples` when fmt is c32
+};
+void launch_cancel(hipStream_t, const CancelArgs&);
+
 // One entry per shipped transform size: launchers for the kernels instantiated on that plan.
 struct DecideArgs;
 struct PlanOps {

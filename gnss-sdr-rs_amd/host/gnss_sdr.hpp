@@ -178,6 +178,17 @@ public:
         check(gm_acq_local_search(h_, d_samples, fmt, cands.data(), uint32_t(cands.size()), &cfg, out.data(), nullptr, nullptr), "local_search");
         return out;
     }
+    // Subtracting found satellites from a dwell (gm_acq_cancel): one amplitude per signal code period and candidate is estimated from
+    // the input (the snapshot of the last search when d_samples is null, else any dwell of dwell_samples() samples, read only) and
+    // the dwell minus the replicas is written as c32 to d_out, which every search entry takes as a dwell (d_out may be the c32 input
+    // itself).  Candidates carry local_search's carrier_hz and code_phase_fine and the signal's true code period.  No detection
+    // decision is made.
+    std::vector<gm_acq_cancel_out> cancel(const std::vector<gm_acq_cancel_cand>& cands, void* d_out, const void* d_samples = nullptr,
+                                          int fmt = GM_FMT_C32) {
+        std::vector<gm_acq_cancel_out> out(cands.size());
+        check(gm_acq_cancel(h_, d_samples, fmt, cands.data(), uint32_t(cands.size()), d_out, out.data(), nullptr, 0), "cancel");
+        return out;
+    }
     // The edge search of a coherent handle (gm_acq_set_edge_search): H ascending period offsets (each 0..63, H <= 32) and an optional
     // secondary row of coherent_periods entries +-1 (empty: all +1); no offsets switch it off.  While it is on a dwell is
     // (K * n_integrations + offsets.back()) * fft_size samples.

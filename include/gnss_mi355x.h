@@ -42,6 +42,7 @@ extern "C" {
                               gm_acq_dwell_samples, gm_acq_code_drift_starts, gm_acq_code_drift_phasors;
                               and the fine Doppler from per-period prompts — gm_acq_refine_doppler, gm_acq_refine_plan;
                               and the lag window x fine Doppler at known cells — gm_acq_local_search, gm_acq_local_plan;
+                              and subtracting found satellites from a dwell — gm_acq_cancel, gm_acq_cancel_plan;
                               8: gm_acq_cfg.any_length, gm_acq_plan_info;
                               7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
@@ -565,6 +566,59 @@ int gm_acq_local_search(gm_acq *a, const void *d_samples /* NULL: the last searc
 int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const gm_acq_local_cfg *cfg, float fs, uint32_t fft_size,
                       uint32_t n_bins, const float *table_freq, uint32_t bin, uint32_t *n_lags, uint32_t *span_periods,
                       uint32_t *n_groups, uint32_t *n_freq, double *half_span_hz, double *step_hz);
+/* ---- Subtracting found satellites from a dwell.  C/A codes isolate about 24 dB: a strong satellite's cross-correlation peaks stand
+ * above a satellite 24 dB weaker in every other PRN's plane.  gm_acq_cancel writes the dwell with the named satellites' signals
+ * subtracted, as c32, into a second device buffer, which every search entry takes as a dwell.  The expected sequence is: search,
+ * gm_acq_local_search on the found cells, gm_acq_cancel, search again on the output.  The library makes NO detection decision.
+ * D = gm_acq_dwell_samples of the handle, N = fft_size, L = code_len, c_w = worker w's raw chips (cfg.codes, or the C/A row of
+ * prn_ids[w]).  A candidate names worker w, f = carrier_hz (IF + Doppler: gm_acq_local_out.carrier_hz), cp = code_phase (samples into
+ * the dwell, of the code's start, in [0, N): gm_acq_local_out.code_phase_fine) and T = period_samples, the signal's TRUE code period
+ * (0: N; else within 8 of N).  The replica must be built from the fine values and the true period: an integer code phase leaves about
+ * 11 dB of cancellation, T = N on a signal 0.4 sample a period off about 1 dB.
+ *   Segments (host, f64): q0 = -ceil(cp / T);  o_k = cp + double(q0 + k) * T;  b_k = clamp(ceil(o_k), 0, D);  segment k is the samples
+ *     b_k <= n < b_{k+1}, k = 0 .. Q-1, with Q the least count with o_Q >= D and b_Q = D;  n_k = b_{k+1} - b_k.  A segment is one code
+ *     period of the SIGNAL; the first and the last are partial, and the last may be empty (then a_k = 0).  gm_acq_cancel_plan returns
+ *     Q and b_0 .. b_Q.
+ *   Replica at sample n of segment k.  Host constants in f64: cpl = L / T, fq = f / fs.  Device, per sample, in f64:
+ *     e = double(n) - o_k;  idx = min(L - 1, (uint32) floor(e * cpl));  cyc = double(n) * fq;
+ *     then turn = float(2.0 * (cyc - floor(cyc))),  (c, s) = (cospif(turn), sinpif(turn)),  r[n] = c_w[idx] * (c + j s)
+ *     — the cycles reduced to one in f64, then the f32 sine / cosine, as gm_acq_refine_doppler forms its phasors.
+ *   Amplitudes, one per segment, ALL taken from the input:  a_k = (sum_{n in segment k} x[n] * conj(r[n])) / n_k, an f32 sum in a
+ *     fixed order (no floating-point atomics: two calls give the same words).  One complex amplitude per code period is a projection:
+ *     data bits, a secondary code and slow phase drift need no model.  Taking every amplitude from the input is PARALLEL cancellation:
+ *     the cross terms between cancelled satellites (about -24 dB) are left in; a caller may run the entry again on its output.
+ *   Output.  GM_FMT_C32 and GM_FMT_I8_IQ: y[n] = x[n] - sum_c a_{c,k_c(n)} r_c[n], the candidates subtracted in ascending index;
+ *     GM_FMT_I8_REAL: the term is 2 Re(a r) and the imaginary part of y is exactly 0 (a real dwell holds half the signal's power:
+ *     the amplitudes are 3 dB noisier).  Every product and sum is rounded on its own.  n_cands = 0: y is x converted to c32, GM_OK.
+ *   out[c] (host, f64, from the amplitude words): n_segments = Q, first_samples = n_0, last_samples = n_{Q-1}, removed_energy =
+ *     sum_k n_k |a_k|^2, amp_rms = sqrt(removed_energy / D), worker echoed.  amps[c][k] = a_k for k < Q (the rest is not written).
+ * Samples.  d_samples NULL: the snapshot of the LAST search on the handle, under gm_acq_local_search's rules (no search yet, or none
+ * since the last gm_acq_set_edge_search / gm_acq_set_code_drift: GM_ERR_INVALID_ARG); fmt is ignored.  Non-NULL: any dwell of D samples
+ * in format fmt, ready on the handle's stream; it is only read and does NOT become the snapshot.  d_out: D c32 samples of device
+ * memory, aligned to 8 bytes (16 for 16-byte stores).  d_out == the c32 input itself is allowed and runs in place (every lane reads
+ * its x[n] and writes its y[n] itself, after the amplitude kernel has ended); if that buffer is the snapshot, later
+ * gm_acq_refine_doppler / gm_acq_local_search / gm_acq_finer_doppler calls see the CANCELLED samples.  Any other overlap of the two
+ * ranges is GM_ERR_INVALID_ARG.
+ * Synchronous, on the handle's stream; runs a pending deferred decision first; changes no metric, choice or result word.
+ * GM_ERR_INVALID_ARG, all checked before anything runs or is written: a null handle (no device is touched), a null cands with
+ * n_cands > 0, a null or misaligned d_out; n_cands > 64; worker >= the handle's workers (the same worker twice is allowed: multipath);
+ * reserved != 0; cp outside [0, N) or not a number; T not 0 and (|T - N| > 8 or not a number); f not a number or |f| >= fs; fmt not
+ * a format (d_samples non-NULL); the snapshot rules; the overlap rule; amps_stride below the largest Q (amps non-NULL).
+ * gm_acq_cancel_plan also refuses fft_size < 16, dwell_samples = 0, above 2^40 or above 2^24 code periods, and bounds_cap < Q + 1
+ * while bounds is non-NULL.
+ * Device memory: one block of about n_cands * (Q + 1) * 24 bytes (o, b and a) plus 48 bytes a candidate, built at the first call and
+ * grown when a call needs more — the new block is allocated before the old one goes (GM_ERR_NOMEM leaves the handle as it was) — and
+ * the raw chips [P][L] as bytes, uploaded once; gm_acq_destroy releases both.
+ * Cost: n_cands + 1 reads of the dwell and one c32 write; per sample and candidate a chip index and a turn in f64 and one sine / cosine.
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct { uint32_t worker, reserved; double carrier_hz, code_phase, period_samples; } gm_acq_cancel_cand;   /* 32 bytes */
+typedef struct { double removed_energy; float amp_rms; uint32_t n_segments, first_samples, last_samples, worker, reserved; } gm_acq_cancel_out; /* 32 bytes */
+int gm_acq_cancel(gm_acq *a, const void *d_samples /* NULL: the last search's snapshot */, int fmt,
+                  const gm_acq_cancel_cand *cands, uint32_t n_cands, void *d_out /* device, c32 [dwell] */,
+                  gm_acq_cancel_out *out /* [n_cands] or NULL */, gm_c32 *amps /* [n_cands][amps_stride] or NULL */, uint32_t amps_stride);
+/* host only, no device: the segment rule above for one candidate on a dwell of dwell_samples samples (n_segments may be NULL) */
+int gm_acq_cancel_plan(uint64_t dwell_samples, uint32_t fft_size, double code_phase, double period_samples,
+                       uint32_t *n_segments, uint64_t *bounds /* [bounds_cap] or NULL */, uint32_t bounds_cap);
 /* Kernel timing of the last gm_acq_search*_dev call, measured with HIP events on the handle's
  * stream: ms_mix_fft (stage F), ms_corr (stage C, the dominant kernel), ms_decide.  Enable first: on = 1 times every
  * search, on = k > 1 every k-th (an event record costs about 2 us of stream time; four per timed search), 0 disables. */

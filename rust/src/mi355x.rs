@@ -101,6 +101,19 @@ pub struct GmAcqLocalOut {          // gm_acq_local_out (88 bytes)
     pub lag_at_edge: u32, pub freq_at_edge: u32, pub n_floor: u32,
     pub doppler_bin: u32, pub offset_periods: u32, pub span_periods: u32, pub n_groups: u32, pub n_freq: u32, pub n_lags: u32,
 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmAcqCancelCand {        // gm_acq_cancel_cand (32 bytes): a found satellite for gm_acq_cancel
+    pub worker: u32, pub reserved: u32,
+    pub carrier_hz: f64,             // IF + Doppler: GmAcqLocalOut::carrier_hz
+    pub code_phase: f64,             // samples into the dwell, [0, fft_size): GmAcqLocalOut::code_phase_fine
+    pub period_samples: f64,         // the signal's true code period; 0: fft_size
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmAcqCancelOut {         // gm_acq_cancel_out (32 bytes)
+    pub removed_energy: f64,         // sum_k n_k |a_k|^2
+    pub amp_rms: f32,
+    pub n_segments: u32, pub first_samples: u32, pub last_samples: u32, pub worker: u32, pub reserved: u32,
+}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {}
 
 extern "C" {
@@ -142,6 +155,12 @@ extern "C" {
     pub fn gm_acq_local_plan(coherent_periods: u32, n_integrations: u32, cfg: *const GmAcqLocalCfg, fs: f32, fft_size: u32,
                              n_bins: u32, table_freq: *const f32, bin: u32, n_lags: *mut u32, span_periods: *mut u32,
                              n_groups: *mut u32, n_freq: *mut u32, half_span_hz: *mut f64, step_hz: *mut f64) -> c_int;
+    // subtracting found satellites from a dwell (additive entries, ABI stays 9): one amplitude per signal code period and candidate,
+    // estimated from the input; the output is c32 in device memory; d_samples null: the snapshot of the last search
+    pub fn gm_acq_cancel(a: *mut GmAcq, d_samples: *const c_void, fmt: c_int, cands: *const GmAcqCancelCand, n_cands: u32,
+                         d_out: *mut c_void, out: *mut GmAcqCancelOut, amps: *mut Complex32, amps_stride: u32) -> c_int;
+    pub fn gm_acq_cancel_plan(dwell_samples: u64, fft_size: u32, code_phase: f64, period_samples: f64, n_segments: *mut u32,
+                              bounds: *mut u64, bounds_cap: u32) -> c_int;
     // do_acquisition.rs:302-313 + :158-226  (par_iter over workers / search_satellite)
     pub fn gm_acq_search_c32(a: *mut GmAcq, samples: *const Complex32, n: usize, local_tail: u64,
                              prn_mask: u64, results: *mut GmAcqResult, found: *mut u8) -> c_int;

@@ -162,6 +162,18 @@ impl AcquisitionEngine {
                                         std::ptr::null_mut(), std::ptr::null_mut()) } != 0 { return Err(AcqError); }
         Ok(out)
     }
+    /// Not in the reference: subtract found satellites from a dwell — one amplitude per signal code period and candidate is estimated
+    /// from the input (the snapshot of the LAST search when `d_samples` is None, else any dwell in device memory, read only) and the
+    /// dwell minus the replicas is written as Complex32 to `d_out` (device memory, `dwell_samples` samples), which the device search
+    /// entries take as a dwell.  No detection decision is made.
+    pub fn cancel(&mut self, cands: &[GmAcqCancelCand], d_out: *mut std::os::raw::c_void,
+                  d_samples: Option<(*const std::os::raw::c_void, i32)>) -> Result<Vec<GmAcqCancelOut>, AcqError> {
+        let mut out = vec![GmAcqCancelOut::default(); cands.len()];
+        let (ptr, fmt) = d_samples.unwrap_or((std::ptr::null(), 0));
+        if unsafe { gm_acq_cancel(self.h, ptr, fmt, cands.as_ptr(), cands.len() as u32, d_out, out.as_mut_ptr(),
+                                  std::ptr::null_mut(), 0) } != 0 { return Err(AcqError); }
+        Ok(out)
+    }
     /// the body of `workers.par_iter_mut().enumerate().filter_map(..search_satellite..)` (:302-313)
     pub fn search(&mut self, chunk: &[Complex32], local_tail: usize, mask: u32) -> Vec<AcquisitionResult> {
         let mut raw = vec![GmAcqResult::default(); self.n_prn];
