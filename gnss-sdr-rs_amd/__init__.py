@@ -4,8 +4,10 @@ The product is the C-ABI shared library built from csrc/ (hand-written HIP for g
 include/gnss_mi355x.h.  This Python package is plumbing around it:
   _lib        ctypes loader (fails loudly when the library is missing; there is no CPU fallback)
   acquisition / tracking / fft   thin mirrors of the reference's Rust API names over the C ABI
+  frontend / resample            the digital front-end, and the rate conversion and pulse blanking it leaves out
   synth       deterministic synthetic IF scenes
   build       hipcc build recipe
 """
 from . import _lib  # noqa: F401
 from ._lib import GmError, lib, library_path  # noqa: F401
+from .resample import Resampler  # noqa: F401

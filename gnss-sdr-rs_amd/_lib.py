@@ -91,6 +91,12 @@ class AcqCancelOut(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class ResamplerCfg(C.Structure):
+    """gm_resampler_cfg (32 bytes): zeros are the defaults"""
+    _fields_ = [("up", C.c_uint32), ("down", C.c_uint32), ("taps", C.c_uint32), ("n_phases", C.c_uint32), ("cutoff", C.c_float),
+                ("kaiser_beta", C.c_float), ("blank_threshold", C.c_float), ("reserved", C.c_uint32)]
+
+
 ACQ_FORM_LDS, ACQ_FORM_COMPOSITE, ACQ_FORM_LONG, ACQ_FORM_LONG_PADDED = 0, 1, 2, 3   # gm_acq_form
 
 
@@ -227,6 +233,18 @@ SIGNATURES = {
     "gm_frontend_synchronize": (_i, [_vp]),
     "gm_frontend_write_ring": (_i, [_vp, _vp, _vp, _sz, _i]),
     "gm_frontend_debug_repairs": (_i, [_vp, C.POINTER(_u32)]),
+    "gm_resampler_plan": (_i, [C.POINTER(ResamplerCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32),
+                           C.POINTER(_u64)]),
+    "gm_resampler_design": (_i, [C.POINTER(ResamplerCfg), _vp]),
+    "gm_resampler_create": (_i, [C.POINTER(ResamplerCfg), C.POINTER(_vp)]),
+    "gm_resampler_destroy": (_i, [_vp]),
+    "gm_resampler_reset": (_i, [_vp, _u64]),
+    "gm_resampler_taps": (_i, [_vp, _vp]),
+    "gm_resampler_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_resampler_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "gm_resampler_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "gm_resampler_synchronize": (_i, [_vp]),
+    "gm_frontend_write_ring_resampled": (_i, [_vp, _vp, _vp, _vp, _sz, _i, C.POINTER(_u64)]),
     "gm_trk_create": (_i, [C.POINTER(TrkCfg), C.POINTER(_vp)]),
     "gm_trk_destroy": (_i, [_vp]),
     "gm_trk_start": (_i, [_vp, _u32, C.POINTER(AcqResult)]),

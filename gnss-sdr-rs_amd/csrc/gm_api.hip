@@ -3505,6 +3505,336 @@ int gm_frontend_write_ring(gm_frontend* f, gm_ring* r, const void* samples, size
 
 }  // extern "C"
 
+// ====================================================================== rate conversion and pulse blanking (gm_resampler)
+// gnss_mi355x.h states the definition; tests/resample_model.py restates it in float64.
+namespace {
+struct ResamplerPlan {
+    uint32_t up = 1, down = 1, T = 0, PHI = 0;
+    double cutoff = 0.9, beta = 8.0;
+    float thr = 0.0f;
+};
+constexpr uint64_t RS_INDEX_MAX = 1ull << 62;
+
+int resampler_rules(const gm_resampler_cfg* c, ResamplerPlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    if (c->reserved) return set_err(GM_ERR_INVALID_ARG, "gm_resampler_cfg.reserved must be 0");
+    if (c->up < 1 || c->down < 1 || c->up > (1u << 24) || c->down > (1u << 24)) return set_err(GM_ERR_INVALID_ARG, "up and down: 1 .. 2^24");
+    uint32_t a = c->up, b = c->down;
+    while (b) { const uint32_t t = a % b; a = b; b = t; }
+    p.up = c->up / a; p.down = c->down / a;
+    if (uint64_t(p.up) > 16ull * p.down || uint64_t(p.down) > 16ull * p.up) return set_err(GM_ERR_INVALID_ARG, "up / down outside [1/16, 16]");
+    if (c->taps) {
+        if (c->taps % 8 || c->taps < 8 || c->taps > 256) return set_err(GM_ERR_INVALID_ARG, "taps: a multiple of 8 in 8 .. 256");
+        p.T = c->taps;
+    } else {
+        const uint32_t ceil_ratio = p.down > p.up ? (p.down + p.up - 1) / p.up : 1;
+        p.T = std::min<uint32_t>(256, 32 * ceil_ratio);
+    }
+    if (c->n_phases) {
+        if (c->n_phases < 16 || c->n_phases > 1024 || (c->n_phases & (c->n_phases - 1))) return set_err(GM_ERR_INVALID_ARG, "n_phases: a power of two in 16 .. 1024");
+        p.PHI = c->n_phases;
+    } else p.PHI = 256;
+    if (!(c->cutoff >= 0.0f && c->cutoff <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "cutoff: (0, 1], 0 for the default");
+    if (!(c->kaiser_beta >= 0.0f && c->kaiser_beta <= 20.0f)) return set_err(GM_ERR_INVALID_ARG, "kaiser_beta: [0, 20]");
+    if (!(c->blank_threshold >= 0.0f)) return set_err(GM_ERR_INVALID_ARG, "blank_threshold: >= 0");
+    p.cutoff = c->cutoff == 0.0f ? 0.9 : double(c->cutoff);
+    p.beta = c->kaiser_beta == 0.0f ? 8.0 : double(c->kaiser_beta);
+    p.thr = c->blank_threshold;
+    return GM_OK;
+}
+
+// total_out(A) = max(0, ceil((A - T/2) * up / down)), with B = A - T/2 = b * down + B': b * up + ceil(B' * up / down); B' * up < 2^48
+uint64_t resampler_total_out(const ResamplerPlan& p, uint64_t A) {
+    const uint64_t half = p.T / 2;
+    if (A <= half) return 0;
+    const uint64_t B = A - half, b = B / p.down, Br = B % p.down;
+    return b * p.up + (Br * p.up + p.down - 1) / p.down;
+}
+
+double bessel_i0(double x) {                      // sum_k ((x/2)^k / k!)^2: every term positive, x <= 20
+    const double h = 0.5 * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 200; ++k) {
+        term *= (h / k) * (h / k);
+        sum += term;
+        if (term < 1e-18 * sum) break;
+    }
+    return sum;
+}
+
+void resampler_design(const ResamplerPlan& p, float* table) {
+    const double PI = 3.14159265358979323846;
+    const double rho = p.up < p.down ? double(p.up) / double(p.down) : 1.0, fc = p.cutoff * rho;
+    const double inv_i0 = 1.0 / bessel_i0(p.beta), halfT = 0.5 * double(p.T);
+    std::vector<double> row(p.T);
+    for (uint32_t phi = 0; phi <= p.PHI; ++phi) {
+        double sum = 0.0;
+        for (uint32_t j = 0; j < p.T; ++j) {
+            const double t = double(j) - (halfT - 1.0) - double(phi) / double(p.PHI);
+            double h = 0.0;
+            if (fabs(t) <= halfT) {
+                const double u = t / halfT, w = 1.0 - u * u, x = fc * t;
+                const double sinc = x == 0.0 ? 1.0 : sin(PI * x) / (PI * x);
+                h = fc * sinc * bessel_i0(p.beta * sqrt(w > 0.0 ? w : 0.0)) * inv_i0;
+            }
+            row[j] = h;
+            sum += h;
+        }
+        for (uint32_t j = 0; j < p.T; ++j) table[size_t(phi) * p.T + j] = float(row[j] / sum);
+    }
+}
+}  // namespace
+
+struct gm_resampler {
+    int device = -1;
+    ResamplerPlan plan;
+    std::vector<float> table;               // [PHI + 1][T]
+    float* d_table = nullptr;
+    cf* d_hist[2] = {nullptr, nullptr};     // the last T blanked inputs: d_hist[cur] is read by the next call, the other written
+    int cur = 0;
+    unsigned long long* d_blanked = nullptr;
+    hipStream_t stream = nullptr, last_stream = nullptr;
+    uint64_t base = 0;                      // absolute index of the first input since create / reset
+    uint64_t inputs = 0, outputs = 0;       // since create / reset
+    void* d_in = nullptr; size_t in_cap = 0;    // bytes; staging of the host-buffer entry
+    cf* d_out = nullptr; size_t out_cap = 0;    // samples
+    cf* d_scratch = nullptr;                // gm_frontend_write_ring_resampled: the front-end's linear output (SLOT_SAMPLES_MAX samples)
+};
+
+// one call's kernels on `st`, outputs to out[(out_start + k) & out_mask]; the caller has checked every argument; n_in > 0
+static int resampler_launch(gm_resampler* r, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t out_start,
+                            uint64_t out_mask, uint64_t n_out) {
+    const ResamplerPlan& p = r->plan;
+    const uint64_t A = r->base + r->inputs, m0 = resampler_total_out(p, A);
+    gm::ResampleArgs a{};
+    a.in = d_in; a.n_in = n_in;
+    a.hist_in = r->d_hist[r->cur]; a.hist_out = r->d_hist[r->cur ^ 1];
+    a.table = r->d_table; a.T = p.T; a.PHI = p.PHI; a.up = p.up; a.down = p.down;
+    a.a0 = m0 / p.up; a.mr0 = m0 % p.up; a.in_index = A;
+    a.n_out = n_out; a.tile_out = gm::resample_tile_out(p.T, p.up, p.down);
+    a.out = out; a.out_start = out_start; a.out_mask = out_mask;
+    a.thr2 = p.thr * p.thr; a.blank = p.thr > 0.0f ? 1 : 0;
+    a.blanked = r->d_blanked;
+    gm::launch_resample(st, a, fmt);
+    HIPC(hipGetLastError());
+    r->cur ^= 1; r->inputs += n_in; r->outputs += n_out; r->last_stream = st;
+    return GM_OK;
+}
+static uint64_t resampler_count(const gm_resampler* r, uint64_t n_in) {
+    const uint64_t A = r->base + r->inputs;
+    return resampler_total_out(r->plan, A + n_in) - resampler_total_out(r->plan, A);
+}
+static int resampler_sync(gm_resampler* r) {
+    HIPC(hipStreamSynchronize(r->stream));
+    if (r->last_stream && r->last_stream != r->stream) HIPC(hipStreamSynchronize(r->last_stream));
+    return GM_OK;
+}
+
+extern "C" {
+
+int gm_resampler_plan(const gm_resampler_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* up_reduced, uint32_t* down_reduced,
+                      uint32_t* taps, uint32_t* n_phases, uint64_t* n_out) {
+    ResamplerPlan p;
+    if (int rc = resampler_rules(cfg, p)) return rc;
+    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (up_reduced) *up_reduced = p.up;
+    if (down_reduced) *down_reduced = p.down;
+    if (taps) *taps = p.T;
+    if (n_phases) *n_phases = p.PHI;
+    if (n_out) *n_out = resampler_total_out(p, inputs_so_far + n_in) - resampler_total_out(p, inputs_so_far);
+    return GM_OK;
+}
+
+int gm_resampler_design(const gm_resampler_cfg* cfg, float* table) {
+    ResamplerPlan p;
+    if (int rc = resampler_rules(cfg, p)) return rc;
+    if (!table) return set_err(GM_ERR_INVALID_ARG, "null table");
+    resampler_design(p, table);
+    return GM_OK;
+}
+
+int gm_resampler_create(const gm_resampler_cfg* cfg, gm_resampler** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    ResamplerPlan p;
+    if (int rc = resampler_rules(cfg, p)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_resampler* r = new gm_resampler;
+    r->device = g_device; r->plan = p;
+    r->table.resize(size_t(p.PHI + 1) * p.T);
+    resampler_design(p, r->table.data());
+    const size_t hist_bytes = size_t(p.T) * sizeof(cf);
+    hipError_t e = hipMalloc(&r->d_table, r->table.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(r->d_table, r->table.data(), r->table.size() * sizeof(float), hipMemcpyHostToDevice);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = hipMalloc(&r->d_hist[i], hist_bytes);
+        if (e == hipSuccess) e = hipMemset(r->d_hist[i], 0, hist_bytes);
+    }
+    if (e == hipSuccess) e = hipMalloc(&r->d_blanked, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(r->d_blanked, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the fills have run before a kernel on a non-blocking stream can touch the state (see gm_ring_create)
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { gm_resampler_destroy(r); return hip_fail(e, "gm_resampler_create"); }
+    *out = r;
+    return GM_OK;
+}
+
+int gm_resampler_destroy(gm_resampler* r) {
+    if (!r) return GM_OK;
+    hipSetDevice(r->device);
+    if (r->last_stream && r->last_stream != r->stream) hipStreamSynchronize(r->last_stream);
+    if (r->stream) { hipStreamSynchronize(r->stream); hipStreamDestroy(r->stream); }
+    hipFree(r->d_table); hipFree(r->d_hist[0]); hipFree(r->d_hist[1]); hipFree(r->d_blanked);
+    hipFree(r->d_in); hipFree(r->d_out); hipFree(r->d_scratch);
+    delete r;
+    return GM_OK;
+}
+
+int gm_resampler_reset(gm_resampler* r, uint64_t input_index) {
+    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (input_index > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "input_index above 2^62");
+    if (int rc = ensure_device(r->device)) return rc;
+    if (int rc = resampler_sync(r)) return rc;
+    const size_t hist_bytes = size_t(r->plan.T) * sizeof(cf);
+    HIPC(hipMemsetAsync(r->d_hist[0], 0, hist_bytes, r->stream));
+    HIPC(hipMemsetAsync(r->d_hist[1], 0, hist_bytes, r->stream));
+    HIPC(hipMemsetAsync(r->d_blanked, 0, sizeof(unsigned long long), r->stream));
+    HIPC(hipStreamSynchronize(r->stream));
+    r->cur = 0; r->base = input_index; r->inputs = 0; r->outputs = 0;
+    return GM_OK;
+}
+
+int gm_resampler_taps(gm_resampler* r, float* table) {
+    if (!r || !table) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    memcpy(table, r->table.data(), r->table.size() * sizeof(float));
+    return GM_OK;
+}
+
+int gm_resampler_stats(gm_resampler* r, uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) {
+    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(r->device)) return rc;
+    if (int rc = resampler_sync(r)) return rc;
+    if (blanked) {
+        unsigned long long b = 0;
+        HIPC(hipMemcpy(&b, r->d_blanked, sizeof(b), hipMemcpyDeviceToHost));
+        *blanked = b;
+    }
+    if (inputs) *inputs = r->inputs;
+    if (outputs) *outputs = r->outputs;
+    return GM_OK;
+}
+
+int gm_resampler_process_dev(gm_resampler* r, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out,
+                             void* stream) {
+    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "resampler input is c32 or int8 IQ");
+    if (!d_in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
+    if (uint64_t(n_in) > (1ull << 31) || r->base + r->inputs + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
+    const uint64_t cnt = resampler_count(r, n_in);
+    if (cnt > out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_cap below the call's output count (gm_resampler_plan gives it)");
+    if (cnt && !d_out) return set_err(GM_ERR_INVALID_ARG, "null output");
+    if (cnt && n_in) {
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), i1 = i0 + n_in * (fmt == GM_FMT_C32 ? 8 : 2);
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + cnt * 8;
+        if (i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
+    }
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(r->device)) return rc;
+    return resampler_launch(r, stream ? static_cast<hipStream_t>(stream) : r->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), 0, ~0ull, cnt);
+}
+
+int gm_resampler_process(gm_resampler* r, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out) {
+    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "resampler input is c32 or int8 IQ");
+    if (!in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
+    if (uint64_t(n_in) > (1ull << 31) || r->base + r->inputs + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
+    const uint64_t cnt = resampler_count(r, n_in);
+    if (cnt > out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_cap below the call's output count (gm_resampler_plan gives it)");
+    if (cnt && !out) return set_err(GM_ERR_INVALID_ARG, "null output");
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(r->device)) return rc;
+    const size_t in_bytes = n_in * (fmt == GM_FMT_C32 ? 8 : 2);
+    if (r->in_cap < in_bytes || r->out_cap < cnt) HIPC(hipStreamSynchronize(r->stream));
+    if (r->in_cap < in_bytes) {
+        hipFree(r->d_in); r->d_in = nullptr; r->in_cap = 0;
+        HIPC(hipMalloc(&r->d_in, in_bytes));
+        r->in_cap = in_bytes;
+    }
+    if (r->out_cap < cnt) {
+        hipFree(r->d_out); r->d_out = nullptr; r->out_cap = 0;
+        HIPC(hipMalloc(reinterpret_cast<void**>(&r->d_out), size_t(cnt) * sizeof(cf)));
+        r->out_cap = size_t(cnt);
+    }
+    if (r->last_stream && r->last_stream != r->stream) HIPC(hipStreamSynchronize(r->last_stream));   // the history the last call wrote
+    HIPC(hipMemcpyAsync(r->d_in, in, in_bytes, hipMemcpyHostToDevice, r->stream));
+    if (int rc = resampler_launch(r, r->stream, r->d_in, fmt, n_in, r->d_out, 0, ~0ull, cnt)) return rc;
+    if (cnt) HIPC(hipMemcpyAsync(out, r->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, r->stream));
+    HIPC(hipStreamSynchronize(r->stream));
+    return GM_OK;
+}
+
+int gm_resampler_synchronize(gm_resampler* r) {
+    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(r->device)) return rc;
+    return resampler_sync(r);
+}
+
+// gm_frontend_write_ring's block loop with the rate conversion as one more step: front-end -> the resampler's linear scratch buffer ->
+// resampler -> the ring at write_pos (ring indices count OUTPUT samples)
+int gm_frontend_write_ring_resampled(gm_frontend* f, gm_resampler* rs, gm_ring* r, const void* samples, size_t n_samples, int fmt,
+                                     uint64_t* n_out_total) {
+    if (!f || !rs || !r || (!samples && n_samples)) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "front-end input is c32 or int8 IQ");
+    if (f->device != r->device || rs->device != r->device) return set_err(GM_ERR_INVALID_ARG, "front-end, resampler and ring live on different devices");
+    if (rs->base + rs->inputs + n_samples > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
+    const uint64_t total = resampler_count(rs, n_samples);
+    if (total > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "write larger than the ring");
+    if (n_out_total) *n_out_total = total;
+    if (int rc = ensure_device(r->device)) return rc;
+    if (int rc = ring_async_init(r)) return rc;
+    if (!r->fe_stream) {      // (as gm_frontend_write_ring creates it)
+        if (gm::diag_int("GM_RING_FE_STREAM", 1) == 0) r->fe_stream = r->copy_stream;
+        else {
+            int least = 0, greatest = 0;
+            HIPC(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            const int pr = gm::diag_int("GM_RING_FE_PRIORITY", 99);
+            HIPC(hipStreamCreateWithPriority(&r->fe_stream, hipStreamNonBlocking, pr == 99 ? greatest : pr));
+        }
+        for (int i = 0; i < gm_ring::SLOTS; ++i) HIPC(hipEventCreateWithFlags(&r->h2d_done[i], hipEventDisableTiming));
+    }
+    if (!rs->d_scratch) HIPC(hipMalloc(reinterpret_cast<void**>(&rs->d_scratch), gm_ring::SLOT_SAMPLES_MAX * sizeof(cf)));
+    if (rs->last_stream && rs->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(rs->last_stream));   // the history the last call wrote
+    const size_t bps = fmt == GM_FMT_C32 ? 8 : 2;
+    const uint8_t* src = static_cast<const uint8_t*>(samples);
+    while (n_samples) {
+        const size_t chunk = n_samples < r->slot_samples ? n_samples : r->slot_samples;
+        const int slot = int(r->slot_seq++ % gm_ring::SLOTS);
+        if (int rc = ring_reclaim_slot(r, slot)) return rc;
+        if (!f->d_raw[slot]) HIPC(hipMalloc(&f->d_raw[slot], gm_ring::SLOT_SAMPLES_MAX * 8));
+        memcpy(r->staging[slot], src, chunk * bps);
+        HIPC(hipMemcpyAsync(f->d_raw[slot], r->staging[slot], chunk * bps, hipMemcpyHostToDevice, r->copy_stream));
+        HIPC(hipEventRecord(r->h2d_done[slot], r->copy_stream));
+        HIPC(hipStreamWaitEvent(r->fe_stream, r->h2d_done[slot], 0));
+        // one scratch buffer serves every block: the stream runs block k's resampler kernel before block k + 1's front-end kernel
+        if (int rc = frontend_launch(f, r->fe_stream, f->d_raw[slot], fmt, rs->d_scratch, 0, ~0ull, chunk)) return rc;
+        const uint64_t cnt = resampler_count(rs, chunk);
+        if (int rc = resampler_launch(rs, r->fe_stream, rs->d_scratch, GM_FMT_C32, chunk, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
+        HIPC(hipEventRecord(r->slot_done[slot], r->fe_stream));
+        r->slot_used[slot] = true;
+        r->write_pos += cnt;
+        if (int rc = ring_enqueue_publish(r, slot, r->fe_stream)) return rc;
+        src += chunk * bps; n_samples -= chunk;
+    }
+    return GM_OK;
+}
+
+}  // extern "C"
+
 // ====================================================================== multi-GPU exchange
 // The path's ONE exchange step: all-gather of the per-(worker, bin) metrics over RCCL, enqueued on the acquisition
 // handle's stream, followed by the regroup to the [3][nranks*P][D] layout gm_acq_decide_dev replays.  RCCL is bound

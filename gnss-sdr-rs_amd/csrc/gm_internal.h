@@ -371,4 +371,28 @@ constexpr int FE_SPEC_K_MAX = 64;     // most workgroups (runs) per block in the
 constexpr int FE_FAST_SEG = 3840;      // samples per pipeline segment of the fast kernel: 480 chain steps = 120 quads x 8 SIMD
                                        // lanes = 960 stage-C items = one per helper lane (the table period is padded to >= this)
 
+// ---------------------------------------------------------------- rate conversion and pulse blanking (resample_kernels.hip)
+// gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of `tile_out` outputs) and one
+// of the state kernel (the next history, the blanked count).  The host hands over the call's first output index as m0 = a0 * up + mr0
+// and the absolute index of the call's first input; the kernel forms every position from 64-bit integers.
+constexpr int RS_SPAN_MAX = 4096;          // LDS samples of a tile's input span; tile_out is chosen so that the span fits (resample_tile_out)
+constexpr int RS_TILE_MAX = 1024;          // 256 lanes x 4 outputs; a lane owns 4, 2 or 1 outputs (tiles of 1024, 512, <= 256)
+struct ResampleArgs {
+    const void* in; uint64_t n_in;         // this call's inputs (c32 or int8 IQ)
+    const cf* hist_in; cf* hist_out;       // [T] the last T blanked inputs before / after this call (two buffers, used alternately)
+    const float* table;                    // [PHI + 1][T]
+    uint32_t T, PHI, up, down;
+    uint64_t a0, mr0;                      // the call's first output: m0 = a0 * up + mr0, mr0 < up
+    uint64_t in_index;                     // absolute index of in[0]
+    uint64_t n_out; uint32_t tile_out;
+    cf* out; uint64_t out_start, out_mask; // linear buffer (out_mask = ~0) or ring base
+    float thr2; int blank;                 // blank_threshold^2 (f32 product); blanking on
+    unsigned long long* blanked;           // device counter, integer atomics only
+};
+inline uint32_t resample_tile_out(uint32_t T, uint32_t up, uint32_t down) {
+    const uint64_t n = uint64_t(RS_SPAN_MAX - int(T) - 1) * up / down + 1;      // the most outputs whose inputs span <= RS_SPAN_MAX samples
+    return n >= 1024 ? 1024u : n >= 512 ? 512u : n >= 256 ? 256u : uint32_t(n);
+}
+void launch_resample(hipStream_t, const ResampleArgs&, int fmt);
+
 }  // namespace gm

@@ -65,15 +65,22 @@ class DigitalFrontend:
         check(lib().gm_frontend_debug_repairs(self._h, C.byref(n)), "gm_frontend_debug_repairs")
         return n.value
 
-    def write_ring(self, ring, samples):
-        """samples: complex64 array, or int8 array of interleaved I/Q."""
+    def write_ring(self, ring, samples, resampler=None):
+        """samples: complex64 array, or int8 array of interleaved I/Q.  With a resample.Resampler the block goes through it on its way
+        into the ring (gm_frontend_write_ring_resampled): ring indices then count output samples, and the outputs enqueued are returned."""
         s = np.ascontiguousarray(samples)
         if s.dtype == np.int8:
             n, fmt = s.size // 2, FMT_I8_IQ
         else:
             s = np.ascontiguousarray(s, np.complex64)
             n, fmt = s.size, FMT_C32
-        check(lib().gm_frontend_write_ring(self._h, ring._h, _p(s), n, fmt), "gm_frontend_write_ring")
+        if resampler is None:
+            check(lib().gm_frontend_write_ring(self._h, ring._h, _p(s), n, fmt), "gm_frontend_write_ring")
+            return None
+        total = C.c_uint64(0)
+        check(lib().gm_frontend_write_ring_resampled(self._h, resampler._h, ring._h, _p(s), n, fmt, C.byref(total)),
+              "gm_frontend_write_ring_resampled")
+        return total.value
 
 
 def process_dev_batch(frontends, d_in_ptrs, fmt, d_out_ptrs, n_samples, stream=None):

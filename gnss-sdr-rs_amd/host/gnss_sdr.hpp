@@ -271,6 +271,43 @@ public:
     }
 };
 
+// ---- rate conversion and pulse blanking (gm_resampler): the two stages rf/frontend.rs names in comments and leaves out.
+// fs_out = fs_in * up / down; every output is defined by absolute sample indices, so the words do not depend on the block cuts.
+class Resampler {
+    gm_resampler* h_ = nullptr;
+public:
+    explicit Resampler(const gm_resampler_cfg& cfg) { check(gm_resampler_create(&cfg, &h_), "Resampler::new"); }
+    Resampler(uint32_t up, uint32_t down, float blank_threshold = 0.0f) {     // every other setting at its default
+        gm_resampler_cfg cfg{};
+        cfg.up = up; cfg.down = down; cfg.blank_threshold = blank_threshold;
+        check(gm_resampler_create(&cfg, &h_), "Resampler::new");
+    }
+    ~Resampler() { gm_resampler_destroy(h_); }
+    Resampler(const Resampler&) = delete;
+    gm_resampler* handle() const { return h_; }
+    // the synchronous host-buffer forms: this call's outputs
+    std::vector<Complex32> process(const std::vector<Complex32>& block) { return run(block.data(), block.size(), GM_FMT_C32); }
+    std::vector<Complex32> process_i8(const int8_t* iq, size_t n) { return run(iq, n, GM_FMT_I8_IQ); }
+    // device pointers, asynchronous on `stream` (nullptr: the handle's own); returns the number of outputs written
+    size_t process_dev(const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, void* stream = nullptr) {
+        size_t n = 0;
+        check(gm_resampler_process_dev(h_, d_in, fmt, n_in, d_out, out_cap, &n, stream), "Resampler::process_dev");
+        return n;
+    }
+    void reset(uint64_t input_index = 0) { check(gm_resampler_reset(h_, input_index), "Resampler::reset"); }
+    void stats(uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) const { check(gm_resampler_stats(h_, inputs, outputs, blanked), "Resampler::stats"); }
+    void taps(float* table) const { check(gm_resampler_taps(h_, table), "Resampler::taps"); }      // (n_phases + 1) * taps words
+    void synchronize() { check(gm_resampler_synchronize(h_), "Resampler::synchronize"); }
+private:
+    std::vector<Complex32> run(const void* in, size_t n, int fmt) {
+        size_t got = 0;
+        std::vector<Complex32> out(n * 16 + 1);                             // a call never delivers more than n * up / down + 1, up / down <= 16
+        check(gm_resampler_process(h_, in, fmt, n, reinterpret_cast<gm_c32*>(out.data()), out.size(), &got), "Resampler::process");
+        out.resize(got);
+        return out;
+    }
+};
+
 // ---- rf::frontend::DigitalFrontend (src/rf/frontend.rs:6-62)
 class DigitalFrontend {
     gm_frontend* h_ = nullptr;
@@ -282,6 +319,18 @@ public:
     // rf_thread's block step (rf_thread.rs:43-48): process_block + write_samples, fused on the GPU, non-blocking
     void write_ring(MulticastRingBuffer& ring, const Complex32* block, size_t n) { check(gm_frontend_write_ring(h_, ring.handle(), block, n, GM_FMT_C32), "write_ring"); }
     void write_ring_i8(MulticastRingBuffer& ring, const int8_t* iq, size_t n) { check(gm_frontend_write_ring(h_, ring.handle(), iq, n, GM_FMT_I8_IQ), "write_ring"); }
+    // the same block step with the rate conversion (and pulse blanking) between the front-end and the ring: ring indices then count
+    // OUTPUT samples (ring index m is input time m * down / up); returns the outputs enqueued
+    uint64_t write_ring(MulticastRingBuffer& ring, const Complex32* block, size_t n, Resampler& resampler) {
+        uint64_t total = 0;
+        check(gm_frontend_write_ring_resampled(h_, resampler.handle(), ring.handle(), block, n, GM_FMT_C32, &total), "write_ring");
+        return total;
+    }
+    uint64_t write_ring_i8(MulticastRingBuffer& ring, const int8_t* iq, size_t n, Resampler& resampler) {
+        uint64_t total = 0;
+        check(gm_frontend_write_ring_resampled(h_, resampler.handle(), ring.handle(), iq, n, GM_FMT_I8_IQ, &total), "write_ring");
+        return total;
+    }
     uint32_t debug_repairs() const { uint32_t n = 0; check(gm_frontend_debug_repairs(h_, &n), "debug_repairs"); return n; }   // runs of the speculative form done again
 };
 

@@ -663,7 +663,9 @@ int gm_ring_wait_head(gm_ring *r, uint64_t required_idx, uint32_t timeout_ms, in
  * rf::frontend::DigitalFrontend (src/rf/frontend.rs:6-62): DC removal (DcRemoverSimd, src/rf/dc_remove.rs:10-29:
  * eight one-pole IIR lanes per component, alpha = 0.001) + LUT NCO down-mix (NcoLut, src/rf/nco_lut.rs:17-42: 2048
  * entries, f32 phase accumulator `% 2048`) + mix_simd (:8-15), bit-exact with the reference's f32 evaluation order.
- * Only whole chunks of 8 samples are processed (chunks_exact_mut(16), :35); a tail passes through unprocessed. */
+ * Only whole chunks of 8 samples are processed (chunks_exact_mut(16), :35); a tail passes through unprocessed.
+ * fs_out is stored only, as in the reference (frontend.rs keeps output_sample_rate as a dead field): the front-end returns fs_in
+ * samples, and the rate is converted by a gm_resampler, declared below. */
 typedef struct gm_frontend gm_frontend;
 int gm_frontend_create(float f_if, float fs_in, float fs_out, gm_frontend **out);     /* ::new :19-30 */
 int gm_frontend_destroy(gm_frontend *f);
@@ -695,6 +697,82 @@ int gm_frontend_write_ring(gm_frontend *f, gm_ring *ring, const void *samples, s
  * (tests/test_gpu_frontend.py::test_speculative_blocks_are_exact spoils every one of them); 0.52 -> 0.15 ms per 2^19-sample block.
  * Diagnostic (not in the reference): *runs = how many runs the verification has had to repeat on this handle so far. */
 int gm_frontend_debug_repairs(gm_frontend *f, uint32_t *runs);
+
+/* ------------------------------------------------------------------ Rate conversion and pulse blanking
+ * The two stages the reference's front-end names and leaves out (rf/frontend.rs: process_block ends with the comments
+ * `// Pulse blanking, e.g., based on amplitude threshold)` and `// Resampling`).  A gm_resampler converts a stream of c32 or int8-IQ
+ * samples at rate fs_in into c32 samples at fs_out = fs_in * up / down with a polyphase windowed-sinc filter, and can zero input
+ * samples whose power exceeds a threshold first.  Every output is defined by ABSOLUTE sample indices alone: the words do not depend
+ * on how the stream is cut into calls.
+ *   Table (host, f64, each word rounded once to f32), layout [PHI + 1][T].  rho = min(1, up / down), fc = cutoff * rho,
+ *     h(t) = fc * sinc(fc t) * I0(beta * sqrt(1 - (2t/T)^2)) / I0(beta)  for |t| <= T/2, else 0;   sinc(x) = sin(pi x) / (pi x)
+ *     g[phi][j] = h(j - (T/2 - 1) - phi / PHI),  then every row divided by its own f64 sum: the DC gain is 1 at every phase.
+ *   Output m = 0, 1, ...: position and phase from 64-bit integers only,
+ *     pos = m * down,  i0 = pos div up,  r = pos mod up,  q = r * PHI,  phi = q div up,  alpha = float(double(q mod up) / double(up))
+ *     c_j = fmaf(alpha, g[phi+1][j] - g[phi][j], g[phi][j])           (the difference rounded to f32 first)
+ *     y[m] = sum_{j<T} c_j * xb[i0 - (T/2 - 1) + j]                   f32, one fmaf per component and tap, from +0, j ASCENDING
+ *     xb = the input after blanking, zero before the stream's first sample.  The order of the T terms is a function of j alone, never
+ *     of where the output falls in a tile, a workgroup or a call.  m = a * up + m' and the input count are decomposed so that no
+ *     product exceeds 2^63: a stream stays correct past 2^32 samples (86 s at 50 Msps).
+ *   Blanking (blank_threshold > 0): an input sample with re*re + im*im > thr*thr is replaced by (0, 0); f32, each product and the sum
+ *     rounded on its own, strictly greater.  int8 samples are converted to f32 first (-128 is -128.0f).
+ *   Timing.  Output m is the signal at input time m * down / up: the filter is centred and adds no timestamp delay.  Only availability
+ *     lags: after A inputs in total, total_out(A) = max(0, ceil((A - T/2) * up / down)) outputs exist, and a call delivers
+ *     total_out(A_after) - total_out(A_before).  The host computes the count with no synchronisation.
+ *   State.  The handle keeps the last T blanked inputs in device memory, in two buffers used alternately (a call reads one while it
+ *     writes the other), and the counters on the host; the blanked count is an integer in device memory.
+ *   Kernel (csrc/resample_kernels.hip): one 256-lane workgroup per tile of outputs; the tile's inputs are converted and blanked once
+ *     into LDS.  With n = floor((4096 - T - 1) * up / down) + 1, the most outputs whose inputs span at most 4096 LDS samples, a tile
+ *     is 1024, 512 or 256 outputs (the largest of them not above n; a lane owns 4, 2 or 1), or n itself below 256.
+ * Zeros in the config mean defaults.  (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct {
+    uint32_t up, down;        /* fs_out = fs_in * up / down; reduced by their gcd inside; each 1 .. 2^24; 1/16 <= up/down <= 16 */
+    uint32_t taps;            /* T, a multiple of 8 in 8 .. 256; 0 -> min(256, 32 * ceil(max(1, down/up))) */
+    uint32_t n_phases;        /* PHI, a power of two 16 .. 1024; 0 -> 256 */
+    float    cutoff;          /* (0, 1], of the narrower Nyquist band; 0 -> 0.9 */
+    float    kaiser_beta;     /* [0, 20]; 0 -> 8.0 */
+    float    blank_threshold; /* 0: off; > 0: an input sample with re^2 + im^2 > thr^2 (f32, each product and the sum rounded on its own) is replaced by (0, 0) */
+    uint32_t reserved;        /* must be 0 */
+} gm_resampler_cfg;
+typedef struct gm_resampler gm_resampler;
+/* host only, no device: the argument rules (GM_ERR_INVALID_ARG: a null cfg, up or down 0 or above 2^24, a ratio outside [1/16, 16],
+ * taps not 0 and not a multiple of 8 in 8 .. 256, n_phases not 0 and not a power of two in 16 .. 1024, cutoff outside [0, 1], kaiser_beta
+ * outside [0, 20], a negative blank_threshold, any of the three not a number, reserved != 0, inputs_so_far + n_in above 2^62) and, for
+ * a stream that has taken inputs_so_far samples, the count n_in more deliver.  Any output pointer may be NULL. */
+int gm_resampler_plan(const gm_resampler_cfg *cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t *up_reduced,
+                      uint32_t *down_reduced, uint32_t *taps, uint32_t *n_phases, uint64_t *n_out);
+/* host only, no device: the (PHI + 1) * T table words */
+int gm_resampler_design(const gm_resampler_cfg *cfg, float *table);
+int gm_resampler_create(const gm_resampler_cfg *cfg, gm_resampler **out);
+int gm_resampler_destroy(gm_resampler *r);
+/* Zeroes the history and the three counters; the stream continues as if input_index zero samples had gone before: the next input has
+ * absolute index input_index, the next output absolute index total_out(input_index).  Synchronous.  input_index above 2^62:
+ * GM_ERR_INVALID_ARG. */
+int gm_resampler_reset(gm_resampler *r, uint64_t input_index);
+/* the (PHI + 1) * T words the device uses (gm_resampler_design's) */
+int gm_resampler_taps(gm_resampler *r, float *table);
+/* inputs taken, outputs delivered and inputs blanked since gm_resampler_create or the last gm_resampler_reset (any pointer may be
+ * NULL).  Each input is counted once.  Synchronises the handle's stream and the stream the last call ran on. */
+int gm_resampler_stats(gm_resampler *r, uint64_t *inputs, uint64_t *outputs, uint64_t *blanked);
+/* d_in (GM_FMT_C32 or GM_FMT_I8_IQ; GM_FMT_I8_REAL: GM_ERR_INVALID_ARG), n_in samples -> d_out (c32), *n_out of them (n_out may be
+ * NULL).  Asynchronous on `stream` (a hipStream_t; NULL: the handle's own non-blocking stream); consecutive calls of a handle must be
+ * ordered against each other (one stream, or the caller's events).  Every argument is checked before anything runs: out_cap below the
+ * count is GM_ERR_OUT_OF_RANGE, d_out overlapping d_in GM_ERR_INVALID_ARG, each with nothing launched and the state unchanged.
+ * n_in = 0: GM_OK, *n_out = 0. */
+int gm_resampler_process_dev(gm_resampler *r, const void *d_in, int fmt, size_t n_in, void *d_out, size_t out_cap, size_t *n_out,
+                             void *stream);
+/* the synchronous host-buffer form (H2D, the kernels, D2H on the handle's stream) */
+int gm_resampler_process(gm_resampler *r, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out);
+int gm_resampler_synchronize(gm_resampler *r);
+/* gm_frontend_write_ring with the rate conversion as one more step per block: the front-end kernel writes a linear device buffer owned
+ * by the resampler, the resampler kernel writes its outputs into the ring at the writer's position (wrapping with the ring's mask), the
+ * position advances by that block's output count and the block is published as gm_frontend_write_ring publishes it.  A block that
+ * yields no output leaves the head where it was.  Ring indices then count OUTPUT samples: ring index m is input time m * down / up,
+ * and gm_acq_result.sample_global_index of a search on this ring lives on that axis, at rate fs_out.  *n_out_total (may be NULL) =
+ * the outputs this call enqueued.  GM_ERR_OUT_OF_RANGE when they exceed the ring; the resampler must not be in use elsewhere
+ * meanwhile and should have been created at its absolute index 0 when the ring was empty.  gm_ring_flush waits for all of it. */
+int gm_frontend_write_ring_resampled(gm_frontend *f, gm_resampler *r, gm_ring *ring, const void *samples, size_t n_samples, int fmt,
+                                     uint64_t *n_out_total);
 
 /* ------------------------------------------------------------------ Tracking
  * The evolving fields of TrackingChannel (src/tracking/do_tracking.rs:88-116). */

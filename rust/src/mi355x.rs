@@ -114,7 +114,17 @@ pub struct GmAcqCancelOut {         // gm_acq_cancel_out (32 bytes)
     pub amp_rms: f32,
     pub n_segments: u32, pub first_samples: u32, pub last_samples: u32, pub worker: u32, pub reserved: u32,
 }
-pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmResamplerCfg {         // gm_resampler_cfg (32 bytes; zeros: the defaults)
+    pub up: u32, pub down: u32,      // fs_out = fs_in * up / down; reduced by their gcd inside; 1/16 <= up/down <= 16
+    pub taps: u32,                   // a multiple of 8 in 8 .. 256; 0: min(256, 32 * ceil(max(1, down/up)))
+    pub n_phases: u32,               // a power of two 16 .. 1024; 0: 256
+    pub cutoff: f32,                 // (0, 1] of the narrower Nyquist band; 0: 0.9
+    pub kaiser_beta: f32,            // [0, 20]; 0: 8.0
+    pub blank_threshold: f32,        // 0: off; > 0: an input sample with re^2 + im^2 > thr^2 is replaced by (0, 0)
+    pub reserved: u32,               // must be 0
+}
+pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {}
 
 extern "C" {
     pub fn gm_init(device: c_int) -> c_int;
@@ -177,6 +187,29 @@ extern "C" {
     pub fn gm_ring_write_samples_async(r: *mut GmRing, s: *const Complex32, n: usize) -> c_int;
     pub fn gm_ring_flush(r: *mut GmRing) -> c_int;
     pub fn gm_ring_get_enqueued_head(r: *mut GmRing, head: *mut u64) -> c_int;
+    // rf/frontend.rs:19-62 (DigitalFrontend::new, process_block) and rf_thread.rs:43-48 (the block step into the ring)
+    pub fn gm_frontend_create(f_if: f32, fs_in: f32, fs_out: f32, out: *mut *mut GmFrontend) -> c_int;
+    pub fn gm_frontend_destroy(f: *mut GmFrontend) -> c_int;
+    pub fn gm_frontend_process_block(f: *mut GmFrontend, raw_floats: *mut f32, n_floats: usize) -> c_int;
+    pub fn gm_frontend_write_ring(f: *mut GmFrontend, ring: *mut GmRing, samples: *const c_void, n_samples: usize, fmt: c_int) -> c_int;
+    // rate conversion and pulse blanking (additive entries, ABI stays 9): the two stages frontend.rs names in comments and leaves out;
+    // fs_out = fs_in * up / down, every output defined by absolute sample indices; plan and design are host only
+    pub fn gm_resampler_plan(cfg: *const GmResamplerCfg, inputs_so_far: u64, n_in: u64, up_reduced: *mut u32, down_reduced: *mut u32,
+                             taps: *mut u32, n_phases: *mut u32, n_out: *mut u64) -> c_int;
+    pub fn gm_resampler_design(cfg: *const GmResamplerCfg, table: *mut f32) -> c_int;
+    pub fn gm_resampler_create(cfg: *const GmResamplerCfg, out: *mut *mut GmResampler) -> c_int;
+    pub fn gm_resampler_destroy(r: *mut GmResampler) -> c_int;
+    pub fn gm_resampler_reset(r: *mut GmResampler, input_index: u64) -> c_int;
+    pub fn gm_resampler_taps(r: *mut GmResampler, table: *mut f32) -> c_int;
+    pub fn gm_resampler_stats(r: *mut GmResampler, inputs: *mut u64, outputs: *mut u64, blanked: *mut u64) -> c_int;
+    pub fn gm_resampler_process_dev(r: *mut GmResampler, d_in: *const c_void, fmt: c_int, n_in: usize, d_out: *mut c_void,
+                                    out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gm_resampler_process(r: *mut GmResampler, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32,
+                                out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn gm_resampler_synchronize(r: *mut GmResampler) -> c_int;
+    /// gm_frontend_write_ring with the resampler between the front-end and the ring: ring indices then count OUTPUT samples
+    pub fn gm_frontend_write_ring_resampled(f: *mut GmFrontend, r: *mut GmResampler, ring: *mut GmRing, samples: *const c_void,
+                                            n_samples: usize, fmt: c_int, n_out_total: *mut u64) -> c_int;
     // do_tracking.rs:118-158, 311-327
     pub fn gm_trk_create(cfg: *const GmTrkCfg, out: *mut *mut GmTrk) -> c_int;
     pub fn gm_trk_destroy(t: *mut GmTrk) -> c_int;
