@@ -5,9 +5,11 @@ include/gnss_mi355x.h.  This Python package is plumbing around it:
   _lib        ctypes loader (fails loudly when the library is missing; there is no CPU fallback)
   acquisition / tracking / fft   thin mirrors of the reference's Rust API names over the C ABI
   frontend / resample            the digital front-end, and the rate conversion and pulse blanking it leaves out
+  excise                         FFT-domain narrowband interference excision (overlap-add filter bank, adaptive per-bin gains)
   synth       deterministic synthetic IF scenes
   build       hipcc build recipe
 """
 from . import _lib  # noqa: F401
 from ._lib import GmError, lib, library_path  # noqa: F401
 from .resample import Resampler  # noqa: F401
+from .excise import Excisor  # noqa: F401

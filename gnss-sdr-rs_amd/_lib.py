@@ -97,6 +97,12 @@ class ResamplerCfg(C.Structure):
                 ("kaiser_beta", C.c_float), ("blank_threshold", C.c_float), ("reserved", C.c_uint32)]
 
 
+class ExcisorCfg(C.Structure):
+    """gm_excisor_cfg (32 bytes): zeros are the defaults"""
+    _fields_ = [("block", C.c_uint32), ("guard_bins", C.c_uint32), ("threshold_factor", C.c_float), ("blank_threshold", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
 ACQ_FORM_LDS, ACQ_FORM_COMPOSITE, ACQ_FORM_LONG, ACQ_FORM_LONG_PADDED = 0, 1, 2, 3   # gm_acq_form
 
 
@@ -245,6 +251,20 @@ SIGNATURES = {
     "gm_resampler_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gm_resampler_synchronize": (_i, [_vp]),
     "gm_frontend_write_ring_resampled": (_i, [_vp, _vp, _vp, _vp, _sz, _i, C.POINTER(_u64)]),
+    "gm_excisor_plan": (_i, [C.POINTER(ExcisorCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_float), C.POINTER(_u64)]),
+    "gm_excisor_windows": (_i, [C.POINTER(ExcisorCfg), _vp, _vp]),
+    "gm_excisor_create": (_i, [C.POINTER(ExcisorCfg), C.POINTER(_vp)]),
+    "gm_excisor_destroy": (_i, [_vp]),
+    "gm_excisor_reset": (_i, [_vp, _u64]),
+    "gm_excisor_set_gains": (_i, [_vp, _vp]),
+    "gm_excisor_gains": (_i, [_vp, _vp]),
+    "gm_excisor_adapt_dev": (_i, [_vp, _vp, _i, _sz, _vp]),
+    "gm_excisor_psd": (_i, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(_u32), C.POINTER(_u32)]),
+    "gm_excisor_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_excisor_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "gm_excisor_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "gm_excisor_synchronize": (_i, [_vp]),
+    "gm_frontend_write_ring_conditioned": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, C.POINTER(_u64)]),
     "gm_trk_create": (_i, [C.POINTER(TrkCfg), C.POINTER(_vp)]),
     "gm_trk_destroy": (_i, [_vp]),
     "gm_trk_start": (_i, [_vp, _u32, C.POINTER(AcqResult)]),

@@ -3835,6 +3835,393 @@ int gm_frontend_write_ring_resampled(gm_frontend* f, gm_resampler* rs, gm_ring* 
 
 }  // extern "C"
 
+// ====================================================================== narrowband interference excision (gm_excisor)
+// gnss_mi355x.h states the definition; tests/excise_model.py restates it in float64.
+namespace {
+struct ExcisorPlan {
+    uint32_t B = 1024, guard = 0;
+    float factor = 4.0f, thr = 0.0f;
+};
+
+int excisor_rules(const gm_excisor_cfg* c, ExcisorPlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    for (int i = 0; i < 4; ++i)
+        if (c->reserved[i]) return set_err(GM_ERR_INVALID_ARG, "gm_excisor_cfg.reserved must be 0");
+    if (c->block) {
+        if (c->block != 256 && c->block != 512 && c->block != 1024 && c->block != 2048 && c->block != 4096)
+            return set_err(GM_ERR_INVALID_ARG, "block: 256, 512, 1024, 2048 or 4096");
+        p.B = c->block;
+    } else p.B = 1024;
+    if (c->guard_bins > 16) return set_err(GM_ERR_INVALID_ARG, "guard_bins: 0 .. 16");
+    if (!(c->threshold_factor == 0.0f || c->threshold_factor > 1.0f)) return set_err(GM_ERR_INVALID_ARG, "threshold_factor: > 1, 0 for the default");
+    if (!(c->blank_threshold >= 0.0f)) return set_err(GM_ERR_INVALID_ARG, "blank_threshold: >= 0");
+    p.guard = c->guard_bins;
+    p.factor = c->threshold_factor == 0.0f ? 4.0f : c->threshold_factor;
+    p.thr = c->blank_threshold;
+    return GM_OK;
+}
+
+// total_out(A) = H * max(0, A div H - 1)
+uint64_t excisor_total_out(const ExcisorPlan& p, uint64_t A) {
+    const uint64_t H = p.B / 2, q = A / H;
+    return q > 1 ? (q - 1) * H : 0;
+}
+
+void excisor_windows(uint32_t B, float* wa, float* ws) {
+    const double PI = 3.14159265358979323846;
+    for (uint32_t i = 0; i < B; ++i) {
+        const double s = sin(PI * double(i) / double(B));
+        if (wa) wa[i] = float(s);
+        if (ws) ws[i] = float(s / double(B));
+    }
+}
+}  // namespace
+
+struct gm_excisor {
+    int device = -1;
+    ExcisorPlan plan;
+    std::vector<float> wa, ws;              // [B] each
+    float *d_wa = nullptr, *d_ws = nullptr, *d_gains = nullptr;
+    float* h_gains = nullptr;               // pinned staging of gm_excisor_set_gains
+    hipEvent_t gains_ev = nullptr; bool gains_pending = false;
+    cf *d_tw_fwd = nullptr, *d_tw_inv = nullptr;
+    cf* d_hist[2] = {nullptr, nullptr};     // the last 3H blanked inputs: d_hist[cur] is read by the next call, the other written
+    int cur = 0;
+    unsigned long long* d_blanked = nullptr;
+    float *d_partial = nullptr, *d_P = nullptr;   // the periodogram's partial sums [EX_CHUNKS_MAX][B] and its words [B]
+    uint32_t* d_stat = nullptr;             // {median word, flagged, zeroed} of the last adapt
+    hipStream_t stream = nullptr, last_stream = nullptr;
+    uint64_t base = 0;                      // absolute index of the first input since create / reset
+    uint64_t inputs = 0, outputs = 0;       // since create / reset
+    void* d_in = nullptr; size_t in_cap = 0;    // bytes; staging of the host-buffer entry
+    cf* d_out = nullptr; size_t out_cap = 0;    // samples
+    cf *d_scratch = nullptr, *d_mid = nullptr;  // gm_frontend_write_ring_conditioned: the front-end's linear output, and the excisor's in front of a resampler
+};
+
+static uint64_t excisor_count(const gm_excisor* x, uint64_t n_in) {
+    const uint64_t A = x->base + x->inputs;
+    return excisor_total_out(x->plan, A + n_in) - excisor_total_out(x->plan, A);
+}
+// one call's kernels on `st`, outputs to out[(out_start + k) & out_mask]; the caller has checked every argument; n_in > 0
+static int excisor_launch(gm_excisor* x, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t out_start,
+                          uint64_t out_mask, uint64_t n_out) {
+    const ExcisorPlan& p = x->plan;
+    const uint64_t H = p.B / 2, A = x->base + x->inputs, s0 = excisor_total_out(p, A) / H;
+    if (x->gains_pending && st != x->stream) HIPC(hipStreamWaitEvent(st, x->gains_ev, 0));     // gains set on the handle's stream
+    gm::ExciseArgs a{};
+    a.in = d_in; a.n_in = n_in;
+    a.hist_in = x->d_hist[x->cur]; a.hist_out = x->d_hist[x->cur ^ 1];
+    a.wa = x->d_wa; a.ws = x->d_ws; a.gains = x->d_gains; a.tw_fwd = x->d_tw_fwd; a.tw_inv = x->d_tw_inv;
+    a.B = p.B;
+    a.rel0 = int64_t(s0 * H) - int64_t(H) - int64_t(A);
+    a.n_seg = uint32_t(n_out / H); a.G = gm::excise_tile_segments(a.n_seg);
+    a.out = out; a.out_start = out_start; a.out_mask = out_mask;
+    a.thr2 = p.thr * p.thr; a.blank = p.thr > 0.0f ? 1 : 0;
+    a.blanked = x->d_blanked;
+    gm::launch_excise(st, a, fmt);
+    HIPC(hipGetLastError());
+    x->cur ^= 1; x->inputs += n_in; x->outputs += n_out; x->last_stream = st;
+    return GM_OK;
+}
+static int excisor_sync(gm_excisor* x) {
+    HIPC(hipStreamSynchronize(x->stream));
+    if (x->last_stream && x->last_stream != x->stream) HIPC(hipStreamSynchronize(x->last_stream));
+    return GM_OK;
+}
+// the checks gm_excisor_process_dev and gm_excisor_process share: nothing is touched when one fails
+static int excisor_check_call(gm_excisor* x, const void* in, int fmt, size_t n_in, const void* out, size_t out_cap, uint64_t* cnt) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "excisor input is c32 or int8 IQ");
+    if (!in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
+    if (uint64_t(n_in) > (1ull << 31) || x->base + x->inputs + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
+    *cnt = excisor_count(x, n_in);
+    if (*cnt > out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_cap below the call's output count (gm_excisor_plan gives it)");
+    if (*cnt && !out) return set_err(GM_ERR_INVALID_ARG, "null output");
+    return GM_OK;
+}
+
+extern "C" {
+
+int gm_excisor_plan(const gm_excisor_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, uint32_t* guard_bins,
+                    float* threshold_factor, uint64_t* n_out) {
+    ExcisorPlan p;
+    if (int rc = excisor_rules(cfg, p)) return rc;
+    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (block) *block = p.B;
+    if (guard_bins) *guard_bins = p.guard;
+    if (threshold_factor) *threshold_factor = p.factor;
+    if (n_out) *n_out = excisor_total_out(p, inputs_so_far + n_in) - excisor_total_out(p, inputs_so_far);
+    return GM_OK;
+}
+
+int gm_excisor_windows(const gm_excisor_cfg* cfg, float* analysis, float* synthesis) {
+    ExcisorPlan p;
+    if (int rc = excisor_rules(cfg, p)) return rc;
+    if (!analysis && !synthesis) return set_err(GM_ERR_INVALID_ARG, "null windows");
+    excisor_windows(p.B, analysis, synthesis);
+    return GM_OK;
+}
+
+int gm_excisor_create(const gm_excisor_cfg* cfg, gm_excisor** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    ExcisorPlan p;
+    if (int rc = excisor_rules(cfg, p)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_excisor* x = new gm_excisor;
+    x->device = g_device; x->plan = p;
+    const size_t B = p.B, wbytes = B * sizeof(float), hist_bytes = 3 * (B / 2) * sizeof(cf);
+    x->wa.resize(B); x->ws.resize(B);
+    excisor_windows(p.B, x->wa.data(), x->ws.data());
+    std::vector<cf> twf(gm::EX_TW_MAX), twi(gm::EX_TW_MAX);
+    int n_fwd = 0, n_inv = 0;
+    gm::excise_twiddles(p.B, twf.data(), twi.data(), &n_fwd, &n_inv);
+    const std::vector<float> ones(B, 1.0f);
+    hipError_t e = hipMalloc(&x->d_wa, wbytes);
+    if (e == hipSuccess) e = hipMalloc(&x->d_ws, wbytes);
+    if (e == hipSuccess) e = hipMalloc(&x->d_gains, wbytes);
+    if (e == hipSuccess) e = hipMalloc(&x->d_P, wbytes);
+    if (e == hipSuccess) e = hipMalloc(&x->d_partial, size_t(gm::EX_CHUNKS_MAX) * wbytes);
+    if (e == hipSuccess) e = hipMalloc(&x->d_stat, 4 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&x->d_tw_fwd, gm::EX_TW_MAX * sizeof(cf));
+    if (e == hipSuccess) e = hipMalloc(&x->d_tw_inv, gm::EX_TW_MAX * sizeof(cf));
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&x->h_gains), wbytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemcpy(x->d_wa, x->wa.data(), wbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(x->d_ws, x->ws.data(), wbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(x->d_gains, ones.data(), wbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(x->d_tw_fwd, twf.data(), gm::EX_TW_MAX * sizeof(cf), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(x->d_tw_inv, twi.data(), gm::EX_TW_MAX * sizeof(cf), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(x->d_P, 0, wbytes);
+    if (e == hipSuccess) e = hipMemset(x->d_stat, 0, 4 * sizeof(uint32_t));
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = hipMalloc(&x->d_hist[i], hist_bytes);
+        if (e == hipSuccess) e = hipMemset(x->d_hist[i], 0, hist_bytes);
+    }
+    if (e == hipSuccess) e = hipMalloc(&x->d_blanked, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(x->d_blanked, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the fills have run before a kernel on a non-blocking stream can touch the state (see gm_ring_create)
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&x->gains_ev, hipEventDisableTiming);
+    if (e != hipSuccess) { gm_excisor_destroy(x); return hip_fail(e, "gm_excisor_create"); }
+    *out = x;
+    return GM_OK;
+}
+
+int gm_excisor_destroy(gm_excisor* x) {
+    if (!x) return GM_OK;
+    hipSetDevice(x->device);
+    if (x->last_stream && x->last_stream != x->stream) hipStreamSynchronize(x->last_stream);
+    if (x->stream) { hipStreamSynchronize(x->stream); hipStreamDestroy(x->stream); }
+    if (x->gains_ev) hipEventDestroy(x->gains_ev);
+    hipFree(x->d_wa); hipFree(x->d_ws); hipFree(x->d_gains); hipFree(x->d_P); hipFree(x->d_partial); hipFree(x->d_stat);
+    hipFree(x->d_tw_fwd); hipFree(x->d_tw_inv); hipFree(x->d_hist[0]); hipFree(x->d_hist[1]); hipFree(x->d_blanked);
+    hipFree(x->d_in); hipFree(x->d_out); hipFree(x->d_scratch); hipFree(x->d_mid);
+    if (x->h_gains) hipHostFree(x->h_gains);
+    delete x;
+    return GM_OK;
+}
+
+int gm_excisor_reset(gm_excisor* x, uint64_t input_index) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (input_index > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "input_index above 2^62");
+    if (int rc = ensure_device(x->device)) return rc;
+    if (int rc = excisor_sync(x)) return rc;
+    const size_t hist_bytes = 3 * size_t(x->plan.B / 2) * sizeof(cf);
+    HIPC(hipMemsetAsync(x->d_hist[0], 0, hist_bytes, x->stream));
+    HIPC(hipMemsetAsync(x->d_hist[1], 0, hist_bytes, x->stream));
+    HIPC(hipMemsetAsync(x->d_blanked, 0, sizeof(unsigned long long), x->stream));
+    HIPC(hipStreamSynchronize(x->stream));
+    x->cur = 0; x->base = input_index; x->inputs = 0; x->outputs = 0;
+    return GM_OK;
+}
+
+int gm_excisor_set_gains(gm_excisor* x, const float* gains) {
+    if (!x || !gains) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    const size_t B = x->plan.B;
+    for (size_t k = 0; k < B; ++k)
+        if (!(gains[k] >= 0.0f && gains[k] <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "every gain in [0, 1]");
+    if (int rc = ensure_device(x->device)) return rc;
+    if (x->gains_pending) HIPC(hipEventSynchronize(x->gains_ev));     // the staging words of the last call have left
+    if (x->last_stream && x->last_stream != x->stream) HIPC(hipStreamSynchronize(x->last_stream));   // a call in flight elsewhere reads the old gains
+    memcpy(x->h_gains, gains, B * sizeof(float));
+    HIPC(hipMemcpyAsync(x->d_gains, x->h_gains, B * sizeof(float), hipMemcpyHostToDevice, x->stream));
+    HIPC(hipEventRecord(x->gains_ev, x->stream));
+    x->gains_pending = true;
+    return GM_OK;
+}
+
+int gm_excisor_gains(gm_excisor* x, float* gains) {
+    if (!x || !gains) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (int rc = ensure_device(x->device)) return rc;
+    if (int rc = excisor_sync(x)) return rc;
+    HIPC(hipMemcpy(gains, x->d_gains, x->plan.B * sizeof(float), hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+int gm_excisor_adapt_dev(gm_excisor* x, const void* d_in, int fmt, size_t n, void* stream) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "excisor input is c32 or int8 IQ");
+    if (!d_in) return set_err(GM_ERR_INVALID_ARG, "null input");
+    const ExcisorPlan& p = x->plan;
+    if (n < p.B || uint64_t(n) > (1ull << 31)) return set_err(GM_ERR_INVALID_ARG, "adapt takes block .. 2^31 samples");
+    if (int rc = ensure_device(x->device)) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : x->stream;
+    if (x->gains_pending && st != x->stream) HIPC(hipStreamWaitEvent(st, x->gains_ev, 0));       // the mask is written behind a set_gains
+    const uint64_t H = p.B / 2, J = (uint64_t(n) - p.B) / H + 1;
+    const uint64_t per = (J + gm::EX_CHUNKS_MAX - 1) / gm::EX_CHUNKS_MAX;
+    gm::ExcisePsdArgs pa{};
+    pa.in = d_in; pa.wa = x->d_wa; pa.tw_fwd = x->d_tw_fwd; pa.B = p.B;
+    pa.J = J; pa.C = uint32_t(per < 4 ? 4 : per); pa.n_chunks = uint32_t((J + pa.C - 1) / pa.C);
+    pa.partial = x->d_partial;
+    pa.thr2 = p.thr * p.thr; pa.blank = p.thr > 0.0f ? 1 : 0;
+    gm::ExciseMaskArgs ma{};
+    ma.partial = x->d_partial; ma.n_chunks = pa.n_chunks; ma.B = p.B;
+    ma.factor = p.factor; ma.guard = p.guard;
+    ma.P = x->d_P; ma.gains = x->d_gains; ma.stat = x->d_stat;
+    gm::launch_excise_adapt(st, pa, ma, fmt);
+    HIPC(hipGetLastError());
+    x->last_stream = st;
+    return GM_OK;
+}
+
+int gm_excisor_psd(gm_excisor* x, float* P, float* median, uint32_t* n_flagged, uint32_t* n_zeroed) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(x->device)) return rc;
+    if (int rc = excisor_sync(x)) return rc;
+    uint32_t stat[4] = {0, 0, 0, 0};
+    HIPC(hipMemcpy(stat, x->d_stat, sizeof(stat), hipMemcpyDeviceToHost));
+    if (P) HIPC(hipMemcpy(P, x->d_P, x->plan.B * sizeof(float), hipMemcpyDeviceToHost));
+    if (median) memcpy(median, &stat[0], sizeof(float));
+    if (n_flagged) *n_flagged = stat[1];
+    if (n_zeroed) *n_zeroed = stat[2];
+    return GM_OK;
+}
+
+int gm_excisor_stats(gm_excisor* x, uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(x->device)) return rc;
+    if (int rc = excisor_sync(x)) return rc;
+    if (blanked) {
+        unsigned long long b = 0;
+        HIPC(hipMemcpy(&b, x->d_blanked, sizeof(b), hipMemcpyDeviceToHost));
+        *blanked = b;
+    }
+    if (inputs) *inputs = x->inputs;
+    if (outputs) *outputs = x->outputs;
+    return GM_OK;
+}
+
+int gm_excisor_process_dev(gm_excisor* x, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out,
+                           void* stream) {
+    uint64_t cnt = 0;
+    if (int rc = excisor_check_call(x, d_in, fmt, n_in, d_out, out_cap, &cnt)) return rc;
+    if (cnt && n_in) {
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), i1 = i0 + n_in * (fmt == GM_FMT_C32 ? 8 : 2);
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + cnt * 8;
+        if (i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
+    }
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(x->device)) return rc;
+    return excisor_launch(x, stream ? static_cast<hipStream_t>(stream) : x->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), 0, ~0ull, cnt);
+}
+
+int gm_excisor_process(gm_excisor* x, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out) {
+    uint64_t cnt = 0;
+    if (int rc = excisor_check_call(x, in, fmt, n_in, out, out_cap, &cnt)) return rc;
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(x->device)) return rc;
+    const size_t in_bytes = n_in * (fmt == GM_FMT_C32 ? 8 : 2);
+    if (x->in_cap < in_bytes || x->out_cap < cnt) HIPC(hipStreamSynchronize(x->stream));
+    if (x->in_cap < in_bytes) {
+        hipFree(x->d_in); x->d_in = nullptr; x->in_cap = 0;
+        HIPC(hipMalloc(&x->d_in, in_bytes));
+        x->in_cap = in_bytes;
+    }
+    if (x->out_cap < cnt) {
+        hipFree(x->d_out); x->d_out = nullptr; x->out_cap = 0;
+        HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_out), size_t(cnt) * sizeof(cf)));
+        x->out_cap = size_t(cnt);
+    }
+    if (x->last_stream && x->last_stream != x->stream) HIPC(hipStreamSynchronize(x->last_stream));   // the history (and the gains) the last call wrote
+    HIPC(hipMemcpyAsync(x->d_in, in, in_bytes, hipMemcpyHostToDevice, x->stream));
+    if (int rc = excisor_launch(x, x->stream, x->d_in, fmt, n_in, x->d_out, 0, ~0ull, cnt)) return rc;
+    if (cnt) HIPC(hipMemcpyAsync(out, x->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, x->stream));
+    HIPC(hipStreamSynchronize(x->stream));
+    return GM_OK;
+}
+
+int gm_excisor_synchronize(gm_excisor* x) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(x->device)) return rc;
+    return excisor_sync(x);
+}
+
+// gm_frontend_write_ring_resampled's block loop with the excisor between the front-end kernel and the resampler: front-end -> the
+// excisor's linear scratch buffer -> excisor -> (rs: a second linear buffer -> resampler ->) the ring at write_pos
+int gm_frontend_write_ring_conditioned(gm_frontend* f, gm_excisor* x, gm_resampler* rs, gm_ring* r, const void* samples, size_t n_samples,
+                                       int fmt, uint64_t* n_out_total) {
+    if (!f || !x || !r || (!samples && n_samples)) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "front-end input is c32 or int8 IQ");
+    if (f->device != r->device || x->device != r->device || (rs && rs->device != r->device))
+        return set_err(GM_ERR_INVALID_ARG, "front-end, excisor, resampler and ring live on different devices");
+    if (x->base + x->inputs + n_samples > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
+    const uint64_t mid_total = excisor_count(x, n_samples);
+    if (rs && rs->base + rs->inputs + mid_total > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
+    const uint64_t total = rs ? resampler_count(rs, mid_total) : mid_total;
+    if (total > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "write larger than the ring");
+    if (n_out_total) *n_out_total = total;
+    if (int rc = ensure_device(r->device)) return rc;
+    if (int rc = ring_async_init(r)) return rc;
+    if (!r->fe_stream) {      // (as gm_frontend_write_ring creates it)
+        if (gm::diag_int("GM_RING_FE_STREAM", 1) == 0) r->fe_stream = r->copy_stream;
+        else {
+            int least = 0, greatest = 0;
+            HIPC(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            const int pr = gm::diag_int("GM_RING_FE_PRIORITY", 99);
+            HIPC(hipStreamCreateWithPriority(&r->fe_stream, hipStreamNonBlocking, pr == 99 ? greatest : pr));
+        }
+        for (int i = 0; i < gm_ring::SLOTS; ++i) HIPC(hipEventCreateWithFlags(&r->h2d_done[i], hipEventDisableTiming));
+    }
+    if (!x->d_scratch) HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_scratch), gm_ring::SLOT_SAMPLES_MAX * sizeof(cf)));
+    if (rs && !x->d_mid) HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_mid), (gm_ring::SLOT_SAMPLES_MAX + gm::EX_BLOCK_MAX) * sizeof(cf)));   // a block's outputs: up to its inputs + H
+    if (x->last_stream && x->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(x->last_stream));       // the history the last call wrote
+    if (rs && rs->last_stream && rs->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(rs->last_stream));
+    const size_t bps = fmt == GM_FMT_C32 ? 8 : 2;
+    const uint8_t* src = static_cast<const uint8_t*>(samples);
+    while (n_samples) {
+        const size_t chunk = n_samples < r->slot_samples ? n_samples : r->slot_samples;
+        const int slot = int(r->slot_seq++ % gm_ring::SLOTS);
+        if (int rc = ring_reclaim_slot(r, slot)) return rc;
+        if (!f->d_raw[slot]) HIPC(hipMalloc(&f->d_raw[slot], gm_ring::SLOT_SAMPLES_MAX * 8));
+        memcpy(r->staging[slot], src, chunk * bps);
+        HIPC(hipMemcpyAsync(f->d_raw[slot], r->staging[slot], chunk * bps, hipMemcpyHostToDevice, r->copy_stream));
+        HIPC(hipEventRecord(r->h2d_done[slot], r->copy_stream));
+        HIPC(hipStreamWaitEvent(r->fe_stream, r->h2d_done[slot], 0));
+        // one buffer of each kind serves every block: the stream runs block k's kernels before block k + 1's front-end kernel
+        if (int rc = frontend_launch(f, r->fe_stream, f->d_raw[slot], fmt, x->d_scratch, 0, ~0ull, chunk)) return rc;
+        const uint64_t mid = excisor_count(x, chunk);
+        uint64_t cnt = mid;
+        if (rs) {
+            if (int rc = excisor_launch(x, r->fe_stream, x->d_scratch, GM_FMT_C32, chunk, x->d_mid, 0, ~0ull, mid)) return rc;
+            cnt = resampler_count(rs, mid);
+            if (mid)
+                if (int rc = resampler_launch(rs, r->fe_stream, x->d_mid, GM_FMT_C32, mid, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
+        } else if (int rc = excisor_launch(x, r->fe_stream, x->d_scratch, GM_FMT_C32, chunk, r->d_buf, r->write_pos, r->mask, mid)) return rc;
+        HIPC(hipEventRecord(r->slot_done[slot], r->fe_stream));
+        r->slot_used[slot] = true;
+        r->write_pos += cnt;
+        if (int rc = ring_enqueue_publish(r, slot, r->fe_stream)) return rc;
+        src += chunk * bps; n_samples -= chunk;
+    }
+    return GM_OK;
+}
+
+}  // extern "C"
+
 // ====================================================================== multi-GPU exchange
 // The path's ONE exchange step: all-gather of the per-(worker, bin) metrics over RCCL, enqueued on the acquisition
 // handle's stream, followed by the regroup to the [3][nranks*P][D] layout gm_acq_decide_dev replays.  RCCL is bound

@@ -395,4 +395,45 @@ inline uint32_t resample_tile_out(uint32_t T, uint32_t up, uint32_t down) {
 }
 void launch_resample(hipStream_t, const ResampleArgs&, int fmt);
 
+// ---------------------------------------------------------------- narrowband interference excision (excise_kernels.hip)
+// gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of G segments of H = B / 2
+// outputs) and one of the state kernel (the next history of 3H blanked inputs, the blanked count).  The host hands over where the
+// call's first block starts relative to the call's first input (rel0 <= 0, >= -3H + 1: the history covers it).
+constexpr int EX_BLOCK_MAX = 4096;         // the largest block length B
+constexpr int EX_TW_MAX = 512;             // words of one base-twiddle set (272 at B = 4096)
+constexpr uint32_t EX_CHUNKS_MAX = 512;    // most partial sums of the periodogram: chunk length C = max(4, ceil(J / 512)) blocks
+struct ExciseArgs {
+    const void* in; uint64_t n_in;         // this call's inputs (c32 or int8 IQ)
+    const cf* hist_in; cf* hist_out;       // [3H] the last 3H blanked inputs before / after this call (two buffers, used alternately)
+    const float *wa, *ws, *gains;          // [B] each
+    const cf *tw_fwd, *tw_inv;             // base twiddles: the plan of B forward, the plan with its radices reversed inverse
+    uint32_t B;
+    int64_t rel0;                          // first input of the call's first block minus the call's first input
+    uint32_t n_seg, G;                     // segments this call delivers; segments per workgroup (not in the words)
+    cf* out; uint64_t out_start, out_mask; // linear buffer (out_mask = ~0) or ring base
+    float thr2; int blank;                 // blank_threshold^2 (f32 product); blanking on
+    unsigned long long* blanked;           // device counter, integer atomics only
+};
+struct ExcisePsdArgs {
+    const void* in;                        // the samples given, from their index 0
+    const float* wa; const cf* tw_fwd;
+    uint32_t B;
+    uint64_t J; uint32_t C, n_chunks;      // blocks, blocks per chunk, chunks (= workgroups)
+    float* partial;                        // [n_chunks][B]
+    float thr2; int blank;
+};
+struct ExciseMaskArgs {
+    const float* partial; uint32_t n_chunks, B;
+    float factor; uint32_t guard;
+    float* P; float* gains;                // [B] each
+    uint32_t* stat;                        // {the median's word, bins flagged, bins zeroed}
+};
+inline uint32_t excise_tile_segments(uint32_t n_seg) {      // enough workgroups to fill the device on a 2^19-sample call, fewer repeated blocks on longer ones
+    const uint32_t g = n_seg / 1024;
+    return g < 1 ? 1u : (g > 8 ? 8u : g);
+}
+int excise_twiddles(uint32_t B, cf* fwd, cf* inv, int* n_fwd, int* n_inv);
+void launch_excise(hipStream_t, const ExciseArgs&, int fmt);
+void launch_excise_adapt(hipStream_t, const ExcisePsdArgs&, const ExciseMaskArgs&, int fmt);
+
 }  // namespace gm

@@ -1,0 +1,161 @@
+"""Narrowband interference excision over the C ABI (gm_excisor, include/gnss_mi355x.h): a 50 % overlap-add filter bank with sine
+windows and a per-bin gain, and a device-side adaptive step that sets the gains from a Welch periodogram.  An Excisor turns a stream of
+complex64 or int8-IQ samples into complex64 samples at the same rate and the same sample index; every output is defined by absolute
+sample indices alone, so the words do not depend on how the stream is cut into calls."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import FMT_C32, FMT_I8_IQ, ExcisorCfg, check, lib
+
+_KEYS = ("guard_bins", "threshold_factor", "blank_threshold")
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+_HIP = None
+
+
+def _hip():
+    """the HIP runtime the library already loaded: Excisor.adapt keeps one plain device buffer for its host samples"""
+    global _HIP
+    if _HIP is None:
+        h = C.CDLL("libamdhip64.so.7")
+        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        h.hipFree.argtypes = [C.c_void_p]
+        _HIP = h
+    return _HIP
+
+
+def _cfg(block=0, guard_bins=0, threshold_factor=0.0, blank_threshold=0.0):
+    return ExcisorCfg(int(block), int(guard_bins), float(threshold_factor), float(blank_threshold), (C.c_uint32 * 4)(0, 0, 0, 0))
+
+
+def plan(block=0, inputs_so_far=0, n_in=0, **cfg):
+    """gm_excisor_plan (host only, no device): the argument rules, the resolved defaults and the number of outputs that n_in more
+    inputs deliver to a stream that has taken inputs_so_far."""
+    c = _cfg(block, **cfg)
+    b, g, f, n = C.c_uint32(0), C.c_uint32(0), C.c_float(0), C.c_uint64(0)
+    check(lib().gm_excisor_plan(C.byref(c), int(inputs_so_far), int(n_in), C.byref(b), C.byref(g), C.byref(f), C.byref(n)),
+          "gm_excisor_plan")
+    return dict(block=b.value, guard_bins=g.value, threshold_factor=f.value, n_out=n.value)
+
+
+def windows(block=0, **cfg):
+    """gm_excisor_windows (host only, no device): the float32 analysis and synthesis windows, [block] each."""
+    c = _cfg(block, **cfg)
+    B = plan(block, **cfg)["block"]
+    wa, ws = np.zeros(B, np.float32), np.zeros(B, np.float32)
+    check(lib().gm_excisor_windows(C.byref(c), _p(wa), _p(ws)), "gm_excisor_windows")
+    return wa, ws
+
+
+def _samples(samples):
+    s = np.ascontiguousarray(samples)
+    if s.dtype == np.int8:
+        return s, s.size // 2, FMT_I8_IQ
+    s = np.ascontiguousarray(s, np.complex64)
+    return s, s.size, FMT_C32
+
+
+class Excisor:
+    def __init__(self, block=0, device=None, **cfg):
+        unknown = set(cfg) - set(_KEYS)
+        if unknown:
+            raise TypeError("unknown excisor settings: %s" % sorted(unknown))
+        _lib.init(device if device is not None else (_lib._initialised or 0))
+        self._cfg = _cfg(block, **cfg)
+        self._settings = dict(cfg)
+        p = plan(block, **cfg)
+        self.block, self.guard_bins, self.threshold_factor = p["block"], p["guard_bins"], p["threshold_factor"]
+        self._d_adapt, self._adapt_cap = None, 0
+        h = C.c_void_p()
+        check(lib().gm_excisor_create(C.byref(self._cfg), C.byref(h)), "gm_excisor_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gm_excisor_destroy(self._h)
+            self._h = None
+        if getattr(self, "_d_adapt", None):
+            _hip().hipFree(self._d_adapt)
+            self._d_adapt = None
+
+    def __del__(self):      # (at interpreter shutdown the module globals close() uses may be gone already)
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def process(self, samples):
+        """samples: complex64 array, or int8 array of interleaved I/Q -> complex64 array of this call's outputs (synchronous)."""
+        s, n, fmt = _samples(samples)
+        out = np.zeros(n + self.block, np.complex64)                    # a call never delivers more than n + H
+        got = C.c_size_t(0)
+        check(lib().gm_excisor_process(self._h, _p(s), fmt, n, _p(out), out.size, C.byref(got)), "gm_excisor_process")
+        return out[:got.value].copy()
+
+    def process_dev(self, d_in, fmt, n_in, d_out, out_cap, stream=None):
+        """device pointers; asynchronous on `stream` (None: the handle's own); returns the number of outputs written to d_out"""
+        got = C.c_size_t(0)
+        check(lib().gm_excisor_process_dev(self._h, d_in, fmt, n_in, d_out, out_cap, C.byref(got), stream), "gm_excisor_process_dev")
+        return got.value
+
+    def adapt_dev(self, d_in, fmt, n, stream=None):
+        """the adaptive step on n samples in device memory: periodogram, median, mask, gains; enqueued, no host wait"""
+        check(lib().gm_excisor_adapt_dev(self._h, d_in, fmt, n, stream), "gm_excisor_adapt_dev")
+
+    def adapt(self, samples):
+        """the adaptive step on host samples (copied to a device buffer the object keeps, then adapt_dev on the handle's stream)"""
+        s, n, fmt = _samples(samples)
+        hip = _hip()
+        if self._adapt_cap < s.nbytes:
+            self.synchronize()
+            if self._d_adapt:
+                hip.hipFree(self._d_adapt)
+            p = C.c_void_p()
+            if hip.hipMalloc(C.byref(p), max(s.nbytes, 1)) != 0:
+                raise MemoryError("hipMalloc")
+            self._d_adapt, self._adapt_cap = p, s.nbytes
+        self.synchronize()                                              # the last adapt has read the buffer
+        if hip.hipMemcpy(self._d_adapt, _p(s), s.nbytes, 1) != 0:
+            raise RuntimeError("hipMemcpy")
+        self.adapt_dev(self._d_adapt, fmt, n)
+
+    def set_gains(self, gains):
+        g = np.ascontiguousarray(gains, np.float32)
+        if g.shape != (self.block,):
+            raise ValueError("gains: %d values" % self.block)
+        check(lib().gm_excisor_set_gains(self._h, _p(g)), "gm_excisor_set_gains")
+
+    def gains(self):
+        g = np.zeros(self.block, np.float32)
+        check(lib().gm_excisor_gains(self._h, _p(g)), "gm_excisor_gains")
+        return g
+
+    def psd(self):
+        """the last adapt's words: dict of P [block] float32, median, n_flagged, n_zeroed (synchronises)"""
+        P = np.zeros(self.block, np.float32)
+        med, nf, nz = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().gm_excisor_psd(self._h, _p(P), C.byref(med), C.byref(nf), C.byref(nz)), "gm_excisor_psd")
+        return dict(P=P, median=np.float32(med.value), n_flagged=nf.value, n_zeroed=nz.value)
+
+    def reset(self, input_index=0):
+        check(lib().gm_excisor_reset(self._h, int(input_index)), "gm_excisor_reset")
+
+    def stats(self):
+        """inputs taken, outputs delivered, inputs blanked since the creation or the last reset (synchronises)"""
+        i, o, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().gm_excisor_stats(self._h, C.byref(i), C.byref(o), C.byref(b)), "gm_excisor_stats")
+        return dict(inputs=i.value, outputs=o.value, blanked=b.value)
+
+    def windows(self):
+        """the float32 analysis and synthesis window words the device uses"""
+        return windows(self.block, **self._settings)
+
+    def synchronize(self):
+        check(lib().gm_excisor_synchronize(self._h), "gm_excisor_synchronize")

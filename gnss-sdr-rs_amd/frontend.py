@@ -65,21 +65,27 @@ class DigitalFrontend:
         check(lib().gm_frontend_debug_repairs(self._h, C.byref(n)), "gm_frontend_debug_repairs")
         return n.value
 
-    def write_ring(self, ring, samples, resampler=None):
+    def write_ring(self, ring, samples, resampler=None, excisor=None):
         """samples: complex64 array, or int8 array of interleaved I/Q.  With a resample.Resampler the block goes through it on its way
-        into the ring (gm_frontend_write_ring_resampled): ring indices then count output samples, and the outputs enqueued are returned."""
+        into the ring (gm_frontend_write_ring_resampled): ring indices then count output samples, and the outputs enqueued are returned.
+        With an excise.Excisor the block goes through it first (gm_frontend_write_ring_conditioned: front-end, excisor, then the
+        resampler if there is one); without a resampler ring indices count the excisor's outputs."""
         s = np.ascontiguousarray(samples)
         if s.dtype == np.int8:
             n, fmt = s.size // 2, FMT_I8_IQ
         else:
             s = np.ascontiguousarray(s, np.complex64)
             n, fmt = s.size, FMT_C32
-        if resampler is None:
+        if resampler is None and excisor is None:
             check(lib().gm_frontend_write_ring(self._h, ring._h, _p(s), n, fmt), "gm_frontend_write_ring")
             return None
         total = C.c_uint64(0)
-        check(lib().gm_frontend_write_ring_resampled(self._h, resampler._h, ring._h, _p(s), n, fmt, C.byref(total)),
-              "gm_frontend_write_ring_resampled")
+        if excisor is None:
+            check(lib().gm_frontend_write_ring_resampled(self._h, resampler._h, ring._h, _p(s), n, fmt, C.byref(total)),
+                  "gm_frontend_write_ring_resampled")
+        else:
+            check(lib().gm_frontend_write_ring_conditioned(self._h, excisor._h, resampler._h if resampler is not None else None, ring._h,
+                                                           _p(s), n, fmt, C.byref(total)), "gm_frontend_write_ring_conditioned")
         return total.value
 
 

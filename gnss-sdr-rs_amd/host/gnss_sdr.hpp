@@ -308,6 +308,62 @@ private:
     }
 };
 
+// ---- narrowband interference excision (gm_excisor): a 50 % overlap-add filter bank with sine windows and a per-bin gain, and a
+// device-side adaptive step that sets the gains from a Welch periodogram.  Same rate, same sample index; every output is defined by
+// absolute sample indices, so the words do not depend on the block cuts.
+class Excisor {
+    gm_excisor* h_ = nullptr;
+    uint32_t block_ = 0;
+public:
+    explicit Excisor(const gm_excisor_cfg& cfg) { init(cfg); }
+    explicit Excisor(uint32_t block = 0, uint32_t guard_bins = 0, float blank_threshold = 0.0f) {   // every other setting at its default
+        gm_excisor_cfg cfg{};
+        cfg.block = block; cfg.guard_bins = guard_bins; cfg.blank_threshold = blank_threshold;
+        init(cfg);
+    }
+    ~Excisor() { gm_excisor_destroy(h_); }
+    Excisor(const Excisor&) = delete;
+    gm_excisor* handle() const { return h_; }
+    uint32_t block() const { return block_; }
+    // the synchronous host-buffer forms: this call's outputs
+    std::vector<Complex32> process(const std::vector<Complex32>& block) { return run(block.data(), block.size(), GM_FMT_C32); }
+    std::vector<Complex32> process_i8(const int8_t* iq, size_t n) { return run(iq, n, GM_FMT_I8_IQ); }
+    // device pointers, asynchronous on `stream` (nullptr: the handle's own); returns the number of outputs written
+    size_t process_dev(const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, void* stream = nullptr) {
+        size_t n = 0;
+        check(gm_excisor_process_dev(h_, d_in, fmt, n_in, d_out, out_cap, &n, stream), "Excisor::process_dev");
+        return n;
+    }
+    // periodogram, median, mask and gains from n device samples, enqueued with no host wait
+    void adapt_dev(const void* d_in, int fmt, size_t n, void* stream = nullptr) { check(gm_excisor_adapt_dev(h_, d_in, fmt, n, stream), "Excisor::adapt_dev"); }
+    void set_gains(const std::vector<float>& gains) {
+        if (gains.size() != block_) throw std::invalid_argument("Excisor::set_gains: one gain per bin");
+        check(gm_excisor_set_gains(h_, gains.data()), "Excisor::set_gains");
+    }
+    std::vector<float> gains() const { std::vector<float> g(block_); check(gm_excisor_gains(h_, g.data()), "Excisor::gains"); return g; }
+    // the last adapt's periodogram; median, flagged and zeroed may be null
+    std::vector<float> psd(float* median = nullptr, uint32_t* n_flagged = nullptr, uint32_t* n_zeroed = nullptr) const {
+        std::vector<float> P(block_);
+        check(gm_excisor_psd(h_, P.data(), median, n_flagged, n_zeroed), "Excisor::psd");
+        return P;
+    }
+    void reset(uint64_t input_index = 0) { check(gm_excisor_reset(h_, input_index), "Excisor::reset"); }
+    void stats(uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) const { check(gm_excisor_stats(h_, inputs, outputs, blanked), "Excisor::stats"); }
+    void synchronize() { check(gm_excisor_synchronize(h_), "Excisor::synchronize"); }
+private:
+    void init(const gm_excisor_cfg& cfg) {
+        check(gm_excisor_plan(&cfg, 0, 0, &block_, nullptr, nullptr, nullptr), "Excisor::new");
+        check(gm_excisor_create(&cfg, &h_), "Excisor::new");
+    }
+    std::vector<Complex32> run(const void* in, size_t n, int fmt) {
+        size_t got = 0;
+        std::vector<Complex32> out(n + block_);                             // a call never delivers more than n + H
+        check(gm_excisor_process(h_, in, fmt, n, reinterpret_cast<gm_c32*>(out.data()), out.size(), &got), "Excisor::process");
+        out.resize(got);
+        return out;
+    }
+};
+
 // ---- rf::frontend::DigitalFrontend (src/rf/frontend.rs:6-62)
 class DigitalFrontend {
     gm_frontend* h_ = nullptr;
@@ -329,6 +385,18 @@ public:
     uint64_t write_ring_i8(MulticastRingBuffer& ring, const int8_t* iq, size_t n, Resampler& resampler) {
         uint64_t total = 0;
         check(gm_frontend_write_ring_resampled(h_, resampler.handle(), ring.handle(), iq, n, GM_FMT_I8_IQ, &total), "write_ring");
+        return total;
+    }
+    // ... and with the excisor between the front-end and the resampler (resampler may be null: ring indices then count the excisor's
+    // outputs, ring index n is input time n); returns the outputs enqueued
+    uint64_t write_ring(MulticastRingBuffer& ring, const Complex32* block, size_t n, Excisor& excisor, Resampler* resampler = nullptr) {
+        uint64_t total = 0;
+        check(gm_frontend_write_ring_conditioned(h_, excisor.handle(), resampler ? resampler->handle() : nullptr, ring.handle(), block, n, GM_FMT_C32, &total), "write_ring");
+        return total;
+    }
+    uint64_t write_ring_i8(MulticastRingBuffer& ring, const int8_t* iq, size_t n, Excisor& excisor, Resampler* resampler = nullptr) {
+        uint64_t total = 0;
+        check(gm_frontend_write_ring_conditioned(h_, excisor.handle(), resampler ? resampler->handle() : nullptr, ring.handle(), iq, n, GM_FMT_I8_IQ, &total), "write_ring");
         return total;
     }
     uint32_t debug_repairs() const { uint32_t n = 0; check(gm_frontend_debug_repairs(h_, &n), "debug_repairs"); return n; }   // runs of the speculative form done again

@@ -774,6 +774,102 @@ int gm_resampler_synchronize(gm_resampler *r);
 int gm_frontend_write_ring_resampled(gm_frontend *f, gm_resampler *r, gm_ring *ring, const void *samples, size_t n_samples, int fmt,
                                      uint64_t *n_out_total);
 
+/* ------------------------------------------------------------------ Narrowband interference excision
+ * Pulse blanking removes what is short in time and wide in frequency; a gm_excisor removes the reverse: a CW or narrowband carrier,
+ * long in time and narrow in frequency, which no amplitude threshold catches.  c32 or int8-IQ samples in, c32 samples out at the same
+ * rate and the same sample index (no timestamp delay).  It is a windowed overlap-add filter bank with a per-bin gain: 50 % overlap,
+ * sine (square-root Hann) analysis and synthesis windows, perfect reconstruction when every gain is 1.  Everything is by ABSOLUTE
+ * sample indices.
+ *   Block length B in {256, 512, 1024, 2048, 4096}, half block H = B / 2.
+ *   Windows (host, f64, each word rounded once to f32): analysis wa[i] = sin(pi i / B), synthesis ws[i] = sin(pi i / B) / B (the
+ *     inverse transform's normalisation folded in): wa[i] ws[i] B + wa[i + H] ws[i + H] B = 1.
+ *   Blanking (blank_threshold > 0), the resampler's rule word for word: an input sample with re*re + im*im > thr*thr is replaced by
+ *     (0, 0); f32, each product and the sum rounded on its own, strictly greater; int8 samples are converted to f32 first.  It is
+ *     applied to the input before anything else (a pulse smears over every bin of its block); blanked inputs are counted once each,
+ *     with integer adds.
+ *   Blocks.  Block b = 0, 1, ... covers absolute inputs [(b - 1) H, (b + 1) H); xb = the input after blanking, zero before the stream's
+ *     first sample.  X_b = forward FFT of wa[i] * xb[(b - 1) H + i], unnormalised; Y_b[k] = g[k] * X_b[k], the f32 gain times each
+ *     component; u_b = inverse FFT of Y_b, unnormalised.
+ *   Output.  For n in segment s = n div H, i = n mod H:  y[n] = ws[i + H] * u_s[i + H] + ws[i] * u_{s+1}[i], each product rounded
+ *     first, then the sum.  A block's words depend on its B inputs and the gains alone: y does not depend on how the stream is cut
+ *     into calls, tiles or workgroups.
+ *   Availability.  After A inputs in total, total_out(A) = H * max(0, A div H - 1) outputs exist, and a call delivers
+ *     total_out(A_after) - total_out(A_before); the host computes the count with no synchronisation.  Output n is the filtered signal
+ *     at input time n.  There is no flush entry: a caller that needs the tail appends B zeros.
+ *   State.  The handle keeps the not yet retired blanked inputs (fewer than 3H) in device memory, in two buffers used alternately (a
+ *     call reads one while it writes the other), and the counters on the host; the blanked count is an integer in device memory.
+ *   Gains g[B], f32 in [0, 1], all ones at creation: gm_excisor_set_gains installs static notches or a taper; gm_excisor_adapt_dev
+ *     sets them on the device from a Welch periodogram of the samples it is given (cut from index 0 of that buffer, independent of the
+ *     stream state, blanked by the same rule), all enqueued with no host wait:
+ *     1. Block j covers [j H, j H + B), J = (n - B) div H + 1 blocks; P[k] = sum_j |FFT(wa * block_j)[k]|^2, each |.|^2 as
+ *        re*re + im*im with every operation rounded.  Fixed order: C = max(4, ceil(J / 512)) blocks a chunk; a chunk's partial sum
+ *        adds its blocks with j ascending from +0, P adds the chunks' sums with the chunk index ascending from +0.  No
+ *        floating-point atomics: two calls on the same input give the same words.
+ *     2. med = the element of rank (B - 1) div 2 of P in ascending order.
+ *     3. flag[k] = P[k] > factor * med (one f32 product, strictly greater); g[k] = 0 where any flag within guard_bins of k is set,
+ *        the distance taken circularly, g[k] = 1 elsewhere.
+ *     The library decides nothing else: no cap on the share of zeroed bins, no smoothing over time; the caller adapts when it wants
+ *     to (J >= 32 blocks advised: with few blocks noise alone crosses factor 4).
+ *   Kernel (csrc/excise_kernels.hip): one workgroup per tile of G consecutive segments runs blocks s0 .. s0 + G in turn on the in-LDS
+ *     transforms of fft_core.h, the inverse on the plan with the forward plan's radices reversed so that the spectrum and the gain
+ *     multiply stay in registers, and keeps a block's weighted second half on chip until the next block's first half exists.  G is
+ *     not in the words.
+ * Zeros in the config mean defaults.  (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct {
+    uint32_t block;            /* B: 256, 512, 1024, 2048 or 4096; 0 -> 1024 */
+    uint32_t guard_bins;       /* 0 .. 16: bins zeroed on either side of a flagged one */
+    float    threshold_factor; /* > 1; 0 -> 4.0: a bin is flagged when P[k] > factor * median */
+    float    blank_threshold;  /* 0: off; > 0: an input sample with re^2 + im^2 > thr^2 is replaced by (0, 0) before anything else */
+    uint32_t reserved[4];      /* must be 0 */
+} gm_excisor_cfg;
+typedef struct gm_excisor gm_excisor;
+/* host only, no device: the argument rules (GM_ERR_INVALID_ARG: a null cfg, a block not in the list, guard_bins above 16, a
+ * threshold_factor not 0 and <= 1 or not a number, a negative blank_threshold or not a number, reserved != 0, inputs_so_far + n_in above
+ * 2^62), the resolved defaults and, for a stream that has taken inputs_so_far samples, the count n_in more deliver.  Any output
+ * pointer may be NULL. */
+int gm_excisor_plan(const gm_excisor_cfg *cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t *block, uint32_t *guard_bins,
+                    float *threshold_factor, uint64_t *n_out);
+/* host only, no device: the B analysis and the B synthesis window words (either pointer may be NULL, not both) */
+int gm_excisor_windows(const gm_excisor_cfg *cfg, float *analysis, float *synthesis);
+int gm_excisor_create(const gm_excisor_cfg *cfg, gm_excisor **out);
+int gm_excisor_destroy(gm_excisor *x);
+/* Zeroes the kept inputs and the three counters; the stream continues as if input_index zero samples had gone before.  The gains are
+ * kept.  Synchronous.  input_index above 2^62: GM_ERR_INVALID_ARG. */
+int gm_excisor_reset(gm_excisor *x, uint64_t input_index);
+/* B host f32 values, each in [0, 1] (outside, or not a number: GM_ERR_INVALID_ARG, nothing changed).  Ordered on the handle's stream:
+ * calls enqueued before it use the old gains, calls after it the new ones. */
+int gm_excisor_set_gains(gm_excisor *x, const float *gains);
+/* reads the B gains back (what gm_excisor_set_gains or gm_excisor_adapt_dev installed last).  Synchronises. */
+int gm_excisor_gains(gm_excisor *x, float *gains);
+/* the adaptive step on n samples at d_in (GM_FMT_C32 or GM_FMT_I8_IQ; n < B, n above 2^31, a null pointer or GM_FMT_I8_REAL:
+ * GM_ERR_INVALID_ARG with nothing enqueued).  Asynchronous on `stream` (NULL: the handle's own); no host wait.  The stream state and
+ * the counters are not touched.  It writes the gains: order it against the handle's other calls as they are ordered against each other
+ * (one stream, or the caller's events); a gm_excisor_process_dev enqueued behind it on the same stream uses the new gains. */
+int gm_excisor_adapt_dev(gm_excisor *x, const void *d_in, int fmt, size_t n, void *stream);
+/* the last adapt's words: P[B], the median, the bins flagged and the bins zeroed (all 0 before the first adapt).  Synchronises.  Any
+ * pointer may be NULL. */
+int gm_excisor_psd(gm_excisor *x, float *P, float *median, uint32_t *n_flagged, uint32_t *n_zeroed);
+/* d_in (GM_FMT_C32 or GM_FMT_I8_IQ; GM_FMT_I8_REAL: GM_ERR_INVALID_ARG), n_in samples -> d_out (c32), *n_out of them (n_out may be
+ * NULL).  Asynchronous on `stream` (a hipStream_t; NULL: the handle's own non-blocking stream); consecutive calls of a handle must be
+ * ordered against each other (one stream, or the caller's events).  Every argument is checked before anything runs: out_cap below the
+ * count is GM_ERR_OUT_OF_RANGE, d_out overlapping d_in GM_ERR_INVALID_ARG, each with nothing launched and the state unchanged.
+ * n_in = 0: GM_OK, *n_out = 0. */
+int gm_excisor_process_dev(gm_excisor *x, const void *d_in, int fmt, size_t n_in, void *d_out, size_t out_cap, size_t *n_out,
+                           void *stream);
+/* the synchronous host-buffer form (H2D, the kernels, D2H on the handle's stream) */
+int gm_excisor_process(gm_excisor *x, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out);
+int gm_excisor_synchronize(gm_excisor *x);
+/* inputs taken, outputs delivered and inputs blanked since gm_excisor_create or the last gm_excisor_reset (any pointer may be NULL).
+ * Each input is counted once.  Synchronises the handle's stream and the stream the last call ran on. */
+int gm_excisor_stats(gm_excisor *x, uint64_t *inputs, uint64_t *outputs, uint64_t *blanked);
+/* gm_frontend_write_ring_resampled's block loop with the excisor between the front-end kernel and the resampler.  r may be NULL: the
+ * excisor's outputs then go into the ring at the writer's position, wrapping, and ring indices count its outputs: ring index n is
+ * input time n.  With r, ring indices count the resampler's outputs as in gm_frontend_write_ring_resampled.  The same publishing and
+ * the same GM_ERR_OUT_OF_RANGE rule (the outputs of the call exceed the ring).  It does no adapt of its own.  *n_out_total (may be
+ * NULL) = the outputs this call enqueued. */
+int gm_frontend_write_ring_conditioned(gm_frontend *f, gm_excisor *x, gm_resampler *r, gm_ring *ring, const void *samples,
+                                       size_t n_samples, int fmt, uint64_t *n_out_total);
+
 /* ------------------------------------------------------------------ Tracking
  * The evolving fields of TrackingChannel (src/tracking/do_tracking.rs:88-116). */
 typedef struct {

@@ -124,7 +124,15 @@ pub struct GmResamplerCfg {         // gm_resampler_cfg (32 bytes; zeros: the de
     pub blank_threshold: f32,        // 0: off; > 0: an input sample with re^2 + im^2 > thr^2 is replaced by (0, 0)
     pub reserved: u32,               // must be 0
 }
-pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmExcisorCfg {           // gm_excisor_cfg (32 bytes; zeros: the defaults)
+    pub block: u32,                  // B: 256, 512, 1024, 2048 or 4096; 0: 1024
+    pub guard_bins: u32,             // 0 .. 16: bins zeroed on either side of a flagged one
+    pub threshold_factor: f32,       // > 1; 0: 4.0 — a bin is flagged when P[k] > factor * median
+    pub blank_threshold: f32,        // 0: off; > 0: an input sample with re^2 + im^2 > thr^2 is replaced by (0, 0) first
+    pub reserved: [u32; 4],          // must be 0
+}
+pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {} pub enum GmExcisor {}
 
 extern "C" {
     pub fn gm_init(device: c_int) -> c_int;
@@ -210,6 +218,28 @@ extern "C" {
     /// gm_frontend_write_ring with the resampler between the front-end and the ring: ring indices then count OUTPUT samples
     pub fn gm_frontend_write_ring_resampled(f: *mut GmFrontend, r: *mut GmResampler, ring: *mut GmRing, samples: *const c_void,
                                             n_samples: usize, fmt: c_int, n_out_total: *mut u64) -> c_int;
+    // narrowband interference excision (additive entries, ABI stays 9): a 50 % overlap-add filter bank with a per-bin gain, same rate
+    // and sample index; every output defined by absolute sample indices; plan and windows are host only
+    pub fn gm_excisor_plan(cfg: *const GmExcisorCfg, inputs_so_far: u64, n_in: u64, block: *mut u32, guard_bins: *mut u32,
+                           threshold_factor: *mut f32, n_out: *mut u64) -> c_int;
+    pub fn gm_excisor_windows(cfg: *const GmExcisorCfg, analysis: *mut f32, synthesis: *mut f32) -> c_int;
+    pub fn gm_excisor_create(cfg: *const GmExcisorCfg, out: *mut *mut GmExcisor) -> c_int;
+    pub fn gm_excisor_destroy(x: *mut GmExcisor) -> c_int;
+    pub fn gm_excisor_reset(x: *mut GmExcisor, input_index: u64) -> c_int;
+    pub fn gm_excisor_set_gains(x: *mut GmExcisor, gains: *const f32) -> c_int;
+    pub fn gm_excisor_gains(x: *mut GmExcisor, gains: *mut f32) -> c_int;
+    /// periodogram, median, mask and gains from n device samples: enqueued on `stream`, no host wait
+    pub fn gm_excisor_adapt_dev(x: *mut GmExcisor, d_in: *const c_void, fmt: c_int, n: usize, stream: *mut c_void) -> c_int;
+    pub fn gm_excisor_psd(x: *mut GmExcisor, p: *mut f32, median: *mut f32, n_flagged: *mut u32, n_zeroed: *mut u32) -> c_int;
+    pub fn gm_excisor_stats(x: *mut GmExcisor, inputs: *mut u64, outputs: *mut u64, blanked: *mut u64) -> c_int;
+    pub fn gm_excisor_process_dev(x: *mut GmExcisor, d_in: *const c_void, fmt: c_int, n_in: usize, d_out: *mut c_void,
+                                  out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gm_excisor_process(x: *mut GmExcisor, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32,
+                              out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn gm_excisor_synchronize(x: *mut GmExcisor) -> c_int;
+    /// gm_frontend_write_ring_resampled with the excisor between the front-end and the resampler; `r` may be null
+    pub fn gm_frontend_write_ring_conditioned(f: *mut GmFrontend, x: *mut GmExcisor, r: *mut GmResampler, ring: *mut GmRing,
+                                              samples: *const c_void, n_samples: usize, fmt: c_int, n_out_total: *mut u64) -> c_int;
     // do_tracking.rs:118-158, 311-327
     pub fn gm_trk_create(cfg: *const GmTrkCfg, out: *mut *mut GmTrk) -> c_int;
     pub fn gm_trk_destroy(t: *mut GmTrk) -> c_int;
