@@ -6,6 +6,7 @@ include/gnss_mi355x.h.  This Python package is plumbing around it:
   acquisition / tracking / fft   thin mirrors of the reference's Rust API names over the C ABI
   frontend / resample            the digital front-end, and the rate conversion and pulse blanking it leaves out
   excise                         FFT-domain narrowband interference excision (overlap-add filter bank, adaptive per-bin gains)
+  ddc                            real-IF int8 down-conversion to complex baseband (exact NCO, the resampler's polyphase filter)
   synth       deterministic synthetic IF scenes
   build       hipcc build recipe
 """
@@ -13,3 +14,4 @@ from . import _lib  # noqa: F401
 from ._lib import GmError, lib, library_path  # noqa: F401
 from .resample import Resampler  # noqa: F401
 from .excise import Excisor  # noqa: F401
+from .ddc import Ddc  # noqa: F401

@@ -97,6 +97,13 @@ class ResamplerCfg(C.Structure):
                 ("kaiser_beta", C.c_float), ("blank_threshold", C.c_float), ("reserved", C.c_uint32)]
 
 
+class DdcCfg(C.Structure):
+    """gm_ddc_cfg (40 bytes): the mix frequency in cycles per input sample, then gm_resampler_cfg's fields"""
+    _fields_ = [("mix_cycles_per_sample", C.c_double), ("up", C.c_uint32), ("down", C.c_uint32), ("taps", C.c_uint32),
+                ("n_phases", C.c_uint32), ("cutoff", C.c_float), ("kaiser_beta", C.c_float), ("blank_threshold", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 class ExcisorCfg(C.Structure):
     """gm_excisor_cfg (32 bytes): zeros are the defaults"""
     _fields_ = [("block", C.c_uint32), ("guard_bins", C.c_uint32), ("threshold_factor", C.c_float), ("blank_threshold", C.c_float),
@@ -265,6 +272,17 @@ SIGNATURES = {
     "gm_excisor_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gm_excisor_synchronize": (_i, [_vp]),
     "gm_frontend_write_ring_conditioned": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, C.POINTER(_u64)]),
+    "gm_ddc_plan": (_i, [C.POINTER(DdcCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u64),
+                         C.POINTER(_u64)]),
+    "gm_ddc_create": (_i, [C.POINTER(DdcCfg), C.POINTER(_vp)]),
+    "gm_ddc_destroy": (_i, [_vp]),
+    "gm_ddc_reset": (_i, [_vp, _u64]),
+    "gm_ddc_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_ddc_synchronize": (_i, [_vp]),
+    "gm_ddc_tables": (_i, [_vp, _vp, _vp, _vp]),
+    "gm_ddc_process_dev": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "gm_ddc_process": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "gm_ddc_write_ring": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_u64)]),
     "gm_trk_create": (_i, [C.POINTER(TrkCfg), C.POINTER(_vp)]),
     "gm_trk_destroy": (_i, [_vp]),
     "gm_trk_start": (_i, [_vp, _u32, C.POINTER(AcqResult)]),

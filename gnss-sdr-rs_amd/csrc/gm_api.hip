@@ -4222,6 +4222,323 @@ int gm_frontend_write_ring_conditioned(gm_frontend* f, gm_excisor* x, gm_resampl
 
 }  // extern "C"
 
+// ====================================================================== real-IF down-conversion (gm_ddc)
+// gnss_mi355x.h states the definition; tests/ddc_model.py restates it.  The filter is the resampler's: its rules, its table, its counts.
+namespace {
+struct DdcPlan {
+    ResamplerPlan rs;
+    uint64_t inc = 0;
+};
+
+int ddc_rules(const gm_ddc_cfg* c, DdcPlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    if (!std::isfinite(c->mix_cycles_per_sample)) return set_err(GM_ERR_INVALID_ARG, "mix_cycles_per_sample must be finite");
+    const gm_resampler_cfg rc{c->up, c->down, c->taps, c->n_phases, c->cutoff, c->kaiser_beta, c->blank_threshold, c->reserved};
+    if (int rc2 = resampler_rules(&rc, p.rs)) return rc2;
+    const double frac = c->mix_cycles_per_sample - floor(c->mix_cycles_per_sample);      // [0, 1]: 1 only when a tiny negative value rounds up
+    p.inc = frac < 1.0 ? uint64_t(floor(ldexp(frac, 64))) : 0;                            // exact: a scaling by 2^64 loses nothing; 2^64 wraps to 0
+    return GM_OK;
+}
+
+// Whi[h] = exp(-j 2 pi h / 2^12), Wlo[l] = exp(-j 2 pi l / 2^24): the f64 value rounded once (either pointer may be null)
+void ddc_phasor_tables(cf* whi, cf* wlo) {
+    const double PI = 3.14159265358979323846;
+    for (int i = 0; i < gm::DDC_TABLE; ++i) {
+        const double ah = 2.0 * PI * double(i) / 4096.0, al = 2.0 * PI * double(i) / 16777216.0;
+        if (whi) { whi[i].x = float(cos(ah)); whi[i].y = float(0.0 - sin(ah)); }       // (0.0 - 0.0: no negative zero in word 0)
+        if (wlo) { wlo[i].x = float(cos(al)); wlo[i].y = float(0.0 - sin(al)); }
+    }
+}
+}  // namespace
+
+struct gm_ddc {
+    int device = -1;
+    DdcPlan plan;
+    std::vector<float> table;               // [PHI + 1][T]
+    std::vector<cf> whi, wlo;               // [DDC_TABLE] each
+    float* d_table = nullptr;
+    cf *d_whi = nullptr, *d_wlo = nullptr;
+    int8_t* d_hist[2] = {nullptr, nullptr}; // the last T blanked input bytes: d_hist[cur] is read by the next call, the other written
+    int cur = 0;
+    unsigned long long* d_blanked = nullptr;
+    hipStream_t stream = nullptr, last_stream = nullptr;
+    uint64_t base = 0;                      // absolute index of the first input since create / reset
+    uint64_t inputs = 0, outputs = 0;       // since create / reset
+    void* d_in = nullptr; size_t in_cap = 0;    // bytes; staging of the host-buffer entry
+    cf* d_out = nullptr; size_t out_cap = 0;    // samples
+    void* d_raw[gm_ring::SLOTS] = {nullptr, nullptr, nullptr, nullptr};   // gm_ddc_write_ring: the landing zones of the raw bytes
+    cf* d_scratch = nullptr;                // gm_ddc_write_ring: the linear output in front of an excisor or a resampler (SLOT_SAMPLES_MAX samples)
+};
+
+static uint64_t ddc_count(const gm_ddc* d, uint64_t n_in) {
+    const uint64_t A = d->base + d->inputs;
+    return resampler_total_out(d->plan.rs, A + n_in) - resampler_total_out(d->plan.rs, A);
+}
+// one call's kernels on `st`, outputs to out[(out_start + k) & out_mask]; the caller has checked every argument; n_in > 0
+static int ddc_launch(gm_ddc* d, hipStream_t st, const void* d_in, uint64_t n_in, cf* out, uint64_t out_start, uint64_t out_mask,
+                      uint64_t n_out) {
+    const ResamplerPlan& p = d->plan.rs;
+    const uint64_t A = d->base + d->inputs, m0 = resampler_total_out(p, A);
+    gm::DdcArgs a{};
+    a.in = static_cast<const int8_t*>(d_in); a.n_in = n_in;
+    a.hist_in = d->d_hist[d->cur]; a.hist_out = d->d_hist[d->cur ^ 1];
+    a.table = d->d_table; a.whi = d->d_whi; a.wlo = d->d_wlo;
+    a.T = p.T; a.PHI = p.PHI; a.up = p.up; a.down = p.down;
+    a.a0 = m0 / p.up; a.mr0 = m0 % p.up; a.in_index = A; a.inc = d->plan.inc;
+    a.n_out = n_out; a.tile_out = gm::resample_tile_out(p.T, p.up, p.down);
+    a.out = out; a.out_start = out_start; a.out_mask = out_mask;
+    a.thr2 = p.thr * p.thr; a.blank = p.thr > 0.0f ? 1 : 0;
+    a.blanked = d->d_blanked;
+    gm::launch_ddc(st, a);
+    HIPC(hipGetLastError());
+    d->cur ^= 1; d->inputs += n_in; d->outputs += n_out; d->last_stream = st;
+    return GM_OK;
+}
+static int ddc_sync(gm_ddc* d) {
+    HIPC(hipStreamSynchronize(d->stream));
+    if (d->last_stream && d->last_stream != d->stream) HIPC(hipStreamSynchronize(d->last_stream));
+    return GM_OK;
+}
+// the checks gm_ddc_process_dev and gm_ddc_process share: nothing is touched when one fails
+static int ddc_check_call(gm_ddc* d, const void* in, size_t n_in, const void* out, size_t out_cap, uint64_t* cnt) {
+    if (!d) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
+    if (uint64_t(n_in) > (1ull << 31) || d->base + d->inputs + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
+    *cnt = ddc_count(d, n_in);
+    if (*cnt > out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_cap below the call's output count (gm_ddc_plan gives it)");
+    if (*cnt && !out) return set_err(GM_ERR_INVALID_ARG, "null output");
+    return GM_OK;
+}
+
+extern "C" {
+
+int gm_ddc_plan(const gm_ddc_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* up_reduced, uint32_t* down_reduced,
+                uint32_t* taps, uint32_t* n_phases, uint64_t* phase_inc, uint64_t* n_out) {
+    DdcPlan p;
+    if (int rc = ddc_rules(cfg, p)) return rc;
+    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (up_reduced) *up_reduced = p.rs.up;
+    if (down_reduced) *down_reduced = p.rs.down;
+    if (taps) *taps = p.rs.T;
+    if (n_phases) *n_phases = p.rs.PHI;
+    if (phase_inc) *phase_inc = p.inc;
+    if (n_out) *n_out = resampler_total_out(p.rs, inputs_so_far + n_in) - resampler_total_out(p.rs, inputs_so_far);
+    return GM_OK;
+}
+
+int gm_ddc_create(const gm_ddc_cfg* cfg, gm_ddc** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    DdcPlan p;
+    if (int rc = ddc_rules(cfg, p)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_ddc* d = new gm_ddc;
+    d->device = g_device; d->plan = p;
+    d->table.resize(size_t(p.rs.PHI + 1) * p.rs.T);
+    resampler_design(p.rs, d->table.data());
+    d->whi.resize(gm::DDC_TABLE); d->wlo.resize(gm::DDC_TABLE);
+    ddc_phasor_tables(d->whi.data(), d->wlo.data());
+    const size_t wbytes = gm::DDC_TABLE * sizeof(cf);
+    hipError_t e = hipMalloc(&d->d_table, d->table.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d->d_table, d->table.data(), d->table.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->d_whi), wbytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->d_wlo), wbytes);
+    if (e == hipSuccess) e = hipMemcpy(d->d_whi, d->whi.data(), wbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d->d_wlo, d->wlo.data(), wbytes, hipMemcpyHostToDevice);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = hipMalloc(reinterpret_cast<void**>(&d->d_hist[i]), p.rs.T);
+        if (e == hipSuccess) e = hipMemset(d->d_hist[i], 0, p.rs.T);
+    }
+    if (e == hipSuccess) e = hipMalloc(&d->d_blanked, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(d->d_blanked, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the fills have run before a kernel on a non-blocking stream can touch the state (see gm_ring_create)
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { gm_ddc_destroy(d); return hip_fail(e, "gm_ddc_create"); }
+    *out = d;
+    return GM_OK;
+}
+
+int gm_ddc_destroy(gm_ddc* d) {
+    if (!d) return GM_OK;
+    hipSetDevice(d->device);
+    if (d->last_stream && d->last_stream != d->stream) hipStreamSynchronize(d->last_stream);
+    if (d->stream) { hipStreamSynchronize(d->stream); hipStreamDestroy(d->stream); }
+    hipFree(d->d_table); hipFree(d->d_whi); hipFree(d->d_wlo); hipFree(d->d_hist[0]); hipFree(d->d_hist[1]); hipFree(d->d_blanked);
+    hipFree(d->d_in); hipFree(d->d_out); hipFree(d->d_scratch);
+    for (void* p : d->d_raw) hipFree(p);
+    delete d;
+    return GM_OK;
+}
+
+int gm_ddc_reset(gm_ddc* d, uint64_t input_index) {
+    if (!d) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (input_index > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "input_index above 2^62");
+    if (int rc = ensure_device(d->device)) return rc;
+    if (int rc = ddc_sync(d)) return rc;
+    HIPC(hipMemsetAsync(d->d_hist[0], 0, d->plan.rs.T, d->stream));
+    HIPC(hipMemsetAsync(d->d_hist[1], 0, d->plan.rs.T, d->stream));
+    HIPC(hipMemsetAsync(d->d_blanked, 0, sizeof(unsigned long long), d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    d->cur = 0; d->base = input_index; d->inputs = 0; d->outputs = 0;
+    return GM_OK;
+}
+
+int gm_ddc_stats(gm_ddc* d, uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) {
+    if (!d) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(d->device)) return rc;
+    if (int rc = ddc_sync(d)) return rc;
+    if (blanked) {
+        unsigned long long b = 0;
+        HIPC(hipMemcpy(&b, d->d_blanked, sizeof(b), hipMemcpyDeviceToHost));
+        *blanked = b;
+    }
+    if (inputs) *inputs = d->inputs;
+    if (outputs) *outputs = d->outputs;
+    return GM_OK;
+}
+
+int gm_ddc_synchronize(gm_ddc* d) {
+    if (!d) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(d->device)) return rc;
+    return ddc_sync(d);
+}
+
+int gm_ddc_tables(gm_ddc* d, float* table, gm_c32* whi, gm_c32* wlo) {
+    if (!d && table) return set_err(GM_ERR_INVALID_ARG, "the filter table needs a handle");
+    if (!d) {                 // the phasor tables are the same for every handle: a null handle gives them without a device
+        ddc_phasor_tables(reinterpret_cast<cf*>(whi), reinterpret_cast<cf*>(wlo));
+        return GM_OK;
+    }
+    if (table) memcpy(table, d->table.data(), d->table.size() * sizeof(float));
+    if (whi) memcpy(whi, d->whi.data(), gm::DDC_TABLE * sizeof(cf));
+    if (wlo) memcpy(wlo, d->wlo.data(), gm::DDC_TABLE * sizeof(cf));
+    return GM_OK;
+}
+
+int gm_ddc_process_dev(gm_ddc* d, const void* d_in, size_t n_in, void* d_out, size_t out_cap, size_t* n_out, void* stream) {
+    uint64_t cnt = 0;
+    if (int rc = ddc_check_call(d, d_in, n_in, d_out, out_cap, &cnt)) return rc;
+    if (cnt && n_in) {
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), i1 = i0 + n_in;
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + cnt * 8;
+        if (i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
+    }
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(d->device)) return rc;
+    return ddc_launch(d, stream ? static_cast<hipStream_t>(stream) : d->stream, d_in, n_in, static_cast<cf*>(d_out), 0, ~0ull, cnt);
+}
+
+int gm_ddc_process(gm_ddc* d, const int8_t* in, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out) {
+    uint64_t cnt = 0;
+    if (int rc = ddc_check_call(d, in, n_in, out, out_cap, &cnt)) return rc;
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(d->device)) return rc;
+    if (d->in_cap < n_in || d->out_cap < cnt) HIPC(hipStreamSynchronize(d->stream));
+    if (d->in_cap < n_in) {
+        hipFree(d->d_in); d->d_in = nullptr; d->in_cap = 0;
+        HIPC(hipMalloc(&d->d_in, n_in));
+        d->in_cap = n_in;
+    }
+    if (d->out_cap < cnt) {
+        hipFree(d->d_out); d->d_out = nullptr; d->out_cap = 0;
+        HIPC(hipMalloc(reinterpret_cast<void**>(&d->d_out), size_t(cnt) * sizeof(cf)));
+        d->out_cap = size_t(cnt);
+    }
+    if (d->last_stream && d->last_stream != d->stream) HIPC(hipStreamSynchronize(d->last_stream));   // the history the last call wrote
+    HIPC(hipMemcpyAsync(d->d_in, in, n_in, hipMemcpyHostToDevice, d->stream));
+    if (int rc = ddc_launch(d, d->stream, d->d_in, n_in, d->d_out, 0, ~0ull, cnt)) return rc;
+    if (cnt) HIPC(hipMemcpyAsync(out, d->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return GM_OK;
+}
+
+// gm_frontend_write_ring_conditioned's block loop with the down-converter in the front-end kernel's place: raw bytes -> down-converter
+// -> (x: a linear buffer -> excisor ->) (rs: a linear buffer -> resampler ->) the ring at write_pos
+int gm_ddc_write_ring(gm_ddc* d, gm_excisor* x, gm_resampler* rs, gm_ring* r, const int8_t* samples, size_t n_samples,
+                      uint64_t* n_out_total) {
+    if (!d || !r || (!samples && n_samples)) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (d->device != r->device || (x && x->device != r->device) || (rs && rs->device != r->device))
+        return set_err(GM_ERR_INVALID_ARG, "down-converter, excisor, resampler and ring live on different devices");
+    if (d->base + d->inputs + n_samples > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
+    uint64_t total = ddc_count(d, n_samples);
+    if (x) {
+        if (x->base + x->inputs + total > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
+        total = excisor_count(x, total);
+    }
+    if (rs) {
+        if (rs->base + rs->inputs + total > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
+        total = resampler_count(rs, total);
+    }
+    if (total > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "write larger than the ring");
+    if (n_out_total) *n_out_total = total;
+    if (int rc = ensure_device(r->device)) return rc;
+    if (int rc = ring_async_init(r)) return rc;
+    if (!r->fe_stream) {      // (as gm_frontend_write_ring creates it)
+        if (gm::diag_int("GM_RING_FE_STREAM", 1) == 0) r->fe_stream = r->copy_stream;
+        else {
+            int least = 0, greatest = 0;
+            HIPC(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            const int pr = gm::diag_int("GM_RING_FE_PRIORITY", 99);
+            HIPC(hipStreamCreateWithPriority(&r->fe_stream, hipStreamNonBlocking, pr == 99 ? greatest : pr));
+        }
+        for (int i = 0; i < gm_ring::SLOTS; ++i) HIPC(hipEventCreateWithFlags(&r->h2d_done[i], hipEventDisableTiming));
+    }
+    if ((x || rs) && !d->d_scratch) HIPC(hipMalloc(reinterpret_cast<void**>(&d->d_scratch), gm_ring::SLOT_SAMPLES_MAX * sizeof(cf)));
+    if (x && rs && !x->d_mid) HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_mid), (gm_ring::SLOT_SAMPLES_MAX + gm::EX_BLOCK_MAX) * sizeof(cf)));   // a block's outputs: up to its inputs + H
+    if (d->last_stream && d->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(d->last_stream));        // the history the last call wrote
+    if (x && x->last_stream && x->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(x->last_stream));
+    if (rs && rs->last_stream && rs->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(rs->last_stream));
+    // a block is at most the ring's staging slot, and, where the down-converter raises the rate, short enough that its outputs fit the
+    // linear buffers (a call delivers at most n * up / down + 1)
+    const ResamplerPlan& p = d->plan.rs;
+    size_t block = r->slot_samples;
+    if (p.up > p.down) block = std::min<size_t>(block, size_t((gm_ring::SLOT_SAMPLES_MAX - 1) * uint64_t(p.down) / p.up));
+    const int8_t* src = samples;
+    while (n_samples) {
+        const size_t chunk = n_samples < block ? n_samples : block;
+        const int slot = int(r->slot_seq++ % gm_ring::SLOTS);
+        if (int rc = ring_reclaim_slot(r, slot)) return rc;
+        if (!d->d_raw[slot]) HIPC(hipMalloc(&d->d_raw[slot], gm_ring::SLOT_SAMPLES_MAX));
+        memcpy(r->staging[slot], src, chunk);
+        HIPC(hipMemcpyAsync(d->d_raw[slot], r->staging[slot], chunk, hipMemcpyHostToDevice, r->copy_stream));
+        HIPC(hipEventRecord(r->h2d_done[slot], r->copy_stream));
+        HIPC(hipStreamWaitEvent(r->fe_stream, r->h2d_done[slot], 0));
+        // one buffer of each kind serves every block: the stream runs block k's kernels before block k + 1's first kernel
+        uint64_t cnt = ddc_count(d, chunk);
+        if (!x && !rs) {
+            if (int rc = ddc_launch(d, r->fe_stream, d->d_raw[slot], chunk, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
+        } else {
+            if (int rc = ddc_launch(d, r->fe_stream, d->d_raw[slot], chunk, d->d_scratch, 0, ~0ull, cnt)) return rc;
+            const cf* mid = d->d_scratch;
+            if (x && cnt) {
+                const uint64_t n1 = cnt;
+                cnt = excisor_count(x, n1);
+                if (rs) {
+                    if (int rc = excisor_launch(x, r->fe_stream, mid, GM_FMT_C32, n1, x->d_mid, 0, ~0ull, cnt)) return rc;
+                    mid = x->d_mid;
+                } else if (int rc = excisor_launch(x, r->fe_stream, mid, GM_FMT_C32, n1, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
+            }
+            if (rs && cnt) {
+                const uint64_t n2 = cnt;
+                cnt = resampler_count(rs, n2);
+                if (int rc = resampler_launch(rs, r->fe_stream, mid, GM_FMT_C32, n2, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
+            }
+        }
+        HIPC(hipEventRecord(r->slot_done[slot], r->fe_stream));
+        r->slot_used[slot] = true;
+        r->write_pos += cnt;
+        if (int rc = ring_enqueue_publish(r, slot, r->fe_stream)) return rc;
+        src += chunk; n_samples -= chunk;
+    }
+    return GM_OK;
+}
+
+}  // extern "C"
+
 // ====================================================================== multi-GPU exchange
 // The path's ONE exchange step: all-gather of the per-(worker, bin) metrics over RCCL, enqueued on the acquisition
 // handle's stream, followed by the regroup to the [3][nranks*P][D] layout gm_acq_decide_dev replays.  RCCL is bound

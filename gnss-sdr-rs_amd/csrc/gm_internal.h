@@ -395,6 +395,27 @@ inline uint32_t resample_tile_out(uint32_t T, uint32_t up, uint32_t down) {
 }
 void launch_resample(hipStream_t, const ResampleArgs&, int fmt);
 
+// ---------------------------------------------------------------- real-IF down-conversion (ddc_kernels.hip)
+// gnss_mi355x.h states the definition.  The rate converter's call shape (the same positions and tap loop; the fields they read carry
+// ResampleArgs' names), with int8 real samples in, the history kept as T blanked BYTES, and the NCO:
+// input n has phase (n * inc) mod 2^64, whose top 24 bits index the two phasor tables.
+constexpr int DDC_TABLE = 4096;            // words of each phasor table
+struct DdcArgs {
+    const int8_t* in; uint64_t n_in;       // this call's inputs, one byte each, at any byte address
+    const int8_t* hist_in; int8_t* hist_out;   // [T] the last T blanked inputs before / after this call (two buffers, used alternately)
+    const float* table;                    // [PHI + 1][T]
+    const cf *whi, *wlo;                   // [DDC_TABLE] each: exp(-j 2 pi h / 2^12), exp(-j 2 pi l / 2^24)
+    uint32_t T, PHI, up, down;
+    uint64_t a0, mr0;                      // the call's first output: m0 = a0 * up + mr0, mr0 < up
+    uint64_t in_index;                     // absolute index of in[0]
+    uint64_t inc;                          // floor(frac(mix_cycles_per_sample) * 2^64)
+    uint64_t n_out; uint32_t tile_out;
+    cf* out; uint64_t out_start, out_mask; // linear buffer (out_mask = ~0) or ring base
+    float thr2; int blank;                 // blank_threshold^2 (f32 product); blanking on
+    unsigned long long* blanked;           // device counter, integer atomics only
+};
+void launch_ddc(hipStream_t, const DdcArgs&);
+
 // ---------------------------------------------------------------- narrowband interference excision (excise_kernels.hip)
 // gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of G segments of H = B / 2
 // outputs) and one of the state kernel (the next history of 3H blanked inputs, the blanked count).  The host hands over where the

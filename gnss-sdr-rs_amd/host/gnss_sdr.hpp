@@ -364,6 +364,55 @@ private:
     }
 };
 
+// ---- real-IF down-conversion (gm_ddc): int8 real samples at an intermediate frequency -> complex baseband at fs_in * up / down: blank,
+// an exact integer NCO, the resampler's centred polyphase filter.  Every output is defined by absolute sample indices.  The stage to
+// put in front of an Excisor, a Resampler or the ring when the capture is real.
+class Ddc {
+    gm_ddc* h_ = nullptr;
+public:
+    explicit Ddc(const gm_ddc_cfg& cfg) { check(gm_ddc_create(&cfg, &h_), "Ddc::new"); }
+    Ddc(double mix_cycles_per_sample, uint32_t up, uint32_t down, float blank_threshold = 0.0f) {     // every other setting at its default
+        gm_ddc_cfg cfg{};
+        cfg.mix_cycles_per_sample = mix_cycles_per_sample; cfg.up = up; cfg.down = down; cfg.blank_threshold = blank_threshold;
+        check(gm_ddc_create(&cfg, &h_), "Ddc::new");
+    }
+    ~Ddc() { gm_ddc_destroy(h_); }
+    Ddc(const Ddc&) = delete;
+    gm_ddc* handle() const { return h_; }
+    // host only: the reduced ratio, the defaults, the NCO's phase increment and a call's output count
+    static uint64_t plan(const gm_ddc_cfg& cfg, uint64_t inputs_so_far, uint64_t n_in, uint64_t* phase_inc = nullptr) {
+        uint64_t n = 0;
+        check(gm_ddc_plan(&cfg, inputs_so_far, n_in, nullptr, nullptr, nullptr, nullptr, phase_inc, &n), "Ddc::plan");
+        return n;
+    }
+    // the synchronous host-buffer form: this call's outputs
+    std::vector<Complex32> process(const int8_t* real, size_t n) {
+        size_t got = 0;
+        std::vector<Complex32> out(n * 16 + 1);                             // a call never delivers more than n * up / down + 1, up / down <= 16
+        check(gm_ddc_process(h_, real, n, reinterpret_cast<gm_c32*>(out.data()), out.size(), &got), "Ddc::process");
+        out.resize(got);
+        return out;
+    }
+    // device pointers (d_in at any byte address), asynchronous on `stream` (nullptr: the handle's own); returns the number of outputs written
+    size_t process_dev(const void* d_in, size_t n_in, void* d_out, size_t out_cap, void* stream = nullptr) {
+        size_t n = 0;
+        check(gm_ddc_process_dev(h_, d_in, n_in, d_out, out_cap, &n, stream), "Ddc::process_dev");
+        return n;
+    }
+    // the block step of a real capture: down-converter, then the excisor and the resampler if given, into the ring; ring indices count
+    // the last stage's outputs; returns the outputs enqueued
+    uint64_t write_ring(MulticastRingBuffer& ring, const int8_t* real, size_t n, Excisor* excisor = nullptr, Resampler* resampler = nullptr) {
+        uint64_t total = 0;
+        check(gm_ddc_write_ring(h_, excisor ? excisor->handle() : nullptr, resampler ? resampler->handle() : nullptr, ring.handle(), real, n, &total), "Ddc::write_ring");
+        return total;
+    }
+    void reset(uint64_t input_index = 0) { check(gm_ddc_reset(h_, input_index), "Ddc::reset"); }
+    void stats(uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) const { check(gm_ddc_stats(h_, inputs, outputs, blanked), "Ddc::stats"); }
+    // the (n_phases + 1) * taps filter words and the 4096 + 4096 phasor words; any pointer may be null
+    void tables(float* table, Complex32* whi, Complex32* wlo) const { check(gm_ddc_tables(h_, table, reinterpret_cast<gm_c32*>(whi), reinterpret_cast<gm_c32*>(wlo)), "Ddc::tables"); }
+    void synchronize() { check(gm_ddc_synchronize(h_), "Ddc::synchronize"); }
+};
+
 // ---- rf::frontend::DigitalFrontend (src/rf/frontend.rs:6-62)
 class DigitalFrontend {
     gm_frontend* h_ = nullptr;

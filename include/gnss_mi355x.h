@@ -870,6 +870,84 @@ int gm_excisor_stats(gm_excisor *x, uint64_t *inputs, uint64_t *outputs, uint64_
 int gm_frontend_write_ring_conditioned(gm_frontend *f, gm_excisor *x, gm_resampler *r, gm_ring *ring, const void *samples,
                                        size_t n_samples, int fmt, uint64_t *n_out_total);
 
+/* ------------------------------------------------------------------ Real-IF down-conversion
+ * The first block of a receiver for IF-sampled data: a gm_ddc takes GM_FMT_I8_REAL samples (one byte each) at fs_in, whose carrier
+ * sits at an intermediate frequency, and delivers c32 samples at complex baseband at fs_out = fs_in * up / down: blank, multiply by
+ * a complex NCO, then the rate converter's centred polyphase low-pass.  A real stream at fs carries fs / 2 of bandwidth: 16.3676 Msps
+ * real at an IF of 4.1304 MHz becomes, with 20460 / 40919, 8.184 Msps complex with a C/A period of exactly 8184 samples.  It is the
+ * stage to put in front of a gm_excisor, a gm_resampler or the ring when the capture is real: those take c32 or int8 IQ only.
+ * Everything is defined by ABSOLUTE input indices: the words do not depend on how the stream is cut into calls, tiles or workgroups,
+ * and stay right past 2^32 samples.
+ *   Table: gm_resampler_design's words for the same up, down, taps, n_phases, cutoff and kaiser_beta (the same rules and defaults).
+ *   NCO, in integers.  frac = mix - floor(mix) in f64 (mix = mix_cycles_per_sample = f_mix / fs_in, any finite value);
+ *     inc = (uint64_t) floor(ldexp(frac, 64)), exact (a tiny negative mix whose frac rounds to 1 gives the wrapped value, inc = 0).
+ *     Input n (absolute index) has phase Theta_n = (n * inc) mod 2^64, a wrapping 64-bit product, and k = Theta_n >> 40 (24 bits).  The
+ *     truncation of the phase to 24 bits is part of the definition, not an error term.
+ *     Two host-built tables of 4096 complex f32 words, each word the f64 value rounded once:
+ *       Whi[h] = exp(-j 2 pi h / 4096),  Wlo[l] = exp(-j 2 pi l / 2^24)
+ *     w[n] = Whi[k >> 12] * Wlo[k & 4095], formed in f32 with no fused operation, every product and sum rounded on its own:
+ *       re = fl(fl(ar br) - fl(ai bi)),  im = fl(fl(ar bi) + fl(ai br))        (within 2^-22 of exp(-j 2 pi k / 2^24) for every k)
+ *   Blanking (blank_threshold > 0): an input with x*x > thr*thr (f32, the int8 value converted first, strictly greater) is replaced by
+ *     0 and counted once, with integer adds.
+ *   Product: p[n] = (fl(xb[n] * re), fl(xb[n] * im)).  The filter rows have DC gain 1 and nothing is rescaled: a real carrier of
+ *     amplitude A at f_mix + delta comes out as a complex tone of amplitude A / 2 at delta; its image at -(2 f_mix + delta) and the
+ *     stream's DC, which lands at -f_mix, are what the low-pass removes.
+ *   Output m: the rate converter's formula with p in xb's place — the same pos, i0, phi, alpha, the same
+ *     c_j = fmaf(alpha, g[phi+1][j] - g[phi][j], g[phi][j]), and y[m] = sum_{j<T} c_j * p[i0 - (T/2 - 1) + j], one fmaf per component
+ *     and tap, from +0, j ASCENDING; p is zero before the stream's first sample.  The same total_out(A) and per-call count, computed
+ *     on the host with no synchronisation; output m is the baseband signal at input time m * down / up.
+ *   State.  The handle keeps the last T blanked input BYTES in device memory, in two buffers used alternately, and the counters on the
+ *     host.  The phase needs no state: it is a function of the absolute index.
+ *   Kernel (csrc/ddc_kernels.hip): one 256-lane workgroup per tile of outputs, the rate converter's tiles; the tile's input span is read
+ *     as bytes (16-byte loads where the address allows, single bytes at the head and the tail: the input may start at ANY byte address),
+ *     blanked and multiplied by its phasor once, and kept in LDS as float pairs for the rate converter's tap loop.
+ * Zeros in the filter fields mean defaults.  (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct {
+    double   mix_cycles_per_sample; /* f_mix / fs_in: the frequency brought to 0, in cycles per input sample; any finite value */
+    uint32_t up, down;        /* as gm_resampler_cfg, field by field */
+    uint32_t taps;
+    uint32_t n_phases;
+    float    cutoff;
+    float    kaiser_beta;
+    float    blank_threshold; /* 0: off; > 0: an input sample with x^2 > thr^2 (f32) is replaced by 0 */
+    uint32_t reserved;        /* must be 0 */
+} gm_ddc_cfg;
+typedef struct gm_ddc gm_ddc;
+/* host only, no device: gm_resampler_plan's argument rules for the fields they share, and GM_ERR_INVALID_ARG for a
+ * mix_cycles_per_sample that is not finite; the reduced ratio, the defaults, *phase_inc = inc and, for a stream that has taken
+ * inputs_so_far samples, the count n_in more deliver (gm_resampler_plan's for the same fields).  Any output pointer may be NULL. */
+int gm_ddc_plan(const gm_ddc_cfg *cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t *up_reduced, uint32_t *down_reduced,
+                uint32_t *taps, uint32_t *n_phases, uint64_t *phase_inc, uint64_t *n_out);
+int gm_ddc_create(const gm_ddc_cfg *cfg, gm_ddc **out);
+int gm_ddc_destroy(gm_ddc *d);
+/* Zeroes the history and the three counters; the next input has absolute index input_index (its phase is input_index * inc), the next
+ * output absolute index total_out(input_index).  Synchronous.  input_index above 2^62: GM_ERR_INVALID_ARG. */
+int gm_ddc_reset(gm_ddc *d, uint64_t input_index);
+/* inputs taken, outputs delivered and inputs blanked since gm_ddc_create or the last gm_ddc_reset (any pointer may be NULL).  Each
+ * input is counted once.  Synchronises the handle's stream and the stream the last call ran on. */
+int gm_ddc_stats(gm_ddc *d, uint64_t *inputs, uint64_t *outputs, uint64_t *blanked);
+int gm_ddc_synchronize(gm_ddc *d);
+/* the words the device uses: the (PHI + 1) * T filter words, and the 4096 words of Whi and of Wlo.  Any pointer may be NULL; the two
+ * phasor tables are the same for every handle, so d may be NULL too when table is (host only, no device then). */
+int gm_ddc_tables(gm_ddc *d, float *table, gm_c32 *whi, gm_c32 *wlo);
+/* d_in (n_in bytes of GM_FMT_I8_REAL, starting at ANY byte address) -> d_out (c32), *n_out of them (n_out may be NULL).  Asynchronous
+ * on `stream` (a hipStream_t; NULL: the handle's own non-blocking stream); consecutive calls of a handle must be ordered against each
+ * other (one stream, or the caller's events).  Every argument is checked before anything runs: out_cap below the count is
+ * GM_ERR_OUT_OF_RANGE, d_out overlapping d_in GM_ERR_INVALID_ARG, each with nothing launched and the state unchanged.  n_in = 0:
+ * GM_OK, *n_out = 0. */
+int gm_ddc_process_dev(gm_ddc *d, const void *d_in, size_t n_in, void *d_out, size_t out_cap, size_t *n_out, void *stream);
+/* the synchronous host-buffer form (H2D, the kernels, D2H on the handle's stream) */
+int gm_ddc_process(gm_ddc *d, const int8_t *in, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out);
+/* gm_frontend_write_ring_conditioned's block loop with the down-converter in the front-end kernel's place, for host int8 real
+ * samples, one byte each.  No gm_frontend takes part: the DC of a real stream lands at -f_mix and the low-pass removes it.  x and r may
+ * each be NULL: down-converter, then the excisor if there is one, then the resampler if there is one; the last stage writes into the
+ * ring at the writer's position, wrapping with the ring's mask, and ring indices count ITS outputs.  A block is the ring's staging
+ * slot, as in the sibling entries (where up > down it is at most floor((2^19 - 1) * down / up) samples, so that a block's outputs fit
+ * the linear buffers between the stages).  The same publishing and the same GM_ERR_OUT_OF_RANGE rule (the outputs of the call exceed
+ * the ring: nothing is enqueued, no state moves).  *n_out_total (may be NULL) = the outputs this call enqueued. */
+int gm_ddc_write_ring(gm_ddc *d, gm_excisor *x, gm_resampler *r, gm_ring *ring, const int8_t *samples, size_t n_samples,
+                      uint64_t *n_out_total);
+
 /* ------------------------------------------------------------------ Tracking
  * The evolving fields of TrackingChannel (src/tracking/do_tracking.rs:88-116). */
 typedef struct {

@@ -132,6 +132,18 @@ pub struct GmExcisorCfg {           // gm_excisor_cfg (32 bytes; zeros: the defa
     pub blank_threshold: f32,        // 0: off; > 0: an input sample with re^2 + im^2 > thr^2 is replaced by (0, 0) first
     pub reserved: [u32; 4],          // must be 0
 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmDdcCfg {               // gm_ddc_cfg (40 bytes; zeros in the filter fields: the defaults)
+    pub mix_cycles_per_sample: f64,  // f_mix / fs_in: the frequency brought to 0, cycles per input sample; any finite value
+    pub up: u32, pub down: u32,      // as GmResamplerCfg, field by field
+    pub taps: u32,
+    pub n_phases: u32,
+    pub cutoff: f32,
+    pub kaiser_beta: f32,
+    pub blank_threshold: f32,        // 0: off; > 0: an input sample with x^2 > thr^2 is replaced by 0
+    pub reserved: u32,               // must be 0
+}
+pub enum GmDdc {}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {} pub enum GmExcisor {}
 
 extern "C" {
@@ -240,6 +252,23 @@ extern "C" {
     /// gm_frontend_write_ring_resampled with the excisor between the front-end and the resampler; `r` may be null
     pub fn gm_frontend_write_ring_conditioned(f: *mut GmFrontend, x: *mut GmExcisor, r: *mut GmResampler, ring: *mut GmRing,
                                               samples: *const c_void, n_samples: usize, fmt: c_int, n_out_total: *mut u64) -> c_int;
+
+    /// real-IF int8 down-conversion to complex baseband: blank, an exact integer NCO, the resampler's polyphase filter
+    pub fn gm_ddc_plan(cfg: *const GmDdcCfg, inputs_so_far: u64, n_in: u64, up_reduced: *mut u32, down_reduced: *mut u32,
+                       taps: *mut u32, n_phases: *mut u32, phase_inc: *mut u64, n_out: *mut u64) -> c_int;
+    pub fn gm_ddc_create(cfg: *const GmDdcCfg, out: *mut *mut GmDdc) -> c_int;
+    pub fn gm_ddc_destroy(d: *mut GmDdc) -> c_int;
+    pub fn gm_ddc_reset(d: *mut GmDdc, input_index: u64) -> c_int;
+    pub fn gm_ddc_stats(d: *mut GmDdc, inputs: *mut u64, outputs: *mut u64, blanked: *mut u64) -> c_int;
+    pub fn gm_ddc_synchronize(d: *mut GmDdc) -> c_int;
+    pub fn gm_ddc_tables(d: *mut GmDdc, table: *mut f32, whi: *mut Complex32, wlo: *mut Complex32) -> c_int;
+    pub fn gm_ddc_process_dev(d: *mut GmDdc, d_in: *const c_void, n_in: usize, d_out: *mut c_void, out_cap: usize,
+                              n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gm_ddc_process(d: *mut GmDdc, input: *const i8, n_in: usize, out: *mut Complex32, out_cap: usize,
+                          n_out: *mut usize) -> c_int;
+    /// gm_frontend_write_ring_conditioned with the down-converter in the front-end's place; `x` and `r` may each be null
+    pub fn gm_ddc_write_ring(d: *mut GmDdc, x: *mut GmExcisor, r: *mut GmResampler, ring: *mut GmRing, samples: *const i8,
+                             n_samples: usize, n_out_total: *mut u64) -> c_int;
     // do_tracking.rs:118-158, 311-327
     pub fn gm_trk_create(cfg: *const GmTrkCfg, out: *mut *mut GmTrk) -> c_int;
     pub fn gm_trk_destroy(t: *mut GmTrk) -> c_int;
