@@ -47,6 +47,9 @@ template <> struct CorrPlanOf<Plan8192> { using type = Plan<8192, 512, 16, 32, 1
 #ifndef GM_NO_HYBRID_PLANS
 using CorrPlan8000 = HybridPlan<8000, 512, 5, 25, 4, 16>;     // 125 * 64: passes of radix 20 / 25 / 16
 template <> struct CorrPlanOf<Plan8000> { using type = CorrPlan8000; };
+// constant twiddles folded into the butterflies of all three passes (fft_core.h FuseTw): 13 % fewer vector instructions per transform,
+// 158.1 -> 151.6 us per headline launch (DESIGN_HISTORY §R7.1, profiles/fused_tw_ab.json)
+template <> struct FuseTw<CorrPlan8000> { static constexpr bool value = true; };
 using CorrPlan16000 = HybridPlan<16000, 1024, 5, 25, 4, 32>;  // 125 * 128: radix 20 / 25 / 32 (the Galileo-E1 geometry's composite base)
 template <> struct CorrPlanOf<Plan16000> { using type = CorrPlan16000; };
 // its pass-0 rows in the order the radix-20 Good-Thomas butterfly consumes them, (5 n1 + 4 N2) mod 20, n1 = 0 .. 3 inside N2 = 0 .. 4

@@ -82,6 +82,29 @@ constexpr long modinv(long a, long m) {  // a^{-1} mod m, gcd == 1
     for (long x = 1; x < m; ++x) if ((a * x) % m == 1) return x;
     return 1;
 }
+// w = exp(-/+ j 2 pi e / m) as a rotation WITHOUT its modulus (FuseTw below): w u = scale * (x - t y, y + t x) with t = s / c where
+// |c| >= |s| (kind 4), = scale * (t x - y, t y + x) with t = c / s otherwise (kind 5): two FMAs, |t| <= 1, and the real scale is
+// left to whoever consumes the value.  Kinds 0 .. 3 are the exact cases 1, w^(m/4), -1, w^(3m/4): scale 1, no arithmetic.
+struct rot { int kind; double t, scale; };
+constexpr rot rotation(long e, long m, bool inv) {
+    e %= m;
+    if (e < 0) e += m;
+    if (e == 0) return {0, 0.0, 1.0};
+    if (4 * e == m) return {1, 0.0, 1.0};
+    if (2 * e == m) return {2, 0.0, 1.0};
+    if (4 * e == 3 * m) return {3, 0.0, 1.0};
+    const cs v = cossin2pi(e, m);
+    const double c = v.c, s = inv ? v.s : -v.s;
+    if ((c < 0 ? -c : c) >= (s < 0 ? -s : s)) return {4, s / c, c};
+    return {5, c / s, s};
+}
+// Scales of the values inside a radix-(a*b) Cooley-Tukey butterfly (n = n2 + b n1, k = k1 + a k2) whose input r carries W_m^{k r}
+// as such a rotation: of input r, and of the first layer's output (n2, k1) once the inner twiddle W_{ab}^{n2 k1} was applied the
+// same way to a sub-DFT that divided by the scale of ITS input 0 (DftS)
+constexpr double tw_in_scale(bool inv, long k, long m, int r) { return rotation(k * r, m, inv).scale; }
+constexpr double tw_mid_scale(bool inv, long k, long m, int a, int b, int n2, int k1) {
+    return tw_in_scale(inv, k, m, n2) * rotation(long(n2) * k1, long(a) * b, inv).scale;
+}
 }  // namespace ct
 
 // w_b^a = exp(-/+ j 2 pi a / b) as a compile-time constant
@@ -316,7 +339,8 @@ template <int R, bool INV> struct Bfly {
     }
     template <class In> static GM_HD void stage1(In&& in, cf (&v)[R]) { s1<0>(in, v); }
 
-    template <class Out> static GM_HD void stage2(const cf (&v)[R], Out&& out) {
+    // DB: the second layer's butterfly (DB::run on cf[B]); DftS<B> with unit scales is the form without plain multiplies
+    template <class DB = Dft<B, INV>, class Out> static GM_HD void stage2(const cf (&v)[R], Out&& out) {
         if constexpr (KIND == 0) {
 #pragma unroll
             for (int k = 0; k < R; ++k) out(k, v[k]);
@@ -326,7 +350,7 @@ template <int R, bool INV> struct Bfly {
                 cf t[B];
 #pragma unroll
                 for (int n2 = 0; n2 < B; ++n2) t[n2] = v[n2 * A + k1];
-                Dft<B, INV>::run(t);
+                DB::run(t);
 #pragma unroll
                 for (int k2 = 0; k2 < B; ++k2) {
                     if constexpr (KIND == 2) out((k1 * EA + k2 * EB) % R, t[k2]);
@@ -571,6 +595,133 @@ template <bool INV, int K, int M, int R> struct ConstTw {
     }
 };
 
+// ------------------------------------------------------------------ constant twiddles folded into the butterflies
+// A constant twiddle as a full complex product costs 2 mul + 2 fma.  As a rotation without its modulus (ct::rotation) it costs 2 fma
+// and leaves a real compile-time scale on the value; the radix-4 / radix-5 butterflies that consume the value only add and subtract
+// their inputs, so the scale turns a +- b into fma(+-ratio, b, a) at no extra instruction (DftS), and the scale pending on input 0
+// of a sub-DFT moves on to the next layer in the same way.  Input 0 of the second layer always carries scale 1: the outputs are the
+// true values.  Which plans run this form: FuseTw.
+template <class PL> struct FuseTw { static constexpr bool value = false; };
+#ifdef GM_NO_FUSED_TW                                        // diagnostics: the plain form everywhere
+template <class PL> inline constexpr bool fuse_tw_v = false;
+#else
+template <class PL> inline constexpr bool fuse_tw_v = FuseTw<PL>::value;
+#endif
+
+// u * W_M^E up to the real factor `scale`; the exponent is a template parameter on purpose (a constexpr table indexed after
+// unrolling is not folded by the device compiler: it loads the table, branches on the kind and spills)
+template <bool INV, long E, long M> struct Rot {
+    static constexpr ct::rot r = ct::rotation(E, M, INV);
+    static constexpr int kind = r.kind;
+    static constexpr double scale = r.scale;
+    static GM_HD cf apply(cf u) {
+        constexpr float t = float(r.t);
+        if constexpr (kind == 0) return u;
+        else if constexpr (kind == 1) return cf_mulj<INV>(u);
+        else if constexpr (kind == 2) return cf_make(-u.x, -u.y);
+        else if constexpr (kind == 3) return cf_mulj<!INV>(u);
+        else if constexpr (kind == 4) return cf_make(__builtin_fmaf(-t, u.y, u.x), __builtin_fmaf(t, u.x, u.y));
+        else return cf_make(__builtin_fmaf(t, u.x, -u.y), __builtin_fmaf(t, u.y, u.x));
+    }
+};
+
+GM_HD cf cf_fma(float a, cf b, cf c) { return cf_make(__builtin_fmaf(a, b.x, c.x), __builtin_fmaf(a, b.y, c.y)); }
+
+// Dft<R> of the values u_r = s_r * u'_r given the held u'_r, DIVIDED by s_0.  Q holds the ratios of the scales as static constexpr
+// doubles — r10 = s1/s0, r20 = s2/s0, r31 = s3/s1 (radix 4); r10, r20, r41 = s4/s1, r32 = s3/s2 (radix 5) — rounded to float once,
+// after radix 5's own constants were merged in.  A ratio of exactly 1 leaves fma(1, b, a), which the compiler turns back into an add.
+template <int R, bool INV, class Q> struct DftS;
+struct UnitScales { static constexpr double r10 = 1.0, r20 = 1.0, r31 = 1.0, r41 = 1.0, r32 = 1.0; };
+
+template <bool INV, class Q> struct DftS<4, INV, Q> {
+    static GM_HD void run(cf (&u)[4]) {
+        constexpr float r10 = float(Q::r10), r20 = float(Q::r20), r31 = float(Q::r31);
+        cf t0 = cf_fma(r20, u[2], u[0]), t1 = cf_fma(-r20, u[2], u[0]);                           // scale s0
+        cf t2 = cf_fma(r31, u[3], u[1]), t3 = cf_mulj<INV>(cf_fma(-r31, u[3], u[1]));             // scale s1
+        u[0] = cf_fma(r10, t2, t0); u[1] = cf_fma(r10, t3, t1); u[2] = cf_fma(-r10, t2, t0); u[3] = cf_fma(-r10, t3, t1);
+    }
+};
+
+template <bool INV, class Q> struct DftS<5, INV, Q> {
+    // (the odd part is scaled too: b1 = s1 t3 + s2 t4 = s1 (t3 + (s2/s1) t4) and b2 = s2 t3 - s1 t4 = s2 (t3 - (s1/s2) t4) leave s1, s2 to the
+    //  outputs' a +- j b, which become FMAs: no plain multiply is left)
+    static GM_HD void run(cf (&u)[5]) {
+        constexpr ct::cs w1 = ct::cossin2pi(1, 5), w2 = ct::cossin2pi(2, 5);
+        constexpr float r10 = float(Q::r10), r20 = float(Q::r20), r41 = float(Q::r41), r32 = float(Q::r32);
+        constexpr float c1a = float(w1.c * Q::r10), c2a = float(w2.c * Q::r10), c1b = float(w1.c * Q::r20), c2b = float(w2.c * Q::r20);
+        constexpr float g1 = float((w2.s * Q::r20) / (w1.s * Q::r10)), g2 = float((w1.s * Q::r20) / (w2.s * Q::r10));
+        constexpr float s1a = float(w1.s * Q::r10), s2a = float(w2.s * Q::r10);
+        cf t1 = cf_fma(r41, u[4], u[1]), t3 = cf_fma(-r41, u[4], u[1]);                           // scale s1
+        cf t2 = cf_fma(r32, u[3], u[2]), t4 = cf_fma(-r32, u[3], u[2]);                           // scale s2
+        cf a1 = cf_fma(c2b, t2, cf_fma(c1a, t1, u[0])), a2 = cf_fma(c1b, t2, cf_fma(c2a, t1, u[0]));
+        cf jb1 = cf_mulj<INV>(cf_fma(g1, t4, t3)), jb2 = cf_mulj<INV>(cf_fma(-g2, t4, t3));       // scales s1a, s2a (over s0)
+        u[0] = cf_fma(r20, t2, cf_fma(r10, t1, u[0]));
+        u[1] = cf_fma(s1a, jb1, a1); u[4] = cf_fma(-s1a, jb1, a1);
+        u[2] = cf_fma(s2a, jb2, a2); u[3] = cf_fma(-s2a, jb2, a2);
+    }
+};
+
+// Bfly<R> (Cooley-Tukey, R = A * B, A and B in {4, 5}) whose input r still lacks its twiddle W_M^{K r}: in(r) yields the RAW input
+//   stage 1, group n2 : rotate the A inputs, DftS<A> by the ratios of their scales, rotate by the inner twiddle, store unscaled
+//   stage 2, row k1   : DftS<B> by the ratios of the pending scales ct::tw_mid_scale(n2, k1); that of n2 = 0 is exactly 1
+template <int R, bool INV, int K, int M> struct BflyTw {
+    static constexpr int A = Fac<R>::A, B = Fac<R>::B;
+    static_assert(Fac<R>::KIND == 1 && (A == 4 || A == 5) && (B == 4 || B == 5), "radix 16 or 25");
+    template <int N2> struct Q1 {
+        static constexpr double s(int n1) { return ct::tw_in_scale(INV, K, M, N2 + B * n1); }
+    };
+    template <int N2> struct R1 {
+        static constexpr double r10 = Q1<N2>::s(1) / Q1<N2>::s(0), r20 = Q1<N2>::s(2) / Q1<N2>::s(0), r31 = Q1<N2>::s(3) / Q1<N2>::s(1);
+        static constexpr double r41 = Q1<N2>::s(A - 1) / Q1<N2>::s(1), r32 = Q1<N2>::s(3) / Q1<N2>::s(2);
+    };
+    template <int K1> struct Q2 {
+        static constexpr double s(int n2) { return ct::tw_mid_scale(INV, K, M, A, B, n2, K1); }
+    };
+    template <int K1> struct R2 {
+        static constexpr double r10 = Q2<K1>::s(1) / Q2<K1>::s(0), r20 = Q2<K1>::s(2) / Q2<K1>::s(0), r31 = Q2<K1>::s(3) / Q2<K1>::s(1);
+        static constexpr double r41 = Q2<K1>::s(B - 1) / Q2<K1>::s(1), r32 = Q2<K1>::s(3) / Q2<K1>::s(2);
+    };
+
+    template <int N2, int N1, class In> static GM_HD void load(In& in, cf (&t)[A]) {
+        if constexpr (N1 < A) {
+            t[N1] = Rot<INV, long(K) * (N2 + B * N1), M>::apply(in(N2 + B * N1));
+            load<N2, N1 + 1>(in, t);
+        }
+    }
+    template <int N2, int K1> static GM_HD void inner_tw(cf (&t)[A]) {
+        if constexpr (K1 < A) {
+            t[K1] = Rot<INV, long(N2) * K1, long(R)>::apply(t[K1]);
+            inner_tw<N2, K1 + 1>(t);
+        }
+    }
+    template <int N2, class In> static GM_HD void s1(In& in, cf (&v)[R]) {
+        if constexpr (N2 < B) {
+            cf t[A];
+            load<N2, 0>(in, t);
+            DftS<A, INV, R1<N2>>::run(t);
+            inner_tw<N2, 1>(t);
+#pragma unroll
+            for (int k1 = 0; k1 < A; ++k1) v[N2 * A + k1] = t[k1];
+            s1<N2 + 1>(in, v);
+        }
+    }
+    template <class In> static GM_HD void stage1(In&& in, cf (&v)[R]) { s1<0>(in, v); }
+
+    template <int K1, class Out> static GM_HD void s2(const cf (&v)[R], Out& out) {
+        if constexpr (K1 < A) {
+            static_assert(Q2<K1>::s(0) == 1.0, "input 0 of the second layer carries no scale");
+            cf t[B];
+#pragma unroll
+            for (int n2 = 0; n2 < B; ++n2) t[n2] = v[n2 * A + K1];
+            DftS<B, INV, R2<K1>>::run(t);
+#pragma unroll
+            for (int k2 = 0; k2 < B; ++k2) out(K1 + A * k2, t[k2]);
+            s2<K1 + 1>(v, out);
+        }
+    }
+    template <class Out> static GM_HD void stage2(const cf (&v)[R], Out&& out) { s2<0>(v, out); }
+};
+
 // ------------------------------------------------------------------ hybrid prime-factor / Cooley-Tukey plan
 // N = A * B with gcd(A, B) = 1, A = A1 * A2, B = B1 * B2, gcd(A1, B1) = 1.  Across the two dimensions the transform is a
 // prime-factor (Good-Thomas) one — no twiddles between A and B — and inside each dimension a two-step Cooley-Tukey one:
@@ -649,6 +800,8 @@ template <int N_, int T_, int A1, int A2, int B1, int B2, bool INV>
 struct Fft<HybridPlan<N_, T_, A1, A2, B1, B2>, INV, false> {
     using PL = HybridPlan<N_, T_, A1, A2, B1, B2>;
     static constexpr int R0 = PL::R[0], R1 = PL::R[1], R2 = PL::R[2];
+    // the constant twiddles of pass 1 / the last pass as full complex products (ConstTw) or folded into the butterflies (BflyTw)
+    static constexpr bool FUSE = fuse_tw_v<PL>;
 
     template <class In> static GM_HD void pass0_stage1(cf (&v)[1][R0], In&& in, int tid) {
         if (tid < PL::NB(0)) Bfly<R0, INV>::stage1([&](int r) { return in(0, r); }, v[0]);
@@ -656,17 +809,26 @@ struct Fft<HybridPlan<N_, T_, A1, A2, B1, B2>, INV, false> {
     static GM_HD void pass0_stage2(const cf (&v)[1][R0], cf* lds, int tid) {
         if (tid < PL::NB(0)) {
             cf* dst = lds + (tid / R2) * PL::STR1 + tid % R2;           // lane b0 = r1 R2 + r2
-            Bfly<R0, INV>::stage2(v[0], [&](int q0, cf val) { dst[(q0 % A1) * PL::GS1 + (q0 % B1) * R2] = val; });
+            // (fused form, radix 20 = 4 x 5: the second layer's radix-5 butterflies in the form without plain multiplies)
+            if constexpr (FUSE && Fac<R0>::B == 5)
+                Bfly<R0, INV>::template stage2<DftS<5, INV, UnitScales>>(v[0], [&](int q0, cf val) { dst[(q0 % A1) * PL::GS1 + (q0 % B1) * R2] = val; });
+            else Bfly<R0, INV>::stage2(v[0], [&](int q0, cf val) { dst[(q0 % A1) * PL::GS1 + (q0 % B1) * R2] = val; });
         }
     }
     // pass 1: wave group k1 = wave / GW1, lane-in-group lambda = j1 R2 + r2
     template <int K1> static GM_HD void p1_s1(cf (&v)[R1], const cf* lds, int lam) {
         const cf* src = lds + K1 * PL::GS1 + lam;
-        Bfly<R1, INV>::stage1([&](int r) { return ConstTw<INV, K1, PL::A, R1>::mul(src[r * PL::STR1], r); }, v);
+        if constexpr (FUSE) BflyTw<R1, INV, K1, PL::A>::stage1([&](int r) { return src[r * PL::STR1]; }, v);
+        else Bfly<R1, INV>::stage1([&](int r) { return ConstTw<INV, K1, PL::A, R1>::mul(src[r * PL::STR1], r); }, v);
     }
     template <int K1> static GM_HD void p1_disp(cf (&v)[R1], const cf* lds, int k1, int lam) {
         if (k1 == K1) p1_s1<K1>(v, lds, lam);
         else if constexpr (K1 + 1 < A1) p1_disp<K1 + 1>(v, lds, k1, lam);
+    }
+    // (fused form: the second layer's ratios depend on k1 as the first layer's do)
+    template <int K1> static GM_HD void p1_s2_disp(const cf (&v)[R1], cf* dst, int k1) {
+        if (k1 == K1) BflyTw<R1, INV, K1, PL::A>::stage2(v, [&](int q1, cf val) { dst[q1 * PL::STR1] = val; });
+        else if constexpr (K1 + 1 < A1) p1_s2_disp<K1 + 1>(v, dst, k1);
     }
     template <int S> static GM_HD void mid_stage1(cf (&v)[1][R1], const cf* lds, const cf*, int tid) {
         static_assert(S == 1, "three passes");
@@ -677,25 +839,35 @@ struct Fft<HybridPlan<N_, T_, A1, A2, B1, B2>, INV, false> {
         const int wave = tid >> 6, k1 = wave / PL::GW1, lam = (wave % PL::GW1) * 64 + (tid & 63);
         if (k1 < A1) {
             cf* dst = lds + k1 * PL::GS1 + lam;                      // the lane's own column: output q1 replaces input r1 = q1
-            Bfly<R1, INV>::stage2(v[0], [&](int q1, cf val) { dst[q1 * PL::STR1] = val; });
+            if constexpr (FUSE) p1_s2_disp<0>(v[0], dst, k1);
+            else Bfly<R1, INV>::stage2(v[0], [&](int q1, cf val) { dst[q1 * PL::STR1] = val; });
         }
     }
     // last pass: lane beta = k1*A2 + q1 of group J1 reads input r2 from row q1, group k1, column J1*R2 + r2
     template <int J1> static GM_HD void p2_s1(cf (&v)[R2], const cf* lds, int beta) {
         const int k1 = beta / A2, q1 = beta - k1 * A2;
         const cf* src = lds + q1 * PL::STR1 + k1 * PL::GS1 + J1 * R2;
-        Bfly<R2, INV>::stage1([&](int r) { return ConstTw<INV, J1, PL::B, R2>::mul(src[r], r); }, v);
+        if constexpr (FUSE) BflyTw<R2, INV, J1, PL::B>::stage1([&](int r) { return src[r]; }, v);
+        else Bfly<R2, INV>::stage1([&](int r) { return ConstTw<INV, J1, PL::B, R2>::mul(src[r], r); }, v);
     }
     template <int J1> static GM_HD void p2_disp(cf (&v)[R2], const cf* lds, int j1, int beta) {
         if (j1 == J1) p2_s1<J1>(v, lds, beta);
         else if constexpr (J1 + 1 < B1) p2_disp<J1 + 1>(v, lds, j1, beta);
+    }
+    template <int J1, class Out> static GM_HD void p2_s2_disp(const cf (&v)[R2], Out& out, int j1) {
+        if (j1 == J1) BflyTw<R2, INV, J1, PL::B>::stage2(v, [&](int q, cf val) { out(0, q, val); });
+        else if constexpr (J1 + 1 < B1) p2_s2_disp<J1 + 1>(v, out, j1);
     }
     static GM_HD void last_stage1(cf (&v)[1][R2], const cf* lds, const cf*, int tid) {
         if (PL::last_active(tid)) p2_disp<0>(v[0], lds, PL::last_j1(tid), PL::last_beta(tid));
     }
     // out(0, q2, value): element PL::out_index(tid, q2)
     template <class Out> static GM_HD void last_stage2(const cf (&v)[1][R2], Out&& out, int tid) {
-        if (PL::last_active(tid)) Bfly<R2, INV>::stage2(v[0], [&](int q, cf val) { out(0, q, val); });
+        if constexpr (FUSE) {
+            if (PL::last_active(tid)) p2_s2_disp<0>(v[0], out, PL::last_j1(tid));
+        } else {
+            if (PL::last_active(tid)) Bfly<R2, INV>::stage2(v[0], [&](int q, cf val) { out(0, q, val); });
+        }
     }
 };
 
