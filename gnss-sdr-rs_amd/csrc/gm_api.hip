@@ -1436,13 +1436,16 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
     if (a->drift.on && !passes.empty() &&
         (uint64_t(*std::max_element(passes.begin(), passes.end())) + periods) * a->N > a->drift.dwell)
         return set_err(GM_ERR_OUT_OF_RANGE, "the code-drift dwell is shorter than the contiguous periods the fine Doppler reads (it is not compensated)");
+    // a code phase lies inside one period: cp + (K*M-1)*N then stays inside the K*M periods a pass reads (:260 would panic beyond
+    // them); checked for every found worker before any pass runs, so no output is half filled
+    for (uint32_t p = 0; p < n_prn; ++p)
+        if (found[p] && results[p].code_phase_samples >= a->N)
+            return set_err(GM_ERR_OUT_OF_RANGE, "result.code_phase_samples is not below fft_size");
     for (const uint32_t o_star : passes) {
     const void* const snap = static_cast<const char*>(a->last_samples) + size_t(o_star) * a->N * bps;
     std::vector<uint32_t> workers, cps, slot(n_prn, 0xFFFFFFFFu);
     for (uint32_t p = 0; p < n_prn; ++p) {
         if (!found[p] || off[p] != o_star) continue;
-        if (results[p].code_phase_samples + size_use > uint64_t(periods) * a->N)
-            return set_err(GM_ERR_OUT_OF_RANGE, "code_phase + (K*M-1)*N exceeds the snapshot (:260 would panic)");
         slot[p] = uint32_t(workers.size());
         workers.push_back(p);
         cps.push_back(uint32_t(results[p].code_phase_samples));

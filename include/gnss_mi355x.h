@@ -243,7 +243,10 @@ int gm_acq_search_ring(gm_acq *a, gm_ring *ring, uint64_t prn_mask, gm_acq_resul
  * gives fine_freq_hz[p] = (idx*fs)/fft_size (:251-253), i.e. IF + Doppler to fs/fft_size (7.6 Hz at 8 Msps, 10 ms).
  * Indices above fft_size/2 are reported as negative frequencies (the legacy indexes out of bounds there, :285-288, and
  * multiplies by (-1)^is_complex, :298-299: neither is reproduced).  Entries of not-found PRNs are left untouched.
- * Any output pointer may be NULL.  Synchronous.  GM_ERR_UNSUPPORTED_N if the long FFT does not factor into two in-LDS plans.
+ * Any output pointer may be NULL.  Synchronous.  GM_ERR_UNSUPPORTED_N if the long FFT does not factor into two in-LDS plans:
+ * 8*next_pow2((K*M-1)*N) must lie in 2^16 .. 2^24, else GM_ERR_UNSUPPORTED_N (K = coherent_periods, M = num_integrations, N = fft_size).
+ * A found result's code_phase_samples is a code phase: below fft_size, else GM_ERR_OUT_OF_RANGE (checked for every found result
+ * before any pass runs, so a refused call fills no output).
  * gm_acq_refine_doppler (below, after the code-drift entries) is the estimator that follows the coherent, edge and drift handles. */
 int gm_acq_finer_doppler(gm_acq *a, const gm_acq_result *results, const uint8_t *found, uint32_t n_prn,
                          float *fine_freq_hz, uint64_t *peak_index, float *peak_mag, uint64_t *fft_size);
