@@ -110,6 +110,11 @@ class ExcisorCfg(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+class ExcisorBlockCfg(C.Structure):
+    """gm_excisor_block_cfg (32 bytes): zeros are the defaults"""
+    _fields_ = [("threshold_factor", C.c_float), ("guard_bins", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
 ACQ_FORM_LDS, ACQ_FORM_COMPOSITE, ACQ_FORM_LONG, ACQ_FORM_LONG_PADDED = 0, 1, 2, 3   # gm_acq_form
 
 
@@ -271,6 +276,10 @@ SIGNATURES = {
     "gm_excisor_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
     "gm_excisor_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gm_excisor_synchronize": (_i, [_vp]),
+    "gm_excisor_block_plan": (_i, [C.POINTER(ExcisorBlockCfg), C.POINTER(C.c_float), C.POINTER(_u32)]),
+    "gm_excisor_set_block_adapt": (_i, [_vp, C.POINTER(ExcisorBlockCfg)]),
+    "gm_excisor_block_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_excisor_block_capture": (_i, [_vp, _vp, _vp, _sz]),
     "gm_frontend_write_ring_conditioned": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, C.POINTER(_u64)]),
     "gm_ddc_plan": (_i, [C.POINTER(DdcCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u64),
                          C.POINTER(_u64)]),

@@ -10,6 +10,9 @@
 //   stored once both terms exist.  G + 1 transform pairs for G segments.  A block's words depend on its B inputs and the gains alone,
 //   so neither G nor the cut of the stream into calls shows in the words.  LDS: one transform image + both twiddle sets (39 KB at
 //   B = 4096: two workgroups a CU and more); the image's layout and its padding are fft_core.h's.  Windows and gains come from L2.
+//   The block-adapt instantiation (ExciseArgs::block_adapt) decides a 0 / 1 mask per block between the two transforms, on the same
+//   registers: power words, a truncated rank selection across the workgroup (15 counting rounds), the flags as a bit image in
+//   LDS, the guard widening, integer counters; the mask multiplies the static gain.  The other instantiation is the kernel as it was.
 // excise_state_kernel: workgroup 0 writes the next history (the last 3H blanked inputs) into the OTHER history buffer; with blanking on,
 //   all workgroups count the blanked inputs of the call, each input once, with integer adds only.
 // excise_psd_kernel: the forward half alone; workgroup c accumulates |X|^2 of blocks c C .. c C + C - 1, C = max(4, ceil(J / 512)), (j ascending, from +0) in registers
@@ -57,12 +60,125 @@ __device__ __forceinline__ void ex_forward(cf (&X)[PL::ITL][PL::RL], In&& in, cf
     Fft<PL, false>::last_stage2(vl, [&](int it, int q, cf val) { X[it][q] = val; }, tid);
 }
 
-template <class PL, int FMT>
+// The sum of v over the wave's 64 lanes, in every lane: the row-shift / row-broadcast DPP ladder (partial sums of 4, 8 and 16 lanes within
+// a row of 16, then rows 0 + 1 and 2 + 3, then both halves), whose total lands in lane 63.  Lanes a step does not write add 0.
+// Integers: the order of the adds is not in the result.
+__device__ __forceinline__ uint32_t ex_wave_sum(uint32_t v) {
+    const int v0 = int(v);
+    int t = v0 + __builtin_amdgcn_update_dpp(0, v0, 0x111, 0xf, 0xf, false)      // row_shr:1
+               + __builtin_amdgcn_update_dpp(0, v0, 0x112, 0xf, 0xf, false)      // row_shr:2
+               + __builtin_amdgcn_update_dpp(0, v0, 0x113, 0xf, 0xf, false);     // row_shr:3
+    t += __builtin_amdgcn_update_dpp(0, t, 0x114, 0xf, 0xe, false);              // row_shr:4, banks 1 .. 3
+    t += __builtin_amdgcn_update_dpp(0, t, 0x118, 0xf, 0xc, false);              // row_shr:8, banks 2 and 3: lane 15 of a row holds the row
+    t += __builtin_amdgcn_update_dpp(0, t, 0x142, 0xa, 0xf, false);              // row_bcast:15 into rows 1 and 3
+    t += __builtin_amdgcn_update_dpp(0, t, 0x143, 0xc, 0xf, false);              // row_bcast:31 into rows 2 and 3: lane 63 holds the wave
+    return uint32_t(__builtin_amdgcn_readlane(t, 63));
+}
+
+// The block-adapt decision of one block, on the forward's last-pass registers (gnss_mi355x.h, "Block-adapt mode"; the rule's lane-local
+// parts are excise_core.h's).  -> zero[it], bit r set where bin (tid + it T) + r NBL is zeroed (m = 0).  Lanes with a butterfly b >= NBL hold no bins.
+//   1. p = re*re + im*im of the lane's bins, kept as words.
+//   2. 15 rounds over bits 30 .. 16: a lane counts its own words below the candidate, ex_wave_sum adds the lanes; where more than one
+//      wave holds bins (B >= 2048) the waves' counts go through one of two LDS rows in turn, so a round costs one barrier (as in
+//      excise_mask_kernel).  Measured on a 2^19-sample call (B = 1024 / 4096, the whole step, mode off 0.0144 / 0.0254 ms): a ballot
+//      and a scalar popcount per word and round 0.0351 / 0.0445 ms, of which the rounds were 0.0125 / 0.0120 ms; three bits a round
+//      with 7 such ballots per word 0.0509 / 0.0659 ms — the ballots, not the exchange, were the cost; the count in the lanes with
+//      one wave sum a round 0.0289 / 0.0424 ms, which is what is built.  LDS integer histograms were not measured.
+//   3. The flags go into LDS as a bit image (a ballot is 64 — or NBL — consecutive bins of one r), with a word per wave that says
+//      whether it flagged; one barrier; every lane widens its own bins by the guard from three words of the image.
+// The LDS rows are written again only behind the barriers of the inverse transform that follows.  any_flag is the block's (the same in
+// every lane); lane_nf and lane_nz are THIS LANE's flagged and zeroed bins: the kernel adds them up over its tile and sums the lanes once.
+template <class PL>
+struct ExBlockLds {
+    static constexpr int W = (PL::T + 63) / 64;
+    uint32_t bits[PL::N / 32];
+    uint32_t round[2][W];
+    uint32_t any[W];
+};
+
+template <class PL>
+__device__ __forceinline__ void ex_block_decide(uint32_t (&zero)[PL::ITL], const cf (&X)[PL::ITL][PL::RL], float factor, int guard,
+                                                float* cap_p, unsigned char* cap_m, bool& any_flag, uint32_t& lane_nf, uint32_t& lane_nz,
+                                                int tid) {
+    __shared__ ExBlockLds<PL> s;                                          // (only the block-adapt instantiations have it)
+    constexpr int B = PL::N, T = PL::T, NBL = PL::NB(PL::NP - 1), W = ExBlockLds<PL>::W;
+    constexpr int VW = (NBL + 63) / 64;                                   // the waves that hold bins
+    constexpr int NV = NBL < 64 ? NBL : 64;                               // valid lanes of a ballot: bins b0 + r NBL .. + NV - 1
+    static_assert(NV % 16 == 0 && (NBL % 64 == 0 || PL::ITL == 1), "a ballot is a run of 16-bit pieces of the bit image");
+    const int lane = tid & 63, wave = tid >> 6;
+    uint32_t w[PL::ITL][PL::RL];
+#pragma unroll
+    for (int it = 0; it < PL::ITL; ++it)
+#pragma unroll
+        for (int r = 0; r < PL::RL; ++r) {
+            const float p = ex_power(X[it][r]);
+            w[it][r] = ex_word(p);
+            if (cap_p && tid + it * T < NBL) cap_p[(tid + it * T) + r * NBL] = p;
+        }
+    const uint32_t rank = uint32_t(B - 1) / 2;
+    uint32_t med = 0;
+    for (int bit = EX_SEL_TOP_BIT; bit >= EX_SEL_LOW_BIT; --bit) {
+        const uint32_t cand = ex_sel_cand(med, bit);
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int it = 0; it < PL::ITL; ++it)
+#pragma unroll
+            for (int r = 0; r < PL::RL; ++r) cnt += tid + it * T < NBL && ex_sel_below(w[it][r], cand) ? 1u : 0u;
+        uint32_t total = ex_wave_sum(cnt);
+        if (VW > 1) {                                                     // (one wave holds every bin up to B = 1024)
+            uint32_t* row = s.round[bit & 1];
+            if (lane == 0) row[wave] = total;
+            __syncthreads();
+            total = 0;
+#pragma unroll
+            for (int v = 0; v < VW; ++v) total += row[v];
+        }
+        med = ex_sel_step(med, cand, total, rank);
+    }
+    const float medf = ex_float(med);
+    uint16_t* bits16 = reinterpret_cast<uint16_t*>(s.bits);               // little-endian: piece c of the image is bits 16 c .. 16 c + 15
+    lane_nf = 0;
+#pragma unroll
+    for (int it = 0; it < PL::ITL; ++it) {
+        const int b0 = (tid - lane) + it * T;                             // the wave's first butterfly
+#pragma unroll
+        for (int r = 0; r < PL::RL; ++r) {
+            const bool f = tid + it * T < NBL && ex_flag(ex_float(w[it][r]), factor, medf);
+            const unsigned long long bal = __ballot(f);
+            lane_nf += f ? 1u : 0u;
+            if (b0 < NBL && lane < NV / 16) bits16[(b0 + r * NBL) / 16 + lane] = uint16_t(bal >> (16 * lane));
+        }
+    }
+    const bool wave_any = __ballot(lane_nf != 0) != 0;
+    if (lane == 0) s.any[wave] = wave_any ? 1u : 0u;
+    __syncthreads();
+    uint32_t n_any = 0;
+#pragma unroll
+    for (int v = 0; v < W; ++v) n_any += s.any[v];
+    any_flag = n_any != 0;
+    lane_nz = 0;
+    static_assert(PL::RL <= 32, "a lane's zeroed bins fit one word");
+#pragma unroll
+    for (int it = 0; it < PL::ITL; ++it) {
+        zero[it] = 0;
+#pragma unroll
+        for (int r = 0; r < PL::RL; ++r) {
+            const int b = tid + it * T, k = b + r * NBL;
+            const bool z = b < NBL && any_flag && ex_zeroed(s.bits, k, guard, B);
+            lane_nz += z ? 1u : 0u;
+            zero[it] |= z ? 1u << r : 0u;
+            if (cap_m && b < NBL) cap_m[k] = z ? 0 : 1;
+        }
+    }
+}
+
+template <class PL, int FMT, bool ADAPT>
 __global__ __launch_bounds__(PL::T) void excise_kernel(ExciseArgs a) {
     using MAP = ExciseMap<PL>;                                             // excise_core.h: the index maps, checked on the CPU
     using RP = typename MAP::RP;
     constexpr int H = MAP::H, T = MAP::T, NBL = MAP::NBL, RNBL = MAP::RNBL, RRL = MAP::RRL, HQ = MAP::HQ, LE = MAP::LDS_ELEMS;
     __shared__ cf lds[LE + PL::TW_TOTAL + RP::TW_TOTAL];
+    uint32_t c_blocks = 0, c_bflag = 0, c_flag = 0, c_zero = 0;             // the tile's counts: blocks (the same in every lane), this lane's bins
     cf* twf = lds + LE;
     cf* twi = twf + PL::TW_TOTAL;
     const int tid = threadIdx.x;
@@ -88,11 +204,23 @@ __global__ __launch_bounds__(PL::T) void excise_kernel(ExciseArgs a) {
             const float w = a.wa[i];
             return cf_make(w * v.x, w * v.y);
         }, lds, twf, tid);
+        uint32_t zero[PL::ITL];
+        if constexpr (ADAPT) {
+            bool any_flag;
+            uint32_t lane_nf, lane_nz;
+            ex_block_decide<PL>(zero, X, a.bfactor, int(a.bguard), a.cap_p ? a.cap_p + size_t(j) * PL::N : nullptr,
+                                a.cap_m ? a.cap_m + size_t(j) * PL::N : nullptr, any_flag, lane_nf, lane_nz, tid);
+            if (j > s0) {                                                  // block j is counted with segment j - 1, which this tile delivers
+                c_flag += lane_nf; c_zero += lane_nz;
+                c_blocks += 1; c_bflag += any_flag ? 1 : 0;
+            }
+        }
         cf u[RP::ITL][RRL];
         {
             cf v0[RP::IT0][RP::R0];
             Fft<RP, true>::pass0_stage1(v0, [&](int it, int r) {
-                const float g = a.gains[(tid + it * T) + r * NBL];
+                float g = a.gains[(tid + it * T) + r * NBL];
+                if constexpr (ADAPT) g = g * ((zero[it] >> r) & 1u ? 0.0f : 1.0f);     // (g * m_b) first
                 return cf_make(g * X[it][r].x, g * X[it][r].y);
             }, tid);
             __syncthreads();                                               // every lane has read the forward's last image
@@ -123,6 +251,24 @@ __global__ __launch_bounds__(PL::T) void excise_kernel(ExciseArgs a) {
                     prev[it][q] = cf_make(w2 * u[it][q + HQ].x, w2 * u[it][q + HQ].y);
                 }
             }
+        }
+    }
+    if constexpr (ADAPT) {
+        // integer adds only: any order gives the same counts.  One set of adds per workgroup, into the counter row of its slot: every
+        // workgroup adding to ONE cache line cost several times the transforms (measured), the rows spread the adds over 64 lines
+        __shared__ uint32_t s_cnt[2][(T + 63) / 64];
+        const uint32_t wave_flag = ex_wave_sum(c_flag), wave_zero = ex_wave_sum(c_zero);
+        if ((tid & 63) == 0) { s_cnt[0][tid >> 6] = wave_flag; s_cnt[1][tid >> 6] = wave_zero; }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long n_flag = 0, n_zero = 0;
+#pragma unroll
+            for (int v = 0; v < (T + 63) / 64; ++v) { n_flag += s_cnt[0][v]; n_zero += s_cnt[1][v]; }
+            unsigned long long* row = a.bstat + size_t(blockIdx.x % EX_BSTAT_SLOTS) * EX_BSTAT_STRIDE;
+            if (c_blocks) atomicAdd(row + 0, (unsigned long long)c_blocks);
+            if (c_bflag) atomicAdd(row + 1, (unsigned long long)c_bflag);
+            if (n_flag) atomicAdd(row + 2, n_flag);
+            if (n_zero) atomicAdd(row + 3, n_zero);
         }
     }
 }
@@ -288,8 +434,11 @@ __global__ __launch_bounds__(EX_MASK_LANES) void excise_mask_kernel(ExciseMaskAr
 template <class PL>
 void launch_excise_plan(hipStream_t s, const ExciseArgs& a, int fmt) {
     const unsigned tiles = (a.n_seg + a.G - 1) / a.G;
-    if (fmt == GM_FMT_C32) excise_kernel<PL, GM_FMT_C32><<<tiles, PL::T, 0, s>>>(a);
-    else excise_kernel<PL, GM_FMT_I8_IQ><<<tiles, PL::T, 0, s>>>(a);
+    if (a.block_adapt) {
+        if (fmt == GM_FMT_C32) excise_kernel<PL, GM_FMT_C32, true><<<tiles, PL::T, 0, s>>>(a);
+        else excise_kernel<PL, GM_FMT_I8_IQ, true><<<tiles, PL::T, 0, s>>>(a);
+    } else if (fmt == GM_FMT_C32) excise_kernel<PL, GM_FMT_C32, false><<<tiles, PL::T, 0, s>>>(a);
+    else excise_kernel<PL, GM_FMT_I8_IQ, false><<<tiles, PL::T, 0, s>>>(a);
 }
 template <class PL>
 void launch_psd_plan(hipStream_t s, const ExcisePsdArgs& a, int fmt) {

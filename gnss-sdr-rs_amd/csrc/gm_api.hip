@@ -3870,6 +3870,20 @@ uint64_t excisor_total_out(const ExcisorPlan& p, uint64_t A) {
     return q > 1 ? (q - 1) * H : 0;
 }
 
+// gm_excisor_block_cfg's argument rules and defaults
+constexpr size_t EX_BSTAT_BYTES = size_t(gm::EX_BSTAT_SLOTS) * gm::EX_BSTAT_STRIDE * sizeof(unsigned long long);
+
+int excisor_block_rules(const gm_excisor_block_cfg* c, float& factor, uint32_t& guard) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    for (int i = 0; i < 6; ++i)
+        if (c->reserved[i]) return set_err(GM_ERR_INVALID_ARG, "gm_excisor_block_cfg.reserved must be 0");
+    if (c->guard_bins > 16) return set_err(GM_ERR_INVALID_ARG, "guard_bins: 0 .. 16");
+    if (!(c->threshold_factor == 0.0f || c->threshold_factor > 1.0f)) return set_err(GM_ERR_INVALID_ARG, "threshold_factor: > 1, 0 for the default");
+    factor = c->threshold_factor == 0.0f ? 16.0f : c->threshold_factor;
+    guard = c->guard_bins;
+    return GM_OK;
+}
+
 void excisor_windows(uint32_t B, float* wa, float* ws) {
     const double PI = 3.14159265358979323846;
     for (uint32_t i = 0; i < B; ++i) {
@@ -3891,6 +3905,9 @@ struct gm_excisor {
     cf* d_hist[2] = {nullptr, nullptr};     // the last 3H blanked inputs: d_hist[cur] is read by the next call, the other written
     int cur = 0;
     unsigned long long* d_blanked = nullptr;
+    bool block_adapt = false; float block_factor = 16.0f; uint32_t block_guard = 0;   // block-adapt mode: host state, handed to every launch
+    unsigned long long* d_bstat = nullptr;  // [EX_BSTAT_SLOTS] rows of {blocks, blocks flagged, bins flagged, bins zeroed}: the counters are the rows' sums
+    float* cap_p = nullptr; unsigned char* cap_m = nullptr; uint64_t cap_blocks = 0;  // the armed capture (the caller's device buffers)
     float *d_partial = nullptr, *d_P = nullptr;   // the periodogram's partial sums [EX_CHUNKS_MAX][B] and its words [B]
     uint32_t* d_stat = nullptr;             // {median word, flagged, zeroed} of the last adapt
     hipStream_t stream = nullptr, last_stream = nullptr;
@@ -3907,7 +3924,7 @@ static uint64_t excisor_count(const gm_excisor* x, uint64_t n_in) {
 }
 // one call's kernels on `st`, outputs to out[(out_start + k) & out_mask]; the caller has checked every argument; n_in > 0
 static int excisor_launch(gm_excisor* x, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t out_start,
-                          uint64_t out_mask, uint64_t n_out) {
+                          uint64_t out_mask, uint64_t n_out, bool capture = false) {
     const ExcisorPlan& p = x->plan;
     const uint64_t H = p.B / 2, A = x->base + x->inputs, s0 = excisor_total_out(p, A) / H;
     if (x->gains_pending && st != x->stream) HIPC(hipStreamWaitEvent(st, x->gains_ev, 0));     // gains set on the handle's stream
@@ -3921,6 +3938,8 @@ static int excisor_launch(gm_excisor* x, hipStream_t st, const void* d_in, int f
     a.out = out; a.out_start = out_start; a.out_mask = out_mask;
     a.thr2 = p.thr * p.thr; a.blank = p.thr > 0.0f ? 1 : 0;
     a.blanked = x->d_blanked;
+    a.block_adapt = x->block_adapt ? 1 : 0; a.bfactor = x->block_factor; a.bguard = x->block_guard; a.bstat = x->d_bstat;
+    if (capture && x->block_adapt) { a.cap_p = x->cap_p; a.cap_m = x->cap_m; }     // (the caller has checked cap_blocks)
     gm::launch_excise(st, a, fmt);
     HIPC(hipGetLastError());
     x->cur ^= 1; x->inputs += n_in; x->outputs += n_out; x->last_stream = st;
@@ -4004,6 +4023,8 @@ int gm_excisor_create(const gm_excisor_cfg* cfg, gm_excisor** out) {
     }
     if (e == hipSuccess) e = hipMalloc(&x->d_blanked, sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(x->d_blanked, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&x->d_bstat, EX_BSTAT_BYTES);
+    if (e == hipSuccess) e = hipMemset(x->d_bstat, 0, EX_BSTAT_BYTES);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the fills have run before a kernel on a non-blocking stream can touch the state (see gm_ring_create)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&x->gains_ev, hipEventDisableTiming);
@@ -4019,7 +4040,7 @@ int gm_excisor_destroy(gm_excisor* x) {
     if (x->stream) { hipStreamSynchronize(x->stream); hipStreamDestroy(x->stream); }
     if (x->gains_ev) hipEventDestroy(x->gains_ev);
     hipFree(x->d_wa); hipFree(x->d_ws); hipFree(x->d_gains); hipFree(x->d_P); hipFree(x->d_partial); hipFree(x->d_stat);
-    hipFree(x->d_tw_fwd); hipFree(x->d_tw_inv); hipFree(x->d_hist[0]); hipFree(x->d_hist[1]); hipFree(x->d_blanked);
+    hipFree(x->d_tw_fwd); hipFree(x->d_tw_inv); hipFree(x->d_hist[0]); hipFree(x->d_hist[1]); hipFree(x->d_blanked); hipFree(x->d_bstat);
     hipFree(x->d_in); hipFree(x->d_out); hipFree(x->d_scratch); hipFree(x->d_mid);
     if (x->h_gains) hipHostFree(x->h_gains);
     delete x;
@@ -4035,6 +4056,7 @@ int gm_excisor_reset(gm_excisor* x, uint64_t input_index) {
     HIPC(hipMemsetAsync(x->d_hist[0], 0, hist_bytes, x->stream));
     HIPC(hipMemsetAsync(x->d_hist[1], 0, hist_bytes, x->stream));
     HIPC(hipMemsetAsync(x->d_blanked, 0, sizeof(unsigned long long), x->stream));
+    HIPC(hipMemsetAsync(x->d_bstat, 0, EX_BSTAT_BYTES, x->stream));
     HIPC(hipStreamSynchronize(x->stream));
     x->cur = 0; x->base = input_index; x->inputs = 0; x->outputs = 0;
     return GM_OK;
@@ -4125,10 +4147,62 @@ int gm_excisor_process_dev(gm_excisor* x, const void* d_in, int fmt, size_t n_in
         const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + cnt * 8;
         if (i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
     }
+    const bool capture = x->block_adapt && (x->cap_p || x->cap_m) && cnt >= x->plan.B / 2;
+    if (capture && x->cap_blocks < cnt / (x->plan.B / 2) + 1)
+        return set_err(GM_ERR_OUT_OF_RANGE, "the armed capture holds fewer blocks than the call's segments + 1");
     if (n_out) *n_out = size_t(cnt);
     if (!n_in) return GM_OK;
     if (int rc = ensure_device(x->device)) return rc;
-    return excisor_launch(x, stream ? static_cast<hipStream_t>(stream) : x->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), 0, ~0ull, cnt);
+    return excisor_launch(x, stream ? static_cast<hipStream_t>(stream) : x->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), 0, ~0ull, cnt,
+                          capture);
+}
+
+int gm_excisor_block_plan(const gm_excisor_block_cfg* cfg, float* threshold_factor, uint32_t* guard_bins) {
+    float factor = 0.0f;
+    uint32_t guard = 0;
+    if (int rc = excisor_block_rules(cfg, factor, guard)) return rc;
+    if (threshold_factor) *threshold_factor = factor;
+    if (guard_bins) *guard_bins = guard;
+    return GM_OK;
+}
+
+int gm_excisor_set_block_adapt(gm_excisor* x, const gm_excisor_block_cfg* cfg) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!cfg) {                                      // off: the armed capture goes with the mode
+        x->block_adapt = false; x->cap_p = nullptr; x->cap_m = nullptr; x->cap_blocks = 0;
+        return GM_OK;
+    }
+    float factor = 0.0f;
+    uint32_t guard = 0;
+    if (int rc = excisor_block_rules(cfg, factor, guard)) return rc;
+    x->block_adapt = true; x->block_factor = factor; x->block_guard = guard;
+    return GM_OK;
+}
+
+int gm_excisor_block_stats(gm_excisor* x, uint64_t* blocks, uint64_t* blocks_flagged, uint64_t* bins_flagged, uint64_t* bins_zeroed) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(x->device)) return rc;
+    if (int rc = excisor_sync(x)) return rc;
+    unsigned long long rows[gm::EX_BSTAT_SLOTS * gm::EX_BSTAT_STRIDE], c[4] = {0, 0, 0, 0};
+    HIPC(hipMemcpy(rows, x->d_bstat, EX_BSTAT_BYTES, hipMemcpyDeviceToHost));
+    for (int r = 0; r < gm::EX_BSTAT_SLOTS; ++r)
+        for (int k = 0; k < 4; ++k) c[k] += rows[r * gm::EX_BSTAT_STRIDE + k];
+    if (blocks) *blocks = c[0];
+    if (blocks_flagged) *blocks_flagged = c[1];
+    if (bins_flagged) *bins_flagged = c[2];
+    if (bins_zeroed) *bins_zeroed = c[3];
+    return GM_OK;
+}
+
+int gm_excisor_block_capture(gm_excisor* x, float* d_power, uint8_t* d_mask, size_t cap_blocks) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!d_power && !d_mask) {
+        x->cap_p = nullptr; x->cap_m = nullptr; x->cap_blocks = 0;
+        return GM_OK;
+    }
+    if (!x->block_adapt) return set_err(GM_ERR_INVALID_ARG, "a capture needs the block-adapt mode on");
+    x->cap_p = d_power; x->cap_m = d_mask; x->cap_blocks = cap_blocks;
+    return GM_OK;
 }
 
 int gm_excisor_process(gm_excisor* x, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out) {

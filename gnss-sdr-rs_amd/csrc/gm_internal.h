@@ -422,6 +422,7 @@ void launch_ddc(hipStream_t, const DdcArgs&);
 // call's first block starts relative to the call's first input (rel0 <= 0, >= -3H + 1: the history covers it).
 constexpr int EX_BLOCK_MAX = 4096;         // the largest block length B
 constexpr int EX_TW_MAX = 512;             // words of one base-twiddle set (272 at B = 4096)
+constexpr int EX_BSTAT_SLOTS = 64, EX_BSTAT_STRIDE = 16;   // block-adapt counter rows of 128 bytes: a cache line each
 constexpr uint32_t EX_CHUNKS_MAX = 512;    // most partial sums of the periodogram: chunk length C = max(4, ceil(J / 512)) blocks
 struct ExciseArgs {
     const void* in; uint64_t n_in;         // this call's inputs (c32 or int8 IQ)
@@ -434,6 +435,11 @@ struct ExciseArgs {
     cf* out; uint64_t out_start, out_mask; // linear buffer (out_mask = ~0) or ring base
     float thr2; int blank;                 // blank_threshold^2 (f32 product); blanking on
     unsigned long long* blanked;           // device counter, integer atomics only
+    // block-adapt mode (launch_excise picks the block-adapt instantiation of excise_kernel when block_adapt is set)
+    int block_adapt; float bfactor; uint32_t bguard;
+    unsigned long long* bstat;             // [EX_BSTAT_SLOTS][EX_BSTAT_STRIDE], {blocks, blocks flagged, bins flagged, bins zeroed} first in a
+                                           // row: device counters, integer atomics only; workgroup w adds to row w mod EX_BSTAT_SLOTS, the host sums the rows
+    float* cap_p; unsigned char* cap_m;    // the capture: [n_seg + 1][B] power words / mask bytes of the call's blocks; either may be null
 };
 struct ExcisePsdArgs {
     const void* in;                        // the samples given, from their index 0

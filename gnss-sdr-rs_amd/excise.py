@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FMT_C32, FMT_I8_IQ, ExcisorCfg, check, lib
+from ._lib import FMT_C32, FMT_I8_IQ, ExcisorBlockCfg, ExcisorCfg, check, lib
 
 _KEYS = ("guard_bins", "threshold_factor", "blank_threshold")
 
@@ -45,6 +45,18 @@ def plan(block=0, inputs_so_far=0, n_in=0, **cfg):
     return dict(block=b.value, guard_bins=g.value, threshold_factor=f.value, n_out=n.value)
 
 
+def _block_cfg(threshold_factor=0.0, guard_bins=0):
+    return ExcisorBlockCfg(float(threshold_factor), int(guard_bins), (C.c_uint32 * 6)(0, 0, 0, 0, 0, 0))
+
+
+def block_plan(threshold_factor=0.0, guard_bins=0):
+    """gm_excisor_block_plan (host only, no device): the block-adapt mode's argument rules and resolved defaults"""
+    c = _block_cfg(threshold_factor, guard_bins)
+    f, g = C.c_float(0), C.c_uint32(0)
+    check(lib().gm_excisor_block_plan(C.byref(c), C.byref(f), C.byref(g)), "gm_excisor_block_plan")
+    return dict(threshold_factor=f.value, guard_bins=g.value)
+
+
 def windows(block=0, **cfg):
     """gm_excisor_windows (host only, no device): the float32 analysis and synthesis windows, [block] each."""
     c = _cfg(block, **cfg)
@@ -72,7 +84,7 @@ class Excisor:
         self._settings = dict(cfg)
         p = plan(block, **cfg)
         self.block, self.guard_bins, self.threshold_factor = p["block"], p["guard_bins"], p["threshold_factor"]
-        self._d_adapt, self._adapt_cap = None, 0
+        self._d_adapt, self._adapt_cap, self._base = None, 0, 0
         h = C.c_void_p()
         check(lib().gm_excisor_create(C.byref(self._cfg), C.byref(h)), "gm_excisor_create")
         self._h = h
@@ -91,9 +103,67 @@ class Excisor:
         except Exception:
             pass
 
-    def process(self, samples):
-        """samples: complex64 array, or int8 array of interleaved I/Q -> complex64 array of this call's outputs (synchronous)."""
+    def set_block_adapt(self, threshold_factor=0.0, guard_bins=0):
+        """the block-adapt mode on (a mask per block, decided on the device between the two transforms; 0 -> factor 16) or, with
+        set_block_adapt(None), off; returns self"""
+        if threshold_factor is None:
+            check(lib().gm_excisor_set_block_adapt(self._h, None), "gm_excisor_set_block_adapt")
+        else:
+            c = _block_cfg(threshold_factor, guard_bins)
+            check(lib().gm_excisor_set_block_adapt(self._h, C.byref(c)), "gm_excisor_set_block_adapt")
+        return self
+
+    def block_stats(self):
+        """the block-adapt counters since the creation or the last reset (synchronises)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        check(lib().gm_excisor_block_stats(self._h, *[C.byref(c) for c in v]), "gm_excisor_block_stats")
+        return dict(zip(("blocks", "blocks_flagged", "bins_flagged", "bins_zeroed"), (c.value for c in v)))
+
+    def block_capture(self, d_power=None, d_mask=None, cap_blocks=0):
+        """arms a capture of the power words (f32 [cap_blocks][block]) and masks (u8 [cap_blocks][block]) of every later process_dev
+        into device buffers; both None disarms it"""
+        check(lib().gm_excisor_block_capture(self._h, d_power, d_mask, int(cap_blocks)), "gm_excisor_block_capture")
+
+    def _process_blocks(self, s, n, fmt):
+        """process(want_blocks=True): process_dev with a capture armed on plain device buffers of this call's own"""
+        hip = _hip()
+        H = self.block // 2
+        n_blocks = plan(self.block, self.stats()["inputs"] + self._base, n, **self._settings)["n_out"] // H + 1
+        sizes = (max(s.nbytes, 1), (n + self.block) * 8, n_blocks * self.block * 4, n_blocks * self.block)
+        bufs = []
+        try:
+            for size in sizes:
+                p = C.c_void_p()
+                if hip.hipMalloc(C.byref(p), size) != 0:
+                    raise MemoryError("hipMalloc")
+                bufs.append(p)
+            d_in, d_out, d_p, d_m = bufs
+            if hip.hipMemcpy(d_in, _p(s), s.nbytes, 1) != 0:
+                raise RuntimeError("hipMemcpy")
+            self.block_capture(d_p, d_m, n_blocks)
+            try:
+                got = self.process_dev(d_in, fmt, n, d_out, n + self.block)
+                self.synchronize()
+            finally:
+                self.block_capture(None, None, 0)
+            out = np.zeros(got, np.complex64)
+            rows = got // H + 1 if got else 0
+            power, mask = np.zeros((rows, self.block), np.float32), np.zeros((rows, self.block), np.uint8)
+            for host, dev in ((out, d_out), (power, d_p), (mask, d_m)):
+                if host.nbytes and hip.hipMemcpy(_p(host), dev, host.nbytes, 2) != 0:
+                    raise RuntimeError("hipMemcpy")
+            return out, power, mask
+        finally:
+            for p in bufs:
+                hip.hipFree(p)
+
+    def process(self, samples, want_blocks=False):
+        """samples: complex64 array, or int8 array of interleaved I/Q -> complex64 array of this call's outputs (synchronous).
+        want_blocks (block-adapt mode on): -> (outputs, power float32 [n_seg + 1][block], mask uint8 [n_seg + 1][block]) of the call's
+        blocks, empty when the call delivers no segment."""
         s, n, fmt = _samples(samples)
+        if want_blocks:
+            return self._process_blocks(s, n, fmt)
         out = np.zeros(n + self.block, np.complex64)                    # a call never delivers more than n + H
         got = C.c_size_t(0)
         check(lib().gm_excisor_process(self._h, _p(s), fmt, n, _p(out), out.size, C.byref(got)), "gm_excisor_process")
@@ -146,6 +216,7 @@ class Excisor:
 
     def reset(self, input_index=0):
         check(lib().gm_excisor_reset(self._h, int(input_index)), "gm_excisor_reset")
+        self._base = int(input_index)
 
     def stats(self):
         """inputs taken, outputs delivered, inputs blanked since the creation or the last reset (synchronises)"""

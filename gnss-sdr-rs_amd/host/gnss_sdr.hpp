@@ -347,6 +347,21 @@ public:
         check(gm_excisor_psd(h_, P.data(), median, n_flagged, n_zeroed), "Excisor::psd");
         return P;
     }
+    // block-adapt mode: a mask per block, decided on the device between the two transforms (threshold_factor 0: 16); off at creation
+    void set_block_adapt(float threshold_factor = 0.0f, uint32_t guard_bins = 0) {
+        gm_excisor_block_cfg cfg{};
+        cfg.threshold_factor = threshold_factor; cfg.guard_bins = guard_bins;
+        check(gm_excisor_set_block_adapt(h_, &cfg), "Excisor::set_block_adapt");
+    }
+    void clear_block_adapt() { check(gm_excisor_set_block_adapt(h_, nullptr), "Excisor::clear_block_adapt"); }
+    // its counters since the creation or the last reset (any pointer may be null); synchronises
+    void block_stats(uint64_t* blocks, uint64_t* blocks_flagged, uint64_t* bins_flagged, uint64_t* bins_zeroed) const {
+        check(gm_excisor_block_stats(h_, blocks, blocks_flagged, bins_flagged, bins_zeroed), "Excisor::block_stats");
+    }
+    // arms a capture of the power words [cap_blocks][block] and masks [cap_blocks][block] of every later process_dev (both null: disarms)
+    void block_capture(float* d_power, uint8_t* d_mask, size_t cap_blocks) {
+        check(gm_excisor_block_capture(h_, d_power, d_mask, cap_blocks), "Excisor::block_capture");
+    }
     void reset(uint64_t input_index = 0) { check(gm_excisor_reset(h_, input_index), "Excisor::reset"); }
     void stats(uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) const { check(gm_excisor_stats(h_, inputs, outputs, blanked), "Excisor::stats"); }
     void synchronize() { check(gm_excisor_synchronize(h_), "Excisor::synchronize"); }

@@ -817,6 +817,28 @@ int gm_frontend_write_ring_resampled(gm_frontend *f, gm_resampler *r, gm_ring *r
  *     transforms of fft_core.h, the inverse on the plan with the forward plan's radices reversed so that the spectrum and the gain
  *     multiply stay in registers, and keeps a block's weighted second half on chip until the next block's first half exists.  G is
  *     not in the words.
+ *   Block-adapt mode (gm_excisor_set_block_adapt): handle state, off at creation.  The static gains remove a carrier that stays in
+ *     place; a sweeper, a hopper or a drifting harmonic needs a decision per block.  When the mode is on, for every block b (the blocks
+ *     above, by absolute index), on chip between the two transforms, with no second pass over the samples and no host wait:
+ *     1. Spectrum.  X_b as above (blanked, windowed, forward FFT, unnormalised); p[k] = re*re + im*im, f32, each product and the sum
+ *        rounded on its own, as the periodogram forms it.
+ *     2. Median.  med_b = the element of rank (B - 1) div 2 of p in ascending order, with the low 16 bits of its f32 word cleared.
+ *        Non-negative floats order as their bit patterns, so med_b is the largest word v with 16 zero low bits and
+ *        count(p < v) <= rank.  The truncation is part of the definition (it lowers the level by at most 2^-7 relative) and lets the
+ *        selection run in 15 bit rounds where the full search takes 32.
+ *     3. Flags and gain.  flag[k] = p[k] > factor * med_b (one f32 product, strictly greater); m_b[k] = 0 where any flag lies within
+ *        guard_bins of k, circularly, 1 elsewhere; Y_b[k] = (g[k] * m_b[k]) * X_b[k]: the static gains stay in force and are
+ *        multiplied in first, so a caller can keep a fixed notch.  With m_b all ones the words are those of the mode off.
+ *     4. Output.  The inverse transform and the overlap-add exactly as above.
+ *     5. m_b depends on the block's B inputs alone: as before, no word depends on how the stream is cut into calls, tiles or
+ *        workgroups, and a block that two tiles or two calls both compute gets the same mask both times.
+ *     6. Counters, integers in device memory, integer adds only: blocks, blocks_flagged (blocks with at least one flag), bins_flagged,
+ *        bins_zeroed.  Block b is counted exactly once, when segment b - 1 is delivered; block 0 is never counted.  gm_excisor_reset
+ *        zeroes them.
+ *     7. With the mode off every word, counter and launch of the handle is as if the mode did not exist.
+ *     A noise-only bin of one block is exponentially distributed: P(p > f * median) = 2^-f, so the default factor is 16 (1.6 % of
+ *     noise-only blocks of B = 1024 carry a flag), not the periodogram's 4.  No cap on the share of zeroed bins and no smoothing
+ *     between blocks: the library reports, the caller decides.
  * Zeros in the config mean defaults.  (ABI 9, additive: a caller detects the feature by the symbol) */
 typedef struct {
     uint32_t block;            /* B: 256, 512, 1024, 2048 or 4096; 0 -> 1024 */
@@ -865,11 +887,34 @@ int gm_excisor_synchronize(gm_excisor *x);
 /* inputs taken, outputs delivered and inputs blanked since gm_excisor_create or the last gm_excisor_reset (any pointer may be NULL).
  * Each input is counted once.  Synchronises the handle's stream and the stream the last call ran on. */
 int gm_excisor_stats(gm_excisor *x, uint64_t *inputs, uint64_t *outputs, uint64_t *blanked);
+/* Block-adapt mode (the definition above).  Zeros mean defaults. */
+typedef struct {
+    float    threshold_factor; /* > 1; 0 -> 16.0: a bin of a block is flagged when p[k] > factor * med_b */
+    uint32_t guard_bins;       /* 0 .. 16: bins zeroed on either side of a flagged one */
+    uint32_t reserved[6];      /* must be 0 */
+} gm_excisor_block_cfg;
+/* host only, no device: the argument rules (GM_ERR_INVALID_ARG: a null cfg, a threshold_factor not 0 and <= 1 or not a number,
+ * guard_bins above 16, reserved != 0) and the resolved defaults.  Either output pointer may be NULL. */
+int gm_excisor_block_plan(const gm_excisor_block_cfg *cfg, float *threshold_factor, uint32_t *guard_bins);
+/* switches the mode on with cfg's settings (again: new settings), or off with cfg == NULL (which also disarms a capture).  Ordered
+ * like gm_excisor_set_gains: calls enqueued before it run as they were enqueued, calls after it in the new mode.  A bad cfg is
+ * GM_ERR_INVALID_ARG and changes nothing.  The counters are kept. */
+int gm_excisor_set_block_adapt(gm_excisor *x, const gm_excisor_block_cfg *cfg);
+/* the four counters since gm_excisor_create or the last gm_excisor_reset.  Synchronises.  Any pointer may be NULL. */
+int gm_excisor_block_stats(gm_excisor *x, uint64_t *blocks, uint64_t *blocks_flagged, uint64_t *bins_flagged, uint64_t *bins_zeroed);
+/* arms a capture into the caller's device buffers (both NULL: disarms it): every later gm_excisor_process_dev that delivers
+ * n_seg >= 1 segments writes, for its blocks j = 0 .. n_seg in call order (block j of the call is the first block of segment j),
+ * p as f32 d_power[j][B] and m as one byte a bin d_mask[j][B] (1: kept, 0: zeroed); either pointer alone may be NULL.  A call with
+ * cap_blocks < n_seg + 1 is GM_ERR_OUT_OF_RANGE before anything runs.  Blocks that two tiles compute write the same words.  The
+ * buffers must stay valid until the capture is disarmed and the handle synchronised.  The other entries (gm_excisor_process, the ring
+ * paths) do not capture.  It needs the mode on: GM_ERR_INVALID_ARG otherwise.  What a test, or a caller's spectrum monitor, reads. */
+int gm_excisor_block_capture(gm_excisor *x, float *d_power, uint8_t *d_mask, size_t cap_blocks);
 /* gm_frontend_write_ring_resampled's block loop with the excisor between the front-end kernel and the resampler.  r may be NULL: the
  * excisor's outputs then go into the ring at the writer's position, wrapping, and ring indices count its outputs: ring index n is
  * input time n.  With r, ring indices count the resampler's outputs as in gm_frontend_write_ring_resampled.  The same publishing and
  * the same GM_ERR_OUT_OF_RANGE rule (the outputs of the call exceed the ring).  It does no adapt of its own.  *n_out_total (may be
- * NULL) = the outputs this call enqueued. */
+ * NULL) = the outputs this call enqueued.  It calls the excisor through the handle: with the block-adapt mode on
+ * (gm_excisor_set_block_adapt) every block gets its own mask and the counters run, with no other entry. */
 int gm_frontend_write_ring_conditioned(gm_frontend *f, gm_excisor *x, gm_resampler *r, gm_ring *ring, const void *samples,
                                        size_t n_samples, int fmt, uint64_t *n_out_total);
 
@@ -947,7 +992,8 @@ int gm_ddc_process(gm_ddc *d, const int8_t *in, size_t n_in, gm_c32 *out, size_t
  * ring at the writer's position, wrapping with the ring's mask, and ring indices count ITS outputs.  A block is the ring's staging
  * slot, as in the sibling entries (where up > down it is at most floor((2^19 - 1) * down / up) samples, so that a block's outputs fit
  * the linear buffers between the stages).  The same publishing and the same GM_ERR_OUT_OF_RANGE rule (the outputs of the call exceed
- * the ring: nothing is enqueued, no state moves).  *n_out_total (may be NULL) = the outputs this call enqueued. */
+ * the ring: nothing is enqueued, no state moves).  *n_out_total (may be NULL) = the outputs this call enqueued.  The excisor is called
+ * through its handle: its block-adapt mode (gm_excisor_set_block_adapt), when on, applies here too. */
 int gm_ddc_write_ring(gm_ddc *d, gm_excisor *x, gm_resampler *r, gm_ring *ring, const int8_t *samples, size_t n_samples,
                       uint64_t *n_out_total);
 

@@ -133,6 +133,12 @@ pub struct GmExcisorCfg {           // gm_excisor_cfg (32 bytes; zeros: the defa
     pub reserved: [u32; 4],          // must be 0
 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmExcisorBlockCfg {      // gm_excisor_block_cfg (32 bytes; zeros: the defaults)
+    pub threshold_factor: f32,       // > 1; 0: 16.0 — a bin of a block is flagged when p[k] > factor * med_b
+    pub guard_bins: u32,             // 0 .. 16: bins zeroed on either side of a flagged one
+    pub reserved: [u32; 6],          // must be 0
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct GmDdcCfg {               // gm_ddc_cfg (40 bytes; zeros in the filter fields: the defaults)
     pub mix_cycles_per_sample: f64,  // f_mix / fs_in: the frequency brought to 0, cycles per input sample; any finite value
     pub up: u32, pub down: u32,      // as GmResamplerCfg, field by field
@@ -249,6 +255,12 @@ extern "C" {
     pub fn gm_excisor_process(x: *mut GmExcisor, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32,
                               out_cap: usize, n_out: *mut usize) -> c_int;
     pub fn gm_excisor_synchronize(x: *mut GmExcisor) -> c_int;
+    /// block-adapt mode: host-only argument rules and defaults; on (cfg) / off (null); the counters; the capture of process_dev
+    pub fn gm_excisor_block_plan(cfg: *const GmExcisorBlockCfg, threshold_factor: *mut f32, guard_bins: *mut u32) -> c_int;
+    pub fn gm_excisor_set_block_adapt(x: *mut GmExcisor, cfg: *const GmExcisorBlockCfg) -> c_int;
+    pub fn gm_excisor_block_stats(x: *mut GmExcisor, blocks: *mut u64, blocks_flagged: *mut u64, bins_flagged: *mut u64,
+                                  bins_zeroed: *mut u64) -> c_int;
+    pub fn gm_excisor_block_capture(x: *mut GmExcisor, d_power: *mut f32, d_mask: *mut u8, cap_blocks: usize) -> c_int;
     /// gm_frontend_write_ring_resampled with the excisor between the front-end and the resampler; `r` may be null
     pub fn gm_frontend_write_ring_conditioned(f: *mut GmFrontend, x: *mut GmExcisor, r: *mut GmResampler, ring: *mut GmRing,
                                               samples: *const c_void, n_samples: usize, fmt: c_int, n_out_total: *mut u64) -> c_int;
