@@ -43,6 +43,10 @@ template <> struct MixPlanOf<Plan<16368, 768, 33, 16, 31>> { using type = GM_MIX
 #endif
 template <> struct MixPlanOf<Plan<16000, 1024, 25, 20, 32>> { using type = GM_MIX_PLAN_16000; };
 #endif
+// Code-spectrum pairs (16 bytes: two pass-0 rows, PairLayout) a lane of acq_corr_kernel loads ONCE and keeps in registers across its
+// item's integrations, instead of asking the texture path for them again in every transform.  The rest is re-read per transform as
+// before.  0 for every plan but the one below (plans whose whole code side fits have PL::KEEP_CODE).
+template <class CP> struct KeepCodePairs { static constexpr int value = 0; };
 template <> struct CorrPlanOf<Plan8192> { using type = Plan<8192, 512, 16, 32, 16>; };     // (fft_plans.h: why the two differ)
 #ifndef GM_NO_HYBRID_PLANS
 using CorrPlan8000 = HybridPlan<8000, 512, 5, 25, 4, 16>;     // 125 * 64: passes of radix 20 / 25 / 16
@@ -50,6 +54,14 @@ template <> struct CorrPlanOf<Plan8000> { using type = CorrPlan8000; };
 // constant twiddles folded into the butterflies of all three passes (fft_core.h FuseTw): 13 % fewer vector instructions per transform,
 // 158.1 -> 151.6 us per headline launch (DESIGN_HISTORY §R7.1, profiles/fused_tw_ab.json)
 template <> struct FuseTw<CorrPlan8000> { static constexpr bool value = true; };
+// all ten code pairs stay in registers: a workgroup re-read its code's 64 KB for each of its integrations, through a texture path
+// whose throughput is what pass 0 waits for.  123 VGPRs of the 128 two workgroups per CU leave, no scratch: the 40 registers sit
+// where only pass 0 was at its peak.  Headline launch, tools/corr_lab minima on one box: 166.7 us as it was, 164.4 / 162.8 / 160.6 /
+// 159.9 with 2 / 4 / 7 / 10 pairs kept (DESIGN_HISTORY R8.1, where the LDS-table form of the same idea is measured and closed)
+#ifndef GM_CORR_KEEP_PAIRS_8000
+#define GM_CORR_KEEP_PAIRS_8000 10
+#endif
+template <> struct KeepCodePairs<CorrPlan8000> { static constexpr int value = GM_CORR_KEEP_PAIRS_8000; };
 using CorrPlan16000 = HybridPlan<16000, 1024, 5, 25, 4, 32>;  // 125 * 128: radix 20 / 25 / 32 (the Galileo-E1 geometry's composite base)
 template <> struct CorrPlanOf<Plan16000> { using type = CorrPlan16000; };
 // its pass-0 rows in the order the radix-20 Good-Thomas butterfly consumes them, (5 n1 + 4 N2) mod 20, n1 = 0 .. 3 inside N2 = 0 .. 4

@@ -340,6 +340,14 @@ __global__ __launch_bounds__(CorrPlanOf<PLX>::type::T, CorrPlanOf<PLX>::type::WA
             }
         }
     }
+    // ... or PART of it (KeepCodePairs, acq_corr_plans.h): the first NKEEP stored pairs are loaded here, once per workgroup, and
+    // only the remaining pairs are requested again in every transform
+    constexpr int NKEEP = (!KEEP_CODE && CODE_PAIRED) ? (KeepCodePairs<PL>::value < PLd::NPAIR ? KeepCodePairs<PL>::value : PLd::NPAIR) : 0;
+    PLd ck[NKEEP > 0 ? PL::IT0 : 1];
+    if constexpr (NKEEP > 0) {
+#pragma unroll
+        for (int it = 0; it < PL::IT0; ++it) ck[it].template load_range<0, NKEEP, false>(crs, tid + it * PL::T, 0);
+    }
     float acc[PL::ITL][PL::RL];
 #pragma unroll
     for (int it = 0; it < PL::ITL; ++it)
@@ -360,7 +368,9 @@ __global__ __launch_bounds__(CorrPlanOf<PLX>::type::T, CorrPlanOf<PLX>::type::WA
 #ifndef GM_CORR_PREFETCH_PAIRS
 #define GM_CORR_PREFETCH_PAIRS 4
 #endif
-    constexpr int NPF = (HYB && CODE_PAIRED && !STAMPS && !KEEP_CODE) ? (GM_CORR_PREFETCH_PAIRS < PLd::NPAIR ? GM_CORR_PREFETCH_PAIRS : PLd::NPAIR) : 0;
+    // (not with the whole code side kept, NKEEP = NPAIR: the registers the pairs ahead occupy through the last pass then cost more than
+    // their early arrival brings — 163.4 against 161.5 us per headline launch, DESIGN_HISTORY R8.1)
+    constexpr int NPF = (HYB && CODE_PAIRED && !STAMPS && !KEEP_CODE && NKEEP < PLd::NPAIR) ? (GM_CORR_PREFETCH_PAIRS < PLd::NPAIR ? GM_CORR_PREFETCH_PAIRS : PLd::NPAIR) : 0;
     PLd xq[PL::IT0];
     auto load_x_ahead = [&](int m_) {
 #pragma unroll
@@ -376,13 +386,16 @@ __global__ __launch_bounds__(CorrPlanOf<PLX>::type::T, CorrPlanOf<PLX>::type::WA
             // pass-0 butterfly get an offset beyond the descriptor's range, which the buffer unit drops without a memory request
             const int b = tid + it * PL::T;
             if constexpr (CODE_PAIRED) xq[it].template load_range<NPF, PLd::NPAIR, true>(xrs, b, m * PL::N);
-            if constexpr (!KEEP_CODE && CODE_PAIRED) cq[it].load(crs, b, 0);
+            if constexpr (!KEEP_CODE && CODE_PAIRED) cq[it].template load_range<NKEEP, PLd::NPAIR, true>(crs, b, 0);
         }
         auto in = [&](int it, int r) {
             const cf a = CODE_PAIRED ? xq[it].get(r) : buf_load_cf(xrs, (tid + it * PL::T) * 8, (m * PL::N + r * NB0) * 8);
             cf c;
             if constexpr (KEEP_CODE) c = cc[it][r];
-            else if constexpr (CODE_PAIRED) { const cf g = cq[it].get(r); c = cf_make(g.x, -g.y); }
+            else if constexpr (CODE_PAIRED) {      // (stored row of r below 2 NKEEP: one of the kept pairs; static after unrolling)
+                const cf g = PairRows<PL>::row(r) < 2 * NKEEP ? ck[it].get(r) : cq[it].get(r);
+                c = cf_make(g.x, -g.y);
+            }
             else { const cf g = buf_load_cf(crs, (tid + it * PL::T) * 8, r * NB0 * 8); c = cf_make(g.x, -g.y); }
             // result_buf[i] *= conj(code[i])  (:184-186).  num-complex multiplies without FMA; here two of the four products are
             // fused (one rounding less each).  The value feeds the inverse FFT, whose own rounding differs from rustfft's by more
