@@ -187,7 +187,7 @@ struct gm_ring {
     // of block k + 1 travels while the kernel of block k runs
     hipStream_t fe_stream = nullptr;
     hipEvent_t h2d_done[SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t last_enq_stream = nullptr;       // the stream ev_enq was last recorded on (see ring_enqueue_publish)
+    hipStream_t last_enq_stream = nullptr;       // the stream ev_enq was last recorded on (see ring_end_block)
     uint64_t write_pos = 0;       // writer-private: samples enqueued so far (>= head)
     uint64_t slot_seq = 0;
     struct Pending { int slot; uint64_t new_head; };
@@ -268,8 +268,34 @@ static int ring_async_init(gm_ring* r) {
     r->write_pos = r->head.load(std::memory_order_relaxed);
     return GM_OK;
 }
-// after the work of one chunk (staging slot `slot`, its event recorded) has been enqueued on `st` (copy_stream or fe_stream)
-static int ring_enqueue_publish(gm_ring* r, int slot, hipStream_t st) {
+// The stream the ring writers' kernels run on, and the events that order it behind the copies (see struct gm_ring).  At the device's
+// HIGHEST priority: see ring_async_init.
+static int ring_fe_init(gm_ring* r) {
+    if (r->fe_stream) return GM_OK;
+    if (gm::diag_int("GM_RING_FE_STREAM", 1) == 0) r->fe_stream = r->copy_stream;      // diagnostic: kernels on the copy stream (round 4's form)
+    else {
+        int least = 0, greatest = 0;
+        HIPC(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        const int pr = gm::diag_int("GM_RING_FE_PRIORITY", 99);
+        HIPC(hipStreamCreateWithPriority(&r->fe_stream, hipStreamNonBlocking, pr == 99 ? greatest : pr));
+    }
+    for (int i = 0; i < gm_ring::SLOTS; ++i) HIPC(hipEventCreateWithFlags(&r->h2d_done[i], hipEventDisableTiming));
+    return GM_OK;
+}
+// The next staging slot, about to be re-used: its previous chunk must have run — and is retired first (its entry names the slot's event)
+static int ring_begin_block(gm_ring* r, int* slot) {
+    *slot = int(r->slot_seq++ % gm_ring::SLOTS);
+    if (!r->slot_used[*slot]) return GM_OK;
+    HIPC(wait_event_polling(r->slot_done[*slot]));
+    ring_refresh_head(r);
+    return GM_OK;
+}
+// The work of one chunk (staging slot `slot`, `cnt` samples at write_pos) has been enqueued on `st` (copy_stream or fe_stream): its event,
+// the writer's position, and the entry that publishes the head once the event has completed
+static int ring_end_block(gm_ring* r, int slot, hipStream_t st, uint64_t cnt) {
+    HIPC(hipEventRecord(r->slot_done[slot], st));
+    r->slot_used[slot] = true;
+    r->write_pos += cnt;
     {
         std::lock_guard<std::mutex> g(r->pend_mu);
         r->pending.push_back(gm_ring::Pending{slot, r->write_pos});
@@ -286,11 +312,29 @@ static int ring_enqueue_publish(gm_ring* r, int slot, hipStream_t st) {
     }
     return GM_OK;
 }
-// a staging slot is about to be re-used: its previous chunk must have run — and is retired first (its entry names the slot's event)
-static int ring_reclaim_slot(gm_ring* r, int slot) {
-    if (!r->slot_used[slot]) return GM_OK;
-    HIPC(wait_event_polling(r->slot_done[slot]));
-    ring_refresh_head(r);
+// The block loop of every writer that runs kernels behind the copy: `n` samples of `bps` bytes each, at most `block` a step.  A step
+// stages its bytes in the next pinned slot, copies them on copy_stream into the caller's landing zone raw[slot] (raw_bytes each,
+// allocated on first use), and makes fe_stream wait for that copy; `stage(d_raw, chunk, &cnt)` then enqueues the block's kernels on
+// fe_stream, the last of them writing `cnt` samples into the ring at write_pos.
+template <class Stage>
+static int ring_write_blocks(gm_ring* r, const void* samples, size_t n, size_t bps, size_t block, void** raw, size_t raw_bytes, Stage&& stage) {
+    const uint8_t* src = static_cast<const uint8_t*>(samples);
+    while (n) {
+        const size_t chunk = n < block ? n : block;
+        int slot = 0;
+        if (int rc = ring_begin_block(r, &slot)) return rc;
+        if (!raw[slot]) HIPC(hipMalloc(&raw[slot], raw_bytes));
+        memcpy(r->staging[slot], src, chunk * bps);
+        // (the kernel reading the pinned staging slot itself instead of a device copy of it — no copy, no event — was measured:
+        //  30 x real time against 52: the front-end's loads then wait on host memory)
+        HIPC(hipMemcpyAsync(raw[slot], r->staging[slot], chunk * bps, hipMemcpyHostToDevice, r->copy_stream));
+        HIPC(hipEventRecord(r->h2d_done[slot], r->copy_stream));
+        HIPC(hipStreamWaitEvent(r->fe_stream, r->h2d_done[slot], 0));
+        uint64_t cnt = 0;
+        if (int rc = stage(raw[slot], chunk, &cnt)) return rc;
+        if (int rc = ring_end_block(r, slot, r->fe_stream, cnt)) return rc;
+        src += chunk * bps; n -= chunk;
+    }
     return GM_OK;
 }
 
@@ -2454,18 +2498,15 @@ int gm_ring_write_samples_async(gm_ring* r, const gm_c32* s, size_t n) {
     const cf* src = reinterpret_cast<const cf*>(s);
     while (n) {
         const size_t chunk = n < r->slot_samples ? n : r->slot_samples;
-        const int slot = int(r->slot_seq++ % gm_ring::SLOTS);
-        if (int rc = ring_reclaim_slot(r, slot)) return rc;
+        int slot = 0;
+        if (int rc = ring_begin_block(r, &slot)) return rc;
         memcpy(r->staging[slot], src, chunk * 8);
         const size_t start = size_t(r->write_pos & r->mask);
         const size_t first = start + chunk <= r->size ? chunk : r->size - start;
         HIPC(hipMemcpyAsync(r->d_buf + start, r->staging[slot], first * 8, hipMemcpyHostToDevice, r->copy_stream));
         if (first < chunk)
             HIPC(hipMemcpyAsync(r->d_buf, r->staging[slot] + first, (chunk - first) * 8, hipMemcpyHostToDevice, r->copy_stream));
-        HIPC(hipEventRecord(r->slot_done[slot], r->copy_stream));
-        r->slot_used[slot] = true;
-        r->write_pos += chunk;
-        if (int rc = ring_enqueue_publish(r, slot, r->copy_stream)) return rc;
+        if (int rc = ring_end_block(r, slot, r->copy_stream, chunk)) return rc;
         src += chunk; n -= chunk;
     }
     return GM_OK;
@@ -3473,40 +3514,152 @@ int gm_frontend_write_ring(gm_frontend* f, gm_ring* r, const void* samples, size
     if (n_samples > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "write larger than the ring");
     if (int rc = ensure_device(r->device)) return rc;
     if (int rc = ring_async_init(r)) return rc;
-    if (!r->fe_stream) {
-        if (gm::diag_int("GM_RING_FE_STREAM", 1) == 0) r->fe_stream = r->copy_stream;      // diagnostic: kernels on the copy stream (round 4's form)
-        else {      // (highest priority: see ring_async_init)
-            int least = 0, greatest = 0;
-            HIPC(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            const int pr = gm::diag_int("GM_RING_FE_PRIORITY", 99);
-            HIPC(hipStreamCreateWithPriority(&r->fe_stream, hipStreamNonBlocking, pr == 99 ? greatest : pr));
-        }
-        for (int i = 0; i < gm_ring::SLOTS; ++i) HIPC(hipEventCreateWithFlags(&r->h2d_done[i], hipEventDisableTiming));
-    }
-    const size_t bps = fmt == GM_FMT_C32 ? 8 : 2;
-    const uint8_t* src = static_cast<const uint8_t*>(samples);
-    while (n_samples) {
-        const size_t chunk = n_samples < r->slot_samples ? n_samples : r->slot_samples;
-        const int slot = int(r->slot_seq++ % gm_ring::SLOTS);
-        if (int rc = ring_reclaim_slot(r, slot)) return rc;
-        if (!f->d_raw[slot]) HIPC(hipMalloc(&f->d_raw[slot], gm_ring::SLOT_SAMPLES_MAX * 8));
-        memcpy(r->staging[slot], src, chunk * bps);
-        // (the kernel reading the pinned staging slot itself instead of a device copy of it — no copy, no event — was measured:
-        //  30 x real time against 52: the front-end's loads then wait on host memory)
-        HIPC(hipMemcpyAsync(f->d_raw[slot], r->staging[slot], chunk * bps, hipMemcpyHostToDevice, r->copy_stream));
-        HIPC(hipEventRecord(r->h2d_done[slot], r->copy_stream));
-        HIPC(hipStreamWaitEvent(r->fe_stream, r->h2d_done[slot], 0));
-        if (int rc = frontend_launch(f, r->fe_stream, f->d_raw[slot], fmt, r->d_buf, r->write_pos, r->mask, chunk)) return rc;
-        HIPC(hipEventRecord(r->slot_done[slot], r->fe_stream));
-        r->slot_used[slot] = true;
-        r->write_pos += chunk;
-        if (int rc = ring_enqueue_publish(r, slot, r->fe_stream)) return rc;
-        src += chunk * bps; n_samples -= chunk;
-    }
-    return GM_OK;
+    if (int rc = ring_fe_init(r)) return rc;
+    return ring_write_blocks(r, samples, n_samples, fmt == GM_FMT_C32 ? 8 : 2, r->slot_samples, f->d_raw, gm_ring::SLOT_SAMPLES_MAX * 8,
+                             [&](const void* d_raw, size_t chunk, uint64_t* cnt) {
+                                 *cnt = chunk;
+                                 return frontend_launch(f, r->fe_stream, d_raw, fmt, r->d_buf, r->write_pos, r->mask, chunk);
+                             });
 }
 
 }  // extern "C"
+
+// ====================================================================== streaming stages: what gm_resampler, gm_excisor and gm_ddc share
+// A stage turns a stream of inputs into a stream of outputs call by call, whatever the cuts: a history of the last inputs travels between
+// calls in two device buffers used alternately, and the counters say where in the stream the next call starts.  Each handle inherits
+// this state and adds its plan, its tables, `*_count` (outputs of the next n inputs) and `*_launch` (that kernel's argument block).
+namespace {
+constexpr uint64_t RS_INDEX_MAX = 1ull << 62;
+
+struct StreamStage {
+    int device = -1;
+    void* d_hist[2] = {nullptr, nullptr};   // the last blanked inputs (hist_bytes each): d_hist[cur] is read by the next call, the other written
+    size_t hist_bytes = 0;
+    int cur = 0;
+    unsigned long long* d_blanked = nullptr;
+    hipStream_t stream = nullptr, last_stream = nullptr;    // the handle's own, and the one the last call ran on
+    uint64_t base = 0;                      // absolute index of the first input since create / reset
+    uint64_t inputs = 0, outputs = 0;       // since create / reset
+    void* d_in = nullptr; size_t in_cap = 0;    // bytes; staging of the host-buffer entry
+    cf* d_out = nullptr; size_t out_cap = 0;    // samples
+};
+
+// the end of a handle's create (behind its own fills): zeroed history and counter, then the stream
+hipError_t stage_create(StreamStage* s, size_t hist_bytes) {
+    s->hist_bytes = hist_bytes;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = hipMalloc(&s->d_hist[i], hist_bytes);
+        if (e == hipSuccess) e = hipMemset(s->d_hist[i], 0, hist_bytes);
+    }
+    if (e == hipSuccess) e = hipMalloc(&s->d_blanked, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(s->d_blanked, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the fills have run before a kernel on a non-blocking stream can touch the state (see gm_ring_create)
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+    return e;
+}
+// the start of a handle's destroy: the streams drained, the shared buffers freed
+void stage_destroy(StreamStage* s) {
+    hipSetDevice(s->device);
+    if (s->last_stream && s->last_stream != s->stream) hipStreamSynchronize(s->last_stream);
+    if (s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
+    hipFree(s->d_hist[0]); hipFree(s->d_hist[1]); hipFree(s->d_blanked); hipFree(s->d_in); hipFree(s->d_out);
+}
+// before work on `st` that reads what the last call wrote (the history; the excisor's gains): that call has run
+int stage_join(StreamStage* s, hipStream_t st) {
+    if (s->last_stream && s->last_stream != st) HIPC(hipStreamSynchronize(s->last_stream));
+    return GM_OK;
+}
+int stage_sync(StreamStage* s) {
+    HIPC(hipStreamSynchronize(s->stream));
+    return stage_join(s, s->stream);
+}
+int stage_synchronize(StreamStage* s) {
+    if (!s) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (int rc = ensure_device(s->device)) return rc;
+    return stage_sync(s);
+}
+int stage_stats(StreamStage* s, uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) {
+    if (int rc = stage_synchronize(s)) return rc;
+    if (blanked) {
+        unsigned long long b = 0;
+        HIPC(hipMemcpy(&b, s->d_blanked, sizeof(b), hipMemcpyDeviceToHost));
+        *blanked = b;
+    }
+    if (inputs) *inputs = s->inputs;
+    if (outputs) *outputs = s->outputs;
+    return GM_OK;
+}
+// `also()` enqueues on the handle's stream whatever else the handle zeroes
+template <class Also>
+int stage_reset(StreamStage* s, uint64_t input_index, Also&& also) {
+    if (!s) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (input_index > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "input_index above 2^62");
+    if (int rc = ensure_device(s->device)) return rc;
+    if (int rc = stage_sync(s)) return rc;
+    HIPC(hipMemsetAsync(s->d_hist[0], 0, s->hist_bytes, s->stream));
+    HIPC(hipMemsetAsync(s->d_hist[1], 0, s->hist_bytes, s->stream));
+    HIPC(hipMemsetAsync(s->d_blanked, 0, sizeof(unsigned long long), s->stream));
+    HIPC(also());
+    HIPC(hipStreamSynchronize(s->stream));
+    s->cur = 0; s->base = input_index; s->inputs = 0; s->outputs = 0;
+    return GM_OK;
+}
+// a launch has gone out on `st`: the history buffers change roles, the counters advance
+int stage_launched(StreamStage* s, hipStream_t st, uint64_t n_in, uint64_t n_out) {
+    HIPC(hipGetLastError());
+    s->cur ^= 1; s->inputs += n_in; s->outputs += n_out; s->last_stream = st;
+    return GM_OK;
+}
+
+// The checks the process entries share: nothing is touched when one fails.  `fmt_err`: the caller's verdict on its format argument, null
+// where it is fine (or there is none); `plan_entry`: the entry that gives the output count; *cnt: that count.
+template <class H>
+int stage_check_call(const H* h, uint64_t (*count)(const H*, uint64_t), const char* fmt_err, const void* in, size_t n_in, const void* out,
+                     size_t out_cap, const char* plan_entry, uint64_t* cnt) {
+    if (!h) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (fmt_err) return set_err(GM_ERR_INVALID_ARG, fmt_err);
+    if (!in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
+    if (uint64_t(n_in) > (1ull << 31) || h->base + h->inputs + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
+    *cnt = count(h, n_in);
+    if (*cnt > out_cap)
+        return set_err(GM_ERR_OUT_OF_RANGE, (std::string("out_cap below the call's output count (") + plan_entry + " gives it)").c_str());
+    if (*cnt && !out) return set_err(GM_ERR_INVALID_ARG, "null output");
+    return GM_OK;
+}
+// the device entries' own refusal: the `cnt` outputs may not lie over the inputs
+int stage_check_overlap(const void* d_in, size_t in_bytes, const void* d_out, uint64_t cnt) {
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), i1 = i0 + in_bytes;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + cnt * 8;
+    if (cnt && in_bytes && i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
+    return GM_OK;
+}
+// The host-buffer entries behind their checks: grow the staging, H2D, `launch(stream, d_in, d_out)`, D2H, wait.
+template <class Launch>
+int stage_process(StreamStage* s, const void* in, size_t in_bytes, gm_c32* out, uint64_t cnt, size_t* n_out, Launch&& launch) {
+    if (n_out) *n_out = size_t(cnt);
+    if (!in_bytes) return GM_OK;
+    if (int rc = ensure_device(s->device)) return rc;
+    if (s->in_cap < in_bytes || s->out_cap < cnt) HIPC(hipStreamSynchronize(s->stream));
+    if (s->in_cap < in_bytes) {
+        hipFree(s->d_in); s->d_in = nullptr; s->in_cap = 0;
+        HIPC(hipMalloc(&s->d_in, in_bytes));
+        s->in_cap = in_bytes;
+    }
+    if (s->out_cap < cnt) {
+        hipFree(s->d_out); s->d_out = nullptr; s->out_cap = 0;
+        HIPC(hipMalloc(reinterpret_cast<void**>(&s->d_out), size_t(cnt) * sizeof(cf)));
+        s->out_cap = size_t(cnt);
+    }
+    if (int rc = stage_join(s, s->stream)) return rc;
+    HIPC(hipMemcpyAsync(s->d_in, in, in_bytes, hipMemcpyHostToDevice, s->stream));
+    if (int rc = launch(s->stream, s->d_in, s->d_out)) return rc;
+    if (cnt) HIPC(hipMemcpyAsync(out, s->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, s->stream));
+    HIPC(hipStreamSynchronize(s->stream));
+    return GM_OK;
+}
+}  // namespace
 
 // ====================================================================== rate conversion and pulse blanking (gm_resampler)
 // gnss_mi355x.h states the definition; tests/resample_model.py restates it in float64.
@@ -3516,7 +3669,6 @@ struct ResamplerPlan {
     double cutoff = 0.9, beta = 8.0;
     float thr = 0.0f;
 };
-constexpr uint64_t RS_INDEX_MAX = 1ull << 62;
 
 int resampler_rules(const gm_resampler_cfg* c, ResamplerPlan& p) {
     if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
@@ -3588,19 +3740,10 @@ void resampler_design(const ResamplerPlan& p, float* table) {
 }
 }  // namespace
 
-struct gm_resampler {
-    int device = -1;
+struct gm_resampler : StreamStage {         // history: the last T blanked inputs (cf)
     ResamplerPlan plan;
     std::vector<float> table;               // [PHI + 1][T]
     float* d_table = nullptr;
-    cf* d_hist[2] = {nullptr, nullptr};     // the last T blanked inputs: d_hist[cur] is read by the next call, the other written
-    int cur = 0;
-    unsigned long long* d_blanked = nullptr;
-    hipStream_t stream = nullptr, last_stream = nullptr;
-    uint64_t base = 0;                      // absolute index of the first input since create / reset
-    uint64_t inputs = 0, outputs = 0;       // since create / reset
-    void* d_in = nullptr; size_t in_cap = 0;    // bytes; staging of the host-buffer entry
-    cf* d_out = nullptr; size_t out_cap = 0;    // samples
     cf* d_scratch = nullptr;                // gm_frontend_write_ring_resampled: the front-end's linear output (SLOT_SAMPLES_MAX samples)
 };
 
@@ -3611,7 +3754,7 @@ static int resampler_launch(gm_resampler* r, hipStream_t st, const void* d_in, i
     const uint64_t A = r->base + r->inputs, m0 = resampler_total_out(p, A);
     gm::ResampleArgs a{};
     a.in = d_in; a.n_in = n_in;
-    a.hist_in = r->d_hist[r->cur]; a.hist_out = r->d_hist[r->cur ^ 1];
+    a.hist_in = static_cast<const cf*>(r->d_hist[r->cur]); a.hist_out = static_cast<cf*>(r->d_hist[r->cur ^ 1]);
     a.table = r->d_table; a.T = p.T; a.PHI = p.PHI; a.up = p.up; a.down = p.down;
     a.a0 = m0 / p.up; a.mr0 = m0 % p.up; a.in_index = A;
     a.n_out = n_out; a.tile_out = gm::resample_tile_out(p.T, p.up, p.down);
@@ -3619,18 +3762,14 @@ static int resampler_launch(gm_resampler* r, hipStream_t st, const void* d_in, i
     a.thr2 = p.thr * p.thr; a.blank = p.thr > 0.0f ? 1 : 0;
     a.blanked = r->d_blanked;
     gm::launch_resample(st, a, fmt);
-    HIPC(hipGetLastError());
-    r->cur ^= 1; r->inputs += n_in; r->outputs += n_out; r->last_stream = st;
-    return GM_OK;
+    return stage_launched(r, st, n_in, n_out);
 }
 static uint64_t resampler_count(const gm_resampler* r, uint64_t n_in) {
     const uint64_t A = r->base + r->inputs;
     return resampler_total_out(r->plan, A + n_in) - resampler_total_out(r->plan, A);
 }
-static int resampler_sync(gm_resampler* r) {
-    HIPC(hipStreamSynchronize(r->stream));
-    if (r->last_stream && r->last_stream != r->stream) HIPC(hipStreamSynchronize(r->last_stream));
-    return GM_OK;
+static const char* resampler_fmt_err(int fmt) {
+    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "resampler input is c32 or int8 IQ" : nullptr;
 }
 
 extern "C" {
@@ -3667,17 +3806,9 @@ int gm_resampler_create(const gm_resampler_cfg* cfg, gm_resampler** out) {
     r->device = g_device; r->plan = p;
     r->table.resize(size_t(p.PHI + 1) * p.T);
     resampler_design(p, r->table.data());
-    const size_t hist_bytes = size_t(p.T) * sizeof(cf);
     hipError_t e = hipMalloc(&r->d_table, r->table.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(r->d_table, r->table.data(), r->table.size() * sizeof(float), hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(&r->d_hist[i], hist_bytes);
-        if (e == hipSuccess) e = hipMemset(r->d_hist[i], 0, hist_bytes);
-    }
-    if (e == hipSuccess) e = hipMalloc(&r->d_blanked, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(r->d_blanked, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the fills have run before a kernel on a non-blocking stream can touch the state (see gm_ring_create)
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = stage_create(r, size_t(p.T) * sizeof(cf));
     if (e != hipSuccess) { gm_resampler_destroy(r); return hip_fail(e, "gm_resampler_create"); }
     *out = r;
     return GM_OK;
@@ -3685,27 +3816,14 @@ int gm_resampler_create(const gm_resampler_cfg* cfg, gm_resampler** out) {
 
 int gm_resampler_destroy(gm_resampler* r) {
     if (!r) return GM_OK;
-    hipSetDevice(r->device);
-    if (r->last_stream && r->last_stream != r->stream) hipStreamSynchronize(r->last_stream);
-    if (r->stream) { hipStreamSynchronize(r->stream); hipStreamDestroy(r->stream); }
-    hipFree(r->d_table); hipFree(r->d_hist[0]); hipFree(r->d_hist[1]); hipFree(r->d_blanked);
-    hipFree(r->d_in); hipFree(r->d_out); hipFree(r->d_scratch);
+    stage_destroy(r);
+    hipFree(r->d_table); hipFree(r->d_scratch);
     delete r;
     return GM_OK;
 }
 
 int gm_resampler_reset(gm_resampler* r, uint64_t input_index) {
-    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (input_index > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "input_index above 2^62");
-    if (int rc = ensure_device(r->device)) return rc;
-    if (int rc = resampler_sync(r)) return rc;
-    const size_t hist_bytes = size_t(r->plan.T) * sizeof(cf);
-    HIPC(hipMemsetAsync(r->d_hist[0], 0, hist_bytes, r->stream));
-    HIPC(hipMemsetAsync(r->d_hist[1], 0, hist_bytes, r->stream));
-    HIPC(hipMemsetAsync(r->d_blanked, 0, sizeof(unsigned long long), r->stream));
-    HIPC(hipStreamSynchronize(r->stream));
-    r->cur = 0; r->base = input_index; r->inputs = 0; r->outputs = 0;
-    return GM_OK;
+    return stage_reset(r, input_index, [] { return hipSuccess; });
 }
 
 int gm_resampler_taps(gm_resampler* r, float* table) {
@@ -3715,34 +3833,14 @@ int gm_resampler_taps(gm_resampler* r, float* table) {
 }
 
 int gm_resampler_stats(gm_resampler* r, uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) {
-    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (int rc = ensure_device(r->device)) return rc;
-    if (int rc = resampler_sync(r)) return rc;
-    if (blanked) {
-        unsigned long long b = 0;
-        HIPC(hipMemcpy(&b, r->d_blanked, sizeof(b), hipMemcpyDeviceToHost));
-        *blanked = b;
-    }
-    if (inputs) *inputs = r->inputs;
-    if (outputs) *outputs = r->outputs;
-    return GM_OK;
+    return stage_stats(r, inputs, outputs, blanked);
 }
 
 int gm_resampler_process_dev(gm_resampler* r, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out,
                              void* stream) {
-    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "resampler input is c32 or int8 IQ");
-    if (!d_in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
-    if (uint64_t(n_in) > (1ull << 31) || r->base + r->inputs + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
-    const uint64_t cnt = resampler_count(r, n_in);
-    if (cnt > out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_cap below the call's output count (gm_resampler_plan gives it)");
-    if (cnt && !d_out) return set_err(GM_ERR_INVALID_ARG, "null output");
-    if (cnt && n_in) {
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), i1 = i0 + n_in * (fmt == GM_FMT_C32 ? 8 : 2);
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + cnt * 8;
-        if (i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
-    }
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(r, resampler_count, resampler_fmt_err(fmt), d_in, n_in, d_out, out_cap, "gm_resampler_plan", &cnt)) return rc;
+    if (int rc = stage_check_overlap(d_in, n_in * (fmt == GM_FMT_C32 ? 8 : 2), d_out, cnt)) return rc;
     if (n_out) *n_out = size_t(cnt);
     if (!n_in) return GM_OK;
     if (int rc = ensure_device(r->device)) return rc;
@@ -3750,91 +3848,14 @@ int gm_resampler_process_dev(gm_resampler* r, const void* d_in, int fmt, size_t 
 }
 
 int gm_resampler_process(gm_resampler* r, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out) {
-    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "resampler input is c32 or int8 IQ");
-    if (!in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
-    if (uint64_t(n_in) > (1ull << 31) || r->base + r->inputs + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
-    const uint64_t cnt = resampler_count(r, n_in);
-    if (cnt > out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_cap below the call's output count (gm_resampler_plan gives it)");
-    if (cnt && !out) return set_err(GM_ERR_INVALID_ARG, "null output");
-    if (n_out) *n_out = size_t(cnt);
-    if (!n_in) return GM_OK;
-    if (int rc = ensure_device(r->device)) return rc;
-    const size_t in_bytes = n_in * (fmt == GM_FMT_C32 ? 8 : 2);
-    if (r->in_cap < in_bytes || r->out_cap < cnt) HIPC(hipStreamSynchronize(r->stream));
-    if (r->in_cap < in_bytes) {
-        hipFree(r->d_in); r->d_in = nullptr; r->in_cap = 0;
-        HIPC(hipMalloc(&r->d_in, in_bytes));
-        r->in_cap = in_bytes;
-    }
-    if (r->out_cap < cnt) {
-        hipFree(r->d_out); r->d_out = nullptr; r->out_cap = 0;
-        HIPC(hipMalloc(reinterpret_cast<void**>(&r->d_out), size_t(cnt) * sizeof(cf)));
-        r->out_cap = size_t(cnt);
-    }
-    if (r->last_stream && r->last_stream != r->stream) HIPC(hipStreamSynchronize(r->last_stream));   // the history the last call wrote
-    HIPC(hipMemcpyAsync(r->d_in, in, in_bytes, hipMemcpyHostToDevice, r->stream));
-    if (int rc = resampler_launch(r, r->stream, r->d_in, fmt, n_in, r->d_out, 0, ~0ull, cnt)) return rc;
-    if (cnt) HIPC(hipMemcpyAsync(out, r->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, r->stream));
-    HIPC(hipStreamSynchronize(r->stream));
-    return GM_OK;
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(r, resampler_count, resampler_fmt_err(fmt), in, n_in, out, out_cap, "gm_resampler_plan", &cnt)) return rc;
+    return stage_process(r, in, n_in * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
+        return resampler_launch(r, st, d_in, fmt, n_in, d_out, 0, ~0ull, cnt);
+    });
 }
 
-int gm_resampler_synchronize(gm_resampler* r) {
-    if (!r) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (int rc = ensure_device(r->device)) return rc;
-    return resampler_sync(r);
-}
-
-// gm_frontend_write_ring's block loop with the rate conversion as one more step: front-end -> the resampler's linear scratch buffer ->
-// resampler -> the ring at write_pos (ring indices count OUTPUT samples)
-int gm_frontend_write_ring_resampled(gm_frontend* f, gm_resampler* rs, gm_ring* r, const void* samples, size_t n_samples, int fmt,
-                                     uint64_t* n_out_total) {
-    if (!f || !rs || !r || (!samples && n_samples)) return set_err(GM_ERR_INVALID_ARG, "null pointer");
-    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "front-end input is c32 or int8 IQ");
-    if (f->device != r->device || rs->device != r->device) return set_err(GM_ERR_INVALID_ARG, "front-end, resampler and ring live on different devices");
-    if (rs->base + rs->inputs + n_samples > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
-    const uint64_t total = resampler_count(rs, n_samples);
-    if (total > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "write larger than the ring");
-    if (n_out_total) *n_out_total = total;
-    if (int rc = ensure_device(r->device)) return rc;
-    if (int rc = ring_async_init(r)) return rc;
-    if (!r->fe_stream) {      // (as gm_frontend_write_ring creates it)
-        if (gm::diag_int("GM_RING_FE_STREAM", 1) == 0) r->fe_stream = r->copy_stream;
-        else {
-            int least = 0, greatest = 0;
-            HIPC(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            const int pr = gm::diag_int("GM_RING_FE_PRIORITY", 99);
-            HIPC(hipStreamCreateWithPriority(&r->fe_stream, hipStreamNonBlocking, pr == 99 ? greatest : pr));
-        }
-        for (int i = 0; i < gm_ring::SLOTS; ++i) HIPC(hipEventCreateWithFlags(&r->h2d_done[i], hipEventDisableTiming));
-    }
-    if (!rs->d_scratch) HIPC(hipMalloc(reinterpret_cast<void**>(&rs->d_scratch), gm_ring::SLOT_SAMPLES_MAX * sizeof(cf)));
-    if (rs->last_stream && rs->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(rs->last_stream));   // the history the last call wrote
-    const size_t bps = fmt == GM_FMT_C32 ? 8 : 2;
-    const uint8_t* src = static_cast<const uint8_t*>(samples);
-    while (n_samples) {
-        const size_t chunk = n_samples < r->slot_samples ? n_samples : r->slot_samples;
-        const int slot = int(r->slot_seq++ % gm_ring::SLOTS);
-        if (int rc = ring_reclaim_slot(r, slot)) return rc;
-        if (!f->d_raw[slot]) HIPC(hipMalloc(&f->d_raw[slot], gm_ring::SLOT_SAMPLES_MAX * 8));
-        memcpy(r->staging[slot], src, chunk * bps);
-        HIPC(hipMemcpyAsync(f->d_raw[slot], r->staging[slot], chunk * bps, hipMemcpyHostToDevice, r->copy_stream));
-        HIPC(hipEventRecord(r->h2d_done[slot], r->copy_stream));
-        HIPC(hipStreamWaitEvent(r->fe_stream, r->h2d_done[slot], 0));
-        // one scratch buffer serves every block: the stream runs block k's resampler kernel before block k + 1's front-end kernel
-        if (int rc = frontend_launch(f, r->fe_stream, f->d_raw[slot], fmt, rs->d_scratch, 0, ~0ull, chunk)) return rc;
-        const uint64_t cnt = resampler_count(rs, chunk);
-        if (int rc = resampler_launch(rs, r->fe_stream, rs->d_scratch, GM_FMT_C32, chunk, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
-        HIPC(hipEventRecord(r->slot_done[slot], r->fe_stream));
-        r->slot_used[slot] = true;
-        r->write_pos += cnt;
-        if (int rc = ring_enqueue_publish(r, slot, r->fe_stream)) return rc;
-        src += chunk * bps; n_samples -= chunk;
-    }
-    return GM_OK;
-}
+int gm_resampler_synchronize(gm_resampler* r) { return stage_synchronize(r); }
 
 }  // extern "C"
 
@@ -3894,27 +3915,18 @@ void excisor_windows(uint32_t B, float* wa, float* ws) {
 }
 }  // namespace
 
-struct gm_excisor {
-    int device = -1;
+struct gm_excisor : StreamStage {           // history: the last 3H blanked inputs (cf)
     ExcisorPlan plan;
     std::vector<float> wa, ws;              // [B] each
     float *d_wa = nullptr, *d_ws = nullptr, *d_gains = nullptr;
     float* h_gains = nullptr;               // pinned staging of gm_excisor_set_gains
     hipEvent_t gains_ev = nullptr; bool gains_pending = false;
     cf *d_tw_fwd = nullptr, *d_tw_inv = nullptr;
-    cf* d_hist[2] = {nullptr, nullptr};     // the last 3H blanked inputs: d_hist[cur] is read by the next call, the other written
-    int cur = 0;
-    unsigned long long* d_blanked = nullptr;
     bool block_adapt = false; float block_factor = 16.0f; uint32_t block_guard = 0;   // block-adapt mode: host state, handed to every launch
     unsigned long long* d_bstat = nullptr;  // [EX_BSTAT_SLOTS] rows of {blocks, blocks flagged, bins flagged, bins zeroed}: the counters are the rows' sums
     float* cap_p = nullptr; unsigned char* cap_m = nullptr; uint64_t cap_blocks = 0;  // the armed capture (the caller's device buffers)
     float *d_partial = nullptr, *d_P = nullptr;   // the periodogram's partial sums [EX_CHUNKS_MAX][B] and its words [B]
     uint32_t* d_stat = nullptr;             // {median word, flagged, zeroed} of the last adapt
-    hipStream_t stream = nullptr, last_stream = nullptr;
-    uint64_t base = 0;                      // absolute index of the first input since create / reset
-    uint64_t inputs = 0, outputs = 0;       // since create / reset
-    void* d_in = nullptr; size_t in_cap = 0;    // bytes; staging of the host-buffer entry
-    cf* d_out = nullptr; size_t out_cap = 0;    // samples
     cf *d_scratch = nullptr, *d_mid = nullptr;  // gm_frontend_write_ring_conditioned: the front-end's linear output, and the excisor's in front of a resampler
 };
 
@@ -3930,7 +3942,7 @@ static int excisor_launch(gm_excisor* x, hipStream_t st, const void* d_in, int f
     if (x->gains_pending && st != x->stream) HIPC(hipStreamWaitEvent(st, x->gains_ev, 0));     // gains set on the handle's stream
     gm::ExciseArgs a{};
     a.in = d_in; a.n_in = n_in;
-    a.hist_in = x->d_hist[x->cur]; a.hist_out = x->d_hist[x->cur ^ 1];
+    a.hist_in = static_cast<const cf*>(x->d_hist[x->cur]); a.hist_out = static_cast<cf*>(x->d_hist[x->cur ^ 1]);
     a.wa = x->d_wa; a.ws = x->d_ws; a.gains = x->d_gains; a.tw_fwd = x->d_tw_fwd; a.tw_inv = x->d_tw_inv;
     a.B = p.B;
     a.rel0 = int64_t(s0 * H) - int64_t(H) - int64_t(A);
@@ -3941,26 +3953,10 @@ static int excisor_launch(gm_excisor* x, hipStream_t st, const void* d_in, int f
     a.block_adapt = x->block_adapt ? 1 : 0; a.bfactor = x->block_factor; a.bguard = x->block_guard; a.bstat = x->d_bstat;
     if (capture && x->block_adapt) { a.cap_p = x->cap_p; a.cap_m = x->cap_m; }     // (the caller has checked cap_blocks)
     gm::launch_excise(st, a, fmt);
-    HIPC(hipGetLastError());
-    x->cur ^= 1; x->inputs += n_in; x->outputs += n_out; x->last_stream = st;
-    return GM_OK;
+    return stage_launched(x, st, n_in, n_out);
 }
-static int excisor_sync(gm_excisor* x) {
-    HIPC(hipStreamSynchronize(x->stream));
-    if (x->last_stream && x->last_stream != x->stream) HIPC(hipStreamSynchronize(x->last_stream));
-    return GM_OK;
-}
-// the checks gm_excisor_process_dev and gm_excisor_process share: nothing is touched when one fails
-static int excisor_check_call(gm_excisor* x, const void* in, int fmt, size_t n_in, const void* out, size_t out_cap, uint64_t* cnt) {
-    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "excisor input is c32 or int8 IQ");
-    if (!in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
-    if (uint64_t(n_in) > (1ull << 31) || x->base + x->inputs + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
-    *cnt = excisor_count(x, n_in);
-    if (*cnt > out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_cap below the call's output count (gm_excisor_plan gives it)");
-    if (*cnt && !out) return set_err(GM_ERR_INVALID_ARG, "null output");
-    return GM_OK;
+static const char* excisor_fmt_err(int fmt) {
+    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "excisor input is c32 or int8 IQ" : nullptr;
 }
 
 extern "C" {
@@ -4017,16 +4013,9 @@ int gm_excisor_create(const gm_excisor_cfg* cfg, gm_excisor** out) {
     if (e == hipSuccess) e = hipMemcpy(x->d_tw_inv, twi.data(), gm::EX_TW_MAX * sizeof(cf), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(x->d_P, 0, wbytes);
     if (e == hipSuccess) e = hipMemset(x->d_stat, 0, 4 * sizeof(uint32_t));
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(&x->d_hist[i], hist_bytes);
-        if (e == hipSuccess) e = hipMemset(x->d_hist[i], 0, hist_bytes);
-    }
-    if (e == hipSuccess) e = hipMalloc(&x->d_blanked, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(x->d_blanked, 0, sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc(&x->d_bstat, EX_BSTAT_BYTES);
     if (e == hipSuccess) e = hipMemset(x->d_bstat, 0, EX_BSTAT_BYTES);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the fills have run before a kernel on a non-blocking stream can touch the state (see gm_ring_create)
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = stage_create(x, hist_bytes);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&x->gains_ev, hipEventDisableTiming);
     if (e != hipSuccess) { gm_excisor_destroy(x); return hip_fail(e, "gm_excisor_create"); }
     *out = x;
@@ -4035,31 +4024,17 @@ int gm_excisor_create(const gm_excisor_cfg* cfg, gm_excisor** out) {
 
 int gm_excisor_destroy(gm_excisor* x) {
     if (!x) return GM_OK;
-    hipSetDevice(x->device);
-    if (x->last_stream && x->last_stream != x->stream) hipStreamSynchronize(x->last_stream);
-    if (x->stream) { hipStreamSynchronize(x->stream); hipStreamDestroy(x->stream); }
+    stage_destroy(x);
     if (x->gains_ev) hipEventDestroy(x->gains_ev);
     hipFree(x->d_wa); hipFree(x->d_ws); hipFree(x->d_gains); hipFree(x->d_P); hipFree(x->d_partial); hipFree(x->d_stat);
-    hipFree(x->d_tw_fwd); hipFree(x->d_tw_inv); hipFree(x->d_hist[0]); hipFree(x->d_hist[1]); hipFree(x->d_blanked); hipFree(x->d_bstat);
-    hipFree(x->d_in); hipFree(x->d_out); hipFree(x->d_scratch); hipFree(x->d_mid);
+    hipFree(x->d_tw_fwd); hipFree(x->d_tw_inv); hipFree(x->d_bstat); hipFree(x->d_scratch); hipFree(x->d_mid);
     if (x->h_gains) hipHostFree(x->h_gains);
     delete x;
     return GM_OK;
 }
 
 int gm_excisor_reset(gm_excisor* x, uint64_t input_index) {
-    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (input_index > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "input_index above 2^62");
-    if (int rc = ensure_device(x->device)) return rc;
-    if (int rc = excisor_sync(x)) return rc;
-    const size_t hist_bytes = 3 * size_t(x->plan.B / 2) * sizeof(cf);
-    HIPC(hipMemsetAsync(x->d_hist[0], 0, hist_bytes, x->stream));
-    HIPC(hipMemsetAsync(x->d_hist[1], 0, hist_bytes, x->stream));
-    HIPC(hipMemsetAsync(x->d_blanked, 0, sizeof(unsigned long long), x->stream));
-    HIPC(hipMemsetAsync(x->d_bstat, 0, EX_BSTAT_BYTES, x->stream));
-    HIPC(hipStreamSynchronize(x->stream));
-    x->cur = 0; x->base = input_index; x->inputs = 0; x->outputs = 0;
-    return GM_OK;
+    return stage_reset(x, input_index, [&] { return hipMemsetAsync(x->d_bstat, 0, EX_BSTAT_BYTES, x->stream); });
 }
 
 int gm_excisor_set_gains(gm_excisor* x, const float* gains) {
@@ -4069,7 +4044,7 @@ int gm_excisor_set_gains(gm_excisor* x, const float* gains) {
         if (!(gains[k] >= 0.0f && gains[k] <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "every gain in [0, 1]");
     if (int rc = ensure_device(x->device)) return rc;
     if (x->gains_pending) HIPC(hipEventSynchronize(x->gains_ev));     // the staging words of the last call have left
-    if (x->last_stream && x->last_stream != x->stream) HIPC(hipStreamSynchronize(x->last_stream));   // a call in flight elsewhere reads the old gains
+    if (int rc = stage_join(x, x->stream)) return rc;                 // a call in flight elsewhere reads the old gains
     memcpy(x->h_gains, gains, B * sizeof(float));
     HIPC(hipMemcpyAsync(x->d_gains, x->h_gains, B * sizeof(float), hipMemcpyHostToDevice, x->stream));
     HIPC(hipEventRecord(x->gains_ev, x->stream));
@@ -4080,14 +4055,14 @@ int gm_excisor_set_gains(gm_excisor* x, const float* gains) {
 int gm_excisor_gains(gm_excisor* x, float* gains) {
     if (!x || !gains) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (int rc = ensure_device(x->device)) return rc;
-    if (int rc = excisor_sync(x)) return rc;
+    if (int rc = stage_sync(x)) return rc;
     HIPC(hipMemcpy(gains, x->d_gains, x->plan.B * sizeof(float), hipMemcpyDeviceToHost));
     return GM_OK;
 }
 
 int gm_excisor_adapt_dev(gm_excisor* x, const void* d_in, int fmt, size_t n, void* stream) {
     if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "excisor input is c32 or int8 IQ");
+    if (const char* err = excisor_fmt_err(fmt)) return set_err(GM_ERR_INVALID_ARG, err);
     if (!d_in) return set_err(GM_ERR_INVALID_ARG, "null input");
     const ExcisorPlan& p = x->plan;
     if (n < p.B || uint64_t(n) > (1ull << 31)) return set_err(GM_ERR_INVALID_ARG, "adapt takes block .. 2^31 samples");
@@ -4114,7 +4089,7 @@ int gm_excisor_adapt_dev(gm_excisor* x, const void* d_in, int fmt, size_t n, voi
 int gm_excisor_psd(gm_excisor* x, float* P, float* median, uint32_t* n_flagged, uint32_t* n_zeroed) {
     if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
     if (int rc = ensure_device(x->device)) return rc;
-    if (int rc = excisor_sync(x)) return rc;
+    if (int rc = stage_sync(x)) return rc;
     uint32_t stat[4] = {0, 0, 0, 0};
     HIPC(hipMemcpy(stat, x->d_stat, sizeof(stat), hipMemcpyDeviceToHost));
     if (P) HIPC(hipMemcpy(P, x->d_P, x->plan.B * sizeof(float), hipMemcpyDeviceToHost));
@@ -4125,28 +4100,14 @@ int gm_excisor_psd(gm_excisor* x, float* P, float* median, uint32_t* n_flagged, 
 }
 
 int gm_excisor_stats(gm_excisor* x, uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) {
-    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (int rc = ensure_device(x->device)) return rc;
-    if (int rc = excisor_sync(x)) return rc;
-    if (blanked) {
-        unsigned long long b = 0;
-        HIPC(hipMemcpy(&b, x->d_blanked, sizeof(b), hipMemcpyDeviceToHost));
-        *blanked = b;
-    }
-    if (inputs) *inputs = x->inputs;
-    if (outputs) *outputs = x->outputs;
-    return GM_OK;
+    return stage_stats(x, inputs, outputs, blanked);
 }
 
 int gm_excisor_process_dev(gm_excisor* x, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out,
                            void* stream) {
     uint64_t cnt = 0;
-    if (int rc = excisor_check_call(x, d_in, fmt, n_in, d_out, out_cap, &cnt)) return rc;
-    if (cnt && n_in) {
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), i1 = i0 + n_in * (fmt == GM_FMT_C32 ? 8 : 2);
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + cnt * 8;
-        if (i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
-    }
+    if (int rc = stage_check_call(x, excisor_count, excisor_fmt_err(fmt), d_in, n_in, d_out, out_cap, "gm_excisor_plan", &cnt)) return rc;
+    if (int rc = stage_check_overlap(d_in, n_in * (fmt == GM_FMT_C32 ? 8 : 2), d_out, cnt)) return rc;
     const bool capture = x->block_adapt && (x->cap_p || x->cap_m) && cnt >= x->plan.B / 2;
     if (capture && x->cap_blocks < cnt / (x->plan.B / 2) + 1)
         return set_err(GM_ERR_OUT_OF_RANGE, "the armed capture holds fewer blocks than the call's segments + 1");
@@ -4182,7 +4143,7 @@ int gm_excisor_set_block_adapt(gm_excisor* x, const gm_excisor_block_cfg* cfg) {
 int gm_excisor_block_stats(gm_excisor* x, uint64_t* blocks, uint64_t* blocks_flagged, uint64_t* bins_flagged, uint64_t* bins_zeroed) {
     if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
     if (int rc = ensure_device(x->device)) return rc;
-    if (int rc = excisor_sync(x)) return rc;
+    if (int rc = stage_sync(x)) return rc;
     unsigned long long rows[gm::EX_BSTAT_SLOTS * gm::EX_BSTAT_STRIDE], c[4] = {0, 0, 0, 0};
     HIPC(hipMemcpy(rows, x->d_bstat, EX_BSTAT_BYTES, hipMemcpyDeviceToHost));
     for (int r = 0; r < gm::EX_BSTAT_SLOTS; ++r)
@@ -4207,94 +4168,95 @@ int gm_excisor_block_capture(gm_excisor* x, float* d_power, uint8_t* d_mask, siz
 
 int gm_excisor_process(gm_excisor* x, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out) {
     uint64_t cnt = 0;
-    if (int rc = excisor_check_call(x, in, fmt, n_in, out, out_cap, &cnt)) return rc;
-    if (n_out) *n_out = size_t(cnt);
-    if (!n_in) return GM_OK;
-    if (int rc = ensure_device(x->device)) return rc;
-    const size_t in_bytes = n_in * (fmt == GM_FMT_C32 ? 8 : 2);
-    if (x->in_cap < in_bytes || x->out_cap < cnt) HIPC(hipStreamSynchronize(x->stream));
-    if (x->in_cap < in_bytes) {
-        hipFree(x->d_in); x->d_in = nullptr; x->in_cap = 0;
-        HIPC(hipMalloc(&x->d_in, in_bytes));
-        x->in_cap = in_bytes;
+    if (int rc = stage_check_call(x, excisor_count, excisor_fmt_err(fmt), in, n_in, out, out_cap, "gm_excisor_plan", &cnt)) return rc;
+    return stage_process(x, in, n_in * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
+        return excisor_launch(x, st, d_in, fmt, n_in, d_out, 0, ~0ull, cnt);
+    });
+}
+
+int gm_excisor_synchronize(gm_excisor* x) { return stage_synchronize(x); }
+
+}  // extern "C"
+
+// ====================================================================== the chain of optional stages behind a ring writer's head stage
+// head stage (front-end kernel or down-converter: the caller's part) -> a linear buffer -> (excisor) -> (resampler) -> the ring at
+// write_pos; ring indices count the LAST stage's outputs.  Either handle may be null.
+
+// `n` samples leave the head stage in this call: *total of them reach the ring — or a stage's stream would pass 2^62
+static int chain_count(const gm_excisor* x, const gm_resampler* rs, uint64_t n, uint64_t* total) {
+    if (x) {
+        if (x->base + x->inputs + n > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
+        n = excisor_count(x, n);
     }
-    if (x->out_cap < cnt) {
-        hipFree(x->d_out); x->d_out = nullptr; x->out_cap = 0;
-        HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_out), size_t(cnt) * sizeof(cf)));
-        x->out_cap = size_t(cnt);
+    if (rs) {
+        if (rs->base + rs->inputs + n > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
+        n = resampler_count(rs, n);
     }
-    if (x->last_stream && x->last_stream != x->stream) HIPC(hipStreamSynchronize(x->last_stream));   // the history (and the gains) the last call wrote
-    HIPC(hipMemcpyAsync(x->d_in, in, in_bytes, hipMemcpyHostToDevice, x->stream));
-    if (int rc = excisor_launch(x, x->stream, x->d_in, fmt, n_in, x->d_out, 0, ~0ull, cnt)) return rc;
-    if (cnt) HIPC(hipMemcpyAsync(out, x->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, x->stream));
-    HIPC(hipStreamSynchronize(x->stream));
+    *total = n;
+    return GM_OK;
+}
+// before a call's first block: the excisor's linear output in front of a resampler, and the histories the stages' last calls wrote
+static int chain_begin(gm_excisor* x, gm_resampler* rs, hipStream_t st) {
+    if (x && rs && !x->d_mid) HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_mid), (gm_ring::SLOT_SAMPLES_MAX + gm::EX_BLOCK_MAX) * sizeof(cf)));   // a block's outputs: up to its inputs + H
+    if (x) if (int rc = stage_join(x, st)) return rc;
+    if (rs) if (int rc = stage_join(rs, st)) return rc;
+    return GM_OK;
+}
+// One block's launches on fe_stream: the head stage has left `n` samples in `lin`; *cnt of them reach the ring.  A stage with no input
+// is not launched (an excisor delivers nothing until it has seen a whole segment), and the head then does not move.  One buffer of each
+// kind serves every block: the stream runs block k's kernels before block k + 1's first kernel.
+static int chain_launch(gm_excisor* x, gm_resampler* rs, gm_ring* r, const cf* lin, uint64_t n, uint64_t* cnt) {
+    if (x && n) {
+        const uint64_t n_in = n;
+        n = excisor_count(x, n_in);
+        if (int rc = excisor_launch(x, r->fe_stream, lin, GM_FMT_C32, n_in, rs ? x->d_mid : r->d_buf, rs ? 0 : r->write_pos, rs ? ~0ull : r->mask, n)) return rc;
+        lin = x->d_mid;
+    }
+    if (rs && n) {
+        const uint64_t n_in = n;
+        n = resampler_count(rs, n_in);
+        if (int rc = resampler_launch(rs, r->fe_stream, lin, GM_FMT_C32, n_in, r->d_buf, r->write_pos, r->mask, n)) return rc;
+    }
+    *cnt = n;
     return GM_OK;
 }
 
-int gm_excisor_synchronize(gm_excisor* x) {
-    if (!x) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (int rc = ensure_device(x->device)) return rc;
-    return excisor_sync(x);
-}
-
-// gm_frontend_write_ring_resampled's block loop with the excisor between the front-end kernel and the resampler: front-end -> the
-// excisor's linear scratch buffer -> excisor -> (rs: a second linear buffer -> resampler ->) the ring at write_pos
-int gm_frontend_write_ring_conditioned(gm_frontend* f, gm_excisor* x, gm_resampler* rs, gm_ring* r, const void* samples, size_t n_samples,
-                                       int fmt, uint64_t* n_out_total) {
-    if (!f || !x || !r || (!samples && n_samples)) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+// gm_frontend_write_ring with the chain behind the front-end kernel, whose linear output lands in the scratch buffer of the chain's first stage
+static int frontend_write_ring_chain(gm_frontend* f, gm_excisor* x, gm_resampler* rs, gm_ring* r, const void* samples, size_t n_samples, int fmt,
+                                     uint64_t* n_out_total, const char* devices_err) {
+    if (!f || !r || (!samples && n_samples)) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "front-end input is c32 or int8 IQ");
-    if (f->device != r->device || x->device != r->device || (rs && rs->device != r->device))
-        return set_err(GM_ERR_INVALID_ARG, "front-end, excisor, resampler and ring live on different devices");
-    if (x->base + x->inputs + n_samples > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
-    const uint64_t mid_total = excisor_count(x, n_samples);
-    if (rs && rs->base + rs->inputs + mid_total > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
-    const uint64_t total = rs ? resampler_count(rs, mid_total) : mid_total;
+    if (f->device != r->device || (x && x->device != r->device) || (rs && rs->device != r->device)) return set_err(GM_ERR_INVALID_ARG, devices_err);
+    uint64_t total = 0;
+    if (int rc = chain_count(x, rs, n_samples, &total)) return rc;
     if (total > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "write larger than the ring");
     if (n_out_total) *n_out_total = total;
     if (int rc = ensure_device(r->device)) return rc;
     if (int rc = ring_async_init(r)) return rc;
-    if (!r->fe_stream) {      // (as gm_frontend_write_ring creates it)
-        if (gm::diag_int("GM_RING_FE_STREAM", 1) == 0) r->fe_stream = r->copy_stream;
-        else {
-            int least = 0, greatest = 0;
-            HIPC(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            const int pr = gm::diag_int("GM_RING_FE_PRIORITY", 99);
-            HIPC(hipStreamCreateWithPriority(&r->fe_stream, hipStreamNonBlocking, pr == 99 ? greatest : pr));
-        }
-        for (int i = 0; i < gm_ring::SLOTS; ++i) HIPC(hipEventCreateWithFlags(&r->h2d_done[i], hipEventDisableTiming));
-    }
-    if (!x->d_scratch) HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_scratch), gm_ring::SLOT_SAMPLES_MAX * sizeof(cf)));
-    if (rs && !x->d_mid) HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_mid), (gm_ring::SLOT_SAMPLES_MAX + gm::EX_BLOCK_MAX) * sizeof(cf)));   // a block's outputs: up to its inputs + H
-    if (x->last_stream && x->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(x->last_stream));       // the history the last call wrote
-    if (rs && rs->last_stream && rs->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(rs->last_stream));
-    const size_t bps = fmt == GM_FMT_C32 ? 8 : 2;
-    const uint8_t* src = static_cast<const uint8_t*>(samples);
-    while (n_samples) {
-        const size_t chunk = n_samples < r->slot_samples ? n_samples : r->slot_samples;
-        const int slot = int(r->slot_seq++ % gm_ring::SLOTS);
-        if (int rc = ring_reclaim_slot(r, slot)) return rc;
-        if (!f->d_raw[slot]) HIPC(hipMalloc(&f->d_raw[slot], gm_ring::SLOT_SAMPLES_MAX * 8));
-        memcpy(r->staging[slot], src, chunk * bps);
-        HIPC(hipMemcpyAsync(f->d_raw[slot], r->staging[slot], chunk * bps, hipMemcpyHostToDevice, r->copy_stream));
-        HIPC(hipEventRecord(r->h2d_done[slot], r->copy_stream));
-        HIPC(hipStreamWaitEvent(r->fe_stream, r->h2d_done[slot], 0));
-        // one buffer of each kind serves every block: the stream runs block k's kernels before block k + 1's front-end kernel
-        if (int rc = frontend_launch(f, r->fe_stream, f->d_raw[slot], fmt, x->d_scratch, 0, ~0ull, chunk)) return rc;
-        const uint64_t mid = excisor_count(x, chunk);
-        uint64_t cnt = mid;
-        if (rs) {
-            if (int rc = excisor_launch(x, r->fe_stream, x->d_scratch, GM_FMT_C32, chunk, x->d_mid, 0, ~0ull, mid)) return rc;
-            cnt = resampler_count(rs, mid);
-            if (mid)
-                if (int rc = resampler_launch(rs, r->fe_stream, x->d_mid, GM_FMT_C32, mid, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
-        } else if (int rc = excisor_launch(x, r->fe_stream, x->d_scratch, GM_FMT_C32, chunk, r->d_buf, r->write_pos, r->mask, mid)) return rc;
-        HIPC(hipEventRecord(r->slot_done[slot], r->fe_stream));
-        r->slot_used[slot] = true;
-        r->write_pos += cnt;
-        if (int rc = ring_enqueue_publish(r, slot, r->fe_stream)) return rc;
-        src += chunk * bps; n_samples -= chunk;
-    }
-    return GM_OK;
+    if (int rc = ring_fe_init(r)) return rc;
+    cf*& lin = x ? x->d_scratch : rs->d_scratch;
+    if (!lin) HIPC(hipMalloc(reinterpret_cast<void**>(&lin), gm_ring::SLOT_SAMPLES_MAX * sizeof(cf)));
+    if (int rc = chain_begin(x, rs, r->fe_stream)) return rc;
+    return ring_write_blocks(r, samples, n_samples, fmt == GM_FMT_C32 ? 8 : 2, r->slot_samples, f->d_raw, gm_ring::SLOT_SAMPLES_MAX * 8,
+                             [&](const void* d_raw, size_t chunk, uint64_t* cnt) {
+                                 if (int rc = frontend_launch(f, r->fe_stream, d_raw, fmt, lin, 0, ~0ull, chunk)) return rc;
+                                 return chain_launch(x, rs, r, lin, chunk, cnt);
+                             });
+}
+
+extern "C" {
+
+int gm_frontend_write_ring_resampled(gm_frontend* f, gm_resampler* rs, gm_ring* r, const void* samples, size_t n_samples, int fmt,
+                                     uint64_t* n_out_total) {
+    if (!rs) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    return frontend_write_ring_chain(f, nullptr, rs, r, samples, n_samples, fmt, n_out_total, "front-end, resampler and ring live on different devices");
+}
+
+int gm_frontend_write_ring_conditioned(gm_frontend* f, gm_excisor* x, gm_resampler* rs, gm_ring* r, const void* samples, size_t n_samples,
+                                       int fmt, uint64_t* n_out_total) {
+    if (!x) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    return frontend_write_ring_chain(f, x, rs, r, samples, n_samples, fmt, n_out_total,
+                                     "front-end, excisor, resampler and ring live on different devices");
 }
 
 }  // extern "C"
@@ -4328,21 +4290,12 @@ void ddc_phasor_tables(cf* whi, cf* wlo) {
 }
 }  // namespace
 
-struct gm_ddc {
-    int device = -1;
+struct gm_ddc : StreamStage {               // history: the last T blanked input bytes (int8)
     DdcPlan plan;
     std::vector<float> table;               // [PHI + 1][T]
     std::vector<cf> whi, wlo;               // [DDC_TABLE] each
     float* d_table = nullptr;
     cf *d_whi = nullptr, *d_wlo = nullptr;
-    int8_t* d_hist[2] = {nullptr, nullptr}; // the last T blanked input bytes: d_hist[cur] is read by the next call, the other written
-    int cur = 0;
-    unsigned long long* d_blanked = nullptr;
-    hipStream_t stream = nullptr, last_stream = nullptr;
-    uint64_t base = 0;                      // absolute index of the first input since create / reset
-    uint64_t inputs = 0, outputs = 0;       // since create / reset
-    void* d_in = nullptr; size_t in_cap = 0;    // bytes; staging of the host-buffer entry
-    cf* d_out = nullptr; size_t out_cap = 0;    // samples
     void* d_raw[gm_ring::SLOTS] = {nullptr, nullptr, nullptr, nullptr};   // gm_ddc_write_ring: the landing zones of the raw bytes
     cf* d_scratch = nullptr;                // gm_ddc_write_ring: the linear output in front of an excisor or a resampler (SLOT_SAMPLES_MAX samples)
 };
@@ -4358,7 +4311,7 @@ static int ddc_launch(gm_ddc* d, hipStream_t st, const void* d_in, uint64_t n_in
     const uint64_t A = d->base + d->inputs, m0 = resampler_total_out(p, A);
     gm::DdcArgs a{};
     a.in = static_cast<const int8_t*>(d_in); a.n_in = n_in;
-    a.hist_in = d->d_hist[d->cur]; a.hist_out = d->d_hist[d->cur ^ 1];
+    a.hist_in = static_cast<const int8_t*>(d->d_hist[d->cur]); a.hist_out = static_cast<int8_t*>(d->d_hist[d->cur ^ 1]);
     a.table = d->d_table; a.whi = d->d_whi; a.wlo = d->d_wlo;
     a.T = p.T; a.PHI = p.PHI; a.up = p.up; a.down = p.down;
     a.a0 = m0 / p.up; a.mr0 = m0 % p.up; a.in_index = A; a.inc = d->plan.inc;
@@ -4367,25 +4320,7 @@ static int ddc_launch(gm_ddc* d, hipStream_t st, const void* d_in, uint64_t n_in
     a.thr2 = p.thr * p.thr; a.blank = p.thr > 0.0f ? 1 : 0;
     a.blanked = d->d_blanked;
     gm::launch_ddc(st, a);
-    HIPC(hipGetLastError());
-    d->cur ^= 1; d->inputs += n_in; d->outputs += n_out; d->last_stream = st;
-    return GM_OK;
-}
-static int ddc_sync(gm_ddc* d) {
-    HIPC(hipStreamSynchronize(d->stream));
-    if (d->last_stream && d->last_stream != d->stream) HIPC(hipStreamSynchronize(d->last_stream));
-    return GM_OK;
-}
-// the checks gm_ddc_process_dev and gm_ddc_process share: nothing is touched when one fails
-static int ddc_check_call(gm_ddc* d, const void* in, size_t n_in, const void* out, size_t out_cap, uint64_t* cnt) {
-    if (!d) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (!in && n_in) return set_err(GM_ERR_INVALID_ARG, "null input");
-    if (uint64_t(n_in) > (1ull << 31) || d->base + d->inputs + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "at most 2^31 samples a call, 2^62 a stream");
-    *cnt = ddc_count(d, n_in);
-    if (*cnt > out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_cap below the call's output count (gm_ddc_plan gives it)");
-    if (*cnt && !out) return set_err(GM_ERR_INVALID_ARG, "null output");
-    return GM_OK;
+    return stage_launched(d, st, n_in, n_out);
 }
 
 extern "C" {
@@ -4424,14 +4359,7 @@ int gm_ddc_create(const gm_ddc_cfg* cfg, gm_ddc** out) {
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->d_wlo), wbytes);
     if (e == hipSuccess) e = hipMemcpy(d->d_whi, d->whi.data(), wbytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d->d_wlo, d->wlo.data(), wbytes, hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(reinterpret_cast<void**>(&d->d_hist[i]), p.rs.T);
-        if (e == hipSuccess) e = hipMemset(d->d_hist[i], 0, p.rs.T);
-    }
-    if (e == hipSuccess) e = hipMalloc(&d->d_blanked, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d->d_blanked, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the fills have run before a kernel on a non-blocking stream can touch the state (see gm_ring_create)
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = stage_create(d, p.rs.T);
     if (e != hipSuccess) { gm_ddc_destroy(d); return hip_fail(e, "gm_ddc_create"); }
     *out = d;
     return GM_OK;
@@ -4439,48 +4367,22 @@ int gm_ddc_create(const gm_ddc_cfg* cfg, gm_ddc** out) {
 
 int gm_ddc_destroy(gm_ddc* d) {
     if (!d) return GM_OK;
-    hipSetDevice(d->device);
-    if (d->last_stream && d->last_stream != d->stream) hipStreamSynchronize(d->last_stream);
-    if (d->stream) { hipStreamSynchronize(d->stream); hipStreamDestroy(d->stream); }
-    hipFree(d->d_table); hipFree(d->d_whi); hipFree(d->d_wlo); hipFree(d->d_hist[0]); hipFree(d->d_hist[1]); hipFree(d->d_blanked);
-    hipFree(d->d_in); hipFree(d->d_out); hipFree(d->d_scratch);
+    stage_destroy(d);
+    hipFree(d->d_table); hipFree(d->d_whi); hipFree(d->d_wlo); hipFree(d->d_scratch);
     for (void* p : d->d_raw) hipFree(p);
     delete d;
     return GM_OK;
 }
 
 int gm_ddc_reset(gm_ddc* d, uint64_t input_index) {
-    if (!d) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (input_index > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "input_index above 2^62");
-    if (int rc = ensure_device(d->device)) return rc;
-    if (int rc = ddc_sync(d)) return rc;
-    HIPC(hipMemsetAsync(d->d_hist[0], 0, d->plan.rs.T, d->stream));
-    HIPC(hipMemsetAsync(d->d_hist[1], 0, d->plan.rs.T, d->stream));
-    HIPC(hipMemsetAsync(d->d_blanked, 0, sizeof(unsigned long long), d->stream));
-    HIPC(hipStreamSynchronize(d->stream));
-    d->cur = 0; d->base = input_index; d->inputs = 0; d->outputs = 0;
-    return GM_OK;
+    return stage_reset(d, input_index, [] { return hipSuccess; });
 }
 
 int gm_ddc_stats(gm_ddc* d, uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) {
-    if (!d) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (int rc = ensure_device(d->device)) return rc;
-    if (int rc = ddc_sync(d)) return rc;
-    if (blanked) {
-        unsigned long long b = 0;
-        HIPC(hipMemcpy(&b, d->d_blanked, sizeof(b), hipMemcpyDeviceToHost));
-        *blanked = b;
-    }
-    if (inputs) *inputs = d->inputs;
-    if (outputs) *outputs = d->outputs;
-    return GM_OK;
+    return stage_stats(d, inputs, outputs, blanked);
 }
 
-int gm_ddc_synchronize(gm_ddc* d) {
-    if (!d) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (int rc = ensure_device(d->device)) return rc;
-    return ddc_sync(d);
-}
+int gm_ddc_synchronize(gm_ddc* d) { return stage_synchronize(d); }
 
 int gm_ddc_tables(gm_ddc* d, float* table, gm_c32* whi, gm_c32* wlo) {
     if (!d && table) return set_err(GM_ERR_INVALID_ARG, "the filter table needs a handle");
@@ -4496,12 +4398,8 @@ int gm_ddc_tables(gm_ddc* d, float* table, gm_c32* whi, gm_c32* wlo) {
 
 int gm_ddc_process_dev(gm_ddc* d, const void* d_in, size_t n_in, void* d_out, size_t out_cap, size_t* n_out, void* stream) {
     uint64_t cnt = 0;
-    if (int rc = ddc_check_call(d, d_in, n_in, d_out, out_cap, &cnt)) return rc;
-    if (cnt && n_in) {
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), i1 = i0 + n_in;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + cnt * 8;
-        if (i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
-    }
+    if (int rc = stage_check_call(d, ddc_count, nullptr, d_in, n_in, d_out, out_cap, "gm_ddc_plan", &cnt)) return rc;
+    if (int rc = stage_check_overlap(d_in, n_in, d_out, cnt)) return rc;
     if (n_out) *n_out = size_t(cnt);
     if (!n_in) return GM_OK;
     if (int rc = ensure_device(d->device)) return rc;
@@ -4510,108 +4408,42 @@ int gm_ddc_process_dev(gm_ddc* d, const void* d_in, size_t n_in, void* d_out, si
 
 int gm_ddc_process(gm_ddc* d, const int8_t* in, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out) {
     uint64_t cnt = 0;
-    if (int rc = ddc_check_call(d, in, n_in, out, out_cap, &cnt)) return rc;
-    if (n_out) *n_out = size_t(cnt);
-    if (!n_in) return GM_OK;
-    if (int rc = ensure_device(d->device)) return rc;
-    if (d->in_cap < n_in || d->out_cap < cnt) HIPC(hipStreamSynchronize(d->stream));
-    if (d->in_cap < n_in) {
-        hipFree(d->d_in); d->d_in = nullptr; d->in_cap = 0;
-        HIPC(hipMalloc(&d->d_in, n_in));
-        d->in_cap = n_in;
-    }
-    if (d->out_cap < cnt) {
-        hipFree(d->d_out); d->d_out = nullptr; d->out_cap = 0;
-        HIPC(hipMalloc(reinterpret_cast<void**>(&d->d_out), size_t(cnt) * sizeof(cf)));
-        d->out_cap = size_t(cnt);
-    }
-    if (d->last_stream && d->last_stream != d->stream) HIPC(hipStreamSynchronize(d->last_stream));   // the history the last call wrote
-    HIPC(hipMemcpyAsync(d->d_in, in, n_in, hipMemcpyHostToDevice, d->stream));
-    if (int rc = ddc_launch(d, d->stream, d->d_in, n_in, d->d_out, 0, ~0ull, cnt)) return rc;
-    if (cnt) HIPC(hipMemcpyAsync(out, d->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, d->stream));
-    HIPC(hipStreamSynchronize(d->stream));
-    return GM_OK;
+    if (int rc = stage_check_call(d, ddc_count, nullptr, in, n_in, out, out_cap, "gm_ddc_plan", &cnt)) return rc;
+    return stage_process(d, in, n_in, out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
+        return ddc_launch(d, st, d_in, n_in, d_out, 0, ~0ull, cnt);
+    });
 }
 
-// gm_frontend_write_ring_conditioned's block loop with the down-converter in the front-end kernel's place: raw bytes -> down-converter
-// -> (x: a linear buffer -> excisor ->) (rs: a linear buffer -> resampler ->) the ring at write_pos
+// The ring writer with the down-converter as the head stage: raw bytes -> down-converter -> the chain of optional stages (through
+// d_scratch) or, with neither, the ring at write_pos
 int gm_ddc_write_ring(gm_ddc* d, gm_excisor* x, gm_resampler* rs, gm_ring* r, const int8_t* samples, size_t n_samples,
                       uint64_t* n_out_total) {
     if (!d || !r || (!samples && n_samples)) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (d->device != r->device || (x && x->device != r->device) || (rs && rs->device != r->device))
         return set_err(GM_ERR_INVALID_ARG, "down-converter, excisor, resampler and ring live on different devices");
     if (d->base + d->inputs + n_samples > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
-    uint64_t total = ddc_count(d, n_samples);
-    if (x) {
-        if (x->base + x->inputs + total > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
-        total = excisor_count(x, total);
-    }
-    if (rs) {
-        if (rs->base + rs->inputs + total > RS_INDEX_MAX) return set_err(GM_ERR_INVALID_ARG, "at most 2^62 samples a stream");
-        total = resampler_count(rs, total);
-    }
+    uint64_t total = 0;
+    if (int rc = chain_count(x, rs, ddc_count(d, n_samples), &total)) return rc;
     if (total > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "write larger than the ring");
     if (n_out_total) *n_out_total = total;
     if (int rc = ensure_device(r->device)) return rc;
     if (int rc = ring_async_init(r)) return rc;
-    if (!r->fe_stream) {      // (as gm_frontend_write_ring creates it)
-        if (gm::diag_int("GM_RING_FE_STREAM", 1) == 0) r->fe_stream = r->copy_stream;
-        else {
-            int least = 0, greatest = 0;
-            HIPC(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            const int pr = gm::diag_int("GM_RING_FE_PRIORITY", 99);
-            HIPC(hipStreamCreateWithPriority(&r->fe_stream, hipStreamNonBlocking, pr == 99 ? greatest : pr));
-        }
-        for (int i = 0; i < gm_ring::SLOTS; ++i) HIPC(hipEventCreateWithFlags(&r->h2d_done[i], hipEventDisableTiming));
-    }
-    if ((x || rs) && !d->d_scratch) HIPC(hipMalloc(reinterpret_cast<void**>(&d->d_scratch), gm_ring::SLOT_SAMPLES_MAX * sizeof(cf)));
-    if (x && rs && !x->d_mid) HIPC(hipMalloc(reinterpret_cast<void**>(&x->d_mid), (gm_ring::SLOT_SAMPLES_MAX + gm::EX_BLOCK_MAX) * sizeof(cf)));   // a block's outputs: up to its inputs + H
-    if (d->last_stream && d->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(d->last_stream));        // the history the last call wrote
-    if (x && x->last_stream && x->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(x->last_stream));
-    if (rs && rs->last_stream && rs->last_stream != r->fe_stream) HIPC(hipStreamSynchronize(rs->last_stream));
+    if (int rc = ring_fe_init(r)) return rc;
+    const bool chained = x || rs;
+    if (chained && !d->d_scratch) HIPC(hipMalloc(reinterpret_cast<void**>(&d->d_scratch), gm_ring::SLOT_SAMPLES_MAX * sizeof(cf)));
+    if (int rc = stage_join(d, r->fe_stream)) return rc;
+    if (int rc = chain_begin(x, rs, r->fe_stream)) return rc;
     // a block is at most the ring's staging slot, and, where the down-converter raises the rate, short enough that its outputs fit the
     // linear buffers (a call delivers at most n * up / down + 1)
     const ResamplerPlan& p = d->plan.rs;
     size_t block = r->slot_samples;
     if (p.up > p.down) block = std::min<size_t>(block, size_t((gm_ring::SLOT_SAMPLES_MAX - 1) * uint64_t(p.down) / p.up));
-    const int8_t* src = samples;
-    while (n_samples) {
-        const size_t chunk = n_samples < block ? n_samples : block;
-        const int slot = int(r->slot_seq++ % gm_ring::SLOTS);
-        if (int rc = ring_reclaim_slot(r, slot)) return rc;
-        if (!d->d_raw[slot]) HIPC(hipMalloc(&d->d_raw[slot], gm_ring::SLOT_SAMPLES_MAX));
-        memcpy(r->staging[slot], src, chunk);
-        HIPC(hipMemcpyAsync(d->d_raw[slot], r->staging[slot], chunk, hipMemcpyHostToDevice, r->copy_stream));
-        HIPC(hipEventRecord(r->h2d_done[slot], r->copy_stream));
-        HIPC(hipStreamWaitEvent(r->fe_stream, r->h2d_done[slot], 0));
-        // one buffer of each kind serves every block: the stream runs block k's kernels before block k + 1's first kernel
-        uint64_t cnt = ddc_count(d, chunk);
-        if (!x && !rs) {
-            if (int rc = ddc_launch(d, r->fe_stream, d->d_raw[slot], chunk, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
-        } else {
-            if (int rc = ddc_launch(d, r->fe_stream, d->d_raw[slot], chunk, d->d_scratch, 0, ~0ull, cnt)) return rc;
-            const cf* mid = d->d_scratch;
-            if (x && cnt) {
-                const uint64_t n1 = cnt;
-                cnt = excisor_count(x, n1);
-                if (rs) {
-                    if (int rc = excisor_launch(x, r->fe_stream, mid, GM_FMT_C32, n1, x->d_mid, 0, ~0ull, cnt)) return rc;
-                    mid = x->d_mid;
-                } else if (int rc = excisor_launch(x, r->fe_stream, mid, GM_FMT_C32, n1, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
-            }
-            if (rs && cnt) {
-                const uint64_t n2 = cnt;
-                cnt = resampler_count(rs, n2);
-                if (int rc = resampler_launch(rs, r->fe_stream, mid, GM_FMT_C32, n2, r->d_buf, r->write_pos, r->mask, cnt)) return rc;
-            }
-        }
-        HIPC(hipEventRecord(r->slot_done[slot], r->fe_stream));
-        r->slot_used[slot] = true;
-        r->write_pos += cnt;
-        if (int rc = ring_enqueue_publish(r, slot, r->fe_stream)) return rc;
-        src += chunk; n_samples -= chunk;
-    }
-    return GM_OK;
+    return ring_write_blocks(r, samples, n_samples, 1, block, d->d_raw, gm_ring::SLOT_SAMPLES_MAX, [&](const void* d_raw, size_t chunk, uint64_t* cnt) {
+        *cnt = ddc_count(d, chunk);
+        if (!chained) return ddc_launch(d, r->fe_stream, d_raw, chunk, r->d_buf, r->write_pos, r->mask, *cnt);
+        if (int rc = ddc_launch(d, r->fe_stream, d_raw, chunk, d->d_scratch, 0, ~0ull, *cnt)) return rc;
+        return chain_launch(x, rs, r, d->d_scratch, *cnt, cnt);
+    });
 }
 
 }  // extern "C"
