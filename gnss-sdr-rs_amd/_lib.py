@@ -147,6 +147,21 @@ class TrkCfg(C.Structure):
                 ("share_device", C.c_int32)]
 
 
+class TrkBankCfg(C.Structure):
+    """gm_trk_bank_cfg (40 bytes): taps in chips, carrier offsets in Hz (NULL with n_offsets 0: the single offset 0)"""
+    _fields_ = [("n_taps", C.c_uint32), ("n_offsets", C.c_uint32), ("taps_chips", C.c_void_p), ("offsets_hz", C.c_void_p),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class TrkBankPlanOut(C.Structure):
+    """gm_trk_bank_plan_out (32 bytes)"""
+    _fields_ = [("n_taps", C.c_uint32), ("n_offsets", C.c_uint32), ("out_words", C.c_uint64), ("samples", C.c_uint64),
+                ("slices", C.c_uint32), ("tap_groups", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 FMT_C32, FMT_I8_IQ, FMT_I8_REAL = 0, 1, 2
 CODE_INDEX_FAITHFUL, CODE_INDEX_FIXED = 0, 1
 
@@ -314,6 +329,9 @@ SIGNATURES = {
     "gm_trk_debug_stamps": (_i, [_vp, _u32, _vp]),
     "gm_trk_enable_timing": (_i, [_vp, _i]),
     "gm_trk_last_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_u32)]),
+    "gm_trk_bank_plan": (_i, [C.POINTER(TrkCfg), C.POINTER(TrkBankCfg), _u32, C.POINTER(TrkBankPlanOut)]),
+    "gm_trk_bank": (_i, [_vp, _vp, _vp, _u32, C.POINTER(TrkBankCfg), _vp, _vp]),
+    "gm_trk_bank_samples": (_i, [_vp, C.POINTER(TrkState), _vp, _sz, C.POINTER(TrkBankCfg), _vp]),
 }
 
 _lib = None

@@ -2643,6 +2643,8 @@ struct gm_trk {
     uint8_t* tk_block = nullptr;          // ONE pinned allocation cut into the TICKETS slots (a pinned allocation costs ~1 ms: not per slot, not in a receiver's loop)
     size_t tk_cap = 0;                    // bytes per slot
     uint64_t next_ticket = 1;
+    // gm_trk_bank: one device block per call shape, [records | taps | offsets | out | done | partials] (trk_bank_run), grown on demand
+    uint8_t* d_bank = nullptr; size_t bank_cap = 0;
 };
 
 static int trk_check_error(gm_trk* t);
@@ -2701,7 +2703,7 @@ int gm_trk_destroy(gm_trk* t) {
     if (!t) return GM_OK;
     if (t->device >= 0) hipSetDevice(t->device);
     hipFree(t->d_codes); hipFree(t->d_states); hipFree(t->d_partials); hipFree(t->d_ready); hipFree(t->d_scratch); hipFree(t->d_terms);
-    hipFree(t->d_res);
+    hipFree(t->d_res); hipFree(t->d_bank);
     if (t->h_res) hipHostFree(t->h_res);
     for (auto& k : t->tk) if (k.done) hipEventDestroy(k.done);
     if (t->tk_block) hipHostFree(t->tk_block);
@@ -2990,6 +2992,166 @@ int gm_trk_correlate(gm_trk* t, uint32_t ch, const gm_c32* samples, size_t n, gm
 }
 int gm_trk_do_work(gm_trk* t, uint32_t ch, const gm_c32* samples, size_t n, gm_trk_out* out, uint8_t* lost, uint8_t* lost_prn) {
     return trk_unit(t, ch, samples, n, gm::TRK_MODE_DO_WORK, out, lost, lost_prn);
+}
+
+}  // extern "C"
+
+// ---- gm_trk_bank: taps x carrier offsets at caller-supplied records (gnss_mi355x.h states the definition and the limits) -------------
+// gm_trk_bank_plan's argument rules, shared by the device entries; F: the effective number of offsets
+static int trk_bank_rules(float fs, bool custom_codes, uint32_t n_codes, uint32_t code_len, const gm_trk_bank_cfg* cfg, uint32_t n_states,
+                          uint32_t& F) {
+    if (!cfg) return set_err(GM_ERR_INVALID_ARG, "null bank cfg");
+    if (!(fs > 0) || !std::isfinite(fs)) return set_err(GM_ERR_INVALID_ARG, "fs is required");
+    if (custom_codes && (!n_codes || !code_len)) return set_err(GM_ERR_INVALID_ARG, "n_codes/code_len required");
+    // the chip row shares the workgroup's 64 KB of LDS with the slice's samples and sign words (44 KB, trk_bank.hip)
+    if (custom_codes && code_len > 16384) return set_err(GM_ERR_OUT_OF_RANGE, "the bank serves codes of at most 16384 chips");
+    if (!cfg->taps_chips) return set_err(GM_ERR_INVALID_ARG, "null taps_chips");
+    if (cfg->n_offsets && !cfg->offsets_hz) return set_err(GM_ERR_INVALID_ARG, "null offsets_hz with n_offsets > 0");
+    F = cfg->n_offsets ? cfg->n_offsets : 1;
+    if (cfg->n_taps < 1 || cfg->n_taps > uint32_t(gm::GM_TRK_BANK_MAX_TAPS)) return set_err(GM_ERR_OUT_OF_RANGE, "n_taps must be in 1 .. 64");
+    if (F > uint32_t(gm::GM_TRK_BANK_MAX_OFFSETS)) return set_err(GM_ERR_OUT_OF_RANGE, "n_offsets must be at most 8");
+    if (F * cfg->n_taps > uint32_t(gm::GM_TRK_BANK_MAX_WORDS)) return set_err(GM_ERR_OUT_OF_RANGE, "n_offsets * n_taps must be at most 256");
+    if (n_states < 1 || n_states > uint32_t(gm::GM_TRK_BANK_MAX_STATES)) return set_err(GM_ERR_OUT_OF_RANGE, "n_states must be in 1 .. 1024");
+    const float half_len = 0.5f * float(custom_codes ? code_len : 1023u);
+    for (uint32_t k = 0; k < cfg->n_taps; ++k) {
+        const float tau = cfg->taps_chips[k];
+        if (!std::isfinite(tau)) return set_err(GM_ERR_INVALID_ARG, "a tap is not finite");
+        if (fabsf(tau) > 64.0f || !(fabsf(tau) < half_len)) return set_err(GM_ERR_OUT_OF_RANGE, "|tap| must be at most 64 chips and below code_len / 2");
+    }
+    for (uint32_t k = 0; k < cfg->n_offsets; ++k) {
+        const float df = cfg->offsets_hz[k];
+        if (!std::isfinite(df)) return set_err(GM_ERR_INVALID_ARG, "a carrier offset is not finite");
+        if (fabsf(df) > 0.5f * fs) return set_err(GM_ERR_OUT_OF_RANGE, "|offset| must be at most fs / 2");
+    }
+    return GM_OK;
+}
+// n = round(fs / (code_rate / code_len)) as the tracker forms it (trk_kernels.hip samples_per_code); false: a record with this n is skipped
+static bool trk_bank_samples_per_code(float fs, float code_rate, float lenf, uint32_t& n) {
+    const float v = roundf(fs / (code_rate / lenf));
+    n = 0;
+    if (!(v > 0.0f) || !(v < 2147483648.0f)) return false;
+    n = uint32_t(v);
+    return true;
+}
+static int trk_bank_row(const gm_trk* t, const gm_trk_state& s) {      // trk_kernels.hip code_row
+    return t->dc.gps_ca ? (t->dc.code_index_mode == GM_CODE_INDEX_FAITHFUL ? int(s.prn) : int(s.prn) - 1) : int(s.prn) - 1;
+}
+// the launch and the copies of both forms: recs carry st, n and run; slices and partial offsets are filled in here
+static int trk_bank_run(gm_trk* t, std::vector<gm::TrkBankRec>& recs, const gm_trk_bank_cfg* cfg, uint32_t F, const cf* base, uint64_t mask,
+                        int linear, gm_c32* out, uint8_t* done) {
+    const uint32_t R = uint32_t(recs.size()), T = cfg->n_taps;
+    uint64_t total = 0;
+    uint32_t max_slices = 0;
+    for (auto& r : recs) {
+        r.slices = r.run ? (r.n + gm::GM_TRK_BANK_SLICE - 1) / gm::GM_TRK_BANK_SLICE : 0;
+        if (total + r.slices > 0xffffffffull) return set_err(GM_ERR_NOMEM, "the call's partial sums exceed 2^32 slices");
+        r.poff = uint32_t(total);
+        total += r.slices;
+        if (r.slices > max_slices) max_slices = r.slices;
+    }
+    std::vector<float> offs(F, 0.0f);
+    for (uint32_t k = 0; k < cfg->n_offsets; ++k) offs[k] = cfg->offsets_hz[k];
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t words = size_t(F) * T;
+    const size_t o_recs = 0, o_taps = o_recs + up(R * sizeof(gm::TrkBankRec)), o_offs = o_taps + up(T * 4), o_out = o_offs + up(F * 4),
+                 o_done = o_out + up(R * words * 8), o_part = o_done + up(R), bytes = o_part + up(size_t(total) * words * 8);
+    if (bytes > t->bank_cap) {
+        HIPC(hipStreamSynchronize(t->stream));
+        hipFree(t->d_bank); t->d_bank = nullptr; t->bank_cap = 0;
+        if (hipMalloc(&t->d_bank, bytes) != hipSuccess) { (void)hipGetLastError(); t->d_bank = nullptr; return set_err(GM_ERR_NOMEM, "gm_trk_bank: device block"); }
+        t->bank_cap = bytes;
+    }
+    uint8_t* d = t->d_bank;
+    HIPC(hipMemcpyAsync(d + o_recs, recs.data(), R * sizeof(gm::TrkBankRec), hipMemcpyHostToDevice, t->stream));
+    HIPC(hipMemcpyAsync(d + o_taps, cfg->taps_chips, T * 4, hipMemcpyHostToDevice, t->stream));
+    HIPC(hipMemcpyAsync(d + o_offs, offs.data(), F * 4, hipMemcpyHostToDevice, t->stream));
+    gm::TrkBankArgs a;
+    a.recs = reinterpret_cast<const gm::TrkBankRec*>(d + o_recs);
+    a.taps = reinterpret_cast<const float*>(d + o_taps); a.offs = reinterpret_cast<const float*>(d + o_offs);
+    a.T = int(T); a.F = int(F);
+    a.base = base; a.mask = mask; a.linear = linear;
+    a.partials = reinterpret_cast<float*>(d + o_part);
+    gm::launch_trk_bank(t->stream, t->dc, t->d_codes, a, int(R), max_slices, reinterpret_cast<gm_c32*>(d + o_out), d + o_done);
+    HIPC(hipGetLastError());
+    // the results land in host blocks of the call's own and reach the caller's only once everything has succeeded
+    std::vector<gm_c32> h_out(size_t(R) * words);
+    std::vector<uint8_t> h_done(R);
+    HIPC(hipMemcpyAsync(h_out.data(), d + o_out, h_out.size() * 8, hipMemcpyDeviceToHost, t->stream));
+    HIPC(hipMemcpyAsync(h_done.data(), d + o_done, R, hipMemcpyDeviceToHost, t->stream));
+    HIPC(hipStreamSynchronize(t->stream));
+    memcpy(out, h_out.data(), h_out.size() * 8);
+    if (done) memcpy(done, h_done.data(), R);
+    return GM_OK;
+}
+
+extern "C" {
+
+int gm_trk_bank_plan(const gm_trk_cfg* trk, const gm_trk_bank_cfg* cfg, uint32_t n_states, gm_trk_bank_plan_out* out) {
+    if (!trk) return set_err(GM_ERR_INVALID_ARG, "null tracking cfg");
+    uint32_t F = 0;
+    if (int rc = trk_bank_rules(trk->fs, trk->codes != nullptr, trk->n_codes, trk->code_len, cfg, n_states, F)) return rc;
+    if (!out) return GM_OK;
+    memset(out, 0, sizeof(*out));
+    out->n_taps = cfg->n_taps; out->n_offsets = F;
+    out->out_words = uint64_t(n_states) * F * cfg->n_taps;
+    uint32_t n = 0;
+    const bool ok = trk_bank_samples_per_code(trk->fs, trk->nominal_code_rate > 0 ? trk->nominal_code_rate : CA_RATE,
+                                              trk->codes ? float(trk->code_len) : 1023.0f, n);
+    out->samples = n;
+    out->slices = ok ? (n + gm::GM_TRK_BANK_SLICE - 1) / gm::GM_TRK_BANK_SLICE : 0;
+    out->tap_groups = (cfg->n_taps + 15) / 16;
+    return GM_OK;
+}
+
+int gm_trk_bank(gm_trk* t, gm_ring* ring, const gm_trk_state* states, uint32_t n_states, const gm_trk_bank_cfg* cfg, gm_c32* out,
+                uint8_t* done) {
+    if (!t || !ring || !out) return set_err(GM_ERR_INVALID_ARG, "null handle, ring or out");
+    if (t->device != ring->device) return set_err(GM_ERR_INVALID_ARG, "ring lives on another device");
+    if (!states && n_states != t->C) return set_err(GM_ERR_INVALID_ARG, "states NULL: n_states must be n_channels");
+    uint32_t F = 0;
+    if (int rc = trk_bank_rules(t->dc.fs, !t->dc.gps_ca, uint32_t(t->dc.n_codes), uint32_t(t->dc.code_len), cfg, n_states, F)) return rc;
+    if (int rc = ensure_device(t->device)) return rc;
+    std::vector<gm::TrkBankRec> recs(n_states);
+    if (states) {
+        for (uint32_t r = 0; r < n_states; ++r) recs[r].st = states[r];
+    } else {        // the handle's own channels as they stand
+        std::vector<gm_trk_state> own(t->C);
+        if (int rc = gm_trk_get_states(t, own.data())) return rc;
+        for (uint32_t r = 0; r < n_states; ++r) recs[r].st = own[r];
+    }
+    ring_refresh_head(ring);
+    const uint64_t head = ring->head.load(std::memory_order_acquire);      // the PUBLISHED head, as gm_trk_update_all reads it
+    for (auto& r : recs) {
+        const gm_trk_state& s = r.st;
+        const int row = trk_bank_row(t, s);
+        bool run = s.active && row >= 0 && row < t->dc.n_codes && trk_bank_samples_per_code(t->dc.fs, s.code_rate, t->dc.code_len_f, r.n);
+        if (run) run = int64_t(head - (s.next_sample_index + r.n)) >= 0;      // the tracker's gate (:170-172)
+        if (run) run = head - s.next_sample_index <= uint64_t(ring->size);   // the epoch's first sample is still in the ring
+        r.run = run ? 1 : 0; r.slices = 0; r.poff = 0;
+        if (!run) r.n = 0;
+    }
+    return trk_bank_run(t, recs, cfg, F, ring->d_buf, ring->mask, 0, out, done);
+}
+
+int gm_trk_bank_samples(gm_trk* t, const gm_trk_state* state, const gm_c32* samples, size_t n, const gm_trk_bank_cfg* cfg, gm_c32* out) {
+    if (!t || !state || !samples || !out) return set_err(GM_ERR_INVALID_ARG, "null handle, state, samples or out");
+    uint32_t F = 0;
+    if (int rc = trk_bank_rules(t->dc.fs, !t->dc.gps_ca, uint32_t(t->dc.n_codes), uint32_t(t->dc.code_len), cfg, 1, F)) return rc;
+    if (n != state->num_samples_per_code || n == 0 || n >= (size_t(1) << 31))
+        return set_err(GM_ERR_OUT_OF_RANGE, "n must equal num_samples_per_code (1 .. 2^31 - 1)");
+    const int row = trk_bank_row(t, *state);
+    if (row < 0 || row >= t->dc.n_codes) return set_err(GM_ERR_OUT_OF_RANGE, "code table row out of bounds");
+    if (int rc = ensure_device(t->device)) return rc;
+    if (n > t->scratch_cap) {
+        HIPC(hipStreamSynchronize(t->stream));
+        hipFree(t->d_scratch); t->d_scratch = nullptr; t->scratch_cap = 0;
+        HIPC(hipMalloc(&t->d_scratch, n * 8 * 2));
+        t->scratch_cap = n * 2;
+    }
+    HIPC(hipMemcpyAsync(t->d_scratch, samples, n * 8, hipMemcpyHostToDevice, t->stream));
+    std::vector<gm::TrkBankRec> recs(1);
+    recs[0].st = *state; recs[0].n = uint32_t(n); recs[0].run = 1; recs[0].slices = 0; recs[0].poff = 0;
+    return trk_bank_run(t, recs, cfg, F, t->d_scratch, ~0ull, 1, out, nullptr);
 }
 
 // The persistent kernel's workgroups wait for one another, so its whole grid must be resident at once: ONE persistent

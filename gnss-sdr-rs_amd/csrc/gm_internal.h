@@ -334,6 +334,24 @@ void launch_trk_persistent(hipStream_t, const TrkDevCfg&, const int8_t* d_codes,
                            unsigned long long* d_xchg, gm_trk_out* d_outs, uint8_t* d_processed, uint8_t* d_lost,
                            uint8_t* d_lost_prn, int* d_error, int* d_error_dev, long long* d_stamps);
 
+// gm_trk_bank / gm_trk_bank_samples (trk_bank.hip, a section of trk_kernels.hip): taps x carrier offsets at caller-supplied records.
+// The host decides which records run (gnss_mi355x.h lists what skips one) and hands the kernel n, the slice count ceil(n / 4096) and
+// the record's first partial; nothing of a record is written.
+constexpr int GM_TRK_BANK_MAX_TAPS = 64, GM_TRK_BANK_MAX_OFFSETS = 8, GM_TRK_BANK_MAX_WORDS = 256, GM_TRK_BANK_MAX_STATES = 1024;
+constexpr uint32_t GM_TRK_BANK_SLICE = 4096;
+struct TrkBankRec { gm_trk_state st; uint32_t n, slices, poff, run; };   // poff: index of the record's first slice among the call's partials
+struct TrkBankArgs {
+    const TrkBankRec* recs;      // [n_records]
+    const float* taps;           // [T] chips
+    const float* offs;           // [F] Hz
+    int T, F;
+    const cf* base; uint64_t mask; int linear;      // the samples, as TrkSrc names them
+    float* partials;             // [sum of slices][F][T] complex
+};
+int trk_bank_tap_group(int n_taps);     // taps per workgroup: the smallest of 1, 4, 8, 16 that holds min(T, 16)
+void launch_trk_bank(hipStream_t, const TrkDevCfg&, const int8_t* d_codes, const TrkBankArgs&, int n_records, uint32_t max_slices,
+                     gm_c32* d_out, uint8_t* d_done);
+
 // ---------------------------------------------------------------- digital front-end (fe_kernels.hip)
 struct FeState { float phase_accumulator; float bias_re[8]; float bias_im[8]; };   // NcoLut.phase_accumulator, DcRemoverSimd.bias_*
 struct FrontendArgs {

@@ -1708,4 +1708,7 @@ void launch_trk_results_to_host(hipStream_t st, const void* d_src, void* h_dst_p
                        static_cast<uint32_t*>(h_dst_pinned), words, static_cast<const uint32_t*>(d_src2), static_cast<uint32_t*>(h_dst2_pinned), words2);
 }
 
+// ---- gm_trk_bank: the correlator bank at tracked states, a section of its own that uses the helpers above ----------------------------
+#include "trk_bank.hip"
+
 }  // namespace gm

@@ -520,6 +520,18 @@ public:
         if (lost) return TrackingMessage{TrackingMessageKind::SatelliteLost, prn};
         return std::nullopt;
     }
+    // gm_trk_bank_samples: taps (chips) x carrier offsets (Hz; empty: the single offset 0) on caller-supplied samples at this channel's
+    // state as it stands, or at *at; nothing is advanced.  -> [F][T]
+    std::vector<Complex32> bank(const std::vector<Complex32>& data_samples, const std::vector<float>& taps,
+                                const std::vector<float>& offsets_hz = {}, const gm_trk_state* at = nullptr) {
+        const gm_trk_state s = at ? *at : state();
+        gm_trk_bank_cfg c{}; c.n_taps = uint32_t(taps.size()); c.n_offsets = uint32_t(offsets_hz.size());
+        c.taps_chips = taps.data(); c.offsets_hz = offsets_hz.empty() ? nullptr : offsets_hz.data();
+        std::vector<Complex32> out(taps.size() * (offsets_hz.empty() ? 1 : offsets_hz.size()));
+        check(gm_trk_bank_samples(h_, &s, reinterpret_cast<const gm_c32*>(data_samples.data()), data_samples.size(), &c,
+                                  reinterpret_cast<gm_c32*>(out.data())), "TrackingChannel::bank");
+        return out;
+    }
 };
 
 class TrackingManager {
@@ -581,6 +593,29 @@ public:
     uint32_t pass_count(uint64_t ticket) const { const auto it = pending_.find(ticket); return it == pending_.end() ? 0 : it->second; }
     // every channel's record in one synchronisation + one copy (ABI 7)
     std::vector<gm_trk_state> states() const { std::vector<gm_trk_state> s(n_); check(gm_trk_get_states(h_, s.data()), "states"); return s; }
+    // gm_trk_bank: taps (chips) x carrier offsets (Hz; empty: the single offset 0) of one code period at tracking records, read from
+    // the ring; nothing is advanced.  records NULL: the handle's own channels as they stand.  -> [R][F][T]; done: [R] flags, 0 for a
+    // skipped record (whose words are zeros)
+    std::vector<Complex32> bank(MulticastRingBuffer& ring, const std::vector<float>& taps, const std::vector<float>& offsets_hz = {},
+                                const std::vector<gm_trk_state>* records = nullptr, std::vector<uint8_t>* done = nullptr) {
+        const uint32_t r = records ? uint32_t(records->size()) : n_;
+        gm_trk_bank_cfg c{}; c.n_taps = uint32_t(taps.size()); c.n_offsets = uint32_t(offsets_hz.size());
+        c.taps_chips = taps.data(); c.offsets_hz = offsets_hz.empty() ? nullptr : offsets_hz.data();
+        std::vector<Complex32> out(size_t(r) * taps.size() * (offsets_hz.empty() ? 1 : offsets_hz.size()));
+        if (done) done->assign(r, 0);
+        check(gm_trk_bank(h_, ring.handle(), records ? records->data() : nullptr, r, &c, reinterpret_cast<gm_c32*>(out.data()),
+                          done ? done->data() : nullptr), "TrackingManager::bank");
+        return out;
+    }
+    // gm_trk_bank_plan (host only): the argument rules and the sizes of a bank call for a tracking configuration
+    static gm_trk_bank_plan_out bank_plan(const gm_trk_cfg& trk, const std::vector<float>& taps, const std::vector<float>& offsets_hz = {},
+                                          uint32_t n_states = 1) {
+        gm_trk_bank_cfg c{}; c.n_taps = uint32_t(taps.size()); c.n_offsets = uint32_t(offsets_hz.size());
+        c.taps_chips = taps.data(); c.offsets_hz = offsets_hz.empty() ? nullptr : offsets_hz.data();
+        gm_trk_bank_plan_out p{};
+        check(gm_trk_bank_plan(&trk, &c, n_states, &p), "TrackingManager::bank_plan");
+        return p;
+    }
 private:
     std::map<uint64_t, uint32_t> pending_;      // ticket -> its pass count
 };

@@ -91,6 +91,33 @@ def _out_tuple(o, arms=3):
     return t + (o.ive, o.qve, o.ivl, o.qvl) if arms == 5 else t
 
 
+def _bank_cfg(taps, offsets_hz):
+    """-> (gm_trk_bank_cfg, the arrays it points into, T, F); offsets_hz None or empty: the single offset 0"""
+    t = np.ascontiguousarray(np.atleast_1d(taps), np.float32)
+    o = np.zeros(0, np.float32) if offsets_hz is None else np.ascontiguousarray(np.atleast_1d(offsets_hz), np.float32)
+    cfg = _lib.TrkBankCfg()
+    cfg.n_taps, cfg.n_offsets = t.size, o.size
+    cfg.taps_chips = t.ctypes.data
+    cfg.offsets_hz = o.ctypes.data if o.size else None
+    return cfg, (t, o), int(t.size), int(max(o.size, 1))
+
+
+def bank_plan(fs, taps, offsets_hz=(0.0,), n_states=1, code_rate=0.0, code_len=0):
+    """gm_trk_bank_plan (host only, no device): the argument rules of the correlator bank and the sizes of a call ->
+    dict(n_taps, n_offsets, out_words, samples, slices, tap_groups).  code_rate 0: 1.023e6; code_len 0: the C/A code's 1023,
+    else the chips per period of a custom table.  Raises GmError where the library refuses."""
+    trk = TrkCfg()
+    trk.fs, trk.n_channels, trk.nominal_code_rate = fs, 1, code_rate
+    dummy = np.ones(max(int(code_len), 1), np.int8)
+    if code_len:
+        trk.codes, trk.n_codes, trk.code_len = dummy.ctypes.data, 1, int(code_len)
+    cfg, keep, _, _ = _bank_cfg(taps, offsets_hz)
+    out = _lib.TrkBankPlanOut()
+    check(lib().gm_trk_bank_plan(C.byref(trk), C.byref(cfg), int(n_states), C.byref(out)), "gm_trk_bank_plan")
+    del keep
+    return out.as_dict()
+
+
 class TrackingManager:
     """TrackingManager::new (:336-348): n channels in one handle; process_channels' rayon fan-out
     (:364-371) becomes update_all()."""
@@ -184,6 +211,20 @@ class TrackingManager:
         w = None if which is None else np.ascontiguousarray(which, np.uint8)
         check(lib().gm_trk_set_states(self._h, C.cast(arr, C.c_void_p), _p(w) if w is not None else None), "gm_trk_set_states")
 
+    def bank(self, ring, taps, offsets_hz=(0.0,), states=None):
+        """gm_trk_bank: T taps (chips) x F carrier offsets (Hz) of one code period at tracking states, read from the ring; nothing is
+        advanced.  states None: the handle's own channels as they stand, else a list of TrkState records (they need not belong to a
+        channel).  -> (out complex64 [R, F, T], done uint8 [R]); a skipped record has done 0 and zeros."""
+        cfg, keep, T, F = _bank_cfg(taps, offsets_hz)
+        R = self.n_channels if states is None else len(states)
+        arr = None if states is None else (TrkState * max(R, 1))(*states)
+        out = np.zeros((R, F, T), np.complex64)
+        done = np.zeros(R, np.uint8)
+        check(lib().gm_trk_bank(self._h, ring._h, None if arr is None else C.cast(arr, C.c_void_p), R, C.byref(cfg), _p(out), _p(done)),
+              "gm_trk_bank")
+        del keep
+        return out, done
+
     def update_all_dev(self, ring, epochs):
         check(lib().gm_trk_update_all_dev(self._h, ring._h, int(epochs)), "gm_trk_update_all_dev")
 
@@ -254,6 +295,17 @@ class TrackingChannel:
             raise IndexError("out of range (the reference panics)")
         check(st, "early_late_correlation")
         return _out_tuple(o, self._m.n_arms)
+
+    def bank(self, data_samples, taps, offsets_hz=(0.0,), state=None):
+        """gm_trk_bank_samples: the bank on caller-supplied samples (as many as num_samples_per_code, like early_late_correlation) at
+        this channel's state as it stands, or at `state`; nothing is advanced.  -> out complex64 [F, T]"""
+        d = np.ascontiguousarray(data_samples, np.complex64)
+        cfg, keep, T, F = _bank_cfg(taps, offsets_hz)
+        s = self.state if state is None else state
+        out = np.zeros((F, T), np.complex64)
+        check(lib().gm_trk_bank_samples(self._m._h, C.byref(s), _p(d), d.size, C.byref(cfg), _p(out)), "gm_trk_bank_samples")
+        del keep
+        return out
 
     def do_work(self, data_samples):
         d = np.ascontiguousarray(data_samples, np.complex64)

@@ -43,6 +43,7 @@ extern "C" {
                               and the fine Doppler from per-period prompts — gm_acq_refine_doppler, gm_acq_refine_plan;
                               and the lag window x fine Doppler at known cells — gm_acq_local_search, gm_acq_local_plan;
                               and subtracting found satellites from a dwell — gm_acq_cancel, gm_acq_cancel_plan;
+                              and the correlator bank at tracked states — gm_trk_bank_plan, gm_trk_bank, gm_trk_bank_samples;
                               8: gm_acq_cfg.any_length, gm_acq_plan_info;
                               7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
@@ -1122,6 +1123,69 @@ int gm_trk_set_stream(gm_trk *t, void *hip_stream);
 int gm_trk_debug_stamps(gm_trk *t, uint32_t cap, long long *out);
 int gm_trk_enable_timing(gm_trk *t, int on);
 int gm_trk_last_timing(gm_trk *t, float *ms_correlate_total, uint32_t *launches);
+
+/* ------------------------------------------------------------------ Correlator bank at tracked states (additive, ABI 9)
+ * T taps x F carrier offsets of one code period at caller-supplied tracking states, formed with the tracker's own per-sample
+ * arithmetic: the correlation function around the prompt (more points than E/P/L), the prompt at carrier offsets around the NCO, a
+ * look at a state a receiver is only considering — without copying the epoch out of the ring and without starting a channel.
+ *
+ * A *record* is a gm_trk_state: a copy of one of the handle's channels (gm_trk_get_states) or anything the caller made up; it need
+ * not belong to a channel.  For record r the epoch is n = round(fs / (code_rate / code_len)) samples, the samples_per_code the
+ * tracker uses, starting at next_sample_index (ring form); in the linear form it is the num_samples_per_code samples the caller
+ * hands in, as gm_trk_correlate takes them.  With T taps tau_t (chips, f32) and F carrier offsets df_f (Hz, f32):
+ *
+ *     f_f      = fl(carrier_freq + df_f)
+ *     phase_i  = carrier_phase + fl(fl(fl(2 pi) * f_f) * i) / fs         the tracker's expression (do_tracking.rs:233) with f_f for carrier_freq
+ *     y_f[i]   = x[i] * (cos phase_i, -sin phase_i)                      num-complex order, as correlate_sample forms it
+ *     c[i]     = (code_phase + i * (code_rate / fs)) mod code_len        as correlate_sample forms it
+ *     out[r][f][t] = sum_{i < n} y_f[i] * chip(fl(c[i] + tau_t))
+ *
+ * chip() is get_ca_chip's look-up in the handle's code_index_mode (FAITHFUL saturates a negative phase to chip 0, FIXED wraps); with
+ * boc11 the sub-carrier sign comes from fract(phase) < 0.5, as the arms take it.  The chips are the +-1 of gm_trk_cfg.codes.  The
+ * division by fs and the sine and cosine are the forms gm_trk_correlate's kernel uses (the exact fast forms where the epoch allows
+ * them, the f64-reduced sine and cosine, glibc's on a strict_libm handle).  strict_sum_order is IGNORED: the bank always sums as a
+ * tree — each lane its samples in order, then lanes, waves and slices of 4096 samples in a fixed order, no floating-point atomics;
+ * the slice count is ceil(n / 4096), a function of n alone, so a record's words depend neither on what else is in the call nor on
+ * repetition.  At df = 0 and tau = 0, +el, -el (and +-vel) the per-sample products are gm_trk_correlate's own; the sums agree with
+ * it, and with the persistent kernel's prompt (whose sine and cosine differ on about 1e-5 of arguments), within the tracking
+ * tolerance of 1e-5 of the envelope, not bit for bit.  NOTHING IS ADVANCED: no record is written, no channel state, loop filter or
+ * lock counter moves.
+ *
+ * Limits, all checked before anything runs (gm_trk_bank_plan holds them; the device entries call the same code): a null cfg, a null
+ * taps_chips, a null offsets_hz with n_offsets > 0, a null out or handle: GM_ERR_INVALID_ARG; a tap or offset that is not finite:
+ * GM_ERR_INVALID_ARG; n_taps outside 1 .. 64, n_offsets above 8, n_offsets * n_taps above 256, n_states outside 1 .. 1024, a |tau_t|
+ * above 64 or not below code_len / 2, a |df_f| above fs / 2, a custom code of more than 16384 chips (the chip row shares the
+ * workgroup's LDS with the slice's samples): GM_ERR_OUT_OF_RANGE.  Taps need not be sorted or distinct.  A refusal leaves the
+ * outputs untouched.
+ * A record is SKIPPED — done[r] = 0, its words zeros, the call still succeeds — when active == 0; when its code row is outside
+ * [0, n_codes); when n == 0 or n >= 2^31; ring form only: while the head has not passed next_sample_index + n (the tracker's own
+ * gate), or when the epoch's first sample has already been overwritten (head - next_sample_index > ring size; the tracker has no such
+ * test, the bank needs one because callers hand it old states). */
+typedef struct {
+    uint32_t n_taps, n_offsets;    /* T; F (0 with offsets_hz NULL: the single offset 0) */
+    const float *taps_chips;       /* [n_taps] */
+    const float *offsets_hz;       /* [n_offsets] or NULL */
+    uint32_t reserved[4];          /* zeros */
+} gm_trk_bank_cfg;
+typedef struct {
+    uint32_t n_taps, n_offsets;    /* T and the effective F */
+    uint64_t out_words;            /* n_states * F * T gm_c32 words */
+    uint64_t samples;              /* n for gm_trk_cfg.nominal_code_rate (0 -> 1.023e6) and code_len (no codes: 1023) */
+    uint32_t slices;               /* ceil(n / 4096); 0 where a record with this n would be skipped */
+    uint32_t tap_groups;           /* workgroups per slice: ceil(T / 16) */
+} gm_trk_bank_plan_out;
+/* host only, no device: the argument rules above, and the sizes of a call.  Of `trk` it reads fs, codes / code_len (the chips per
+ * period) and nominal_code_rate (the code_rate n is reported for).  out may be NULL. */
+int gm_trk_bank_plan(const gm_trk_cfg *trk, const gm_trk_bank_cfg *cfg, uint32_t n_states, gm_trk_bank_plan_out *out);
+/* The ring form.  Synchronous, on the handle's stream, with gm_trk_update_all's ordering against the ring's writer and its head (the
+ * published one).  states NULL: the handle's own channels as they stand, n_states = n_channels.  out: [n_states][F][T]; done:
+ * [n_states] or NULL. */
+int gm_trk_bank(gm_trk *t, gm_ring *ring, const gm_trk_state *states, uint32_t n_states, const gm_trk_bank_cfg *cfg, gm_c32 *out,
+                uint8_t *done);
+/* The linear form: one record on caller-supplied samples.  n must equal state->num_samples_per_code (and be in 1 .. 2^31 - 1), the
+ * rule of gm_trk_correlate: GM_ERR_OUT_OF_RANGE otherwise, and for a code row outside the table.  Like gm_trk_correlate it runs
+ * whatever `active` says.  out: [F][T]. */
+int gm_trk_bank_samples(gm_trk *t, const gm_trk_state *state, const gm_c32 *samples, size_t n, const gm_trk_bank_cfg *cfg, gm_c32 *out);
 
 /* ------------------------------------------------------------------ Bit sync + nav-bit accumulation
  * src/decoding.rs:8,40-227 (legacy file outside the reference's module tree): 20-bin histogram of prompt-I sign

@@ -138,6 +138,23 @@ pub struct GmExcisorBlockCfg {      // gm_excisor_block_cfg (32 bytes; zeros: th
     pub guard_bins: u32,             // 0 .. 16: bins zeroed on either side of a flagged one
     pub reserved: [u32; 6],          // must be 0
 }
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct GmTrkBankCfg {           // gm_trk_bank_cfg (40 bytes): the correlator bank at tracked states
+    pub n_taps: u32,                 // T: 1 .. 64
+    pub n_offsets: u32,              // F: 0 .. 8, F * T <= 256; 0 with offsets_hz null: the single offset 0
+    pub taps_chips: *const f32,      // [n_taps] chips, |tau| <= 64 and < code_len / 2
+    pub offsets_hz: *const f32,      // [n_offsets] Hz, |df| <= fs / 2, or null
+    pub reserved: [u32; 4],          // must be 0
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmTrkBankPlanOut {       // gm_trk_bank_plan_out (32 bytes)
+    pub n_taps: u32,
+    pub n_offsets: u32,              // the effective F
+    pub out_words: u64,              // n_states * F * T complex words
+    pub samples: u64,                // n for the configuration's nominal code rate
+    pub slices: u32,                 // ceil(n / 4096)
+    pub tap_groups: u32,             // ceil(T / 16)
+}
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct GmDdcCfg {               // gm_ddc_cfg (40 bytes; zeros in the filter fields: the defaults)
     pub mix_cycles_per_sample: f64,  // f_mix / fs_in: the frequency brought to 0, cycles per input sample; any finite value
@@ -306,6 +323,13 @@ extern "C" {
     /// every channel's record in one synchronisation + one copy; `which`: NULL = all, else per-channel flags
     pub fn gm_trk_get_states(t: *mut GmTrk, out: *mut GmTrkState) -> c_int;
     pub fn gm_trk_set_states(t: *mut GmTrk, states: *const GmTrkState, which: *const u8) -> c_int;
+    /// the correlator bank at tracked states: T taps x F carrier offsets of one code period per record, nothing advanced
+    /// (states null: the handle's own channels, n_states = n_channels; out: [n_states][F][T]; done: [n_states] or null)
+    pub fn gm_trk_bank_plan(trk: *const GmTrkCfg, cfg: *const GmTrkBankCfg, n_states: u32, out: *mut GmTrkBankPlanOut) -> c_int;
+    pub fn gm_trk_bank(t: *mut GmTrk, ring: *mut GmRing, states: *const GmTrkState, n_states: u32, cfg: *const GmTrkBankCfg,
+                       out: *mut Complex32, done: *mut u8) -> c_int;
+    pub fn gm_trk_bank_samples(t: *mut GmTrk, state: *const GmTrkState, s: *const Complex32, n: usize, cfg: *const GmTrkBankCfg,
+                               out: *mut Complex32) -> c_int;
     // fft.rs:5-56
     pub fn gm_fft_c2c_f32(n: usize, dir: c_int, inout: *mut Complex32, batch: usize) -> c_int;
     pub fn gm_fft_power_spectrum_f32(n: usize, inout: *mut Complex32, power: *mut f32) -> c_int;

@@ -374,6 +374,25 @@ impl TrackingManager {
         self.collect_ready(false);
     }
 
+    /// The correlator bank (gm_trk_bank): `taps` (chips) x `offsets_hz` (empty: the single offset 0) of one code period at
+    /// `records` — None: the handle's channels as they stand — read from the device mirror of the ring.  Nothing is advanced.
+    /// -> (out [R][F][T], done [R]); a skipped record has done 0 and zeros.  Not part of the reference.
+    pub fn bank(&mut self, taps: &[f32], offsets_hz: &[f32], records: Option<&[GmTrkState]>) -> (Vec<Complex32>, Vec<u8>) {
+        self.collect_ready(true);                                        // nothing in flight moves a record under the call
+        self.push_dirty();
+        let r = records.map_or(self.channels.len(), |s| s.len());
+        let f = offsets_hz.len().max(1);
+        let cfg = GmTrkBankCfg { n_taps: taps.len() as u32, n_offsets: offsets_hz.len() as u32, taps_chips: taps.as_ptr(),
+                                 offsets_hz: if offsets_hz.is_empty() { std::ptr::null() } else { offsets_hz.as_ptr() }, reserved: [0; 4] };
+        let (mut out, mut done): (Vec<Complex32>, Vec<u8>) = (Vec::new(), Vec::new());      // (a caller's look, not the loop: it allocates)
+        out.resize(r * f * taps.len(), Complex32::new(0.0, 0.0));
+        done.resize(r, 0u8);
+        let st = unsafe { gm_trk_bank(self.h, self.ring, records.map_or(std::ptr::null(), |s| s.as_ptr()), r as u32, &cfg,
+                                      out.as_mut_ptr(), done.as_mut_ptr()) };
+        assert_eq!(st, 0, "gm_trk_bank: {}", last_error());
+        (out, done)
+    }
+
     fn next_tracking_index(&self) -> usize {                             // :373-381 on the PLANNED positions (= the fields when nothing is in flight)
         (0..self.channels.len()).filter(|i| self.channels[*i].is_active())
             .map(|i| self.planned_index(i) + self.channels[i].num_samples_per_code).min().unwrap_or(0)
