@@ -2722,6 +2722,7 @@ int gm_trk_create(const gm_trk_cfg* cfg, gm_trk** out) {
     const uint32_t arms = cfg->n_arms ? cfg->n_arms : 3;
     if (arms != 3 && arms != 5) return set_err(GM_ERR_INVALID_ARG, "n_arms must be 3 or 5");
     if (cfg->codes && (!cfg->n_codes || !cfg->code_len)) return set_err(GM_ERR_INVALID_ARG, "n_codes/code_len required");
+    if (cfg->codes && cfg->code_len > (1u << 24)) return set_err(GM_ERR_OUT_OF_RANGE, "code_len beyond 2^24 chips (chip phases are f32)");
     {   // the kernels replace `% code_len` by one conditional subtraction: arm spacings must stay below a code period
         const float len = cfg->codes ? float(cfg->code_len) : 1023.0f;
         if (cfg->early_late_space >= len || cfg->very_early_late_space >= len || cfg->early_late_space < 0 ||
@@ -2752,6 +2753,19 @@ int gm_trk_create(const gm_trk_cfg* cfg, gm_trk** out) {
     d.dll_dt = cfg->dll_dt > 0 ? cfg->dll_dt : 0.001f;
     d.nominal_code_rate = cfg->nominal_code_rate > 0 ? cfg->nominal_code_rate : CA_RATE;
     gm::fill_trk_derived(d);
+    {   // the persistent kernel keeps the channel's chip row in LDS as floats (three tables of it for BOC): a code that cannot fit is
+        // refused here, from the kernel's own static size and the device's limit, not found out by a launch that fails
+        size_t need = 0, limit = 0;
+        const hipError_t e = gm::trk_persistent_lds_need(d, t->device, &need, &limit);
+        if (e != hipSuccess) { gm_trk_destroy(t); return hip_fail(e, "trk_persistent_lds_need"); }
+        if (need > limit) {
+            gm_trk_destroy(t);
+            char msg[192];
+            snprintf(msg, sizeof(msg), "code_len %d needs %zu bytes of LDS per workgroup (chip tables + the kernel's own), the device allows %zu bytes",
+                     d.code_len, need, limit);
+            return set_err(GM_ERR_OUT_OF_RANGE, msg);
+        }
+    }
     if (cfg->codes) t->h_codes.assign(cfg->codes, cfg->codes + size_t(cfg->n_codes) * cfg->code_len);
     else t->h_codes.assign(&ca_table().rows[0][0], &ca_table().rows[0][0] + 32 * 1023);
 

@@ -325,6 +325,8 @@ constexpr int TRK_PERSIST_WG_PER_CU = GM_TRK_WG_PER_CU;
 
 inline int trk_persistent_slots(int n_channels) { return (n_channels + 7) / 8 * 8; }   // grid = slots * G workgroups
 int trk_persistent_blocks_per_cu(const TrkDevCfg&);   // resident workgroups per CU of the instantiation this config selects
+// bytes of LDS a workgroup of that instantiation needs (static + chip tables) and the device's limit per workgroup
+hipError_t trk_persistent_lds_need(const TrkDevCfg&, int device, size_t* need, size_t* limit);
 // persistent multi-epoch tracking (one launch = `epochs` passes over all channels); G workgroups per channel
 int trk_persistent_granule_stride(int G);      // granules per arm in the exchange block of the persistent kernel (16 for G <= 16)
 void launch_trk_results_to_host(hipStream_t, const void* d_src, void* h_dst_pinned, size_t bytes, const void* d_src2 = nullptr, void* h_dst2_pinned = nullptr,

@@ -124,10 +124,10 @@ __device__ __forceinline__ void reset_state(gm_trk_state& s) {
 #ifndef GM_TRK_IL5
 #define GM_TRK_IL5 2          // samples per straight-line block of the five-arm fast path (2 or 4)
 #endif
-// persistent kernel's dynamic LDS.  Plain: [code_len + 2 floats of the padded chip row].  BOC: [2 code_len + 4 half chips, whole
+// persistent kernel's dynamic LDS.  Plain: [code_len + 3 floats of the padded chip row].  BOC: [2 code_len + 6 half chips, whole
 // float4s][the padded chip row] — the table the fast path reads sits FIRST, at a compile-time LDS address, so that its look-ups are
 // `v_lshlrev` + `ds_read offset:constant` (a run-time base costs a half-rate v_lshl_add with a scalar source per look-up)
-__host__ __device__ __forceinline__ int boc_plain_offset(int code_len) { return (2 * code_len + 4 + 3) & ~3; }
+__host__ __device__ __forceinline__ int boc_plain_offset(int code_len) { return (2 * code_len + 6 + 3) & ~3; }
 
 // per-epoch constants of one channel, derived from its state exactly once per epoch
 struct EpochConsts {
@@ -149,8 +149,10 @@ __device__ __forceinline__ EpochConsts epoch_consts(const TrkDevCfg& cfg, const 
 
 // once per epoch: may the exact fast forms be used for samples 0..n-1 ?
 //  * fmod_code: code_phase in [0, len), 0 <= step, n*step < 1.99 len -> one conditional subtraction, result in [0, len);
-//  * chip look-ups: with the chip phase in [0, len) and arm spacings in (0, 1] every arm's floor lies in [-1, len], so one
-//    select per arm replaces the general modulo (chip_index_arm);
+//  * chip look-ups: with the chip phase in [0, len) and arm spacings in (0, 1] every arm's floor lies in [-1, len + 1], so one
+//    select per arm replaces the general modulo (chip_index_arm).  len + 1 is reached in f32 when len is a power of two and the
+//    spacing is 1.0: nextbelow(len) + 1.0 lies halfway between two floats of the next binade and rounds (to even) to len + 1.
+//    For any other length len - ulp + 1 is representable, and a sum that crosses a binade rounds to at most len + 1;
 //  * x / fs: q0 = x*r, q = fma(fma(-q0, fs, x), r, q0) with r = RN(1/fs) is the correctly rounded quotient (Markstein)
 //    unless fs's significand is all ones or the quotient leaves the normal range — excluded here.  Checked against IEEE
 //    division on 1.3e9 operands for 21 sample rates (tools/ubench note in DESIGN.md); only the sign of a zero quotient can
@@ -178,12 +180,12 @@ __device__ __forceinline__ float div_by_fs(float x, float fs, float inv_fs) {
     return __builtin_fmaf(__builtin_fmaf(-q0, fs, x), inv_fs, q0);
 }
 
-// get_ca_chip's index (:275) for phase = chip_idx +- spacing when floor(phase) is known to lie in [-1, len]:
-// len -> 0 (`% len`), -1 -> 0 in FAITHFUL mode (`as usize` saturates) or len-1 in FIXED mode (wrap)
+// get_ca_chip's index (:275) for phase = chip_idx +- spacing when floor(phase) is known to lie in [-1, len + 1] (fast_code_ok):
+// len -> 0 and len + 1 -> 1 (`% len`), -1 -> 0 in FAITHFUL mode (`as usize` saturates) or len-1 in FIXED mode (wrap)
 __device__ __forceinline__ int chip_index_arm(float phase, int len, int mode) {
     const int i = int(floorf(phase));
-    if (mode == GM_CODE_INDEX_FAITHFUL) return i >= len ? 0 : (i < 0 ? 0 : i);
-    return i >= len ? 0 : (i < 0 ? len - 1 : i);
+    if (mode == GM_CODE_INDEX_FAITHFUL) return i >= len ? i - len : (i < 0 ? 0 : i);
+    return i >= len ? i - len : (i < 0 ? len - 1 : i);
 }
 
 // one sample: carrier wipe-off fused with the replica multiplies (early_late_correlation :231-263)
@@ -193,6 +195,10 @@ __device__ __forceinline__ int chip_index_arm(float phase, int len, int mode) {
 template <class CT> __device__ __forceinline__ float chip_at(const CT* t, int k);
 template <> __device__ __forceinline__ float chip_at<int8_t>(const int8_t* t, int k) { return float(t[k]); }
 template <> __device__ __forceinline__ float chip_at<float>(const float* t, int k) { return t[k + 1]; }
+// an arm's chip when floor(phase) is known to lie in [-1, len + 1] (fast_code_ok): through chip_index_arm on the stored row; straight
+// from the padded row, whose guard entries hold what -1, len and len + 1 read (trk_persistent_kernel), with no select at all
+__device__ __forceinline__ float chip_arm(const int8_t* t, float phase, int len, int mode) { return float(t[chip_index_arm(phase, len, mode)]); }
+__device__ __forceinline__ float chip_arm(const float* t, float phase, int, int) { return t[int(floorf(phase)) + 1]; }
 
 template <int ARMS, bool FAST, int MODE_T = -1, int BOC_T = -1, class CT = int8_t, int STRICT_T = -1>
 __device__ __forceinline__ void correlate_sample(const EpochConsts& c, const CT* chips, cf d, uint32_t i,
@@ -214,8 +220,8 @@ __device__ __forceinline__ void correlate_sample(const EpochConsts& c, const CT*
     float pc, ec, lc;
     if (FAST) {   // chip_idx in [0, len): the prompt index needs no reduction, the arms one select each
         pc = chip_at(chips, int(floorf(chip_idx)));
-        ec = chip_at(chips, chip_index_arm(chip_idx + c.el, c.len, mode));
-        lc = chip_at(chips, chip_index_arm(chip_idx - c.el, c.len, mode));
+        ec = chip_arm(chips, chip_idx + c.el, c.len, mode);
+        lc = chip_arm(chips, chip_idx - c.el, c.len, mode);
     } else {
         pc = chip_at(chips, chip_index(chip_idx, c.len, mode));
         ec = chip_at(chips, chip_index(chip_idx + c.el, c.len, mode));
@@ -233,8 +239,8 @@ __device__ __forceinline__ void correlate_sample(const EpochConsts& c, const CT*
     acc[4] = __builtin_fmaf(xr, lc, acc[4]); acc[5] = __builtin_fmaf(xi, lc, acc[5]);
     if constexpr (ARMS == 5) {
         const float ve = chip_idx + c.vel, vl = chip_idx - c.vel;
-        float vec = chip_at(chips, FAST ? chip_index_arm(ve, c.len, mode) : chip_index(ve, c.len, mode));
-        float vlc = chip_at(chips, FAST ? chip_index_arm(vl, c.len, mode) : chip_index(vl, c.len, mode));
+        float vec = FAST ? chip_arm(chips, ve, c.len, mode) : chip_at(chips, chip_index(ve, c.len, mode));
+        float vlc = FAST ? chip_arm(chips, vl, c.len, mode) : chip_at(chips, chip_index(vl, c.len, mode));
         if (boc) {
             vec = (ve - floorf(ve)) < 0.5f ? vec : -vec;
             vlc = (vl - floorf(vl)) < 0.5f ? vlc : -vlc;
@@ -247,9 +253,10 @@ __device__ __forceinline__ void correlate_sample(const EpochConsts& c, const CT*
 // ---- the persistent kernel's sample, for epochs that passed fast_car_ok / fast_code_ok.  Same arithmetic as
 // correlate_sample<.., FAST = true> on the values that reach the sums, with the instruction count of the hot loop cut
 // (it is bound by VALU issue slots: ~115 -> ~80 issue units per sample):
-//  * the chip row is a float table padded by one entry at each end — tab[0] is what floor = -1 reads (chip 0 in
-//    FAITHFUL mode, the last chip in FIXED mode), tab[len + 1] = chip 0 is what floor = len reads (`% len`) — so an arm
-//    is floor -> load, with no selects and no int -> float conversion;
+//  * the chip row is a float table padded by one entry in front and two behind — tab[0] is what floor = -1 reads (chip 0 in
+//    FAITHFUL mode, the last chip in FIXED mode), tab[len + 1] = chip 0 and tab[len + 2] = chip 1 are what floor = len and
+//    floor = len + 1 read (`% len`; len + 1: power-of-two lengths at spacing 1.0, see fast_code_ok) — so an arm is
+//    floor -> load, with no selects and no int -> float conversion;
 //  * the code phase's conditional subtractions are one unsigned minimum: t >= 0, so of {t, t - len, t - 2 len} the
 //    non-negative ones order like their bit patterns and the negative ones (sign bit set) compare above all of them —
 //    the minimum is the reduced phase, the same value fmod_code<true> selects;
@@ -303,7 +310,7 @@ __device__ __forceinline__ void correlate_sample_fast(const EpochConsts& c, cons
 // scheduler, which kept the samples one after another (least registers): a wave then issued one DEPENDENT instruction per
 // ~8 cycles and sat out an LDS round trip per sample.  Values are bit-identical to the one-sample form.
 // BOC(1,1) (BOC_T): `tab` is the HALF-CHIP table (trk_persistent_kernel: entry j + 2 = chip floor(j / 2) x the sub-carrier sign of
-// half chip j, j = -2 .. 2 len + 1).  An arm's phase p = fl(chip_idx + s) is looked up at j = floor(2 p), and 2 p = fl(2 chip_idx
+// half chip j, j = -2 .. 2 len + 3).  An arm's phase p = fl(chip_idx + s) is looked up at j = floor(2 p), and 2 p = fl(2 chip_idx
 // + 2 s) EXACTLY — binary rounding commutes with the doubling — so one fused multiply-add gives the index of the chip AND of its
 // sub-carrier half: floor(p) = floor(j / 2), fract(p) < 0.5 <=> j even.  Same values as the chip look-up + fract / compare / select
 // of the plain table, bit for bit (the products are exact either way), at 4 instructions per arm instead of 8 (round 6: the
@@ -996,7 +1003,7 @@ __global__ __launch_bounds__(T, TRK_PERSIST_WG_PER_CU * T / 256) void trk_persis
     __shared__ gm_trk_state st_sh[2];
     static_assert(NW >= 4, "waves 0/1 run the two halves of the serial section, waves 2/3 the phase advances");
     __shared__ float gathered[2][256];  // the G*NV partials of one epoch (G other than 16 / 32): one staging area per gathering wave
-    extern __shared__ float chips_pad[];   // the channel's chip row as floats, one guard entry at each end (correlate_sample_fast);
+    extern __shared__ float chips_pad[];   // the channel's chip row as floats, one guard entry in front and two behind (correlate_sample_fast);
     // BOC: the half-chip table (with the sub-carrier sign) in FRONT of it (boc_plain_offset)
     float* const chips = BOC_T == 1 ? chips_pad + boc_plain_offset(cfg.code_len) : chips_pad;
     const float* const fast_tab = chips_pad;
@@ -1030,16 +1037,19 @@ __global__ __launch_bounds__(T, TRK_PERSIST_WG_PER_CU * T / 256) void trk_persis
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int8_t* crow = a.codes + size_t(row) * cfg.code_len;
         for (int i = tid; i < cfg.code_len; i += T) chips[i + 1] = float(crow[i]);
-        if (tid == 0) {   // what floor(phase) = -1 and = len read (get_ca_chip :275: `as usize` saturates / FIXED wraps; `% len`)
+        if (tid == 0) {   // what floor(phase) = -1, = len and = len + 1 read (get_ca_chip :275: `as usize` saturates / FIXED wraps; `% len`)
             chips[0] = float(crow[cfg.code_index_mode == GM_CODE_INDEX_FAITHFUL ? 0 : cfg.code_len - 1]);
             chips[cfg.code_len + 1] = float(crow[0]);
+            chips[cfg.code_len + 2] = float(crow[cfg.code_len > 1 ? 1 : 0]);
         }
-        if constexpr (BOC_T == 1) {   // the half-chip table of correlate_block_fast: entry j + 2 <-> half chip j = -2 .. 2 len + 1
+        if constexpr (BOC_T == 1) {   // the half-chip table of correlate_block_fast: entry j + 2 <-> half chip j = -2 .. 2 len + 3
             float* const t2 = chips_pad;
             for (int j = tid; j < 2 * cfg.code_len; j += T) t2[j + 2] = (j & 1) ? -float(crow[j >> 1]) : float(crow[j >> 1]);
             if (tid == 0) {
                 const float lo = float(crow[cfg.code_index_mode == GM_CODE_INDEX_FAITHFUL ? 0 : cfg.code_len - 1]), hi = float(crow[0]);
+                const float hi1 = float(crow[cfg.code_len > 1 ? 1 : 0]);
                 t2[0] = lo; t2[1] = -lo; t2[2 * cfg.code_len + 2] = hi; t2[2 * cfg.code_len + 3] = -hi;
+                t2[2 * cfg.code_len + 4] = hi1; t2[2 * cfg.code_len + 5] = -hi1;
             }
         }
         // an upper bound of any epoch's sample count in this launch, for the fast forms' range checks
@@ -1520,9 +1530,9 @@ __global__ __launch_bounds__(T, TRK_PERSIST_WG_PER_CU * T / 256) void trk_persis
 // granules per arm in the exchange block (TrkPersistArgs::GS); the block is 2 * n_channels * GS * (2 * arms) granules + n_channels * G
 int trk_persistent_granule_stride(int G) { return G <= 16 ? 16 : G; }
 
-// dynamic LDS of the persistent kernel: the chip row as floats with one guard entry at each end, rounded up to 16 B
+// dynamic LDS of the persistent kernel: the chip row as floats with one guard entry in front and two behind, rounded up to 16 B
 static size_t trk_persistent_lds(const TrkDevCfg& cfg) {
-    size_t floats = size_t(cfg.code_len + 2);                                    // the padded chip row
+    size_t floats = size_t(cfg.code_len) + 3;                                    // the padded chip row
     if (cfg.boc11) floats += size_t(boc_plain_offset(cfg.code_len));             // + the half-chip table of the BOC fast path in front of it
     return (floats * sizeof(float) + 15) & ~size_t(15);
 }
@@ -1641,6 +1651,38 @@ int trk_persistent_blocks_per_cu(const TrkDevCfg& cfg) {
 #undef GM_TRK_OCC
     if (e != hipSuccess || n < 1) n = 1;
     return n < TRK_PERSIST_WG_PER_CU ? n : TRK_PERSIST_WG_PER_CU;
+}
+
+// LDS one workgroup of the persistent kernel asks for with this configuration — the static share of the instantiation it selects
+// (read from the code object) plus the chip tables — and the most the device gives a workgroup.  Asked at gm_trk_create, so that a
+// code too long for the tables is refused there and never reaches a launch.
+hipError_t trk_persistent_lds_need(const TrkDevCfg& cfg, int device, size_t* need, size_t* limit) {
+    const int key = (cfg.n_arms == 5 ? 4 : 0) | (cfg.code_index_mode == GM_CODE_INDEX_FIXED ? 2 : 0) | (cfg.boc11 ? 1 : 0);
+    constexpr int T = TRK_PERSIST_THREADS;
+    hipFuncAttributes fa;
+    hipError_t e = hipSuccess;
+#define GM_TRK_ATTR(A, M, B) \
+    e = cfg.strict_libm ? hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&trk_persistent_kernel<A, M, B, T, 1>)) \
+                        : hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&trk_persistent_kernel<A, M, B, T, 0>)); \
+    break
+    switch (key) {
+        case 0: GM_TRK_ATTR(3, 0, 0);
+        case 1: GM_TRK_ATTR(3, 0, 1);
+        case 2: GM_TRK_ATTR(3, 1, 0);
+        case 3: GM_TRK_ATTR(3, 1, 1);
+        case 4: GM_TRK_ATTR(5, 0, 0);
+        case 5: GM_TRK_ATTR(5, 0, 1);
+        case 6: GM_TRK_ATTR(5, 1, 0);
+        default: GM_TRK_ATTR(5, 1, 1);
+    }
+#undef GM_TRK_ATTR
+    if (e != hipSuccess) return e;
+    int per_block = 0;
+    e = hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+    if (e != hipSuccess) return e;
+    *need = size_t(fa.sharedSizeBytes) + trk_persistent_lds(cfg);
+    *limit = size_t(per_block > 0 ? per_block : 0);
+    return hipSuccess;
 }
 
 template <int ARMS>

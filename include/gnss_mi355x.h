@@ -1029,7 +1029,11 @@ typedef struct {
     int32_t code_index_mode;   /* FAITHFUL: get_ca_chip indexes row `prn` and saturates negative phases to
                                   chip 0 exactly like :274-277; FIXED: row prn-1, wrapping */
     int32_t boc11;             /* 1: multiply the chip by the BOC(1,1) sub-carrier sign (no reference code) */
-    const int8_t *codes;       /* optional [n_codes][code_len] custom +-1 chips (NULL: GPS C/A table) */
+    const int8_t *codes;       /* optional [n_codes][code_len] custom +-1 chips (NULL: GPS C/A table).  The tracking kernel keeps
+                                  a channel's row in LDS as floats: 4 (code_len + 3) bytes, 12 code_len + 48 with boc11, beside
+                                  ~2.6 KB of its own, within the device's LDS per workgroup.  gm_trk_create checks this against
+                                  the kernel and the device it runs on and returns GM_ERR_OUT_OF_RANGE (the sizes in
+                                  gm_last_error) for a code that does not fit; 10 230 chips without boc11 (41 KB) do. */
     uint32_t n_codes, code_len;
     float nominal_code_rate;   /* 0 -> 1.023e6 */
     /* loop constants (:16-27); 0 -> reference value */

@@ -85,17 +85,9 @@ def _compare(mgr, ring, oring, starts, make_oracle, arms, epochs_req, epochs_exp
     return worst
 
 
-@pytest.mark.parametrize("mode,exchange", [(0, "l2"), (1, "l2"), (1, "write-through")])
-def test_cfg3_32_channels_25msps(gpu, oracle, mode, exchange, monkeypatch):
-    """BASELINE configs[2]: 32 channels x 25 Msps, E/P/L (G = 16: the DPP-row totals of trk_persistent_kernel).
-    exchange: "l2" — a channel's workgroups agree on their XCD after the first epoch and publish with plain stores (the
-    form the benchmark runs); "write-through" — the cross-XCD form kept for every epoch (GM_TRK_FORCE_SC1=1), which is
-    what a grid whose workgroups land on different XCDs would run."""
+def _cfg3_case(oracle, mode):
+    """BASELINE configs[2] on a ring -> (mgr, ring, oring, starts, make_oracle, E)"""
     from gnss_sdr_rs_amd import tracking as T, synth
-    if exchange == "write-through":
-        monkeypatch.setenv("GM_TRK_FORCE_SC1", "1")
-    else:
-        monkeypatch.delenv("GM_TRK_FORCE_SC1", raising=False)
     fs, n, C, E = 25.0e6, 25000, 32, 12
     t = oracle.ca_code_table()
     # FAITHFUL indexes GPS_CA_CODE_32_PRN[prn] (do_tracking.rs:276): PRN 32 would index row 32 (the reference panics), so
@@ -112,18 +104,92 @@ def test_cfg3_32_channels_25msps(gpu, oracle, mode, exchange, monkeypatch):
     by_prn = {s["prn"]: s for s in sc["sats"]}
     starts = [_acq_result(p, by_prn[p]["doppler_hz"] + 20.0 - 1.5 * (i // 31), fs, by_prn[p]["code_start"])
               for i, p in enumerate(prns)]
-    w = _compare(mgr, ring, oring, starts, lambda i: oracle.TrackingChannel(i, fs, code_index_mode=mode), 3, E, E)
+    return mgr, ring, oring, starts, lambda i: oracle.TrackingChannel(i, fs, code_index_mode=mode), E
+
+
+# The forced write-through exchange in a process of its own: gm::diag_int reads an override only when the process was STARTED with
+# GM_DIAGNOSTICS=1 (and decides that once), so setting GM_TRK_FORCE_SC1 inside the test process changes nothing.  The child runs the
+# comparison itself and prints the worst fractions, and shows that its gate was open: GM_TRK_STAMP_WG names the workgroup whose
+# phase stamps gm_trk_debug_stamps collects (default: workgroup 0).  Started with a workgroup number the grid does not have, the
+# compared launch — the one that reads GM_TRK_FORCE_SC1 in the same launch_trk_persistent — must leave every stamp zero; with the
+# variable changed to 0 in the same process a second launch must fill them.
+_WRITE_THROUGH_SCRIPT = r"""
+import ctypes as C, json, os, sys
+import numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from oracle import oracle
+from gnss_sdr_rs_amd import _lib, tracking as T
+import test_gpu_tracking_shapes as S
+_lib.init(0)
+L = _lib.lib()
+
+
+def stamped(fn, mgr, E):
+    _lib.check(L.gm_trk_debug_stamps(mgr._h, E, None), "arm")
+    out = fn()
+    buf = np.zeros((E, 48), np.int64)
+    _lib.check(L.gm_trk_debug_stamps(mgr._h, E, buf.ctypes.data_as(C.c_void_p)), "read")
+    return out, int(np.count_nonzero(buf))
+
+
+assert os.environ["GM_DIAGNOSTICS"] == "1" and os.environ["GM_TRK_FORCE_SC1"] == "1" and int(os.environ["GM_TRK_STAMP_WG"]) >= 1 << 20
+mgr, ring, oring, starts, mk, E = S._cfg3_case(oracle, 1)
+worst, moved = stamped(lambda: S._compare(mgr, ring, oring, starts, mk, 3, E, E), mgr, E)
+mgr.close()
+os.environ["GM_TRK_STAMP_WG"] = "0"
+mgr = T.TrackingManager(25.0e6, n_channels=len(starts), code_index_mode=1)        # the same channels on the same ring
+for i, r in enumerate(starts):
+    mgr.channels[i].start(r)
+done, default = stamped(lambda: mgr.update_all(ring, 2)[3], mgr, 2)
+mgr.close(); ring.close()
+print(json.dumps(dict(worst=worst, stamps_with_absent_workgroup=moved, stamps_with_workgroup_0=default, done=int(done))))
+"""
+
+
+@pytest.mark.parametrize("mode,exchange", [(0, "l2"), (1, "l2"), (1, "write-through")])
+def test_cfg3_32_channels_25msps(gpu, oracle, mode, exchange, monkeypatch):
+    """BASELINE configs[2]: 32 channels x 25 Msps, E/P/L (G = 16: the DPP-row totals of trk_persistent_kernel).
+    exchange: "l2" — a channel's workgroups agree on their XCD after the first epoch and publish with plain stores (the
+    form the benchmark runs); "write-through" — the cross-XCD form kept for every epoch (GM_TRK_FORCE_SC1=1), which is
+    what a grid whose workgroups land on different XCDs would run.
+
+    The write-through case runs in a child process started with GM_DIAGNOSTICS=1 GM_TRK_FORCE_SC1=1 (see _WRITE_THROUGH_SCRIPT): the
+    same _compare, the same bars, asserted in the child.  What its gate check proves: the child's library honoured a GM_TRK_*
+    override read by the very launch that was compared (launch_trk_persistent reads GM_TRK_STAMP_WG and GM_TRK_FORCE_SC1 side by
+    side), so force_write_through was 1 in that launch.  What it does not prove: that the two store forms differ in effect on this
+    placement (they give the same sums by design — only their route through the memory system differs), nor anything about a grid
+    whose workgroups really sit on different XCDs: here they share one, and only the exchange form is forced."""
+    if exchange == "write-through":
+        import json
+        import os
+        import subprocess
+        import sys
+        from conftest import ROOT
+        env = {k: v for k, v in os.environ.items() if not k.startswith("GM_")}
+        env.update(GM_DIAGNOSTICS="1", GM_TRK_FORCE_SC1="1", GM_TRK_STAMP_WG=str(1 << 20))
+        r = subprocess.run([sys.executable, "-c", _WRITE_THROUGH_SCRIPT % (ROOT, os.path.join(ROOT, "tests"))], env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        got = json.loads(r.stdout.strip().splitlines()[-1])
+        print("cfg3 mode", mode, "write-through (child)", got)
+        assert got["stamps_with_absent_workgroup"] == 0 and got["stamps_with_workgroup_0"] > 0 and got["done"] == 2, got
+        w = got["worst"]
+        assert w["forced"] <= REL and w["f64"] <= F64_REL and w["free"] <= FREE_REL and w["ulps"] == 0, w
+        return
+    monkeypatch.delenv("GM_TRK_FORCE_SC1", raising=False)
+    mgr, ring, oring, starts, mk, E = _cfg3_case(oracle, mode)
+    w = _compare(mgr, ring, oring, starts, mk, 3, E, E)
     print("cfg3 mode", mode, w)
     mgr.close(); ring.close()
 
 
-def _boc_scene(codes, fs, rate, L, n_samples, dopp, starts, amp=0.6, sigma=8.0, seed=5):
+def _boc_scene(codes, fs, rate, L, n_samples, dopp, starts, amp=0.6, sigma=8.0, seed=5, boc=True):
     tt = np.arange(n_samples, dtype=np.float64)
     rng = np.random.default_rng(seed)
     x = (rng.standard_normal(n_samples) + 1j * rng.standard_normal(n_samples)) * sigma
     for c in range(codes.shape[0]):
         cp = ((tt - starts[c]) * rate / fs) % L
-        sub = np.where((cp - np.floor(cp)) < 0.5, 1.0, -1.0)
+        sub = np.where((cp - np.floor(cp)) < 0.5, 1.0, -1.0) if boc else 1.0      # boc = False: the same scene without the sub-carrier
         x += amp * codes[c][np.floor(cp).astype(np.int64)] * sub * np.exp(2j * np.pi * dopp[c] * tt / fs + 0.3j * c)
     return x.astype(np.complex64)
 
