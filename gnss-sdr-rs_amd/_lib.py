@@ -266,6 +266,7 @@ SIGNATURES = {
     "gm_frontend_synchronize": (_i, [_vp]),
     "gm_frontend_write_ring": (_i, [_vp, _vp, _vp, _sz, _i]),
     "gm_frontend_debug_repairs": (_i, [_vp, C.POINTER(_u32)]),
+    "gm_frontend_debug_forms": (_i, [_vp, C.POINTER(_u32)]),
     "gm_resampler_plan": (_i, [C.POINTER(ResamplerCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32),
                            C.POINTER(_u64)]),
     "gm_resampler_design": (_i, [C.POINTER(ResamplerCfg), _vp]),

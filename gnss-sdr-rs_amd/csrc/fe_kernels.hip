@@ -303,7 +303,9 @@ __global__ __launch_bounds__(FF_T) void frontend_fast_kernel(FrontendArgs a) {
         load_sample<FMT>(st.in, i, o.x, o.y);
         reinterpret_cast<float2*>(st.out)[(st.out_start + i) & st.out_mask] = o;
     }
-    if (tid == 0) st.state->phase_accumulator = st.ph_table[st.tab_pos_end] * st.tab_scale;   // -0.0 for a negative chain on 0
+    // -0.0 for a negative chain on 0; a block without a whole chunk has not stepped the chain: its phase keeps its bits (+0.0 on a fresh
+    // handle, whatever zero was set), which entry 0 of the table times +-2048 need not be
+    if (tid == 0 && n8) st.state->phase_accumulator = st.ph_table[st.tab_pos_end] * st.tab_scale;
     if (tid < 16) { if (tid < 8) st.state->bias_re[tid] = bias; else st.state->bias_im[tid - 8] = bias; }
 }
 

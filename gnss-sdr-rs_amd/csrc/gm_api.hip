@@ -3426,6 +3426,7 @@ struct gm_frontend {
     uint32_t tab_mu = 0, tab_lambda = 0;           // lambda' = the period repeated until >= FE_FAST_SEG
     uint32_t pos = 0;                              // table index of the next sample
     float* d_spec = nullptr;                       // [FE_SPEC_K][32] + 1 floats: the speculative form's run records (fe_kernels.hip)
+    uint32_t forms[3] = {0, 0, 0};                 // launches on behalf of this handle: sequential, table, speculative (gm_frontend_debug_forms)
 };
 static constexpr int FE_SPEC_K = gm::FE_SPEC_K_MAX;
 static constexpr size_t FE_SPEC_MIN = size_t(gm::FE_FAST_SEG) * 48;     // blocks shorter than 48 pipeline segments stay on one workgroup
@@ -3513,8 +3514,9 @@ static int frontend_launch(gm_frontend* f, hipStream_t st, const void* d_in, int
         a.spec_buf = f->d_spec; a.spec_poison = spec == 2 ? 1 : 0;
         a.spec_repairs = reinterpret_cast<unsigned int*>(f->d_spec + size_t(FE_SPEC_K) * 32);
         gm::launch_frontend_spec(st, a, fmt);
-    } else if (a.one.ph_table) gm::launch_frontend_fast(st, a, 1, fmt);
-    else gm::launch_frontend(st, a, 1, fmt);
+        ++f->forms[2];
+    } else if (a.one.ph_table) { gm::launch_frontend_fast(st, a, 1, fmt); ++f->forms[1]; }
+    else { gm::launch_frontend(st, a, 1, fmt); ++f->forms[0]; }
     HIPC(hipGetLastError());
     return GM_OK;
 }
@@ -3564,6 +3566,12 @@ int gm_frontend_debug_repairs(gm_frontend* f, uint32_t* runs) {
     if (int rc = ensure_device(f->device)) return rc;
     HIPC(hipDeviceSynchronize());
     HIPC(hipMemcpy(runs, f->d_spec + size_t(FE_SPEC_K) * 32, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+int gm_frontend_debug_forms(gm_frontend* f, uint32_t counts[3]) {
+    if (!f || !counts) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    memcpy(counts, f->forms, sizeof(f->forms));
     return GM_OK;
 }
 
@@ -3669,6 +3677,7 @@ int gm_frontend_process_dev_batch(gm_frontend* const* fes, uint32_t n_streams, c
     for (uint32_t i = 0; i < n_streams; ++i) all_fast = all_fast && h[i].ph_table != nullptr;
     if (all_fast) gm::launch_frontend_fast(st, a, int(n_streams), fmt);
     else gm::launch_frontend(st, a, int(n_streams), fmt);
+    for (uint32_t i = 0; i < n_streams; ++i) ++fes[i]->forms[all_fast ? 1 : 0];      // the launched form, once for every member
     HIPC(hipGetLastError());
     return GM_OK;
 }

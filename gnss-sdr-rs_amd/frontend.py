@@ -65,6 +65,12 @@ class DigitalFrontend:
         check(lib().gm_frontend_debug_repairs(self._h, C.byref(n)), "gm_frontend_debug_repairs")
         return n.value
 
+    def debug_forms(self):
+        """launches on behalf of this handle since create, by kernel form: (sequential, table, speculative) (diagnostic)"""
+        c = (C.c_uint32 * 3)()
+        check(lib().gm_frontend_debug_forms(self._h, c), "gm_frontend_debug_forms")
+        return tuple(c)
+
     def write_ring(self, ring, samples, resampler=None, excisor=None):
         """samples: complex64 array, or int8 array of interleaved I/Q.  With a resample.Resampler the block goes through it on its way
         into the ring (gm_frontend_write_ring_resampled): ring indices then count output samples, and the outputs enqueued are returned.

@@ -3,6 +3,7 @@
 // reference (file:line in the comments) so call sites port one to one; errors the reference turns into panics
 // become gnss::Panic exceptions HERE (above the ABI — nothing unwinds across it).
 #pragma once
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <complex>
@@ -464,6 +465,7 @@ public:
         return total;
     }
     uint32_t debug_repairs() const { uint32_t n = 0; check(gm_frontend_debug_repairs(h_, &n), "debug_repairs"); return n; }   // runs of the speculative form done again
+    std::array<uint32_t, 3> debug_forms() const { std::array<uint32_t, 3> c{}; check(gm_frontend_debug_forms(h_, c.data()), "debug_forms"); return c; }   // launches: sequential, table, speculative
 };
 
 // ---- decoding::NavSyncStatus + nav_decoding's per-epoch step up to frame sync (src/decoding.rs:40-227, legacy)

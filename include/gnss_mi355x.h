@@ -701,6 +701,11 @@ int gm_frontend_write_ring(gm_frontend *f, gm_ring *ring, const void *samples, s
  * (tests/test_gpu_frontend.py::test_speculative_blocks_are_exact spoils every one of them); 0.52 -> 0.15 ms per 2^19-sample block.
  * Diagnostic (not in the reference): *runs = how many runs the verification has had to repeat on this handle so far. */
 int gm_frontend_debug_repairs(gm_frontend *f, uint32_t *runs);
+/* Diagnostic (not in the reference; host counters, no device traffic): kernel launches on behalf of this handle since create, by the
+ * form that ran: counts[0] the sequential kernel (no phase table, a phase set off the tabulated orbit, or a batch with such a member),
+ * counts[1] the table form, counts[2] the speculative form.  A batch counts the launched form once for every member.
+ * (tests/test_gpu_frontend_forms.py asserts with it that each form ran where it was meant to.) */
+int gm_frontend_debug_forms(gm_frontend *f, uint32_t counts[3]);
 
 /* ------------------------------------------------------------------ Rate conversion and pulse blanking
  * The two stages the reference's front-end names and leaves out (rf/frontend.rs: process_block ends with the comments

@@ -89,6 +89,10 @@ def test_null_handles_are_refused_not_dereferenced(gm):
     assert L.gm_trk_get_states(None, C.cast(st, C.c_void_p)) == -1 and L.gm_trk_set_states(None, C.cast(st, C.c_void_p), None) == -1
     assert L.gm_ring_get_enqueued_head(None, C.byref(h)) == -1 and h.value == 9
     assert L.gm_frontend_debug_repairs(None, C.byref(runs)) == -1 and runs.value == 9
+    # the front-end's form counters (an additive export): null handle, and a null array
+    forms = (C.c_uint32 * 3)(9, 9, 9)
+    assert L.gm_frontend_debug_forms(None, forms) == -1 and list(forms) == [9, 9, 9]
+    assert b"null pointer" in L.gm_last_error()
 
 
 def test_ca_table_and_resampler_host(gm, oracle):
