@@ -7,6 +7,7 @@ include/gnss_mi355x.h.  This Python package is plumbing around it:
   frontend / resample            the digital front-end, and the rate conversion and pulse blanking it leaves out
   excise                         FFT-domain narrowband interference excision (overlap-add filter bank, adaptive per-bin gains)
   ddc                            real-IF int8 down-conversion to complex baseband (exact NCO, the resampler's polyphase filter)
+  channelizer                    polyphase filter bank: M sub-bands of one stream (FDMA carriers), and the GLONASS L1OF code
   synth       deterministic synthetic IF scenes
   build       hipcc build recipe
 """
@@ -15,3 +16,4 @@ from ._lib import GmError, lib, library_path  # noqa: F401
 from .resample import Resampler  # noqa: F401
 from .excise import Excisor  # noqa: F401
 from .ddc import Ddc  # noqa: F401
+from .channelizer import Channelizer  # noqa: F401

@@ -104,6 +104,13 @@ class DdcCfg(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class ChannelizerCfg(C.Structure):
+    """gm_channelizer_cfg (40 bytes): zeros are the defaults; out_channels points at n_out_channels uint32 words, or is NULL"""
+    _fields_ = [("n_channels", C.c_uint32), ("decim", C.c_uint32), ("taps_per_branch", C.c_uint32), ("cutoff", C.c_float),
+                ("kaiser_beta", C.c_float), ("blank_threshold", C.c_float), ("n_out_channels", C.c_uint32), ("reserved", C.c_uint32),
+                ("out_channels", C.POINTER(C.c_uint32))]
+
+
 class ExcisorCfg(C.Structure):
     """gm_excisor_cfg (32 bytes): zeros are the defaults"""
     _fields_ = [("block", C.c_uint32), ("guard_bins", C.c_uint32), ("threshold_factor", C.c_float), ("blank_threshold", C.c_float),
@@ -308,6 +315,17 @@ SIGNATURES = {
     "gm_ddc_process_dev": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
     "gm_ddc_process": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gm_ddc_write_ring": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_u64)]),
+    "gm_channelizer_plan": (_i, [C.POINTER(ChannelizerCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u64)]),
+    "gm_channelizer_design": (_i, [C.POINTER(ChannelizerCfg), _vp]),
+    "gm_channelizer_create": (_i, [C.POINTER(ChannelizerCfg), C.POINTER(_vp)]),
+    "gm_channelizer_destroy": (_i, [_vp]),
+    "gm_channelizer_reset": (_i, [_vp, _u64]),
+    "gm_channelizer_taps": (_i, [_vp, _vp]),
+    "gm_channelizer_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_channelizer_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, _sz, C.POINTER(_sz), _vp]),
+    "gm_channelizer_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "gm_channelizer_synchronize": (_i, [_vp]),
+    "gm_glonass_code": (_i, [_vp]),
     "gm_trk_create": (_i, [C.POINTER(TrkCfg), C.POINTER(_vp)]),
     "gm_trk_destroy": (_i, [_vp]),
     "gm_trk_start": (_i, [_vp, _u32, C.POINTER(AcqResult)]),

@@ -3820,11 +3820,14 @@ int stage_check_overlap(const void* d_in, size_t in_bytes, const void* d_out, ui
     if (cnt && in_bytes && i0 < o1 && o0 < i1) return set_err(GM_ERR_INVALID_ARG, "d_out overlaps d_in");
     return GM_OK;
 }
-// The host-buffer entries behind their checks: grow the staging, H2D, `launch(stream, d_in, d_out)`, D2H, wait.
+// The host-buffer entries behind their checks: grow the staging, H2D, `launch(stream, d_in, d_out)`, D2H, wait.  A stage with several
+// output planes (the channelizer) stages them as [planes][per_plane] and delivers plane i at out + i * out_pitch.
 template <class Launch>
-int stage_process(StreamStage* s, const void* in, size_t in_bytes, gm_c32* out, uint64_t cnt, size_t* n_out, Launch&& launch) {
-    if (n_out) *n_out = size_t(cnt);
+int stage_process(StreamStage* s, const void* in, size_t in_bytes, gm_c32* out, uint64_t per_plane, size_t* n_out, Launch&& launch,
+                  uint64_t planes = 1, size_t out_pitch = 0) {
+    if (n_out) *n_out = size_t(per_plane);
     if (!in_bytes) return GM_OK;
+    const uint64_t cnt = per_plane * planes;
     if (int rc = ensure_device(s->device)) return rc;
     if (s->in_cap < in_bytes || s->out_cap < cnt) HIPC(hipStreamSynchronize(s->stream));
     if (s->in_cap < in_bytes) {
@@ -3840,7 +3843,9 @@ int stage_process(StreamStage* s, const void* in, size_t in_bytes, gm_c32* out, 
     if (int rc = stage_join(s, s->stream)) return rc;
     HIPC(hipMemcpyAsync(s->d_in, in, in_bytes, hipMemcpyHostToDevice, s->stream));
     if (int rc = launch(s->stream, s->d_in, s->d_out)) return rc;
-    if (cnt) HIPC(hipMemcpyAsync(out, s->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, s->stream));
+    if (cnt && planes == 1) HIPC(hipMemcpyAsync(out, s->d_out, size_t(cnt) * sizeof(cf), hipMemcpyDeviceToHost, s->stream));
+    for (uint64_t i = 0; cnt && planes > 1 && i < planes; ++i)
+        HIPC(hipMemcpyAsync(out + i * out_pitch, s->d_out + i * per_plane, size_t(per_plane) * sizeof(cf), hipMemcpyDeviceToHost, s->stream));
     HIPC(hipStreamSynchronize(s->stream));
     return GM_OK;
 }
@@ -4629,6 +4634,218 @@ int gm_ddc_write_ring(gm_ddc* d, gm_excisor* x, gm_resampler* rs, gm_ring* r, co
         if (int rc = ddc_launch(d, r->fe_stream, d_raw, chunk, d->d_scratch, 0, ~0ull, *cnt)) return rc;
         return chain_launch(x, rs, r, d->d_scratch, *cnt, cnt);
     });
+}
+
+}  // extern "C"
+
+// ====================================================================== polyphase filter bank (gm_channelizer)
+// gnss_mi355x.h states the definition; tests/channelizer_model.py restates it in float64.
+namespace {
+struct ChannelizerPlan {
+    uint32_t M = 0, D = 0, P = 0, L = 0, C = 0;
+    uint32_t channels[gm::CH_M_MAX] = {};
+    double cutoff = 0.9, beta = 8.0;
+    float thr = 0.0f;
+};
+
+int channelizer_rules(const gm_channelizer_cfg* c, ChannelizerPlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    if (c->reserved) return set_err(GM_ERR_INVALID_ARG, "gm_channelizer_cfg.reserved must be 0");
+    const uint32_t M = c->n_channels;
+    if (M != 4 && M != 8 && M != 16 && M != 32 && M != 64) return set_err(GM_ERR_INVALID_ARG, "n_channels: 4, 8, 16, 32 or 64");
+    if (c->decim < 1 || c->decim > M) return set_err(GM_ERR_INVALID_ARG, "decim: 1 .. n_channels");
+    if (c->taps_per_branch && (c->taps_per_branch < 2 || c->taps_per_branch > 32)) return set_err(GM_ERR_INVALID_ARG, "taps_per_branch: 2 .. 32, 0 for the default");
+    if (!std::isfinite(c->cutoff) || !std::isfinite(c->kaiser_beta) || !std::isfinite(c->blank_threshold))
+        return set_err(GM_ERR_INVALID_ARG, "cutoff, kaiser_beta and blank_threshold must be finite");
+    if (!(c->cutoff >= 0.0f && c->cutoff <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "cutoff: (0, 1], 0 for the default");
+    if (!(c->kaiser_beta >= 0.0f && c->kaiser_beta <= 20.0f)) return set_err(GM_ERR_INVALID_ARG, "kaiser_beta: [0, 20]");
+    if (!(c->blank_threshold >= 0.0f)) return set_err(GM_ERR_INVALID_ARG, "blank_threshold: >= 0");
+    p.M = M; p.D = c->decim; p.P = c->taps_per_branch ? c->taps_per_branch : 16; p.L = p.M * p.P;
+    if (c->n_out_channels == 0) {
+        if (c->out_channels) return set_err(GM_ERR_INVALID_ARG, "out_channels without n_out_channels");
+        p.C = M;
+        for (uint32_t k = 0; k < M; ++k) p.channels[k] = k;
+    } else {
+        if (c->n_out_channels > M || !c->out_channels) return set_err(GM_ERR_INVALID_ARG, "n_out_channels: at most n_channels, with the list");
+        uint64_t seen = 0;
+        for (uint32_t i = 0; i < c->n_out_channels; ++i) {
+            const uint32_t k = c->out_channels[i];
+            if (k >= M) return set_err(GM_ERR_INVALID_ARG, "out_channels: an index outside 0 .. n_channels - 1");
+            if (seen >> k & 1) return set_err(GM_ERR_INVALID_ARG, "out_channels: an index listed twice");
+            seen |= 1ull << k;
+            p.channels[i] = k;
+        }
+        p.C = c->n_out_channels;
+    }
+    p.cutoff = c->cutoff == 0.0f ? 0.9 : double(c->cutoff);
+    p.beta = c->kaiser_beta == 0.0f ? 8.0 : double(c->kaiser_beta);
+    p.thr = c->blank_threshold;
+    return GM_OK;
+}
+
+// total_out(A) = max(0, ceil((A - L/2) / D))
+uint64_t channelizer_total_out(const ChannelizerPlan& p, uint64_t A) {
+    const uint64_t half = p.L / 2;
+    return A <= half ? 0 : (A - half + p.D - 1) / p.D;
+}
+
+void channelizer_design(const ChannelizerPlan& p, float* g) {
+    const double PI = 3.14159265358979323846;
+    const double fc = p.cutoff / double(p.D), inv_i0 = 1.0 / bessel_i0(p.beta), halfL = 0.5 * double(p.L);
+    std::vector<double> h(p.L);
+    double sum = 0.0;
+    for (uint32_t j = 0; j < p.L; ++j) {
+        const double t = double(j) - (halfL - 1.0);
+        const double u = t / halfL, w = 1.0 - u * u, x = fc * t;
+        const double sinc = x == 0.0 ? 1.0 : sin(PI * x) / (PI * x);
+        h[j] = fc * sinc * bessel_i0(p.beta * sqrt(w > 0.0 ? w : 0.0)) * inv_i0;      // |t| <= L/2 for every j
+        sum += h[j];
+    }
+    for (uint32_t j = 0; j < p.L; ++j) g[j] = float(h[j] / sum);
+}
+}  // namespace
+
+struct gm_channelizer : StreamStage {       // history: the last L blanked inputs (cf)
+    ChannelizerPlan plan;
+    std::vector<float> taps;                // [L]
+    float* d_taps = nullptr;
+    cf* d_rot = nullptr;                    // [M] exp(-j 2 pi e / M)
+};
+
+// one call's kernels on `st`, plane i to out + i * out_stride; the caller has checked every argument; n_in > 0
+static int channelizer_launch(gm_channelizer* c, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t out_stride,
+                              uint64_t n_out) {
+    const ChannelizerPlan& p = c->plan;
+    const uint64_t A = c->base + c->inputs;
+    gm::ChannelizerArgs a{};
+    a.in = d_in; a.n_in = n_in;
+    a.hist_in = static_cast<const cf*>(c->d_hist[c->cur]); a.hist_out = static_cast<cf*>(c->d_hist[c->cur ^ 1]);
+    a.taps = c->d_taps; a.rot = c->d_rot;
+    a.M = p.M; a.D = p.D; a.P = p.P; a.L = p.L;
+    a.m0 = channelizer_total_out(p, A); a.in_index = A;
+    a.n_out = n_out; a.tile_out = gm::channelizer_tile_out(p.L, p.D);
+    a.pad_shift = p.D % 64 == 0 ? 6 : 5;
+    a.out = out; a.out_stride = out_stride;
+    for (int k = 0; k < gm::CH_M_MAX; ++k) a.plane_of[k] = -1;
+    for (uint32_t i = 0; i < p.C; ++i) a.plane_of[p.channels[i]] = int8_t(i);
+    a.thr2 = p.thr * p.thr; a.blank = p.thr > 0.0f ? 1 : 0;
+    a.blanked = c->d_blanked;
+    gm::launch_channelizer(st, a, fmt);
+    return stage_launched(c, st, n_in, n_out);
+}
+static uint64_t channelizer_count(const gm_channelizer* c, uint64_t n_in) {
+    const uint64_t A = c->base + c->inputs;
+    return channelizer_total_out(c->plan, A + n_in) - channelizer_total_out(c->plan, A);
+}
+static const char* channelizer_fmt_err(int fmt) {
+    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "channelizer input is c32 or int8 IQ (a real stream takes a gm_ddc in front)" : nullptr;
+}
+
+extern "C" {
+
+int gm_channelizer_plan(const gm_channelizer_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* n_out_channels,
+                        uint32_t* taps_per_branch, uint32_t* n_taps, uint64_t* n_out) {
+    ChannelizerPlan p;
+    if (int rc = channelizer_rules(cfg, p)) return rc;
+    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (n_out_channels) *n_out_channels = p.C;
+    if (taps_per_branch) *taps_per_branch = p.P;
+    if (n_taps) *n_taps = p.L;
+    if (n_out) *n_out = channelizer_total_out(p, inputs_so_far + n_in) - channelizer_total_out(p, inputs_so_far);
+    return GM_OK;
+}
+
+int gm_channelizer_design(const gm_channelizer_cfg* cfg, float* taps) {
+    ChannelizerPlan p;
+    if (int rc = channelizer_rules(cfg, p)) return rc;
+    if (!taps) return set_err(GM_ERR_INVALID_ARG, "null taps");
+    channelizer_design(p, taps);
+    return GM_OK;
+}
+
+int gm_channelizer_create(const gm_channelizer_cfg* cfg, gm_channelizer** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    ChannelizerPlan p;
+    if (int rc = channelizer_rules(cfg, p)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_channelizer* c = new gm_channelizer;
+    c->device = g_device; c->plan = p;
+    c->taps.resize(p.L);
+    channelizer_design(p, c->taps.data());
+    std::vector<cf> rot(p.M);
+    for (uint32_t e = 0; e < p.M; ++e) {
+        const gm::ct::cs v = gm::ct::cossin2pi(long(e), long(p.M));
+        rot[e] = gm::cf_make(float(v.c), float(-v.s));
+    }
+    hipError_t e = hipMalloc(&c->d_taps, p.L * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(c->d_taps, c->taps.data(), p.L * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_rot), p.M * sizeof(cf));
+    if (e == hipSuccess) e = hipMemcpy(c->d_rot, rot.data(), p.M * sizeof(cf), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = stage_create(c, size_t(p.L) * sizeof(cf));
+    if (e != hipSuccess) { gm_channelizer_destroy(c); return hip_fail(e, "gm_channelizer_create"); }
+    *out = c;
+    return GM_OK;
+}
+
+int gm_channelizer_destroy(gm_channelizer* c) {
+    if (!c) return GM_OK;
+    stage_destroy(c);
+    hipFree(c->d_taps); hipFree(c->d_rot);
+    delete c;
+    return GM_OK;
+}
+
+int gm_channelizer_reset(gm_channelizer* c, uint64_t input_index) {
+    return stage_reset(c, input_index, [] { return hipSuccess; });
+}
+
+int gm_channelizer_taps(gm_channelizer* c, float* taps) {
+    if (!c || !taps) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    memcpy(taps, c->taps.data(), c->taps.size() * sizeof(float));
+    return GM_OK;
+}
+
+int gm_channelizer_stats(gm_channelizer* c, uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) {
+    return stage_stats(c, inputs, outputs, blanked);
+}
+
+int gm_channelizer_process_dev(gm_channelizer* c, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_stride, size_t out_cap,
+                               size_t* n_out, void* stream) {
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(c, channelizer_count, channelizer_fmt_err(fmt), d_in, n_in, d_out, out_cap, "gm_channelizer_plan", &cnt)) return rc;
+    if (out_stride < out_cap) return set_err(GM_ERR_OUT_OF_RANGE, "out_stride below out_cap");
+    if (cnt)
+        if (int rc = stage_check_overlap(d_in, n_in * (fmt == GM_FMT_C32 ? 8 : 2), d_out, uint64_t(c->plan.C) * out_stride)) return rc;
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(c->device)) return rc;
+    return channelizer_launch(c, stream ? static_cast<hipStream_t>(stream) : c->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), out_stride, cnt);
+}
+
+int gm_channelizer_process(gm_channelizer* c, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out) {
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(c, channelizer_count, channelizer_fmt_err(fmt), in, n_in, out, out_cap, "gm_channelizer_plan", &cnt)) return rc;
+    return stage_process(c, in, n_in * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
+        return channelizer_launch(c, st, d_in, fmt, n_in, d_out, cnt, cnt);
+    }, c->plan.C, out_cap);
+}
+
+int gm_channelizer_synchronize(gm_channelizer* c) { return stage_synchronize(c); }
+
+// The GLONASS L1OF ranging code: nine stages, all ones; each clock the output is stage 7, then stage 5 xor stage 9 enters stage 1
+int gm_glonass_code(int8_t* out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    unsigned s[10];
+    for (int i = 1; i <= 9; ++i) s[i] = 1;
+    for (int n = 0; n < 511; ++n) {
+        out[n] = s[7] ? -1 : 1;              // +1 stands for logic 0
+        const unsigned in = s[5] ^ s[9];
+        for (int i = 9; i > 1; --i) s[i] = s[i - 1];
+        s[1] = in;
+    }
+    return GM_OK;
 }
 
 }  // extern "C"

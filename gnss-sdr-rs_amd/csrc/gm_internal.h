@@ -436,6 +436,33 @@ struct DdcArgs {
 };
 void launch_ddc(hipStream_t, const DdcArgs&);
 
+// ---------------------------------------------------------------- polyphase filter bank (channelizer_kernels.hip)
+// gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of `tile_out` output times) and
+// one of the state kernel (the next history, the blanked count).  The host hands over the absolute index m0 of the call's first output
+// time and that of the call's first input; the kernel forms every position from 64-bit integers.
+constexpr int CH_SPAN_MAX = 4096;          // LDS samples of a tile's input span; tile_out is chosen so that (tile_out - 1) D + L fits
+constexpr int CH_M_MAX = 64;
+struct ChannelizerArgs {
+    const void* in; uint64_t n_in;         // this call's inputs (c32 or int8 IQ)
+    const cf* hist_in; cf* hist_out;       // [L] the last L blanked inputs before / after this call (two buffers, used alternately)
+    const float* taps;                     // [L] the prototype filter
+    const cf* rot;                         // [M] exp(-j 2 pi e / M)
+    uint32_t M, D, P, L;
+    uint64_t m0;                           // absolute index of the call's first output time
+    uint64_t in_index;                     // absolute index of the call's first input
+    uint64_t n_out; uint32_t tile_out;     // output times of the call; per workgroup
+    uint32_t pad_shift;                    // LDS word of sample i of a tile: i + (i >> pad_shift); >= 5
+    cf* out; uint64_t out_stride;          // [C][out_stride]
+    int8_t plane_of[CH_M_MAX];             // the plane of channel k, -1: not listed
+    float thr2; int blank;                 // blank_threshold^2 (f32 product); blanking on
+    unsigned long long* blanked;           // device counter, integer atomics only
+};
+inline uint32_t channelizer_tile_out(uint32_t L, uint32_t D) {
+    const uint32_t n = (uint32_t(CH_SPAN_MAX) - L) / D + 1;      // the most output times whose inputs span <= CH_SPAN_MAX samples (L <= 2048)
+    return n >= 1024 ? 1024u : n >= 512 ? 512u : n >= 256 ? 256u : n;
+}
+void launch_channelizer(hipStream_t, const ChannelizerArgs&, int fmt);
+
 // ---------------------------------------------------------------- narrowband interference excision (excise_kernels.hip)
 // gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of G segments of H = B / 2
 // outputs) and one of the state kernel (the next history of 3H blanked inputs, the blanked count).  The host hands over where the

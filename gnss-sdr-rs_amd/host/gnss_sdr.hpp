@@ -429,6 +429,69 @@ public:
     void synchronize() { check(gm_ddc_synchronize(h_), "Ddc::synchronize"); }
 };
 
+// ---- polyphase filter bank (gm_channelizer): M sub-bands of one complex stream, each its own Complex32 stream at fs / D; channel k is
+// centred at k fs / M.  Every output is defined by absolute sample indices.  With glonass_code() the front of a GLONASS L1OF search:
+// fourteen FDMA carriers of one capture, one plane each, a plane pointer going straight into Acquisition's device search.
+class Channelizer {
+    gm_channelizer* h_ = nullptr;
+    uint32_t planes_ = 0, decim_ = 1;
+public:
+    // channels empty: all n_channels in order; every other setting at its default unless given in a cfg
+    Channelizer(uint32_t n_channels, uint32_t decim, const std::vector<uint32_t>& channels = {}, float blank_threshold = 0.0f) {
+        gm_channelizer_cfg cfg{};
+        cfg.n_channels = n_channels; cfg.decim = decim; cfg.blank_threshold = blank_threshold;
+        cfg.n_out_channels = uint32_t(channels.size()); cfg.out_channels = channels.empty() ? nullptr : channels.data();
+        init(cfg);
+    }
+    explicit Channelizer(const gm_channelizer_cfg& cfg) { init(cfg); }
+    ~Channelizer() { gm_channelizer_destroy(h_); }
+    Channelizer(const Channelizer&) = delete;
+    gm_channelizer* handle() const { return h_; }
+    uint32_t planes() const { return planes_; }
+    // the L1OF ranging code, 511 chips (+1 for logic 0), and the channel indices of its carriers k = -7 .. 6 in a bank of n_channels
+    static std::vector<int8_t> glonass_code() {
+        std::vector<int8_t> chips(511);
+        check(gm_glonass_code(chips.data()), "Channelizer::glonass_code");
+        return chips;
+    }
+    static std::vector<uint32_t> glonass_channels(uint32_t n_channels) {
+        std::vector<uint32_t> ch;
+        for (int k = -7; k <= 6; ++k) ch.push_back(uint32_t((k + int(n_channels)) % int(n_channels)));
+        return ch;
+    }
+    // the synchronous host-buffer form: this call's outputs, [planes][*n_out] behind each other
+    std::vector<Complex32> process(const void* in, int fmt, size_t n, size_t* n_out) {
+        const size_t cap = n / decim_ + 2;                                  // a call never delivers more than n / D + 1
+        std::vector<Complex32> out(size_t(planes_) * cap), packed;
+        size_t got = 0;
+        check(gm_channelizer_process(h_, in, fmt, n, reinterpret_cast<gm_c32*>(out.data()), cap, &got), "Channelizer::process");
+        for (uint32_t i = 0; i < planes_; ++i) packed.insert(packed.end(), out.begin() + i * cap, out.begin() + i * cap + got);
+        if (n_out) *n_out = got;
+        return packed;
+    }
+    // device pointers, d_out [planes][out_stride]; asynchronous on `stream` (nullptr: the handle's own); returns the outputs written per plane
+    size_t process_dev(const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_stride, size_t out_cap, void* stream = nullptr) {
+        size_t n = 0;
+        check(gm_channelizer_process_dev(h_, d_in, fmt, n_in, d_out, out_stride, out_cap, &n, stream), "Channelizer::process_dev");
+        return n;
+    }
+    void reset(uint64_t input_index = 0) { check(gm_channelizer_reset(h_, input_index), "Channelizer::reset"); }
+    void stats(uint64_t* inputs, uint64_t* outputs, uint64_t* blanked) const { check(gm_channelizer_stats(h_, inputs, outputs, blanked), "Channelizer::stats"); }
+    std::vector<float> taps() const {
+        std::vector<float> g(n_taps_);
+        check(gm_channelizer_taps(h_, g.data()), "Channelizer::taps");
+        return g;
+    }
+    void synchronize() { check(gm_channelizer_synchronize(h_), "Channelizer::synchronize"); }
+private:
+    uint32_t n_taps_ = 0;
+    void init(const gm_channelizer_cfg& cfg) {
+        check(gm_channelizer_plan(&cfg, 0, 0, &planes_, nullptr, &n_taps_, nullptr), "Channelizer::new");
+        decim_ = cfg.decim;
+        check(gm_channelizer_create(&cfg, &h_), "Channelizer::new");
+    }
+};
+
 // ---- rf::frontend::DigitalFrontend (src/rf/frontend.rs:6-62)
 class DigitalFrontend {
     gm_frontend* h_ = nullptr;

@@ -79,6 +79,11 @@ int gm_ca_code_row(int row, int8_t out_chips[1023]);
  * Not in the reference (its README names BeiDou, its code has GPS only): provided for BASELINE configs[3]'s grid, to be
  * passed as gm_acq_cfg.codes.  n_chips = 2046 for the ICD's code; 2047 yields the untruncated period. */
 int gm_b1i_code(uint32_t prn, int8_t *out_chips, uint32_t n_chips);
+/* The GLONASS L1OF ranging code (GLONASS ICD L1/L2: 511 chips at 511 kcps, the same for every satellite; +1 <-> logic 0, as in
+ * gm_b1i_code).  Nine stages s1 .. s9, all ones at the start; each clock the output is s7, then s5 xor s9 is shifted into s1.  The
+ * period is 511; the first 24 logic chips are 111111100000111101111100 and 256 of the 511 are ones.  The satellites differ in their
+ * carriers (FDMA: k = -7 .. 6 at 1602 MHz + k 562.5 kHz), which a gm_channelizer separates; pass the code as gm_acq_cfg.codes. */
+int gm_glonass_code(int8_t out_chips[511]);
 /* generate_ca_code_samples(prn, code_rate, f_sampling) (src/utilities/ca_code.rs:12-27).
  * *n_out = round(fs/(code_rate/1023)); writes min(n, cap) samples.  GM_ERR_OUT_OF_RANGE where the
  * reference would panic (prn not in 1..=32, chip index reaching 1023). */
@@ -1002,6 +1007,78 @@ int gm_ddc_process(gm_ddc *d, const int8_t *in, size_t n_in, gm_c32 *out, size_t
  * through its handle: its block-adapt mode (gm_excisor_set_block_adapt), when on, applies here too. */
 int gm_ddc_write_ring(gm_ddc *d, gm_excisor *x, gm_resampler *r, gm_ring *ring, const int8_t *samples, size_t n_samples,
                       uint64_t *n_out_total);
+
+/* ------------------------------------------------------------------ Polyphase filter bank: sub-bands of one stream
+ * A gm_channelizer cuts a c32 or int8-IQ stream at fs into M sub-bands, each delivered as its own c32 stream at fs / D: one prototype
+ * low-pass of L = M P taps and one M-point transform per output time, in place of M mixers and M filters.  It is what an FDMA
+ * constellation needs (GLONASS L1OF: fourteen carriers 562.5 kHz apart in one capture, one code: gm_glonass_code) and what a wide
+ * capture holding several signals needs before a search at a small fft_size.  Everything is defined by ABSOLUTE input indices: the
+ * words do not depend on how the stream is cut into calls, tiles or workgroups, and stay right past 2^32 samples.
+ *   Prototype filter, built on the host in f64, every word rounded once to f32:
+ *     fc = cutoff / D;  h(t) = fc sinc(fc t) I0(beta sqrt(1 - (2t/L)^2)) / I0(beta) for |t| <= L/2, else 0;
+ *     g[j] = h(j - (L/2 - 1)) for j = 0 .. L-1, divided by the f64 sum: DC gain 1.
+ *   Channel k is centred at k fs / M; k >= M/2 means (k - M) fs / M.  Output m = 0, 1, ... of channel k:
+ *     n0 = m D - (L/2 - 1)                                  (64-bit integers)
+ *     u[r]  = sum_{p<P} g[r + pM] * xb[n0 + r + pM]         f32, one fmaf per component and tap from +0, p ASCENDING;  r = 0 .. M-1
+ *     y_k[m] = sum_{r<M} u[r] * exp(-j 2 pi k (n0 + r) / M) = the M-point forward DFT of u, rotated by n0 mod M
+ *     xb is the input after blanking (the resampler's rule: blank_threshold > 0 and re*re + im*im > thr*thr in f32, strictly greater,
+ *     replaces the sample by 0 and counts it once), and zero before the stream's first sample; an int8 sample is converted to f32
+ *     first (-128 is -128.0f).  The phase depends on (n0 + r) mod M only: exact at any absolute index, no NCO table.  The device forms
+ *     the DFT with f32 butterflies and multiplies bin k by the f32 word of exp(-j 2 pi ((k n0) mod M) / M), each product and sum rounded
+ *     on its own: within (P + 4 log2 M + 8) 2^-24 sum_j |g_j| |xb[n0 + j]| of the exact value.
+ *   Timing.  The filter is centred: output m is the signal at input time m D, with no timestamp delay.  After A inputs
+ *     total_out(A) = max(0, ceil((A - L/2) / D)) outputs exist per channel (gm_resampler's formula at 1/D); a call delivers the
+ *     difference, computed on the host with no synchronisation.
+ *   State.  The handle keeps the last L blanked inputs in device memory, in two buffers used alternately, and the counters on the host.
+ *   Kernel (csrc/channelizer_kernels.hip): one 256-lane workgroup per tile of output times; the tile's input span, (tile - 1) D + L <=
+ *     4096 samples (tile = min((4096 - L) / D + 1, 1024), rounded down to 512 or 256 above those), is read, converted and blanked once
+ *     into a padded LDS image; a lane owns an output time, keeps the M branch sums in registers, transforms them there and stores the
+ *     listed bins, so consecutive lanes store consecutive words of a plane.
+ * Zeros in the filter fields mean defaults.  Not built: ring writers (C planes would need C rings), synthesis (the inverse bank).
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct {
+    uint32_t n_channels;      /* M: 4, 8, 16, 32 or 64 */
+    uint32_t decim;           /* D: 1 .. M; need not divide M */
+    uint32_t taps_per_branch; /* P: 2 .. 32, L = M P taps in all; 0 -> 16 */
+    float    cutoff;          /* (0, 1]: the pass band edge as a fraction of the output Nyquist frequency fs / (2 D); 0 -> 0.9 */
+    float    kaiser_beta;     /* [0, 20]; 0 -> 8 */
+    float    blank_threshold; /* 0: off; > 0: an input sample with re^2 + im^2 > thr^2 (f32) is replaced by 0, before the filter */
+    uint32_t n_out_channels;  /* C <= M; 0 (with out_channels NULL): all M channels in order */
+    uint32_t reserved;        /* must be 0 */
+    const uint32_t *out_channels; /* [C] distinct indices 0 .. M-1 in any order: plane i of the output is channel out_channels[i].  Only
+                                 the listed planes are computed to the end and stored.  Read during the call that takes the cfg only. */
+} gm_channelizer_cfg;
+typedef struct gm_channelizer gm_channelizer;
+/* host only, no device: the argument rules (GM_ERR_INVALID_ARG for a value outside its range, a non-finite float, reserved != 0, a
+ * channel index listed twice or outside 0 .. M-1, a list without a count or a count without a list, inputs_so_far + n_in above 2^62);
+ * *n_out_channels = C, *taps_per_branch = P, *n_taps = L and, for a stream that has taken inputs_so_far samples, the count of outputs
+ * per channel that n_in more deliver.  Any output pointer may be NULL. */
+int gm_channelizer_plan(const gm_channelizer_cfg *cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t *n_out_channels,
+                        uint32_t *taps_per_branch, uint32_t *n_taps, uint64_t *n_out);
+/* host only, no device: the L words g[j] */
+int gm_channelizer_design(const gm_channelizer_cfg *cfg, float *taps);
+int gm_channelizer_create(const gm_channelizer_cfg *cfg, gm_channelizer **out);
+int gm_channelizer_destroy(gm_channelizer *c);
+/* Zeroes the history and the three counters; the next input has absolute index input_index, as if that many zeros had gone before, and
+ * the next output absolute index total_out(input_index).  Synchronous.  input_index above 2^62: GM_ERR_INVALID_ARG. */
+int gm_channelizer_reset(gm_channelizer *c, uint64_t input_index);
+/* the L words the device uses (gm_channelizer_design's) */
+int gm_channelizer_taps(gm_channelizer *c, float *taps);
+/* inputs taken, outputs delivered PER CHANNEL and inputs blanked since gm_channelizer_create or the last gm_channelizer_reset (any
+ * pointer may be NULL).  Each input is counted once.  Synchronises the handle's stream and the stream the last call ran on. */
+int gm_channelizer_stats(gm_channelizer *c, uint64_t *inputs, uint64_t *outputs, uint64_t *blanked);
+/* d_in (n_in samples of GM_FMT_C32 or GM_FMT_I8_IQ; GM_FMT_I8_REAL is refused: a real stream takes a gm_ddc in front) -> d_out, c32
+ * [C][out_stride]: plane i holds this call's *n_out outputs of channel out_channels[i] as one contiguous stream, so a plane pointer
+ * goes straight into gm_acq_search_dev; words of a plane behind *n_out are not touched (n_out may be NULL).  Asynchronous on `stream`
+ * (a hipStream_t; NULL: the handle's own non-blocking stream); consecutive calls of a handle must be ordered against each other (one
+ * stream, or the caller's events).  Every argument is checked before anything runs: out_cap below the count or out_stride below
+ * out_cap is GM_ERR_OUT_OF_RANGE, the C * out_stride words at d_out overlapping d_in GM_ERR_INVALID_ARG, each with nothing launched and
+ * the state unchanged.  n_in = 0: GM_OK, *n_out = 0.  At most 2^31 samples a call. */
+int gm_channelizer_process_dev(gm_channelizer *c, const void *d_in, int fmt, size_t n_in, void *d_out, size_t out_stride, size_t out_cap,
+                               size_t *n_out, void *stream);
+/* the synchronous host-buffer form (H2D, the kernels, D2H on the handle's stream); out is [C][out_cap] */
+int gm_channelizer_process(gm_channelizer *c, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out);
+int gm_channelizer_synchronize(gm_channelizer *c);
 
 /* ------------------------------------------------------------------ Tracking
  * The evolving fields of TrackingChannel (src/tracking/do_tracking.rs:88-116). */

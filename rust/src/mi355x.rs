@@ -167,6 +167,19 @@ pub struct GmDdcCfg {               // gm_ddc_cfg (40 bytes; zeros in the filter
     pub reserved: u32,               // must be 0
 }
 pub enum GmDdc {}
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct GmChannelizerCfg {       // gm_channelizer_cfg (40 bytes; zeros in the filter fields: the defaults)
+    pub n_channels: u32,             // M: 4, 8, 16, 32 or 64
+    pub decim: u32,                  // D: 1 .. M
+    pub taps_per_branch: u32,        // P: 2 .. 32, L = M P taps in all; 0 -> 16
+    pub cutoff: f32,                 // (0, 1] of the output Nyquist frequency; 0 -> 0.9
+    pub kaiser_beta: f32,            // [0, 20]; 0 -> 8
+    pub blank_threshold: f32,        // 0: off; > 0: an input sample with re^2 + im^2 > thr^2 is replaced by 0
+    pub n_out_channels: u32,         // C <= M; 0 with a null list: all M in order
+    pub reserved: u32,               // must be 0
+    pub out_channels: *const u32,    // [C] distinct indices 0 .. M-1: plane i is channel out_channels[i]
+}
+pub enum GmChannelizer {}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {} pub enum GmExcisor {}
 
 extern "C" {
@@ -298,6 +311,23 @@ extern "C" {
     /// gm_frontend_write_ring_conditioned with the down-converter in the front-end's place; `x` and `r` may each be null
     pub fn gm_ddc_write_ring(d: *mut GmDdc, x: *mut GmExcisor, r: *mut GmResampler, ring: *mut GmRing, samples: *const i8,
                              n_samples: usize, n_out_total: *mut u64) -> c_int;
+
+    /// polyphase filter bank: M sub-bands of one c32 / int8-IQ stream, each a c32 stream at fs / D; d_out is [C][out_stride]
+    pub fn gm_channelizer_plan(cfg: *const GmChannelizerCfg, inputs_so_far: u64, n_in: u64, n_out_channels: *mut u32,
+                               taps_per_branch: *mut u32, n_taps: *mut u32, n_out: *mut u64) -> c_int;
+    pub fn gm_channelizer_design(cfg: *const GmChannelizerCfg, taps: *mut f32) -> c_int;
+    pub fn gm_channelizer_create(cfg: *const GmChannelizerCfg, out: *mut *mut GmChannelizer) -> c_int;
+    pub fn gm_channelizer_destroy(c: *mut GmChannelizer) -> c_int;
+    pub fn gm_channelizer_reset(c: *mut GmChannelizer, input_index: u64) -> c_int;
+    pub fn gm_channelizer_taps(c: *mut GmChannelizer, taps: *mut f32) -> c_int;
+    pub fn gm_channelizer_stats(c: *mut GmChannelizer, inputs: *mut u64, outputs: *mut u64, blanked: *mut u64) -> c_int;
+    pub fn gm_channelizer_process_dev(c: *mut GmChannelizer, d_in: *const c_void, fmt: c_int, n_in: usize, d_out: *mut c_void,
+                                      out_stride: usize, out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gm_channelizer_process(c: *mut GmChannelizer, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32,
+                                  out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn gm_channelizer_synchronize(c: *mut GmChannelizer) -> c_int;
+    /// the GLONASS L1OF ranging code: 511 chips, +1 for logic 0
+    pub fn gm_glonass_code(out_chips: *mut i8) -> c_int;
     // do_tracking.rs:118-158, 311-327
     pub fn gm_trk_create(cfg: *const GmTrkCfg, out: *mut *mut GmTrk) -> c_int;
     pub fn gm_trk_destroy(t: *mut GmTrk) -> c_int;
