@@ -8,6 +8,7 @@ include/gnss_mi355x.h.  This Python package is plumbing around it:
   excise                         FFT-domain narrowband interference excision (overlap-add filter bank, adaptive per-bin gains)
   ddc                            real-IF int8 down-conversion to complex baseband (exact NCO, the resampler's polyphase filter)
   channelizer                    polyphase filter bank: M sub-bands of one stream (FDMA carriers), and the GLONASS L1OF code
+  nuller                         adaptive spatial nulling: A interleaved antennas combined per block with weights from the block's covariance
   synth       deterministic synthetic IF scenes
   build       hipcc build recipe
 """
@@ -17,3 +18,4 @@ from .resample import Resampler  # noqa: F401
 from .excise import Excisor  # noqa: F401
 from .ddc import Ddc  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
+from .nuller import Nuller  # noqa: F401

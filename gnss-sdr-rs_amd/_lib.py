@@ -111,6 +111,12 @@ class ChannelizerCfg(C.Structure):
                 ("out_channels", C.POINTER(C.c_uint32))]
 
 
+class NullerCfg(C.Structure):
+    """gm_nuller_cfg (24 bytes): zeros are the defaults; steering points at n_antennas complex64 words, or is NULL (e_0)"""
+    _fields_ = [("n_antennas", C.c_uint32), ("block", C.c_uint32), ("loading", C.c_float), ("reserved", C.c_uint32),
+                ("steering", C.c_void_p)]
+
+
 class ExcisorCfg(C.Structure):
     """gm_excisor_cfg (32 bytes): zeros are the defaults"""
     _fields_ = [("block", C.c_uint32), ("guard_bins", C.c_uint32), ("threshold_factor", C.c_float), ("blank_threshold", C.c_float),
@@ -326,6 +332,16 @@ SIGNATURES = {
     "gm_channelizer_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gm_channelizer_synchronize": (_i, [_vp]),
     "gm_glonass_code": (_i, [_vp]),
+    "gm_nuller_plan": (_i, [C.POINTER(NullerCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(C.c_float), C.POINTER(_u64)]),
+    "gm_nuller_create": (_i, [C.POINTER(NullerCfg), C.POINTER(_vp)]),
+    "gm_nuller_destroy": (_i, [_vp]),
+    "gm_nuller_reset": (_i, [_vp, _u64]),
+    "gm_nuller_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_nuller_synchronize": (_i, [_vp]),
+    "gm_nuller_set_weights": (_i, [_vp, _vp]),
+    "gm_nuller_capture": (_i, [_vp, _vp, _vp, _sz]),
+    "gm_nuller_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "gm_nuller_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
     "gm_trk_create": (_i, [C.POINTER(TrkCfg), C.POINTER(_vp)]),
     "gm_trk_destroy": (_i, [_vp]),
     "gm_trk_start": (_i, [_vp, _u32, C.POINTER(AcqResult)]),

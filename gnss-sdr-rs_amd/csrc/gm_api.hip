@@ -4850,6 +4850,184 @@ int gm_glonass_code(int8_t* out) {
 
 }  // extern "C"
 
+// ====================================================================== adaptive spatial nulling of an antenna array (gm_nuller)
+// gnss_mi355x.h states the definition; tests/nuller_model.py restates it in float64.
+namespace {
+struct NullerPlan {
+    uint32_t A = 0, B = 0;
+    float loading = 0.0f;
+    cf s[gm::NL_A_MAX] = {};
+};
+
+bool nuller_finite(const gm_c32* v, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i].re) || !std::isfinite(v[i].im)) return false;
+    return true;
+}
+
+int nuller_rules(const gm_nuller_cfg* c, NullerPlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    if (c->reserved) return set_err(GM_ERR_INVALID_ARG, "gm_nuller_cfg.reserved must be 0");
+    if (c->n_antennas < 2 || c->n_antennas > uint32_t(gm::NL_A_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_antennas: 2 .. 8");
+    const uint32_t B = c->block ? c->block : 1024;
+    if (B < 256 || B > 16384 || (B & (B - 1))) return set_err(GM_ERR_INVALID_ARG, "block: a power of two in 256 .. 16384, 0 for the default");
+    if (!std::isfinite(c->loading)) return set_err(GM_ERR_INVALID_ARG, "loading must be finite");
+    if (c->loading != 0.0f && !(c->loading >= 1e-6f && c->loading <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "loading: [1e-6, 1], 0 for the default");
+    p.A = c->n_antennas; p.B = B; p.loading = c->loading == 0.0f ? 1e-4f : c->loading;
+    for (uint32_t i = 0; i < uint32_t(gm::NL_A_MAX); ++i) p.s[i] = gm::cf_make(i == 0 ? 1.0f : 0.0f, 0.0f);
+    if (c->steering) {
+        if (!nuller_finite(c->steering, p.A)) return set_err(GM_ERR_INVALID_ARG, "steering must be finite");
+        bool any = false;
+        for (uint32_t i = 0; i < p.A; ++i) {
+            p.s[i] = gm::cf_make(c->steering[i].re, c->steering[i].im);
+            any = any || c->steering[i].re != 0.0f || c->steering[i].im != 0.0f;
+        }
+        if (!any) return set_err(GM_ERR_INVALID_ARG, "steering is all zero");
+    }
+    return GM_OK;
+}
+
+// total_out(T) = B * (T div B)
+uint64_t nuller_total_out(const NullerPlan& p, uint64_t T) { return T / p.B * p.B; }
+}  // namespace
+
+struct gm_nuller : StreamStage {            // history: the converted time samples of the unfinished block (cf [B][A])
+    NullerPlan plan;
+    bool fixed = false;                     // static mode
+    cf w[gm::NL_A_MAX] = {};
+    cf* cap_R = nullptr; cf* cap_w = nullptr; size_t cap_blocks = 0;     // the caller's capture (device)
+    cf* d_blk = nullptr; size_t blk_cap = 0;                             // blocks; the host-buffer entry's own capture: [blk_cap][A][A] then [blk_cap][A]
+};
+
+// one call's kernels on `st`; the caller has checked every argument; n_in > 0
+static int nuller_launch(gm_nuller* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t n_out, cf* cap_R, cf* cap_w) {
+    const NullerPlan& p = n->plan;
+    const uint64_t T = n->base + n->inputs;
+    gm::NullerArgs a{};
+    a.in = d_in; a.n_in = n_in;
+    a.hist_in = static_cast<const cf*>(n->d_hist[n->cur]); a.hist_out = static_cast<cf*>(n->d_hist[n->cur ^ 1]);
+    a.A = p.A; a.B = p.B;
+    a.pending = uint32_t(T % p.B); a.pending_out = uint32_t((T + n_in) % p.B);
+    a.n_blocks = n_out / p.B;
+    a.out = out; a.cap_R = cap_R; a.cap_w = cap_w;
+    a.loading = p.loading; a.adaptive = n->fixed ? 0 : 1;
+    a.in_wide = reinterpret_cast<uintptr_t>(d_in) % gm::nuller_in_align(p.A, fmt) == 0 ? 1 : 0;
+    for (int i = 0; i < gm::NL_A_MAX; ++i) { a.s[i] = p.s[i]; a.w[i] = n->w[i]; }
+    gm::launch_nuller(st, a, fmt);
+    return stage_launched(n, st, n_in, n_out);
+}
+static uint64_t nuller_count(const gm_nuller* n, uint64_t n_in) {
+    const uint64_t T = n->base + n->inputs;
+    return nuller_total_out(n->plan, T + n_in) - nuller_total_out(n->plan, T);
+}
+static const char* nuller_fmt_err(int fmt) {
+    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "nuller input is interleaved c32 or int8 IQ" : nullptr;
+}
+
+extern "C" {
+
+int gm_nuller_plan(const gm_nuller_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, float* loading, uint64_t* n_out) {
+    NullerPlan p;
+    if (int rc = nuller_rules(cfg, p)) return rc;
+    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (block) *block = p.B;
+    if (loading) *loading = p.loading;
+    if (n_out) *n_out = nuller_total_out(p, inputs_so_far + n_in) - nuller_total_out(p, inputs_so_far);
+    return GM_OK;
+}
+
+int gm_nuller_create(const gm_nuller_cfg* cfg, gm_nuller** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    NullerPlan p;
+    if (int rc = nuller_rules(cfg, p)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_nuller* n = new gm_nuller;
+    n->device = g_device; n->plan = p;
+    hipError_t e = stage_create(n, size_t(p.B) * p.A * sizeof(cf));
+    if (e != hipSuccess) { gm_nuller_destroy(n); return hip_fail(e, "gm_nuller_create"); }
+    *out = n;
+    return GM_OK;
+}
+
+int gm_nuller_destroy(gm_nuller* n) {
+    if (!n) return GM_OK;
+    stage_destroy(n);
+    hipFree(n->d_blk);
+    delete n;
+    return GM_OK;
+}
+
+int gm_nuller_reset(gm_nuller* n, uint64_t input_index) {
+    return stage_reset(n, input_index, [] { return hipSuccess; });
+}
+
+int gm_nuller_stats(gm_nuller* n, uint64_t* inputs, uint64_t* outputs, uint64_t* blocks) {
+    if (int rc = stage_stats(n, inputs, outputs, nullptr)) return rc;
+    if (blocks) *blocks = n->outputs / n->plan.B;
+    return GM_OK;
+}
+
+int gm_nuller_synchronize(gm_nuller* n) { return stage_synchronize(n); }
+
+int gm_nuller_set_weights(gm_nuller* n, const gm_c32* w) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!w) { n->fixed = false; return GM_OK; }
+    if (!nuller_finite(w, n->plan.A)) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
+    for (uint32_t i = 0; i < n->plan.A; ++i) n->w[i] = gm::cf_make(w[i].re, w[i].im);
+    n->fixed = true;
+    return GM_OK;
+}
+
+int gm_nuller_capture(gm_nuller* n, void* d_R, void* d_w, size_t cap_blocks) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if ((d_R == nullptr) != (d_w == nullptr)) return set_err(GM_ERR_INVALID_ARG, "d_R and d_w: both or neither");
+    if ((d_R == nullptr) != (cap_blocks == 0)) return set_err(GM_ERR_INVALID_ARG, "cap_blocks: 0 exactly where the pointers are null");
+    n->cap_R = static_cast<cf*>(d_R); n->cap_w = static_cast<cf*>(d_w); n->cap_blocks = cap_blocks;
+    return GM_OK;
+}
+
+int gm_nuller_process_dev(gm_nuller* n, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out, void* stream) {
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(n, nuller_count, nuller_fmt_err(fmt), d_in, n_in, d_out, out_cap, "gm_nuller_plan", &cnt)) return rc;
+    if (n->cap_w && cnt / n->plan.B > n->cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "the capture is smaller than the call's blocks");
+    if (int rc = stage_check_overlap(d_in, n_in * n->plan.A * (fmt == GM_FMT_C32 ? 8 : 2), d_out, cnt)) return rc;
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(n->device)) return rc;
+    return nuller_launch(n, stream ? static_cast<hipStream_t>(stream) : n->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), cnt, n->cap_R, n->cap_w);
+}
+
+int gm_nuller_process(gm_nuller* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out, gm_c32* R, gm_c32* w,
+                      size_t cap_blocks) {
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(n, nuller_count, nuller_fmt_err(fmt), in, n_in, out, out_cap, "gm_nuller_plan", &cnt)) return rc;
+    const uint64_t blocks = cnt / n->plan.B;
+    const bool want = (R || w) && blocks;
+    if ((R || w) && blocks > cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "cap_blocks below the call's blocks");
+    const size_t AA = size_t(n->plan.A) * n->plan.A, A = n->plan.A;
+    if (want && n->blk_cap < blocks) {
+        if (int rc = ensure_device(n->device)) return rc;
+        if (int rc = stage_sync(n)) return rc;
+        hipFree(n->d_blk); n->d_blk = nullptr; n->blk_cap = 0;
+        HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_blk), size_t(blocks) * (AA + A) * sizeof(cf)));
+        n->blk_cap = size_t(blocks);
+    }
+    cf* d_R = want ? n->d_blk : nullptr;
+    cf* d_w = want ? n->d_blk + n->blk_cap * AA : nullptr;
+    if (int rc = stage_process(n, in, n_in * A * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
+            return nuller_launch(n, st, d_in, fmt, n_in, d_out, cnt, d_R, d_w);
+        })) return rc;
+    if (want) {      // stage_process has waited for the kernels
+        if (R && !n->fixed) HIPC(hipMemcpy(R, d_R, size_t(blocks) * AA * sizeof(cf), hipMemcpyDeviceToHost));
+        if (w) HIPC(hipMemcpy(w, d_w, size_t(blocks) * A * sizeof(cf), hipMemcpyDeviceToHost));
+    }
+    return GM_OK;
+}
+
+}  // extern "C"
+
 // ====================================================================== multi-GPU exchange
 // The path's ONE exchange step: all-gather of the per-(worker, bin) metrics over RCCL, enqueued on the acquisition
 // handle's stream, followed by the regroup to the [3][nranks*P][D] layout gm_acq_decide_dev replays.  RCCL is bound

@@ -463,6 +463,32 @@ inline uint32_t channelizer_tile_out(uint32_t L, uint32_t D) {
 }
 void launch_channelizer(hipStream_t, const ChannelizerArgs&, int fmt);
 
+// ---------------------------------------------------------------- adaptive spatial nulling of an antenna array (nuller_kernels.hip)
+// gnss_mi355x.h states the definition.  One call = one launch of the block kernel (a workgroup per finished block of B time samples:
+// covariance, weights, output) and one of the state kernel (the time samples of the unfinished block, carried to the next call).  Time
+// sample v of the call's span is word v of the old history for v < pending, else time sample v - pending of the call's input.
+constexpr int NL_A_MAX = 8;
+struct NullerArgs {
+    const void* in; uint64_t n_in;         // this call's TIME samples, each A interleaved elements (c32 or int8 IQ)
+    const cf* hist_in; cf* hist_out;       // [B][A] the converted time samples of the unfinished block before / after this call
+    uint32_t A, B;
+    uint32_t pending, pending_out;         // time samples in hist_in (< B); in hist_out after this call (< B)
+    uint64_t n_blocks;                     // blocks this call finishes
+    cf* out;                               // [n_blocks * B]
+    cf* cap_R; cf* cap_w;                  // [n_blocks][A][A], [n_blocks][A]; null: not captured
+    float loading;
+    int adaptive;                          // 0: the fixed weights `w` for every block, no covariance pass
+    int in_wide;                           // `in` is aligned for the widest load of a time sample (nuller_in_align)
+    cf s[NL_A_MAX];                        // the steering vector
+    cf w[NL_A_MAX];                        // the fixed weights
+};
+// the widest power-of-two load (bytes, at most 16) that divides a time sample of A elements
+inline uint32_t nuller_in_align(uint32_t A, int fmt) {
+    const uint32_t bytes = A * (fmt == GM_FMT_C32 ? 8u : 2u);
+    return bytes % 16 == 0 ? 16u : bytes % 8 == 0 ? 8u : bytes % 4 == 0 ? 4u : 2u;
+}
+void launch_nuller(hipStream_t, const NullerArgs&, int fmt);
+
 // ---------------------------------------------------------------- narrowband interference excision (excise_kernels.hip)
 // gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of G segments of H = B / 2
 // outputs) and one of the state kernel (the next history of 3H blanked inputs, the blanked count).  The host hands over where the

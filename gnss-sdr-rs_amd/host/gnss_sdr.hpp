@@ -492,6 +492,62 @@ private:
     }
 };
 
+// ---- adaptive spatial nulling (gm_nuller): A coherent antennas interleaved time sample by time sample in one stream, one Complex32
+// stream out at the same rate; per block of B time samples the weights come from the block's own covariance (a null on whatever
+// dominates it, the response held at 1 towards the steering vector; none: antenna 0 as the reference).  All counts are time samples.
+class Nuller {
+    gm_nuller* h_ = nullptr;
+    uint32_t antennas_ = 0, block_ = 0;
+public:
+    // block 0: 1024; loading 0: 1e-4; steering empty: e_0
+    explicit Nuller(uint32_t n_antennas, uint32_t block = 0, float loading = 0.0f, const std::vector<Complex32>& steering = {}) {
+        gm_nuller_cfg cfg{};
+        cfg.n_antennas = n_antennas; cfg.block = block; cfg.loading = loading;
+        if (!steering.empty() && steering.size() != n_antennas) check(GM_ERR_INVALID_ARG, "Nuller::new (steering: n_antennas words)");
+        cfg.steering = steering.empty() ? nullptr : reinterpret_cast<const gm_c32*>(steering.data());
+        check(gm_nuller_plan(&cfg, 0, 0, &block_, nullptr, nullptr), "Nuller::new");
+        antennas_ = n_antennas;
+        check(gm_nuller_create(&cfg, &h_), "Nuller::new");
+    }
+    ~Nuller() { gm_nuller_destroy(h_); }
+    Nuller(const Nuller&) = delete;
+    gm_nuller* handle() const { return h_; }
+    uint32_t antennas() const { return antennas_; }
+    uint32_t block() const { return block_; }
+    // the synchronous host-buffer form: n time samples (n * antennas elements) -> this call's outputs; R ([blocks][A][A]) and w
+    // ([blocks][A]) receive the words each of the call's blocks was combined with, where given
+    std::vector<Complex32> process(const void* in, int fmt, size_t n, std::vector<Complex32>* R = nullptr, std::vector<Complex32>* w = nullptr) {
+        const size_t cap = n + block_, nb = cap / block_;
+        std::vector<Complex32> out(cap);
+        if (R) R->assign(nb * antennas_ * antennas_, Complex32{});
+        if (w) w->assign(nb * antennas_, Complex32{});
+        size_t got = 0;
+        check(gm_nuller_process(h_, in, fmt, n, reinterpret_cast<gm_c32*>(out.data()), cap, &got,
+                                R ? reinterpret_cast<gm_c32*>(R->data()) : nullptr, w ? reinterpret_cast<gm_c32*>(w->data()) : nullptr, nb),
+              "Nuller::process");
+        out.resize(got);
+        if (R) R->resize(got / block_ * antennas_ * antennas_);
+        if (w) w->resize(got / block_ * antennas_);
+        return out;
+    }
+    // device pointers; asynchronous on `stream` (nullptr: the handle's own); returns the outputs written
+    size_t process_dev(const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, void* stream = nullptr) {
+        size_t n = 0;
+        check(gm_nuller_process_dev(h_, d_in, fmt, n_in, d_out, out_cap, &n, stream), "Nuller::process_dev");
+        return n;
+    }
+    // fixed weights for every later block (static mode); empty: back to the adaptive rule
+    void set_weights(const std::vector<Complex32>& w) {
+        if (!w.empty() && w.size() != antennas_) check(GM_ERR_INVALID_ARG, "Nuller::set_weights (n_antennas words)");
+        check(gm_nuller_set_weights(h_, w.empty() ? nullptr : reinterpret_cast<const gm_c32*>(w.data())), "Nuller::set_weights");
+    }
+    // device buffers [cap_blocks][A][A] and [cap_blocks][A] that every later process_dev fills from word 0; nulls and 0 end it
+    void capture(void* d_R, void* d_w, size_t cap_blocks) { check(gm_nuller_capture(h_, d_R, d_w, cap_blocks), "Nuller::capture"); }
+    void reset(uint64_t input_index = 0) { check(gm_nuller_reset(h_, input_index), "Nuller::reset"); }
+    void stats(uint64_t* inputs, uint64_t* outputs, uint64_t* blocks) const { check(gm_nuller_stats(h_, inputs, outputs, blocks), "Nuller::stats"); }
+    void synchronize() { check(gm_nuller_synchronize(h_), "Nuller::synchronize"); }
+};
+
 // ---- rf::frontend::DigitalFrontend (src/rf/frontend.rs:6-62)
 class DigitalFrontend {
     gm_frontend* h_ = nullptr;

@@ -1080,6 +1080,86 @@ int gm_channelizer_process_dev(gm_channelizer *c, const void *d_in, int fmt, siz
 int gm_channelizer_process(gm_channelizer *c, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out);
 int gm_channelizer_synchronize(gm_channelizer *c);
 
+/* ------------------------------------------------------------------ Adaptive spatial nulling of an antenna array
+ * A gm_nuller takes A coherent antennas (2 .. 8) as ONE interleaved stream of GM_FMT_C32 or GM_FMT_I8_IQ elements — time sample n of
+ * antenna a is element n * A + a, the layout a multi-channel SDR delivers — and combines them into one c32 stream at the same rate
+ * and time index (no timestamp delay) with weights that put a null on whatever dominates the block's covariance: the wideband noise
+ * jammer, long in time and as wide as the signal, that neither blanking nor a notch can touch.  Every count below is in TIME samples.
+ * Everything is defined by ABSOLUTE indices: the words do not depend on how the stream is cut into calls, and two runs give the same
+ * words.
+ *   Blocks.  Block b covers the time samples [b B, (b+1) B); B is a power of two in 256 .. 16384.  After T time samples
+ *     total_out(T) = B * (T div B) outputs exist; a call delivers the difference, computed on the host with no synchronisation.  The
+ *     (converted) time samples of the unfinished block travel between calls in the handle's history buffers.  There is no flush: a
+ *     caller that needs the tail appends zeros.
+ *   Covariance, from the block's own samples, f32:  R[i][j] = sum_{t<B} x_i[bB + t] conj(x_j[bB + t])  for i <= j; an int8 sample is
+ *     converted to f32 first (-128 is -128.0f).  The diagonal's imaginary part is 0 and R[j][i] = conj(R[i][j]).  THE ORDER: 256 lane
+ *     sums S[l], l = 0 .. 255, each over t = l, l + 256, l + 512, ... ascending from +0 with, per t,
+ *       re = fmaf(xi.re, xj.re, re);  re = fmaf(xi.im, xj.im, re);  im = fmaf(xi.im, xj.re, im);  im = fmaf(-xi.re, xj.im, im);
+ *     then, within each group of 64 lanes, S[l] = S[l] + S[l + d] for d = 32, 16, 8, 4, 2, 1 (the group's sum W is its lane 0), then
+ *     R = (W0 + W1) + (W2 + W3).  A function of the block-relative t alone; no floating-point atomics.  Within
+ *     (B/256 + 12) 2^-24 sum_t |x_i| |x_j| of the exact sum.
+ *   Weights, f64 from the f32 words of R:  tr = sum_i Re R[i][i] (i ascending);  Rl = R + loading * (tr / A) * I, loading being the
+ *     f32 word widened;  u = Rl^-1 s;  w = u / (s^H u);  each component of w rounded once to f32.  The device solves by Cholesky,
+ *     Rl = L L^H: z = L^-1 s, s^H u = z^H z (real by construction), u = L^-H z.  tr = 0 (an all-zero block): w = s / (s^H s).
+ *     s is the caller's steering vector (A c32 words, not all zero): the response is held at 1 in its direction.  NULL means e_0 —
+ *     power inversion with antenna 0 as the reference, and Re w[0] comes out as 1.0f.
+ *   Output, f32:  y[bB + t] = sum_a conj(w[a]) x_a[bB + t], w the f32 words just rounded: from +0, a ASCENDING, per a
+ *       re = fmaf(w.re, x.re, re);  re = fmaf(w.im, x.im, re);  im = fmaf(w.re, x.im, im);  im = fmaf(-w.im, x.re, im);
+ *     within (A + 2) 2^-24 sum_a |w[a]| |x_a| of the exact value.
+ *   Static mode.  gm_nuller_set_weights installs A fixed weights used for every block; the covariance pass is skipped; counts and
+ *     block delivery are unchanged.
+ *   Monitor.  gm_nuller_capture names device buffers that every later gm_nuller_process_dev fills with its blocks' R and w words.
+ *   Kernel (csrc/nuller_kernels.hip): one 256-lane workgroup per block: the sums in registers, shuffles and LDS for the tree, the
+ *     solve in wave 0 fully unrolled on A, a second read of the block (from L2) for y; a state kernel carries the unfinished block.
+ * Not built: a ring writer with the nuller as head stage; wiring into receiver_harness.cpp; taps in time (STAP); array calibration;
+ * blanking inside the stage (its output goes into a gm_excisor or gm_resampler, which blank); any decision — the library reports R
+ * and w, the caller judges.
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct {
+    uint32_t n_antennas;      /* A: 2 .. 8 */
+    uint32_t block;           /* B: a power of two in 256 .. 16384; 0 -> 1024 */
+    float    loading;         /* [1e-6, 1]: diagonal loading as a fraction of the mean antenna power tr / A; 0 -> 1e-4 */
+    uint32_t reserved;        /* must be 0 */
+    const gm_c32 *steering;   /* [A] c32 words, finite, not all zero; NULL -> e_0.  Read during the call that takes the cfg only. */
+} gm_nuller_cfg;
+typedef struct gm_nuller gm_nuller;
+/* host only, no device: the argument rules (GM_ERR_INVALID_ARG for an A, B or loading outside its range, a non-finite loading or
+ * steering word, an all-zero steering, reserved != 0, inputs_so_far + n_in above 2^62); *block = B, *loading = the f32 word used and,
+ * for a stream that has taken inputs_so_far time samples, the count of outputs that n_in more deliver.  Any output pointer may be
+ * NULL. */
+int gm_nuller_plan(const gm_nuller_cfg *cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t *block, float *loading, uint64_t *n_out);
+int gm_nuller_create(const gm_nuller_cfg *cfg, gm_nuller **out);
+int gm_nuller_destroy(gm_nuller *n);
+/* Zeroes the history and the counters; the stream continues as if input_index zero time samples had gone before: the first block
+ * delivered is block input_index div B, whose first input_index mod B samples are those zeros.  Keeps the weights mode and the
+ * capture.  Synchronous.  input_index above 2^62: GM_ERR_INVALID_ARG. */
+int gm_nuller_reset(gm_nuller *n, uint64_t input_index);
+/* time samples taken, outputs delivered and blocks finished since gm_nuller_create or the last gm_nuller_reset, each counted once
+ * (any pointer may be NULL).  Synchronises the handle's stream and the stream the last call ran on. */
+int gm_nuller_stats(gm_nuller *n, uint64_t *inputs, uint64_t *outputs, uint64_t *blocks);
+int gm_nuller_synchronize(gm_nuller *n);
+/* w: A finite c32 words used for every later block (static mode: y = sum_a conj(w[a]) x_a, no covariance pass); NULL returns the
+ * handle to the adaptive rule.  The words are copied during the call and travel with each later call's launch, so the change is
+ * ordered with the handle's calls: every call made before it used the old rule, every later one uses the new. */
+int gm_nuller_set_weights(gm_nuller *n, const gm_c32 *w);
+/* Every later gm_nuller_process_dev writes its blocks' words to device memory, block k of the CALL at d_R + k A A (c32 [A][A], row
+ * i column j = R[i][j]) and d_w + k A (c32 [A]), from word 0 on each call; a call that finishes more than cap_blocks blocks is
+ * refused (GM_ERR_OUT_OF_RANGE) before anything runs.  In static mode only w is written.  d_R = d_w = NULL with cap_blocks = 0 ends
+ * the capture; one pointer without the other, or pointers with cap_blocks = 0, is GM_ERR_INVALID_ARG. */
+int gm_nuller_capture(gm_nuller *n, void *d_R, void *d_w, size_t cap_blocks);
+/* d_in (n_in TIME samples, n_in * A elements of GM_FMT_C32 or GM_FMT_I8_IQ; GM_FMT_I8_REAL is refused) -> d_out, c32: this call's
+ * *n_out outputs; words behind them are not touched (n_out may be NULL).  Asynchronous on `stream` (a hipStream_t; NULL: the handle's
+ * own non-blocking stream); consecutive calls of a handle must be ordered against each other (one stream, or the caller's events).
+ * Every argument is checked before anything runs: out_cap below the count is GM_ERR_OUT_OF_RANGE, as is a capture too small for the
+ * call's blocks; d_out overlapping d_in, a NULL where a pointer is needed, more than 2^31 time samples in a call or a stream index
+ * above 2^62 GM_ERR_INVALID_ARG; each with nothing launched and the state unchanged.  n_in = 0: GM_OK, *n_out = 0. */
+int gm_nuller_process_dev(gm_nuller *n, const void *d_in, int fmt, size_t n_in, void *d_out, size_t out_cap, size_t *n_out, void *stream);
+/* the synchronous host-buffer form (H2D, the kernels, D2H on the handle's stream).  R ([blocks][A][A]) and w ([blocks][A]) are host
+ * buffers for the call's block words, each may be NULL; with either given, cap_blocks below the call's blocks is GM_ERR_OUT_OF_RANGE.
+ * In static mode R is left untouched.  A device capture set by gm_nuller_capture is not written by this form. */
+int gm_nuller_process(gm_nuller *n, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out, gm_c32 *R,
+                      gm_c32 *w, size_t cap_blocks);
+
 /* ------------------------------------------------------------------ Tracking
  * The evolving fields of TrackingChannel (src/tracking/do_tracking.rs:88-116). */
 typedef struct {

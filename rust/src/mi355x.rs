@@ -180,6 +180,15 @@ pub struct GmChannelizerCfg {       // gm_channelizer_cfg (40 bytes; zeros in th
     pub out_channels: *const u32,    // [C] distinct indices 0 .. M-1: plane i is channel out_channels[i]
 }
 pub enum GmChannelizer {}
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct GmNullerCfg {            // gm_nuller_cfg (24 bytes; zeros: the defaults)
+    pub n_antennas: u32,             // A: 2 .. 8, interleaved time sample by time sample in one stream
+    pub block: u32,                  // B: a power of two in 256 .. 16384; 0 -> 1024
+    pub loading: f32,                // [1e-6, 1] of the mean antenna power; 0 -> 1e-4
+    pub reserved: u32,               // must be 0
+    pub steering: *const Complex32,  // [A] finite words, not all zero; null -> e_0 (antenna 0 as the reference)
+}
+pub enum GmNuller {}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {} pub enum GmExcisor {}
 
 extern "C" {
@@ -328,6 +337,24 @@ extern "C" {
     pub fn gm_channelizer_synchronize(c: *mut GmChannelizer) -> c_int;
     /// the GLONASS L1OF ranging code: 511 chips, +1 for logic 0
     pub fn gm_glonass_code(out_chips: *mut i8) -> c_int;
+
+    /// adaptive spatial nulling: A interleaved antennas -> one c32 stream, the weights of a block from its own covariance; every
+    /// count is in TIME samples
+    pub fn gm_nuller_plan(cfg: *const GmNullerCfg, inputs_so_far: u64, n_in: u64, block: *mut u32, loading: *mut f32,
+                          n_out: *mut u64) -> c_int;
+    pub fn gm_nuller_create(cfg: *const GmNullerCfg, out: *mut *mut GmNuller) -> c_int;
+    pub fn gm_nuller_destroy(n: *mut GmNuller) -> c_int;
+    pub fn gm_nuller_reset(n: *mut GmNuller, input_index: u64) -> c_int;
+    pub fn gm_nuller_stats(n: *mut GmNuller, inputs: *mut u64, outputs: *mut u64, blocks: *mut u64) -> c_int;
+    pub fn gm_nuller_synchronize(n: *mut GmNuller) -> c_int;
+    /// static mode: A fixed weights for every later block; null: back to the adaptive rule
+    pub fn gm_nuller_set_weights(n: *mut GmNuller, w: *const Complex32) -> c_int;
+    /// device buffers [cap_blocks][A][A] and [cap_blocks][A] that every later gm_nuller_process_dev fills from word 0
+    pub fn gm_nuller_capture(n: *mut GmNuller, d_r: *mut c_void, d_w: *mut c_void, cap_blocks: usize) -> c_int;
+    pub fn gm_nuller_process_dev(n: *mut GmNuller, d_in: *const c_void, fmt: c_int, n_in: usize, d_out: *mut c_void, out_cap: usize,
+                                 n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gm_nuller_process(n: *mut GmNuller, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32, out_cap: usize,
+                             n_out: *mut usize, r: *mut Complex32, w: *mut Complex32, cap_blocks: usize) -> c_int;
     // do_tracking.rs:118-158, 311-327
     pub fn gm_trk_create(cfg: *const GmTrkCfg, out: *mut *mut GmTrk) -> c_int;
     pub fn gm_trk_destroy(t: *mut GmTrk) -> c_int;
