@@ -21,6 +21,10 @@
  *     on that stream), or synchronise the producer first.  gm_acq_prepare_dev takes the producer's stream per call
  *     (`ready_stream`).  The reference copies its 10 ms out of the ring and THEN searches them (do_acquisition.rs:297-313): the
  *     stream order is that sequence.  INTEGRATION.md §3.3; tests/test_gpu_acquisition.py::test_caller_stream_orders_...
+ *     The streaming stage handles (gm_frontend, gm_resampler, gm_excisor, gm_ddc, gm_channelizer, gm_nuller) take the producer's
+ *     stream per call, as the `stream` argument of their `_dev` entries: the call runs behind what the caller has queued there, its
+ *     outputs and the handle's history are ready on that stream, and the handle's own queries, reset, host-buffer entry and ring
+ *     writers wait for it (gm_frontend's wait for the handle's own stream only); tests/test_gpu_caller_streams.py.
  *   - arithmetic type: f32 everywhere, as in the reference (num_complex::Complex32 = {f32 re, im})
  *   - the compute path is HIP on gfx950 only; there is NO CPU fallback — without a usable device
  *     every compute entry returns GM_ERR_NO_DEVICE
@@ -689,7 +693,8 @@ int gm_frontend_process_block(gm_frontend *f, float *raw_floats, size_t n_floats
 int gm_frontend_process_dev(gm_frontend *f, const void *d_in, int fmt, void *d_out, size_t n_samples, void *stream);
 /* n_streams independent streams (antennas, bands) in one launch, one workgroup each: fes[i] processes d_in[i] -> d_out[i]
  * (n_samples each); every front-end keeps its own state and NCO step; a handle may appear once per call.
- * Asynchronous on `stream` (NULL -> fes[0]'s own). */
+ * The launch goes out on `stream` (NULL -> fes[0]'s own) and is not waited for; the call itself WAITS ON THE HOST for what is
+ * queued on `stream` in front of it, once, while the streams' descriptors travel to the device. */
 int gm_frontend_process_dev_batch(gm_frontend *const *fes, uint32_t n_streams, const void *const *d_in, int fmt,
                                   void *const *d_out, size_t n_samples, void *stream);
 int gm_frontend_synchronize(gm_frontend *f);

@@ -10,6 +10,7 @@ Tolerances (stated here, used below):
 import numpy as np
 import pytest
 
+import stream_stall as SS     # (imports torch before the HIP library; the held caller's stream of the two stream tests)
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -601,10 +602,6 @@ def test_prepare_dev_is_safe_to_misuse(gpu, hipbuf, N, fmt_name):
     d_met = hipbuf.alloc(words * 4)
     d_buf = hipbuf.alloc(nbytes)                               # ONE buffer, refilled: the ring slot
     hip = hipbuf.hip
-    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
-    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-    hip.hipStreamDestroy.argtypes = [C.c_void_p]
 
     def fill(k):
         eng.synchronize()
@@ -643,29 +640,28 @@ def test_prepare_dev_is_safe_to_misuse(gpu, hipbuf, N, fmt_name):
     with pytest.raises(_lib.GmError):
         eng.search_prepared_dev(t2, d_met)
     assert (words_now() == want[1 if composite else 0]).all()  # nothing was launched by the refused calls
-    # ready_stream: the samples arrive by an asynchronous copy on another stream, queued BEHIND a long kernel-free delay
-    # (a second copy of a large block in front of it); stage F must wait for that stream, not read the buffer as it is
+    # ready_stream: the samples arrive by an asynchronous copy on another stream, queued BEHIND a delay that is provably still
+    # running when both entries have returned (stream_stall.py); stage F must wait for that stream, not read the buffer as it is
     fill(1)
-    s_copy = C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(s_copy), 1) == 0      # hipStreamNonBlocking
-    big = np.zeros(64 << 20, np.uint8)
-    d_big = hipbuf.alloc(big.nbytes)
-    assert hip.hipMemcpyAsync(d_big, big.ctypes.data, big.nbytes, 1, s_copy) == 0     # pageable: staged, takes a while
-    assert hip.hipMemcpyAsync(d_buf, snaps[0].ctypes.data, nbytes, 1, s_copy) == 0
-    tok = eng.prepare_dev(d_buf, fmt, ready_stream=s_copy.value)
-    # (composite sizes prepare nothing — the search itself reads the buffer — but keep the promise: the event recorded on
-    # ready_stream at prepare time is what the search waits for on the handle's stream; no host synchronisation here)
-    eng.search_prepared_dev(tok, d_met)
-    assert (words_now() == want[0]).all()
-    assert hip.hipStreamSynchronize(s_copy) == 0 and hip.hipStreamDestroy(s_copy) == 0
+    with SS.HeldStream() as S:
+        staged = S.stage(snaps[0])
+        S.hold("prepare_dev ready_stream")
+        S.h2d(d_buf, staged)
+        tok = eng.prepare_dev(d_buf, fmt, ready_stream=S.stream)
+        # (composite sizes prepare nothing — the search itself reads the buffer — but keep the promise: the event recorded on
+        # ready_stream at prepare time is what the search waits for on the handle's stream; no host synchronisation here)
+        eng.search_prepared_dev(tok, d_met)
+        S.assert_held()
+        assert (words_now() == want[0]).all()
     eng.close()
 
 
 @pytest.mark.parametrize("N", [2048, 32000])
 def test_caller_stream_orders_the_samples_without_a_synchronise(gpu, hipbuf, oracle, N):
     """The stream contract of include/gnss_mi355x.h (STREAMS) in its positive form — the hazard commit 50b74e7 found in a test
-    helper, turned round: the samples of a dwell are produced by ASYNCHRONOUS work on a caller's non-blocking stream (a slow
-    pageable copy of a large block in front of them, then the fill of the sample buffer, then a clear of the metrics block), the
+    helper, turned round: the samples of a dwell are produced by ASYNCHRONOUS work on a caller's non-blocking stream (a delay in
+    front of them that is provably still running when the last entry has returned: stream_stall.py; then the fill of the sample
+    buffer, then a clear of the metrics block), the
     handle is given that stream (gm_acq_set_stream), and search_dev + decide_dev + a D2H copy of the metrics are enqueued behind
     it with NO host synchronisation in between.  The words and the detections are those of the same scene searched
     synchronously; the snapshot-then-search order this stands for is do_acquisition.rs:297-313.  An in-LDS size and a composite."""
@@ -688,39 +684,27 @@ def test_caller_stream_orders_the_samples_without_a_synchronise(gpu, hipbuf, ora
     want_res = eng.fetch_results(P)
     want = hipbuf.download(d_met_ref, words * 4, np.uint32).copy()
     assert want_res[1] and want_res[3] and not want_res[0] and want_res[1]["code_phase_samples"] == N // 3
-    hip = hipbuf.hip
-    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
-    hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
-    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-    hip.hipStreamDestroy.argtypes = [C.c_void_p]
-    hip.hipHostMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_uint]
-    hip.hipHostFree.argtypes = [C.c_void_p]
     d_buf = hipbuf.upload(other)                                  # holds ANOTHER scene until the caller's stream refills it
     d_met = hipbuf.alloc(words * 4, fill=0xFF)
-    s_user = C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(s_user), 1) == 0  # hipStreamNonBlocking, like the library's own
-    h_met = C.c_void_p()
-    assert hip.hipHostMalloc(C.byref(h_met), words * 4, 0) == 0
-    C.memset(h_met, 0xEE, words * 4)
-    big = np.zeros(96 << 20, np.uint8)
-    d_big = hipbuf.alloc(big.nbytes)
-    eng.set_stream(s_user.value)
-    # producer (caller's stream): a long pageable copy, then the samples, then a clear of the metrics block ...
-    assert hip.hipMemcpyAsync(d_big, big.ctypes.data, big.nbytes, 1, s_user) == 0
-    assert hip.hipMemcpyAsync(d_buf, x.ctypes.data, x.nbytes, 1, s_user) == 0
-    assert hip.hipMemsetAsync(d_met, 0, words * 4, s_user) == 0
-    # ... the library's dwell behind it, in stream order, and the consumer behind the dwell: no synchronise anywhere in between
-    eng.search_dev(d_buf, A.FMT_I8_IQ, d_met)
-    eng.decide_dev(d_met)
-    assert hip.hipMemcpyAsync(h_met, d_met, words * 4, 2, s_user) == 0
-    assert hip.hipStreamSynchronize(s_user) == 0
-    got = np.frombuffer(C.string_at(h_met, words * 4), np.uint32)
-    assert (got == want).all()
-    key = lambda r: r and (r["prn"], r["code_phase_samples"], r["doppler_bin"], r["mag_relative"])
-    assert [key(r) for r in eng.fetch_results(P)] == [key(r) for r in want_res]
-    eng.close()
-    assert hip.hipHostFree(h_met) == 0 and hip.hipStreamDestroy(s_user) == 0
+    with SS.HeldStream() as S:                                    # a non-blocking stream, like the library's own
+        staged, h_met = S.stage(x), S.pinned(words * 4, fill=0xEE)
+        eng.set_stream(S.stream)
+        S.own(eng)                                                # (closed before the stream goes, whatever happens below)
+        # producer (caller's stream): the delay, then the samples, then a clear of the metrics block ...
+        S.hold("search_dev behind set_stream")
+        S.h2d(d_buf, staged)
+        S.memset(d_met, 0, words * 4)
+        # ... the library's dwell behind it, in stream order, and the consumer behind the dwell: no synchronise anywhere in between
+        eng.search_dev(d_buf, A.FMT_I8_IQ, d_met)
+        eng.decide_dev(d_met)
+        S.d2h(d_met, words * 4, h_met)
+        S.assert_held()                                           # ... and the delay outlasted all of it
+        S.sync()
+        got = h_met.view(np.uint32).copy()
+        assert (got == want).all()
+        key = lambda r: r and (r["prn"], r["code_phase_samples"], r["doppler_bin"], r["mag_relative"])
+        assert [key(r) for r in eng.fetch_results(P)] == [key(r) for r in want_res]
+        eng.close()
 
 
 @pytest.mark.parametrize("opts", [dict(strict_sum_order=True), dict(reference_products=True), dict()])
