@@ -9,6 +9,7 @@ include/gnss_mi355x.h.  This Python package is plumbing around it:
   ddc                            real-IF int8 down-conversion to complex baseband (exact NCO, the resampler's polyphase filter)
   channelizer                    polyphase filter bank: M sub-bands of one stream (FDMA carriers), and the GLONASS L1OF code
   nuller                         adaptive spatial nulling: A interleaved antennas combined per block with weights from the block's covariance
+  stap                           space-time adaptive nulling: the nuller with L taps in time behind every antenna
   synth       deterministic synthetic IF scenes
   build       hipcc build recipe
 """
@@ -19,3 +20,4 @@ from .excise import Excisor  # noqa: F401
 from .ddc import Ddc  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
 from .nuller import Nuller  # noqa: F401
+from .stap import Stap  # noqa: F401

@@ -117,6 +117,13 @@ class NullerCfg(C.Structure):
                 ("steering", C.c_void_p)]
 
 
+class StapCfg(C.Structure):
+    """gm_stap_cfg (32 bytes): zeros are the defaults; steering points at taps * n_antennas complex64 words [taps][n_antennas], or is
+    NULL (e_0)"""
+    _fields_ = [("n_antennas", C.c_uint32), ("taps", C.c_uint32), ("block", C.c_uint32), ("loading", C.c_float),
+                ("steering", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class ExcisorCfg(C.Structure):
     """gm_excisor_cfg (32 bytes): zeros are the defaults"""
     _fields_ = [("block", C.c_uint32), ("guard_bins", C.c_uint32), ("threshold_factor", C.c_float), ("blank_threshold", C.c_float),
@@ -342,6 +349,16 @@ SIGNATURES = {
     "gm_nuller_capture": (_i, [_vp, _vp, _vp, _sz]),
     "gm_nuller_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
     "gm_nuller_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
+    "gm_stap_plan": (_i, [C.POINTER(StapCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(C.c_float), C.POINTER(_u64)]),
+    "gm_stap_create": (_i, [C.POINTER(StapCfg), C.POINTER(_vp)]),
+    "gm_stap_destroy": (_i, [_vp]),
+    "gm_stap_reset": (_i, [_vp, _u64]),
+    "gm_stap_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_stap_synchronize": (_i, [_vp]),
+    "gm_stap_set_weights": (_i, [_vp, _vp]),
+    "gm_stap_capture": (_i, [_vp, _vp, _vp, _sz]),
+    "gm_stap_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "gm_stap_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
     "gm_trk_create": (_i, [C.POINTER(TrkCfg), C.POINTER(_vp)]),
     "gm_trk_destroy": (_i, [_vp]),
     "gm_trk_start": (_i, [_vp, _u32, C.POINTER(AcqResult)]),

@@ -5028,6 +5028,180 @@ int gm_nuller_process(gm_nuller* n, const void* in, int fmt, size_t n_in, gm_c32
 
 }  // extern "C"
 
+// ====================================================================== space-time adaptive nulling, taps on every antenna (gm_stap)
+// gnss_mi355x.h states the definition; tests/stap_model.py restates it in float64.
+namespace {
+struct StapPlan {
+    uint32_t A = 0, L = 0, M = 0, B = 0;
+    float loading = 0.0f;
+    cf s[gm::ST_M_MAX] = {};
+};
+
+int stap_rules(const gm_stap_cfg* c, StapPlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    if (c->reserved) return set_err(GM_ERR_INVALID_ARG, "gm_stap_cfg.reserved must be 0");
+    if (c->n_antennas < 2 || c->n_antennas > uint32_t(gm::NL_A_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_antennas: 2 .. 8");
+    if (c->taps < 1 || c->taps > uint32_t(gm::ST_L_MAX)) return set_err(GM_ERR_INVALID_ARG, "taps: 1 .. 8");
+    if (c->n_antennas * c->taps > uint32_t(gm::ST_M_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_antennas * taps: at most 32");
+    const uint32_t B = c->block ? c->block : 1024;
+    if (B < 256 || B > 16384 || (B & (B - 1))) return set_err(GM_ERR_INVALID_ARG, "block: a power of two in 256 .. 16384, 0 for the default");
+    if (!std::isfinite(c->loading)) return set_err(GM_ERR_INVALID_ARG, "loading must be finite");
+    if (c->loading != 0.0f && !(c->loading >= 1e-6f && c->loading <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "loading: [1e-6, 1], 0 for the default");
+    p.A = c->n_antennas; p.L = c->taps; p.M = p.A * p.L; p.B = B; p.loading = c->loading == 0.0f ? 1e-4f : c->loading;
+    for (uint32_t i = 0; i < uint32_t(gm::ST_M_MAX); ++i) p.s[i] = gm::cf_make(i == 0 ? 1.0f : 0.0f, 0.0f);
+    if (c->steering) {
+        if (!nuller_finite(c->steering, p.M)) return set_err(GM_ERR_INVALID_ARG, "steering must be finite");
+        bool any = false;
+        for (uint32_t i = 0; i < p.M; ++i) {
+            p.s[i] = gm::cf_make(c->steering[i].re, c->steering[i].im);
+            any = any || c->steering[i].re != 0.0f || c->steering[i].im != 0.0f;
+        }
+        if (!any) return set_err(GM_ERR_INVALID_ARG, "steering is all zero");
+    }
+    return GM_OK;
+}
+
+// total_out(T) = B * (T div B)
+uint64_t stap_total_out(const StapPlan& p, uint64_t T) { return T / p.B * p.B; }
+}  // namespace
+
+struct gm_stap : StreamStage {              // history: the L - 1 converted time samples in front of the unfinished block, then that
+    StapPlan plan;                          // block's (cf [L - 1 + B][A]); d_blanked counts the fallback blocks
+    bool fixed = false;                     // static mode
+    cf w[gm::ST_M_MAX] = {};
+    cf* cap_R = nullptr; cf* cap_w = nullptr; size_t cap_blocks = 0;     // the caller's capture (device)
+    cf* d_blk = nullptr; size_t blk_cap = 0;                             // blocks; the host-buffer entry's own capture: [blk_cap][M][M] then [blk_cap][M]
+};
+
+// one call's kernels on `st`; the caller has checked every argument; n_in > 0
+static int stap_launch(gm_stap* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t n_out, cf* cap_R, cf* cap_w) {
+    const StapPlan& p = n->plan;
+    const uint64_t T = n->base + n->inputs;
+    gm::StapArgs a{};
+    a.in = d_in; a.n_in = n_in; a.fmt = fmt;
+    a.hist_in = static_cast<const cf*>(n->d_hist[n->cur]); a.hist_out = static_cast<cf*>(n->d_hist[n->cur ^ 1]);
+    a.A = p.A; a.L = p.L; a.B = p.B;
+    a.pending = uint32_t(T % p.B); a.pending_out = uint32_t((T + n_in) % p.B);
+    a.n_blocks = n_out / p.B;
+    a.out = out; a.cap_R = cap_R; a.cap_w = cap_w;
+    a.loading = p.loading; a.adaptive = n->fixed ? 0 : 1;
+    a.fallbacks = n->d_blanked;
+    for (int i = 0; i < gm::ST_M_MAX; ++i) { a.s[i] = p.s[i]; a.w[i] = n->w[i]; }
+    gm::launch_stap(st, a);
+    return stage_launched(n, st, n_in, n_out);
+}
+static uint64_t stap_count(const gm_stap* n, uint64_t n_in) {
+    const uint64_t T = n->base + n->inputs;
+    return stap_total_out(n->plan, T + n_in) - stap_total_out(n->plan, T);
+}
+static const char* stap_fmt_err(int fmt) {
+    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "stap input is interleaved c32 or int8 IQ" : nullptr;
+}
+
+extern "C" {
+
+int gm_stap_plan(const gm_stap_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, float* loading, uint64_t* n_out) {
+    StapPlan p;
+    if (int rc = stap_rules(cfg, p)) return rc;
+    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (block) *block = p.B;
+    if (loading) *loading = p.loading;
+    if (n_out) *n_out = stap_total_out(p, inputs_so_far + n_in) - stap_total_out(p, inputs_so_far);
+    return GM_OK;
+}
+
+int gm_stap_create(const gm_stap_cfg* cfg, gm_stap** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    StapPlan p;
+    if (int rc = stap_rules(cfg, p)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_stap* n = new gm_stap;
+    n->device = g_device; n->plan = p;
+    hipError_t e = stage_create(n, (size_t(p.B) + p.L - 1) * p.A * sizeof(cf));
+    if (e != hipSuccess) { gm_stap_destroy(n); return hip_fail(e, "gm_stap_create"); }
+    *out = n;
+    return GM_OK;
+}
+
+int gm_stap_destroy(gm_stap* n) {
+    if (!n) return GM_OK;
+    stage_destroy(n);
+    hipFree(n->d_blk);
+    delete n;
+    return GM_OK;
+}
+
+int gm_stap_reset(gm_stap* n, uint64_t input_index) {
+    return stage_reset(n, input_index, [] { return hipSuccess; });
+}
+
+int gm_stap_stats(gm_stap* n, uint64_t* inputs, uint64_t* outputs, uint64_t* blocks, uint64_t* fallback_blocks) {
+    if (int rc = stage_stats(n, inputs, outputs, fallback_blocks)) return rc;
+    if (blocks) *blocks = n->outputs / n->plan.B;
+    return GM_OK;
+}
+
+int gm_stap_synchronize(gm_stap* n) { return stage_synchronize(n); }
+
+int gm_stap_set_weights(gm_stap* n, const gm_c32* w) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!w) { n->fixed = false; return GM_OK; }
+    if (!nuller_finite(w, n->plan.M)) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
+    for (uint32_t i = 0; i < n->plan.M; ++i) n->w[i] = gm::cf_make(w[i].re, w[i].im);
+    n->fixed = true;
+    return GM_OK;
+}
+
+int gm_stap_capture(gm_stap* n, void* d_R, void* d_w, size_t cap_blocks) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if ((d_R == nullptr) != (d_w == nullptr)) return set_err(GM_ERR_INVALID_ARG, "d_R and d_w: both or neither");
+    if ((d_R == nullptr) != (cap_blocks == 0)) return set_err(GM_ERR_INVALID_ARG, "cap_blocks: 0 exactly where the pointers are null");
+    n->cap_R = static_cast<cf*>(d_R); n->cap_w = static_cast<cf*>(d_w); n->cap_blocks = cap_blocks;
+    return GM_OK;
+}
+
+int gm_stap_process_dev(gm_stap* n, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out, void* stream) {
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(n, stap_count, stap_fmt_err(fmt), d_in, n_in, d_out, out_cap, "gm_stap_plan", &cnt)) return rc;
+    if (n->cap_w && cnt / n->plan.B > n->cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "the capture is smaller than the call's blocks");
+    if (int rc = stage_check_overlap(d_in, n_in * n->plan.A * (fmt == GM_FMT_C32 ? 8 : 2), d_out, cnt)) return rc;
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(n->device)) return rc;
+    return stap_launch(n, stream ? static_cast<hipStream_t>(stream) : n->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), cnt, n->cap_R, n->cap_w);
+}
+
+int gm_stap_process(gm_stap* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out, gm_c32* R, gm_c32* w,
+                    size_t cap_blocks) {
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(n, stap_count, stap_fmt_err(fmt), in, n_in, out, out_cap, "gm_stap_plan", &cnt)) return rc;
+    const uint64_t blocks = cnt / n->plan.B;
+    const bool want = (R || w) && blocks;
+    if ((R || w) && blocks > cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "cap_blocks below the call's blocks");
+    const size_t M = n->plan.M, MM = M * M, A = n->plan.A;
+    if (want && n->blk_cap < blocks) {
+        if (int rc = ensure_device(n->device)) return rc;
+        if (int rc = stage_sync(n)) return rc;
+        hipFree(n->d_blk); n->d_blk = nullptr; n->blk_cap = 0;
+        HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_blk), size_t(blocks) * (MM + M) * sizeof(cf)));
+        n->blk_cap = size_t(blocks);
+    }
+    cf* d_R = want ? n->d_blk : nullptr;
+    cf* d_w = want ? n->d_blk + n->blk_cap * MM : nullptr;
+    if (int rc = stage_process(n, in, n_in * A * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
+            return stap_launch(n, st, d_in, fmt, n_in, d_out, cnt, d_R, d_w);
+        })) return rc;
+    if (want) {      // stage_process has waited for the kernels
+        if (R && !n->fixed) HIPC(hipMemcpy(R, d_R, size_t(blocks) * MM * sizeof(cf), hipMemcpyDeviceToHost));
+        if (w) HIPC(hipMemcpy(w, d_w, size_t(blocks) * M * sizeof(cf), hipMemcpyDeviceToHost));
+    }
+    return GM_OK;
+}
+
+}  // extern "C"
+
 // ====================================================================== multi-GPU exchange
 // The path's ONE exchange step: all-gather of the per-(worker, bin) metrics over RCCL, enqueued on the acquisition
 // handle's stream, followed by the regroup to the [3][nranks*P][D] layout gm_acq_decide_dev replays.  RCCL is bound

@@ -489,6 +489,29 @@ inline uint32_t nuller_in_align(uint32_t A, int fmt) {
 }
 void launch_nuller(hipStream_t, const NullerArgs&, int fmt);
 
+// ---------------------------------------------------------------- space-time adaptive nulling, taps on every antenna (stap_kernels.hip)
+// gnss_mi355x.h states the definition.  One call = one launch of the block kernel (a workgroup per finished block of B time samples: Gram
+// matrix, weights, output) and one of the state kernel.  The call's span starts H = L - 1 time samples in front of the unfinished block:
+// time sample v of the span is word v of the old history for v < H + pending, else time sample v - (H + pending) of the call's input.
+constexpr int ST_L_MAX = 8;
+constexpr int ST_M_MAX = 32;               // A L at most
+struct StapArgs {
+    const void* in; uint64_t n_in;         // this call's TIME samples, each A interleaved elements (c32 or int8 IQ)
+    int fmt;                               // GM_FMT_C32 or GM_FMT_I8_IQ
+    const cf* hist_in; cf* hist_out;       // [L - 1 + B][A] the converted time samples in front of and in the unfinished block, before / after
+    uint32_t A, L, B;
+    uint32_t pending, pending_out;         // time samples of the unfinished block in hist_in (< B); in hist_out after this call (< B)
+    uint64_t n_blocks;                     // blocks this call finishes
+    cf* out;                               // [n_blocks * B]
+    cf* cap_R; cf* cap_w;                  // [n_blocks][M][M], [n_blocks][M]; null: not captured
+    float loading;
+    int adaptive;                          // 0: the fixed weights `w` for every block, no Gram matrix
+    unsigned long long* fallbacks;         // device counter of the blocks that took w = s / (s^H s): integer atomics only
+    cf s[ST_M_MAX];                        // the constraint vector [L][A]
+    cf w[ST_M_MAX];                        // the fixed weights
+};
+void launch_stap(hipStream_t, const StapArgs&);
+
 // ---------------------------------------------------------------- narrowband interference excision (excise_kernels.hip)
 // gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of G segments of H = B / 2
 // outputs) and one of the state kernel (the next history of 3H blanked inputs, the blanked count).  The host hands over where the

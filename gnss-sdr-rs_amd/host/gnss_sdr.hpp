@@ -548,6 +548,66 @@ public:
     void synchronize() { check(gm_nuller_synchronize(h_), "Nuller::synchronize"); }
 };
 
+// ---- space-time adaptive nulling (gm_stap): the nuller's interleaved stream with `taps` taps in time behind every antenna; per block
+// of B time samples the M = antennas * taps weights come from the exact Gram matrix of the block's stacked samples, so that a narrowband
+// interferer costs a temporal degree of freedom, not a spatial one.  Steering and weights are laid out [taps][antennas].
+class Stap {
+    gm_stap* h_ = nullptr;
+    uint32_t antennas_ = 0, taps_ = 0, block_ = 0;
+public:
+    // block 0: 1024; loading 0: 1e-4; steering empty: e_0 (antenna 0 at tap 0)
+    Stap(uint32_t n_antennas, uint32_t taps, uint32_t block = 0, float loading = 0.0f, const std::vector<Complex32>& steering = {}) {
+        gm_stap_cfg cfg{};
+        cfg.n_antennas = n_antennas; cfg.taps = taps; cfg.block = block; cfg.loading = loading;
+        if (!steering.empty() && steering.size() != size_t(n_antennas) * taps) check(GM_ERR_INVALID_ARG, "Stap::new (steering: taps * n_antennas words)");
+        cfg.steering = steering.empty() ? nullptr : reinterpret_cast<const gm_c32*>(steering.data());
+        check(gm_stap_plan(&cfg, 0, 0, &block_, nullptr, nullptr), "Stap::new");
+        antennas_ = n_antennas; taps_ = taps;
+        check(gm_stap_create(&cfg, &h_), "Stap::new");
+    }
+    ~Stap() { gm_stap_destroy(h_); }
+    Stap(const Stap&) = delete;
+    gm_stap* handle() const { return h_; }
+    uint32_t antennas() const { return antennas_; }
+    uint32_t taps() const { return taps_; }
+    uint32_t weights() const { return antennas_ * taps_; }
+    uint32_t block() const { return block_; }
+    // the synchronous host-buffer form: n time samples (n * antennas elements) -> this call's outputs; R ([blocks][M][M]) and w
+    // ([blocks][M]) receive the words each of the call's blocks was combined with, where given
+    std::vector<Complex32> process(const void* in, int fmt, size_t n, std::vector<Complex32>* R = nullptr, std::vector<Complex32>* w = nullptr) {
+        const size_t cap = n + block_, nb = cap / block_, M = weights();
+        std::vector<Complex32> out(cap);
+        if (R) R->assign(nb * M * M, Complex32{});
+        if (w) w->assign(nb * M, Complex32{});
+        size_t got = 0;
+        check(gm_stap_process(h_, in, fmt, n, reinterpret_cast<gm_c32*>(out.data()), cap, &got,
+                              R ? reinterpret_cast<gm_c32*>(R->data()) : nullptr, w ? reinterpret_cast<gm_c32*>(w->data()) : nullptr, nb),
+              "Stap::process");
+        out.resize(got);
+        if (R) R->resize(got / block_ * M * M);
+        if (w) w->resize(got / block_ * M);
+        return out;
+    }
+    // device pointers; asynchronous on `stream` (nullptr: the handle's own); returns the outputs written
+    size_t process_dev(const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, void* stream = nullptr) {
+        size_t n = 0;
+        check(gm_stap_process_dev(h_, d_in, fmt, n_in, d_out, out_cap, &n, stream), "Stap::process_dev");
+        return n;
+    }
+    // fixed weights for every later block (static mode); empty: back to the adaptive rule
+    void set_weights(const std::vector<Complex32>& w) {
+        if (!w.empty() && w.size() != weights()) check(GM_ERR_INVALID_ARG, "Stap::set_weights (taps * n_antennas words)");
+        check(gm_stap_set_weights(h_, w.empty() ? nullptr : reinterpret_cast<const gm_c32*>(w.data())), "Stap::set_weights");
+    }
+    // device buffers [cap_blocks][M][M] and [cap_blocks][M] that every later process_dev fills from word 0; nulls and 0 end it
+    void capture(void* d_R, void* d_w, size_t cap_blocks) { check(gm_stap_capture(h_, d_R, d_w, cap_blocks), "Stap::capture"); }
+    void reset(uint64_t input_index = 0) { check(gm_stap_reset(h_, input_index), "Stap::reset"); }
+    void stats(uint64_t* inputs, uint64_t* outputs, uint64_t* blocks, uint64_t* fallback_blocks = nullptr) const {
+        check(gm_stap_stats(h_, inputs, outputs, blocks, fallback_blocks), "Stap::stats");
+    }
+    void synchronize() { check(gm_stap_synchronize(h_), "Stap::synchronize"); }
+};
+
 // ---- rf::frontend::DigitalFrontend (src/rf/frontend.rs:6-62)
 class DigitalFrontend {
     gm_frontend* h_ = nullptr;

@@ -21,8 +21,8 @@
  *     on that stream), or synchronise the producer first.  gm_acq_prepare_dev takes the producer's stream per call
  *     (`ready_stream`).  The reference copies its 10 ms out of the ring and THEN searches them (do_acquisition.rs:297-313): the
  *     stream order is that sequence.  INTEGRATION.md §3.3; tests/test_gpu_acquisition.py::test_caller_stream_orders_...
- *     The streaming stage handles (gm_frontend, gm_resampler, gm_excisor, gm_ddc, gm_channelizer, gm_nuller) take the producer's
- *     stream per call, as the `stream` argument of their `_dev` entries: the call runs behind what the caller has queued there, its
+ *     The streaming stage handles (gm_frontend, gm_resampler, gm_excisor, gm_ddc, gm_channelizer, gm_nuller, gm_stap) take the
+ *     producer's stream per call, as the `stream` argument of their `_dev` entries: the call runs behind what the caller has queued there, its
  *     outputs and the handle's history are ready on that stream, and the handle's own queries, reset, host-buffer entry and ring
  *     writers wait for it (gm_frontend's wait for the handle's own stream only); tests/test_gpu_caller_streams.py.
  *   - arithmetic type: f32 everywhere, as in the reference (num_complex::Complex32 = {f32 re, im})
@@ -1116,7 +1116,8 @@ int gm_channelizer_synchronize(gm_channelizer *c);
  *   Monitor.  gm_nuller_capture names device buffers that every later gm_nuller_process_dev fills with its blocks' R and w words.
  *   Kernel (csrc/nuller_kernels.hip): one 256-lane workgroup per block: the sums in registers, shuffles and LDS for the tree, the
  *     solve in wave 0 fully unrolled on A, a second read of the block (from L2) for y; a state kernel carries the unfinished block.
- * Not built: a ring writer with the nuller as head stage; wiring into receiver_harness.cpp; taps in time (STAP); array calibration;
+ * Not built: a ring writer with the nuller as head stage; wiring into receiver_harness.cpp; array calibration (taps in time are a
+ * stage of their own, gm_stap below);
  * blanking inside the stage (its output goes into a gm_excisor or gm_resampler, which blank); any decision — the library reports R
  * and w, the caller judges.
  * (ABI 9, additive: a caller detects the feature by the symbol) */
@@ -1164,6 +1165,91 @@ int gm_nuller_process_dev(gm_nuller *n, const void *d_in, int fmt, size_t n_in, 
  * In static mode R is left untouched.  A device capture set by gm_nuller_capture is not written by this form. */
 int gm_nuller_process(gm_nuller *n, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out, gm_c32 *R,
                       gm_c32 *w, size_t cap_blocks);
+
+/* ------------------------------------------------------------------ Space-time adaptive nulling: taps on every antenna
+ * A gm_stap is a gm_nuller with L taps in time (1 .. 8) behind each of the A antennas (2 .. 8), M = A L <= 32 weights in all: a
+ * narrowband interferer then costs one temporal degree of freedom, not one of the A - 1 spatial ones.  The input is the nuller's: ONE
+ * interleaved stream of GM_FMT_C32 or GM_FMT_I8_IQ elements, time sample n of antenna a being element n * A + a; the output one c32
+ * stream at the same rate and time index (no timestamp delay).  Every count is in TIME samples; everything is defined by ABSOLUTE
+ * indices: the words do not depend on how the stream is cut into calls, and two runs give the same words.
+ *   Blocks.  Block b covers the time samples [b B, (b+1) B); B is a power of two in 256 .. 16384.  After T time samples
+ *     total_out(T) = B * (T div B) outputs exist; a call delivers the difference, computed on the host with no synchronisation.  There
+ *     is no flush.  The handle's history carries the (converted) time samples of the unfinished block and the L - 1 in front of it.
+ *   Stacked sample.  z[t][l A + a] = x_a[t - l], t absolute, l = 0 .. L - 1; an int8 sample is converted to f32 first (-128 is
+ *     -128.0f).  Samples before the stream's start are zeros, and after gm_stap_reset(input_index) so are those before input_index.
+ *   Covariance, f32: the exact Gram matrix of the block's stacked samples (not a Toeplitz approximation),
+ *       R[p][q] = sum_{t in [bB, (b+1)B)} z_p[t] conj(z_q[t]),
+ *     Hermitian word for word, the diagonal's imaginary part +0.  THE ORDER, for p = l A + a <= q = (l + k) A + b, with u = t - l
+ *     relative to the block's start and the term of u being x_a[u] conj(x_b[u - k]), accumulated as
+ *       re = fmaf(xa.re, xb.re, re);  re = fmaf(xa.im, xb.im, re);  im = fmaf(xa.im, xb.re, im);  im = fmaf(-xa.re, xb.im, im):
+ *     (1) the INTERIOR u in [0, B - L + 1), which all entries of a lag k and pair (a, b) share, in groups of 1024 (the last one
+ *     shorter; one group where B <= 1024): per group 64 lane sums S[j], each over u = j, j + 64, j + 128, ... of the group ascending from
+ *     +0, then S[j] = S[j] + S[j + d] for d = 32, 16, 8, 4, 2, 1, the group's sum being S[0]; the groups' sums are added in ascending
+ *     order, from +0.  (2) Then the entry's own L - 1 edge terms, one by one: u = -l .. -1, then u = B - L + 1 .. B - l - 1.
+ *     A function of the block-relative position alone; no floating-point atomics.  Each component goes through at most
+ *     min(B, 1024) / 32 + 6 + B / 1024 + 2 (L - 1) roundings (68 at B = 16384, L = 8), so the entry is within
+ *     sqrt(2) * 68 * 2^-24 = 5.8e-6 of sum_t |z_p| |z_q| of the exact sum.
+ *   Weights, f64 from the f32 words of R:  tr = sum_p Re R[p][p] (p ascending);  Rl = R + loading * (tr / M) * I, loading being the f32
+ *     word widened;  u = Rl^-1 s;  w = u / (s^H u);  each component of w rounded once to f32.  The device solves by Cholesky,
+ *     Rl = C C^H (left-looking, columns ascending): z = C^-1 s, s^H u = z^H z, u = C^-H z.
+ *     s is the caller's constraint vector, M c32 words [L][A], not all zero; NULL means e_0 (antenna 0 at tap 0: power inversion with
+ *     no delay), and Re w[0] comes out as 1.0f.
+ *   Fallback.  w = s / (s^H s) where tr = 0, or a Cholesky pivot (or z^H z) is not greater than 0 or not finite; the block is counted
+ *     in fallback_blocks.  Finite input never produces a NaN.
+ *   Output, f32:  y[t] = sum_l sum_a conj(w[l A + a]) x_a[t - l], w the f32 words just rounded: from +0, l ASCENDING, then a ascending,
+ *       re = fmaf(w.re, x.re, re);  re = fmaf(w.im, x.im, re);  im = fmaf(w.re, x.im, im);  im = fmaf(-w.im, x.re, im);
+ *     within (M + 2) 2^-24 sum |w| |z| of the exact value.  Block b's weights serve all B of its outputs, the taps that reach back into
+ *     block b - 1 included.
+ *   Static mode.  gm_stap_set_weights installs M fixed weights used for every block; no Gram matrix is formed.
+ *   Monitor.  gm_stap_capture names device buffers that every later gm_stap_process_dev fills with its blocks' R and w words.
+ *   Kernel (csrc/stap_kernels.hip): one 256-lane workgroup per block; the block passes through LDS in chunks of 256 + L - 1 samples;
+ *     the four waves share the lags; the solve in LDS in f64; a second pass through the same chunks for y; a state kernel.
+ * Limits (README, measured by tests/stap_model.py): ONE constraint shapes the signal's spectrum — at L = 2 a correlation peak can land
+ * a sample off; a reference on tap l0 delays the peak by l0 samples; a quantiser's clipping products are not low rank.
+ * Not built: a ring writer with the stage at its head; wiring into receiver_harness.cpp; more than one constraint (distortionless or
+ * multi-beam forms); array calibration; any decision — the library reports R, w and the fallback count, the caller judges.
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct {
+    uint32_t n_antennas;      /* A: 2 .. 8 */
+    uint32_t taps;            /* L: 1 .. 8, A L <= 32 */
+    uint32_t block;           /* B: a power of two in 256 .. 16384; 0 -> 1024 */
+    float    loading;         /* [1e-6, 1]: diagonal loading as a fraction of the mean stacked power tr / M; 0 -> 1e-4 */
+    const gm_c32 *steering;   /* [L][A] c32 words, finite, not all zero; NULL -> e_0.  Read during the call that takes the cfg only. */
+    uint64_t reserved;        /* must be 0 */
+} gm_stap_cfg;
+typedef struct gm_stap gm_stap;
+/* host only, no device: the argument rules (GM_ERR_INVALID_ARG for an A, L, A L, B or loading outside its range, a non-finite loading
+ * or steering word, an all-zero steering, reserved != 0, inputs_so_far + n_in above 2^62); *block = B, *loading = the f32 word used
+ * and, for a stream that has taken inputs_so_far time samples, the count of outputs that n_in more deliver.  Any output pointer may
+ * be NULL. */
+int gm_stap_plan(const gm_stap_cfg *cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t *block, float *loading, uint64_t *n_out);
+int gm_stap_create(const gm_stap_cfg *cfg, gm_stap **out);
+int gm_stap_destroy(gm_stap *n);
+/* Zeroes the history and the counters; the stream continues as if input_index zero time samples had gone before.  Keeps the weights
+ * mode and the capture.  Synchronous.  input_index above 2^62: GM_ERR_INVALID_ARG. */
+int gm_stap_reset(gm_stap *n, uint64_t input_index);
+/* time samples taken, outputs delivered, blocks finished and blocks that took the fallback weights since gm_stap_create or the last
+ * gm_stap_reset (any pointer may be NULL).  Synchronises the handle's stream and the stream the last call ran on. */
+int gm_stap_stats(gm_stap *n, uint64_t *inputs, uint64_t *outputs, uint64_t *blocks, uint64_t *fallback_blocks);
+int gm_stap_synchronize(gm_stap *n);
+/* w: M finite c32 words [L][A] used for every later block (static mode); NULL returns the handle to the adaptive rule.  The words
+ * are copied during the call and travel with each later call's launch. */
+int gm_stap_set_weights(gm_stap *n, const gm_c32 *w);
+/* Every later gm_stap_process_dev writes its blocks' words to device memory, block k of the CALL at d_R + k M M (c32 [M][M], row p
+ * column q = R[p][q]) and d_w + k M (c32 [M]), from word 0 on each call; a call that finishes more than cap_blocks blocks is refused
+ * (GM_ERR_OUT_OF_RANGE) before anything runs.  In static mode only w is written.  d_R = d_w = NULL with cap_blocks = 0 ends the
+ * capture; one pointer without the other, or pointers with cap_blocks = 0, is GM_ERR_INVALID_ARG. */
+int gm_stap_capture(gm_stap *n, void *d_R, void *d_w, size_t cap_blocks);
+/* d_in (n_in TIME samples, n_in * A elements of GM_FMT_C32 or GM_FMT_I8_IQ; GM_FMT_I8_REAL is refused) -> d_out, c32: this call's
+ * *n_out outputs; words behind them are not touched (n_out may be NULL).  Asynchronous on `stream` (a hipStream_t; NULL: the handle's
+ * own non-blocking stream); consecutive calls of a handle must be ordered against each other.  Every argument is checked before
+ * anything runs, with gm_nuller_process_dev's refusals; each with nothing launched and the state unchanged.  n_in = 0: GM_OK. */
+int gm_stap_process_dev(gm_stap *n, const void *d_in, int fmt, size_t n_in, void *d_out, size_t out_cap, size_t *n_out, void *stream);
+/* the synchronous host-buffer form (H2D, the kernels, D2H on the handle's stream).  R ([blocks][M][M]) and w ([blocks][M]) are host
+ * buffers for the call's block words, each may be NULL; with either given, cap_blocks below the call's blocks is GM_ERR_OUT_OF_RANGE.
+ * In static mode R is left untouched.  A device capture set by gm_stap_capture is not written by this form. */
+int gm_stap_process(gm_stap *n, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out, gm_c32 *R,
+                    gm_c32 *w, size_t cap_blocks);
 
 /* ------------------------------------------------------------------ Tracking
  * The evolving fields of TrackingChannel (src/tracking/do_tracking.rs:88-116). */

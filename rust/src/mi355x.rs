@@ -189,6 +189,16 @@ pub struct GmNullerCfg {            // gm_nuller_cfg (24 bytes; zeros: the defau
     pub steering: *const Complex32,  // [A] finite words, not all zero; null -> e_0 (antenna 0 as the reference)
 }
 pub enum GmNuller {}
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct GmStapCfg {              // gm_stap_cfg (32 bytes; zeros: the defaults)
+    pub n_antennas: u32,             // A: 2 .. 8, interleaved time sample by time sample in one stream
+    pub taps: u32,                   // L: 1 .. 8 taps in time behind every antenna, A L <= 32
+    pub block: u32,                  // B: a power of two in 256 .. 16384; 0 -> 1024
+    pub loading: f32,                // [1e-6, 1] of the mean stacked power; 0 -> 1e-4
+    pub steering: *const Complex32,  // [L][A] finite words, not all zero; null -> e_0 (antenna 0 at tap 0)
+    pub reserved: u64,               // must be 0
+}
+pub enum GmStap {}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {} pub enum GmExcisor {}
 
 extern "C" {
@@ -355,6 +365,24 @@ extern "C" {
                                  n_out: *mut usize, stream: *mut c_void) -> c_int;
     pub fn gm_nuller_process(n: *mut GmNuller, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32, out_cap: usize,
                              n_out: *mut usize, r: *mut Complex32, w: *mut Complex32, cap_blocks: usize) -> c_int;
+
+    /// space-time adaptive nulling: the nuller's stream with L taps in time behind every antenna, M = A L weights a block from the
+    /// exact Gram matrix of its stacked samples z[t][l A + a] = x_a[t - l]; every count is in TIME samples
+    pub fn gm_stap_plan(cfg: *const GmStapCfg, inputs_so_far: u64, n_in: u64, block: *mut u32, loading: *mut f32,
+                        n_out: *mut u64) -> c_int;
+    pub fn gm_stap_create(cfg: *const GmStapCfg, out: *mut *mut GmStap) -> c_int;
+    pub fn gm_stap_destroy(n: *mut GmStap) -> c_int;
+    pub fn gm_stap_reset(n: *mut GmStap, input_index: u64) -> c_int;
+    pub fn gm_stap_stats(n: *mut GmStap, inputs: *mut u64, outputs: *mut u64, blocks: *mut u64, fallback_blocks: *mut u64) -> c_int;
+    pub fn gm_stap_synchronize(n: *mut GmStap) -> c_int;
+    /// static mode: M fixed weights [L][A] for every later block; null: back to the adaptive rule
+    pub fn gm_stap_set_weights(n: *mut GmStap, w: *const Complex32) -> c_int;
+    /// device buffers [cap_blocks][M][M] and [cap_blocks][M] that every later gm_stap_process_dev fills from word 0
+    pub fn gm_stap_capture(n: *mut GmStap, d_r: *mut c_void, d_w: *mut c_void, cap_blocks: usize) -> c_int;
+    pub fn gm_stap_process_dev(n: *mut GmStap, d_in: *const c_void, fmt: c_int, n_in: usize, d_out: *mut c_void, out_cap: usize,
+                               n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gm_stap_process(n: *mut GmStap, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32, out_cap: usize,
+                           n_out: *mut usize, r: *mut Complex32, w: *mut Complex32, cap_blocks: usize) -> c_int;
     // do_tracking.rs:118-158, 311-327
     pub fn gm_trk_create(cfg: *const GmTrkCfg, out: *mut *mut GmTrk) -> c_int;
     pub fn gm_trk_destroy(t: *mut GmTrk) -> c_int;
