@@ -10,6 +10,7 @@ include/gnss_mi355x.h.  This Python package is plumbing around it:
   channelizer                    polyphase filter bank: M sub-bands of one stream (FDMA carriers), and the GLONASS L1OF code
   nuller                         adaptive spatial nulling: A interleaved antennas combined per block with weights from the block's covariance
   stap                           space-time adaptive nulling: the nuller with L taps in time behind every antenna
+  beamformer                     one beam per satellite: P constraint rows on stap's stream, one Gram matrix and one factor a block
   synth       deterministic synthetic IF scenes
   build       hipcc build recipe
 """
@@ -21,3 +22,4 @@ from .ddc import Ddc  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
 from .nuller import Nuller  # noqa: F401
 from .stap import Stap  # noqa: F401
+from .beamformer import Beamformer  # noqa: F401

@@ -124,6 +124,13 @@ class StapCfg(C.Structure):
                 ("steering", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+class BeamformerCfg(C.Structure):
+    """gm_beamformer_cfg (40 bytes): zeros are the defaults of block and loading; steering points at n_beams * taps * n_antennas
+    complex64 words [n_beams][taps][n_antennas] and is required"""
+    _fields_ = [("n_antennas", C.c_uint32), ("taps", C.c_uint32), ("block", C.c_uint32), ("loading", C.c_float),
+                ("n_beams", C.c_uint32), ("reserved32", C.c_uint32), ("steering", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class ExcisorCfg(C.Structure):
     """gm_excisor_cfg (32 bytes): zeros are the defaults"""
     _fields_ = [("block", C.c_uint32), ("guard_bins", C.c_uint32), ("threshold_factor", C.c_float), ("blank_threshold", C.c_float),
@@ -359,6 +366,17 @@ SIGNATURES = {
     "gm_stap_capture": (_i, [_vp, _vp, _vp, _sz]),
     "gm_stap_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
     "gm_stap_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
+    "gm_beamformer_plan": (_i, [C.POINTER(BeamformerCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(C.c_float), C.POINTER(_u64)]),
+    "gm_beamformer_create": (_i, [C.POINTER(BeamformerCfg), C.POINTER(_vp)]),
+    "gm_beamformer_destroy": (_i, [_vp]),
+    "gm_beamformer_reset": (_i, [_vp, _u64]),
+    "gm_beamformer_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_beamformer_synchronize": (_i, [_vp]),
+    "gm_beamformer_set_steering": (_i, [_vp, _u32, _vp]),
+    "gm_beamformer_set_weights": (_i, [_vp, _vp]),
+    "gm_beamformer_capture": (_i, [_vp, _vp, _vp, _sz]),
+    "gm_beamformer_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "gm_beamformer_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
     "gm_trk_create": (_i, [C.POINTER(TrkCfg), C.POINTER(_vp)]),
     "gm_trk_destroy": (_i, [_vp]),
     "gm_trk_start": (_i, [_vp, _u32, C.POINTER(AcqResult)]),

@@ -5202,6 +5202,210 @@ int gm_stap_process(gm_stap* n, const void* in, int fmt, size_t n_in, gm_c32* ou
 
 }  // extern "C"
 
+// ====================================================================== one beam per constraint row from a shared Gram matrix (gm_beamformer)
+// gnss_mi355x.h states the definition; tests/beam_model.py restates it in float64 on stap_model.py.
+namespace {
+struct BeamPlan {
+    StapPlan st;                            // A, L, M, B, loading: gm_stap's rules (st.s is not used)
+    uint32_t P = 0;
+};
+
+// one constraint row: M finite words, not all zero
+int beam_row_rules(const gm_c32* s, uint32_t M) {
+    if (!nuller_finite(s, M)) return set_err(GM_ERR_INVALID_ARG, "steering must be finite");
+    bool any = false;
+    for (uint32_t i = 0; i < M; ++i) any = any || s[i].re != 0.0f || s[i].im != 0.0f;
+    if (!any) return set_err(GM_ERR_INVALID_ARG, "a steering row is all zero");
+    return GM_OK;
+}
+
+int beam_rules(const gm_beamformer_cfg* c, BeamPlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    if (c->reserved || c->reserved32) return set_err(GM_ERR_INVALID_ARG, "gm_beamformer_cfg.reserved32 and reserved must be 0");
+    gm_stap_cfg sc{};
+    sc.n_antennas = c->n_antennas; sc.taps = c->taps; sc.block = c->block; sc.loading = c->loading;
+    if (int rc = stap_rules(&sc, p.st)) return rc;
+    if (c->n_beams < 1 || c->n_beams > uint32_t(gm::BM_P_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_beams: 1 .. 16");
+    if (!c->steering) return set_err(GM_ERR_INVALID_ARG, "steering is required: n_beams rows of taps * n_antennas words");
+    for (uint32_t b = 0; b < c->n_beams; ++b)
+        if (int rc = beam_row_rules(c->steering + size_t(b) * p.st.M, p.st.M)) return rc;
+    p.P = c->n_beams;
+    return GM_OK;
+}
+}  // namespace
+
+struct gm_beamformer : StreamStage {        // history: gm_stap's (cf [L - 1 + B][A]); d_blanked is not used, the counters are per beam
+    BeamPlan plan;
+    bool fixed = false;                     // static mode
+    cf* d_s = nullptr; cf* d_w = nullptr;   // [P][M] each: the constraint rows, the fixed weights
+    unsigned long long* d_fb = nullptr;     // [P] fallback counters
+    cf* cap_R = nullptr; cf* cap_w = nullptr; size_t cap_blocks = 0;     // the caller's capture (device)
+    cf* d_blk = nullptr; size_t blk_cap = 0;                             // blocks; the host-buffer entry's own capture: [blk_cap][M][M] then [blk_cap][P][M]
+};
+
+// one call's kernels on `st`; the caller has checked every argument; n_in > 0
+static int beam_launch(gm_beamformer* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t out_stride, uint64_t n_out,
+                       cf* cap_R, cf* cap_w) {
+    const StapPlan& p = n->plan.st;
+    const uint64_t T = n->base + n->inputs;
+    gm::BeamArgs a{};
+    a.in = d_in; a.n_in = n_in; a.fmt = fmt;
+    a.hist_in = static_cast<const cf*>(n->d_hist[n->cur]); a.hist_out = static_cast<cf*>(n->d_hist[n->cur ^ 1]);
+    a.A = p.A; a.L = p.L; a.B = p.B; a.P = n->plan.P;
+    a.pending = uint32_t(T % p.B); a.pending_out = uint32_t((T + n_in) % p.B);
+    a.n_blocks = n_out / p.B;
+    a.out = out; a.out_stride = out_stride; a.cap_R = cap_R; a.cap_w = cap_w;
+    a.loading = p.loading; a.adaptive = n->fixed ? 0 : 1;
+    a.fallbacks = n->d_fb; a.s = n->d_s; a.w = n->d_w;
+    gm::launch_beam(st, a);
+    return stage_launched(n, st, n_in, n_out);
+}
+static uint64_t beam_count(const gm_beamformer* n, uint64_t n_in) {
+    const uint64_t T = n->base + n->inputs;
+    return stap_total_out(n->plan.st, T + n_in) - stap_total_out(n->plan.st, T);
+}
+static const char* beam_fmt_err(int fmt) {
+    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "beamformer input is interleaved c32 or int8 IQ" : nullptr;
+}
+// the words of the handle that kernels read are replaced only when no call of the handle is in flight, on any stream
+static int beam_install(gm_beamformer* n, cf* d_dst, const gm_c32* src, size_t words) {
+    if (int rc = ensure_device(n->device)) return rc;
+    if (int rc = stage_sync(n)) return rc;
+    HIPC(hipMemcpy(d_dst, src, words * sizeof(cf), hipMemcpyHostToDevice));
+    return GM_OK;
+}
+
+extern "C" {
+
+int gm_beamformer_plan(const gm_beamformer_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, float* loading, uint64_t* n_out) {
+    BeamPlan p;
+    if (int rc = beam_rules(cfg, p)) return rc;
+    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (block) *block = p.st.B;
+    if (loading) *loading = p.st.loading;
+    if (n_out) *n_out = stap_total_out(p.st, inputs_so_far + n_in) - stap_total_out(p.st, inputs_so_far);
+    return GM_OK;
+}
+
+int gm_beamformer_create(const gm_beamformer_cfg* cfg, gm_beamformer** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    BeamPlan p;
+    if (int rc = beam_rules(cfg, p)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_beamformer* n = new gm_beamformer;
+    n->device = g_device; n->plan = p;
+    const size_t words = size_t(gm::BM_P_MAX) * gm::ST_M_MAX;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&n->d_s), words * sizeof(cf));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&n->d_w), words * sizeof(cf));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&n->d_fb), gm::BM_P_MAX * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(n->d_s, 0, words * sizeof(cf));
+    if (e == hipSuccess) e = hipMemset(n->d_w, 0, words * sizeof(cf));
+    if (e == hipSuccess) e = hipMemset(n->d_fb, 0, gm::BM_P_MAX * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemcpy(n->d_s, cfg->steering, size_t(p.P) * p.st.M * sizeof(cf), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = stage_create(n, (size_t(p.st.B) + p.st.L - 1) * p.st.A * sizeof(cf));
+    if (e != hipSuccess) { gm_beamformer_destroy(n); return hip_fail(e, "gm_beamformer_create"); }
+    *out = n;
+    return GM_OK;
+}
+
+int gm_beamformer_destroy(gm_beamformer* n) {
+    if (!n) return GM_OK;
+    stage_destroy(n);
+    hipFree(n->d_blk); hipFree(n->d_s); hipFree(n->d_w); hipFree(n->d_fb);
+    delete n;
+    return GM_OK;
+}
+
+int gm_beamformer_reset(gm_beamformer* n, uint64_t input_index) {
+    return stage_reset(n, input_index, [&] { return hipMemsetAsync(n->d_fb, 0, gm::BM_P_MAX * sizeof(unsigned long long), n->stream); });
+}
+
+int gm_beamformer_stats(gm_beamformer* n, uint64_t* inputs, uint64_t* outputs, uint64_t* blocks, uint64_t* fallbacks) {
+    if (int rc = stage_stats(n, inputs, outputs, nullptr)) return rc;
+    if (blocks) *blocks = n->outputs / n->plan.st.B;
+    if (fallbacks) {
+        unsigned long long fb[gm::BM_P_MAX] = {};
+        HIPC(hipMemcpy(fb, n->d_fb, n->plan.P * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (uint32_t p = 0; p < n->plan.P; ++p) fallbacks[p] = fb[p];
+    }
+    return GM_OK;
+}
+
+int gm_beamformer_synchronize(gm_beamformer* n) { return stage_synchronize(n); }
+
+int gm_beamformer_set_steering(gm_beamformer* n, uint32_t beam, const gm_c32* s) {
+    if (!n || !s) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (beam >= n->plan.P) return set_err(GM_ERR_INVALID_ARG, "beam: below n_beams");
+    const uint32_t M = n->plan.st.M;
+    if (int rc = beam_row_rules(s, M)) return rc;
+    return beam_install(n, n->d_s + size_t(beam) * M, s, M);
+}
+
+int gm_beamformer_set_weights(gm_beamformer* n, const gm_c32* w) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!w) { n->fixed = false; return GM_OK; }
+    const size_t words = size_t(n->plan.P) * n->plan.st.M;
+    if (!nuller_finite(w, uint32_t(words))) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
+    if (int rc = beam_install(n, n->d_w, w, words)) return rc;
+    n->fixed = true;
+    return GM_OK;
+}
+
+int gm_beamformer_capture(gm_beamformer* n, void* d_R, void* d_w, size_t cap_blocks) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if ((d_R == nullptr) != (d_w == nullptr)) return set_err(GM_ERR_INVALID_ARG, "d_R and d_w: both or neither");
+    if ((d_R == nullptr) != (cap_blocks == 0)) return set_err(GM_ERR_INVALID_ARG, "cap_blocks: 0 exactly where the pointers are null");
+    n->cap_R = static_cast<cf*>(d_R); n->cap_w = static_cast<cf*>(d_w); n->cap_blocks = cap_blocks;
+    return GM_OK;
+}
+
+int gm_beamformer_process_dev(gm_beamformer* n, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_stride, size_t* n_out,
+                              void* stream) {
+    uint64_t cnt = 0;      // (a plane's room is its stride: a count above it is out of range)
+    if (int rc = stage_check_call(n, beam_count, beam_fmt_err(fmt), d_in, n_in, d_out, out_stride, "gm_beamformer_plan", &cnt)) return rc;
+    const StapPlan& p = n->plan.st;
+    if (n->cap_w && cnt / p.B > n->cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "the capture is smaller than the call's blocks");
+    if (cnt)
+        if (int rc = stage_check_overlap(d_in, n_in * p.A * (fmt == GM_FMT_C32 ? 8 : 2), d_out, uint64_t(n->plan.P - 1) * out_stride + cnt)) return rc;
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(n->device)) return rc;
+    return beam_launch(n, stream ? static_cast<hipStream_t>(stream) : n->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), out_stride, cnt,
+                       n->cap_R, n->cap_w);
+}
+
+int gm_beamformer_process(gm_beamformer* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_stride, size_t* n_out, gm_c32* R,
+                          gm_c32* w, size_t cap_blocks) {
+    uint64_t cnt = 0;
+    if (int rc = stage_check_call(n, beam_count, beam_fmt_err(fmt), in, n_in, out, out_stride, "gm_beamformer_plan", &cnt)) return rc;
+    const StapPlan& p = n->plan.st;
+    const uint64_t blocks = cnt / p.B;
+    const bool want = (R || w) && blocks;
+    if ((R || w) && blocks > cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "cap_blocks below the call's blocks");
+    const size_t M = p.M, MM = M * M, PM = size_t(n->plan.P) * M, A = p.A;
+    if (want && n->blk_cap < blocks) {
+        if (int rc = ensure_device(n->device)) return rc;
+        if (int rc = stage_sync(n)) return rc;
+        hipFree(n->d_blk); n->d_blk = nullptr; n->blk_cap = 0;
+        HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_blk), size_t(blocks) * (MM + PM) * sizeof(cf)));
+        n->blk_cap = size_t(blocks);
+    }
+    cf* d_R = want ? n->d_blk : nullptr;
+    cf* d_w = want ? n->d_blk + n->blk_cap * MM : nullptr;
+    if (int rc = stage_process(n, in, n_in * A * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
+            return beam_launch(n, st, d_in, fmt, n_in, d_out, cnt, cnt, d_R, d_w);
+        }, n->plan.P, out_stride)) return rc;
+    if (want) {      // stage_process has waited for the kernels
+        if (R && !n->fixed) HIPC(hipMemcpy(R, d_R, size_t(blocks) * MM * sizeof(cf), hipMemcpyDeviceToHost));
+        if (w) HIPC(hipMemcpy(w, d_w, size_t(blocks) * PM * sizeof(cf), hipMemcpyDeviceToHost));
+    }
+    return GM_OK;
+}
+
+}  // extern "C"
+
 // ====================================================================== multi-GPU exchange
 // The path's ONE exchange step: all-gather of the per-(worker, bin) metrics over RCCL, enqueued on the acquisition
 // handle's stream, followed by the regroup to the [3][nranks*P][D] layout gm_acq_decide_dev replays.  RCCL is bound

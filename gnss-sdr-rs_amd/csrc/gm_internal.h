@@ -511,6 +511,29 @@ struct StapArgs {
     cf w[ST_M_MAX];                        // the fixed weights
 };
 void launch_stap(hipStream_t, const StapArgs&);
+void launch_stap_state(hipStream_t, const StapArgs&);      // the state kernel alone
+
+// ---------------------------------------------------------------- one beam per constraint row from a shared Gram matrix (beam_kernels.hip)
+// gnss_mi355x.h states the definition.  gm_stap's call with P constraint rows: one launch of the block kernel (a workgroup per finished
+// block: ONE Gram matrix and ONE factor, then per beam a substitution and an output plane) and one of gm_stap's state kernel.  The span,
+// the history and the counts are gm_stap's.  The rows and the static weights are too many words for the argument block: device memory.
+constexpr int BM_P_MAX = 16;
+struct BeamArgs {
+    const void* in; uint64_t n_in;         // this call's TIME samples, each A interleaved elements (c32 or int8 IQ)
+    int fmt;                               // GM_FMT_C32 or GM_FMT_I8_IQ
+    const cf* hist_in; cf* hist_out;       // gm_stap's history, before / after
+    uint32_t A, L, B, P;
+    uint32_t pending, pending_out;
+    uint64_t n_blocks;                     // blocks this call finishes
+    cf* out; uint64_t out_stride;          // beam p's plane: out + p * out_stride, [n_blocks * B] words of it written
+    cf* cap_R; cf* cap_w;                  // [n_blocks][M][M], [n_blocks][P][M]; null: not captured
+    float loading;
+    int adaptive;                          // 0: the fixed weights `w` for every block, no Gram matrix
+    unsigned long long* fallbacks;         // [P] device counters of the blocks whose beam p took s_p / (s_p^H s_p): integer atomics only
+    const cf* s;                           // device [P][M]: the constraint rows, each [L][A]
+    const cf* w;                           // device [P][M]: the fixed weights
+};
+void launch_beam(hipStream_t, const BeamArgs&);
 
 // ---------------------------------------------------------------- narrowband interference excision (excise_kernels.hip)
 // gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of G segments of H = B / 2

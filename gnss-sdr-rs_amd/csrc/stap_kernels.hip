@@ -20,168 +20,34 @@
 //     LDS broadcasts; consecutive lanes store consecutive 8-byte words.
 // stap_state_kernel: the converted elements of the L - 1 samples in front of the unfinished block and of that block, from the old history
 //   (a call that finishes no block) or from this call's input, into the OTHER history buffer.
+// The staging, pass 1, the assembly and the factorisation are stap_core.h's, which beam_kernels.hip (gm_beamformer) includes too.
 // Compiled with -ffp-contract=off: every fused operation is written as __builtin_fmaf / __builtin_fma.
-#include "gm_internal.h"
+#include "stap_core.h"
 
 namespace gm {
 namespace {
-constexpr int ST_LANES = 256;
-constexpr int ST_CHUNK = 256;                                    // time samples staged at once
-constexpr int ST_GROUP = 1024;                                   // time samples between two reductions of the lane sums
-constexpr int ST_ROW = ST_CHUNK + ST_L_MAX - 1;                  // words of one antenna's staged row
-
-__device__ __forceinline__ float st_wave_sum(float v) {
-    for (int d = 32; d; d >>= 1) v = v + __shfl_down(v, d, 64);
-    return v;                                                    // lane 0 of the wave holds the tree's root
-}
-
-// element e (= time sample * A + antenna) of the call's span: the history for the first (H + pending) time samples, else the call's input
-__device__ __forceinline__ float2 st_element(const StapArgs& a, uint64_t e, uint64_t old) {
-    float2 r;
-    if (e < old) { const cf t = a.hist_in[e]; r.x = t.x; r.y = t.y; }
-    else if (a.fmt == GM_FMT_C32) { const cf t = reinterpret_cast<const cf*>(a.in)[e - old]; r.x = t.x; r.y = t.y; }
-    else { const char2 c = reinterpret_cast<const char2*>(a.in)[e - old]; r.x = float(c.x); r.y = float(c.y); }
-    return r;
-}
-
 template <int A, int NL>
 __global__ __launch_bounds__(ST_LANES) void stap_kernel(StapArgs a) {
     __shared__ float2 s_x[A][ST_ROW];                            // the staged chunk: s_x[ant][i] = time sample chunk start - H + i
-    __shared__ float2 s_edge[A][3 * (ST_L_MAX - 1)];             // [0, H): the H samples before the block; [H, 3H): its last 2H
+    __shared__ float2 s_edge[A][ST_EDGE];                        // [0, H): the H samples before the block; [H, 3H): its last 2H
     __shared__ float2 s_C[NL * 4][A][A];                         // the lag sums over the interior
     __shared__ float2 s_R[ST_M_MAX * ST_M_MAX];                  // the Gram matrix, f32 words, [M][M]
     __shared__ double s_Lr[ST_M_MAX + 1][ST_M_MAX], s_Li[ST_M_MAX + 1][ST_M_MAX];   // the Cholesky factor; row M: z^H
     __shared__ double s_inv[ST_M_MAX], s_ur[ST_M_MAX], s_ui[ST_M_MAX];
     __shared__ float2 s_w[ST_M_MAX];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int B = int(a.B), L = int(a.L), H = L - 1, M = A * L;
     const int n_chunks = B / ST_CHUNK;
     const uint64_t old = (uint64_t(H) + a.pending) * A;          // elements of the span that lie in the history
     const uint64_t e0 = uint64_t(blockIdx.x) * uint64_t(B) * A;  // the span element of time sample (block start - H), antenna 0
 
-    // chunk c into LDS (every lane; the caller puts the barriers around it)
-    auto stage = [&](int c) {
-        const uint64_t base = e0 + uint64_t(c) * ST_CHUNK * A;
-        const int n = (ST_CHUNK + H) * A;
-        for (int e = tid; e < n; e += ST_LANES) s_x[e % A][e / A] = st_element(a, base + uint64_t(e), old);
-    };
-
     if (a.adaptive) {
-        for (int e = tid; e < NL * 4 * A * A; e += ST_LANES) (&s_C[0][0][0])[e] = make_float2(0.0f, 0.0f);
-        float re[NL][A][A], im[NL][A][A];
-#pragma unroll
-        for (int n = 0; n < NL; ++n)
-#pragma unroll
-            for (int i = 0; i < A; ++i)
-#pragma unroll
-                for (int j = 0; j < A; ++j) { re[n][i][j] = 0.0f; im[n][i][j] = 0.0f; }
+        st_gram<A, NL>(a, s_x, s_edge, s_C, s_R, e0, old);
 
-        for (int c = 0; c < n_chunks; ++c) {
-            __syncthreads();                                     // the chunk before has been read
-            stage(c);
-            __syncthreads();
-            if (c == 0)
-                for (int e = tid; e < H * A; e += ST_LANES) s_edge[e % A][e / A] = s_x[e % A][e / A];
-            if (c == n_chunks - 1)
-                for (int e = tid; e < 2 * H * A; e += ST_LANES) s_edge[e % A][H + e / A] = s_x[e % A][ST_CHUNK + H - 2 * H + e / A];
-            if (wave < L) {
-                const int end = B - H - c * ST_CHUNK;            // interior samples of this chunk: local i < end
-                for (int i = lane; i < ST_CHUNK && i < end; i += 64) {
-                    float2 x[A];
-#pragma unroll
-                    for (int k = 0; k < A; ++k) x[k] = s_x[k][i + H];
-#pragma unroll
-                    for (int n = 0; n < NL; ++n) {
-                        const int lag = wave + 4 * n;
-                        if (lag < L) {
-                            float2 z[A];
-#pragma unroll
-                            for (int k = 0; k < A; ++k) z[k] = s_x[k][i + H - lag];
-#pragma unroll
-                            for (int p = 0; p < A; ++p) {
-#pragma unroll
-                                for (int q = 0; q < A; ++q) {
-                                    re[n][p][q] = __builtin_fmaf(x[p].x, z[q].x, re[n][p][q]);
-                                    re[n][p][q] = __builtin_fmaf(x[p].y, z[q].y, re[n][p][q]);
-                                    im[n][p][q] = __builtin_fmaf(x[p].y, z[q].x, im[n][p][q]);
-                                    im[n][p][q] = __builtin_fmaf(-x[p].x, z[q].y, im[n][p][q]);
-                                }
-                            }
-                        }
-                    }
-                }
-                if ((c + 1) % (ST_GROUP / ST_CHUNK) == 0 || c == n_chunks - 1) {     // the group's lane sums into the lag sums
-#pragma unroll
-                    for (int n = 0; n < NL; ++n) {
-                        const int lag = wave + 4 * n;
-                        if (lag < L) {
-#pragma unroll
-                            for (int p = 0; p < A; ++p) {
-#pragma unroll
-                                for (int q = 0; q < A; ++q) {
-                                    const float r = st_wave_sum(re[n][p][q]), i = st_wave_sum(im[n][p][q]);
-                                    if (lane == 0) { float2 t = s_C[lag][p][q]; t.x = t.x + r; t.y = t.y + i; s_C[lag][p][q] = t; }
-                                    re[n][p][q] = 0.0f; im[n][p][q] = 0.0f;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-
-        // the Gram matrix: the lag sum plus the entry's own edge terms
-        for (int e = tid; e < M * M; e += ST_LANES) {
-            const int p = e / M, q = e % M;
-            if (p > q) continue;
-            const int l = p / A, ant = p % A, k = q / A - l, bnt = q % A;
-            float2 r = s_C[k][ant][bnt];
-            for (int t = 0; t < H; ++t) {
-                // head terms u = -l .. -1 (s_edge word u + H), then tail terms u = B - H .. B - l - 1 (s_edge word H + u - (B - 2H))
-                const int iu = t < l ? H - l + t : 2 * H + (t - l);
-                const float2 xa = s_edge[ant][iu], xb = s_edge[bnt][iu - k];
-                r.x = __builtin_fmaf(xa.x, xb.x, r.x);
-                r.x = __builtin_fmaf(xa.y, xb.y, r.x);
-                r.y = __builtin_fmaf(xa.y, xb.x, r.y);
-                r.y = __builtin_fmaf(-xa.x, xb.y, r.y);
-            }
-            if (p == q) r.y = 0.0f;
-            s_R[p * M + q] = r;
-            if (p != q) { r.y = -r.y; s_R[q * M + p] = r; }
-        }
-        __syncthreads();
-
-        // the weights, f64 from the f32 words
-        double tr = 0.0;
-        for (int p = 0; p < M; ++p) tr += double(s_R[p * M + p].x);
-        const double load = double(a.loading) * (tr / double(M));
-        bool bad = tr == 0.0;
-        const int row = tid;                                     // rows 0 .. M - 1 of Rl, row M = s^H
-        for (int j = 0; j < M; ++j) {
-            double pj = double(s_R[j * M + j].x) + load;
-            double xr = 0.0, xi = 0.0;
-            if (row >= j && row <= M) {
-                if (row < M) { xr = double(s_R[row * M + j].x) + (row == j ? load : 0.0); xi = row == j ? 0.0 : double(s_R[row * M + j].y); }
-                else { xr = double(a.s[j].x); xi = -double(a.s[j].y); }
-            }
-            for (int k = 0; k < j; ++k) {
-                const double jr = s_Lr[j][k], ji = s_Li[j][k];
-                pj = __builtin_fma(-jr, jr, pj);
-                pj = __builtin_fma(-ji, ji, pj);
-                if (row > j && row <= M) {                       // - L[row][k] conj(L[j][k])
-                    const double ir = s_Lr[row][k], ii = s_Li[row][k];
-                    xr -= ir * jr + ii * ji;
-                    xi -= ii * jr - ir * ji;
-                }
-            }
-            if (!(pj > 0.0) || !(pj <= 1.7976931348623157e308)) bad = true;
-            const double d = sqrt(pj), inv = 1.0 / d;
-            if (row == j) { s_Lr[j][j] = d; s_Li[j][j] = 0.0; s_inv[j] = inv; }
-            else if (row > j && row <= M) { s_Lr[row][j] = xr * inv; s_Li[row][j] = xi * inv; }
-            __syncthreads();
-        }
+        // the weights, f64 from the f32 words; row M of the factor is s^H
+        bool bad = st_factor(M, M + 1, a.loading, s_R, s_Lr, s_Li, s_inv, [&](int, int j) { return a.s[j]; });
+        const int row = tid;
         double dd = 0.0;                                         // z^H z: s^H Rl^-1 s, real by construction
         for (int j = 0; j < M; ++j) { const double zr = s_Lr[M][j], zi = s_Li[M][j]; dd += zr * zr + zi * zi; }
         double rr = 0.0, ri = 0.0;                               // u = L^-H z, from the last column
@@ -220,7 +86,7 @@ __global__ __launch_bounds__(ST_LANES) void stap_kernel(StapArgs a) {
     for (int c = 0; c < n_chunks; ++c) {
         if (!(c == 0 && n_chunks == 1 && a.adaptive)) {          // a block of one chunk is still staged from pass 1
             __syncthreads();
-            stage(c);
+            st_stage<A>(a, s_x, e0, old, c);
             __syncthreads();
         }
         float2 y; y.x = 0.0f; y.y = 0.0f;
@@ -268,6 +134,11 @@ void launch_stap(hipStream_t s, const StapArgs& a) {
             default: launch_blocks<8>(s, a); break;
         }
     }
+    launch_stap_state(s, a);
+}
+
+// the state kernel alone (gm_beamformer's call ends with it too); reads in, fmt, hist_in, hist_out, A, L, B, pending, pending_out, n_blocks
+void launch_stap_state(hipStream_t s, const StapArgs& a) {
     const uint64_t n = (uint64_t(a.L) - 1 + a.pending_out) * a.A;
     if (n) stap_state_kernel<<<unsigned((n + ST_LANES - 1) / ST_LANES), ST_LANES, 0, s>>>(a);
 }

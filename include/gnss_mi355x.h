@@ -21,7 +21,7 @@
  *     on that stream), or synchronise the producer first.  gm_acq_prepare_dev takes the producer's stream per call
  *     (`ready_stream`).  The reference copies its 10 ms out of the ring and THEN searches them (do_acquisition.rs:297-313): the
  *     stream order is that sequence.  INTEGRATION.md §3.3; tests/test_gpu_acquisition.py::test_caller_stream_orders_...
- *     The streaming stage handles (gm_frontend, gm_resampler, gm_excisor, gm_ddc, gm_channelizer, gm_nuller, gm_stap) take the
+ *     The streaming stage handles (gm_frontend, gm_resampler, gm_excisor, gm_ddc, gm_channelizer, gm_nuller, gm_stap, gm_beamformer) take the
  *     producer's stream per call, as the `stream` argument of their `_dev` entries: the call runs behind what the caller has queued there, its
  *     outputs and the handle's history are ready on that stream, and the handle's own queries, reset, host-buffer entry and ring
  *     writers wait for it (gm_frontend's wait for the handle's own stream only); tests/test_gpu_caller_streams.py.
@@ -1206,8 +1206,9 @@ int gm_nuller_process(gm_nuller *n, const void *in, int fmt, size_t n_in, gm_c32
  *     the four waves share the lags; the solve in LDS in f64; a second pass through the same chunks for y; a state kernel.
  * Limits (README, measured by tests/stap_model.py): ONE constraint shapes the signal's spectrum — at L = 2 a correlation peak can land
  * a sample off; a reference on tap l0 delays the peak by l0 samples; a quantiser's clipping products are not low rank.
- * Not built: a ring writer with the stage at its head; wiring into receiver_harness.cpp; more than one constraint (distortionless or
- * multi-beam forms); array calibration; any decision — the library reports R, w and the fallback count, the caller judges.
+ * Not built: a ring writer with the stage at its head; wiring into receiver_harness.cpp; several constraints on ONE beam (LCMV; one
+ * beam per constraint is gm_beamformer below); array calibration; any decision — the library reports R, w and the fallback count, the
+ * caller judges.
  * (ABI 9, additive: a caller detects the feature by the symbol) */
 typedef struct {
     uint32_t n_antennas;      /* A: 2 .. 8 */
@@ -1250,6 +1251,83 @@ int gm_stap_process_dev(gm_stap *n, const void *d_in, int fmt, size_t n_in, void
  * In static mode R is left untouched.  A device capture set by gm_stap_capture is not written by this form. */
 int gm_stap_process(gm_stap *n, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_cap, size_t *n_out, gm_c32 *R,
                     gm_c32 *w, size_t cap_blocks);
+
+/* ------------------------------------------------------------------ One beam per satellite from a shared covariance
+ * A gm_beamformer is a gm_stap with P constraint vectors (1 .. 16) in place of one: a receiver with an array wants a beam per satellite
+ * it tracks, plus a power-inversion beam to search in, and all of them share the block's Gram matrix and its Cholesky factor.  What a
+ * beam costs beyond that is one more substitution and one more output pass over a block already staged on chip.
+ *   Input and parameters.  gm_stap's: ONE interleaved stream of A antennas (2 .. 8), GM_FMT_C32 or GM_FMT_I8_IQ; L taps (1 .. 8),
+ *     M = A L <= 32; B a power of two in 256 .. 16384 (0 -> 1024); loading in [1e-6, 1] (0 -> 1e-4).  Blocks, counts
+ *     (total_out(T) = B * (T div B) PER BEAM), the history, gm_beamformer_reset and the zero halo are gm_stap's.
+ *   Beams.  Beam p has its own constraint vector s_p: M c32 words [L][A], finite, not all zero.  `steering` is [P][L][A] and is
+ *     required; a caller who wants power inversion passes e_0 as a row.
+ *   Per block.  ONE Gram matrix R, gm_stap's, in gm_stap's stated order; ONE loaded matrix Rl and ONE factor Rl = C C^H.  Per beam:
+ *     z_p = C^-1 s_p, u_p = C^-H z_p = Rl^-1 s_p, w_p = u_p / (z_p^H z_p), each component rounded once to f32, and
+ *     y_p[t] = sum_l sum_a conj(w_p[l A + a]) x_a[t - l] in gm_stap's order.
+ *   THE CONTRACT THAT FIXES EVERY WORD.  Beam p's R, w and y words and its fallback count are word for word those of a gm_stap created
+ *     with the same A, L, B, loading and steering = s_p, fed the same stream.  So a beam's words depend neither on P nor on the other
+ *     rows, nor on how the stream is cut into calls, nor on repetition.
+ *   Fallback.  gm_stap's rule per beam: tr = 0 or a bad pivot sends every beam of the block to w_p = s_p / (s_p^H s_p); a z_p^H z_p
+ *     that is not greater than 0 or not finite sends beam p alone.  The counters are per beam.
+ *   Output, planar: beam p's stream is d_out + p * out_stride (c32 elements), so a plane goes straight into gm_acq_search_dev, an
+ *     excisor or a resampler.  out_stride below the call's count is GM_ERR_OUT_OF_RANGE.  Words of a plane behind the count, and
+ *     between planes, are not touched.
+ *   Moving beams.  gm_beamformer_set_steering replaces one row, gm_beamformer_set_weights installs P M fixed weights (static mode, no
+ *     Gram matrix).  Both apply to every block finished by a LATER call; blocks of earlier calls keep the old words.  The P M words
+ *     (up to 4 KB each for s and w) live in device memory of the handle, and BOTH ENTRIES ARE SYNCHRONOUS: they first wait for every
+ *     call of the handle in flight (on the handle's stream and on the stream the last call ran on), then copy, and return when the
+ *     words are in place.  (A caller whose own stream is held back behind an event it has yet to record must not call them before.)
+ *   Monitor.  gm_beamformer_capture names device buffers that every later gm_beamformer_process_dev fills with its blocks' R
+ *     ([blocks][M][M]) and w ([blocks][P][M]) words.
+ *   Kernel (csrc/beam_kernels.hip): gm_stap's workgroup per block with gm_stap's own code (csrc/stap_core.h) for the staging, the
+ *     Gram matrix and the factorisation, the P rows riding below the matrix; the substitution eight beams at a time; the output pass
+ *     four beams at a time from one read of the staged samples; gm_stap's state kernel.
+ * Not built: several constraints on ONE beam (LCMV); a ring writer; wiring into receiver_harness.cpp; array calibration; deriving the
+ * rows from satellite directions; any decision.
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct {
+    uint32_t n_antennas;      /* A: 2 .. 8 */
+    uint32_t taps;            /* L: 1 .. 8, A L <= 32 */
+    uint32_t block;           /* B: a power of two in 256 .. 16384; 0 -> 1024 */
+    float    loading;         /* [1e-6, 1]; 0 -> 1e-4 */
+    uint32_t n_beams;         /* P: 1 .. 16 */
+    uint32_t reserved32;      /* must be 0 */
+    const gm_c32 *steering;   /* [P][L][A] c32 words, every row finite and not all zero; required.  Read during the call that takes the cfg only. */
+    uint64_t reserved;        /* must be 0 */
+} gm_beamformer_cfg;
+typedef struct gm_beamformer gm_beamformer;
+/* host only, no device: gm_stap_plan's rules, and GM_ERR_INVALID_ARG for P outside 1 .. 16, a NULL steering, a row that is not finite
+ * or all zero, reserved32 != 0 or reserved != 0.  *n_out is the count PER BEAM.  Any output pointer may be NULL. */
+int gm_beamformer_plan(const gm_beamformer_cfg *cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t *block, float *loading,
+                       uint64_t *n_out);
+int gm_beamformer_create(const gm_beamformer_cfg *cfg, gm_beamformer **out);
+int gm_beamformer_destroy(gm_beamformer *h);
+/* gm_stap_reset: zeroes the history and every counter; keeps the rows, the weights mode and the capture.  Synchronous. */
+int gm_beamformer_reset(gm_beamformer *h, uint64_t input_index);
+/* time samples taken, outputs delivered PER BEAM, blocks finished, and in fallbacks[p] (P words) the blocks whose beam p took the
+ * fallback weights, since gm_beamformer_create or the last reset (any pointer may be NULL).  Synchronises like gm_stap_stats. */
+int gm_beamformer_stats(gm_beamformer *h, uint64_t *inputs, uint64_t *outputs, uint64_t *blocks, uint64_t *fallbacks);
+int gm_beamformer_synchronize(gm_beamformer *h);
+/* s: the M words [L][A] of beam `beam`'s new row (finite, not all zero; beam >= P, a bad row or a NULL: GM_ERR_INVALID_ARG with
+ * nothing changed).  Synchronous, see "Moving beams". */
+int gm_beamformer_set_steering(gm_beamformer *h, uint32_t beam, const gm_c32 *s);
+/* w: P M finite c32 words [P][L][A] used for every later block (static mode); NULL returns the handle to the adaptive rule (and
+ * waits for nothing).  Synchronous, see "Moving beams". */
+int gm_beamformer_set_weights(gm_beamformer *h, const gm_c32 *w);
+/* gm_stap_capture with block k of the CALL at d_R + k M M (c32 [M][M]) and d_w + k P M (c32 [P][M]).  In static mode only w is
+ * written. */
+int gm_beamformer_capture(gm_beamformer *h, void *d_R, void *d_w, size_t cap_blocks);
+/* d_in (n_in TIME samples, n_in * A elements) -> beam p's *n_out outputs at d_out + p * out_stride (c32 elements).  Asynchronous on
+ * `stream` like gm_stap_process_dev, with its refusals, all before anything runs and with state, outputs and captures untouched;
+ * out_stride below the call's count is GM_ERR_OUT_OF_RANGE, and the overlap check against d_in covers
+ * [d_out, d_out + (P - 1) out_stride + count).  n_in = 0: GM_OK. */
+int gm_beamformer_process_dev(gm_beamformer *h, const void *d_in, int fmt, size_t n_in, void *d_out, size_t out_stride, size_t *n_out,
+                              void *stream);
+/* the synchronous host-buffer form; beam p's outputs at out + p * out_stride.  R ([blocks][M][M]) and w ([blocks][P][M]) are host
+ * buffers for the call's block words, each may be NULL; with either given, cap_blocks below the call's blocks is GM_ERR_OUT_OF_RANGE.
+ * In static mode R is left untouched.  A device capture set by gm_beamformer_capture is not written by this form. */
+int gm_beamformer_process(gm_beamformer *h, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_stride, size_t *n_out,
+                          gm_c32 *R, gm_c32 *w, size_t cap_blocks);
 
 /* ------------------------------------------------------------------ Tracking
  * The evolving fields of TrackingChannel (src/tracking/do_tracking.rs:88-116). */

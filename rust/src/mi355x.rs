@@ -199,6 +199,18 @@ pub struct GmStapCfg {              // gm_stap_cfg (32 bytes; zeros: the default
     pub reserved: u64,               // must be 0
 }
 pub enum GmStap {}
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct GmBeamformerCfg {        // gm_beamformer_cfg (40 bytes; zeros: the defaults of block and loading)
+    pub n_antennas: u32,             // A: 2 .. 8, gm_stap's stream
+    pub taps: u32,                   // L: 1 .. 8, A L <= 32
+    pub block: u32,                  // B: a power of two in 256 .. 16384; 0 -> 1024
+    pub loading: f32,                // [1e-6, 1] of the mean stacked power; 0 -> 1e-4
+    pub n_beams: u32,                // P: 1 .. 16
+    pub reserved32: u32,             // must be 0
+    pub steering: *const Complex32,  // [P][L][A], every row finite and not all zero; required
+    pub reserved: u64,               // must be 0
+}
+pub enum GmBeamformer {}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {} pub enum GmExcisor {}
 
 extern "C" {
@@ -383,6 +395,27 @@ extern "C" {
                                n_out: *mut usize, stream: *mut c_void) -> c_int;
     pub fn gm_stap_process(n: *mut GmStap, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32, out_cap: usize,
                            n_out: *mut usize, r: *mut Complex32, w: *mut Complex32, cap_blocks: usize) -> c_int;
+
+    /// one beam per constraint row from ONE Gram matrix and ONE factor a block: beam p's words are those of a gm_stap with
+    /// steering = row p; planar output, beam p at d_out + p * out_stride; every count is in TIME samples, n_out per beam
+    pub fn gm_beamformer_plan(cfg: *const GmBeamformerCfg, inputs_so_far: u64, n_in: u64, block: *mut u32, loading: *mut f32,
+                              n_out: *mut u64) -> c_int;
+    pub fn gm_beamformer_create(cfg: *const GmBeamformerCfg, out: *mut *mut GmBeamformer) -> c_int;
+    pub fn gm_beamformer_destroy(h: *mut GmBeamformer) -> c_int;
+    pub fn gm_beamformer_reset(h: *mut GmBeamformer, input_index: u64) -> c_int;
+    /// fallbacks: P words, one per beam
+    pub fn gm_beamformer_stats(h: *mut GmBeamformer, inputs: *mut u64, outputs: *mut u64, blocks: *mut u64, fallbacks: *mut u64) -> c_int;
+    pub fn gm_beamformer_synchronize(h: *mut GmBeamformer) -> c_int;
+    /// beam `beam`'s new row of M words for every block a later call finishes; synchronous
+    pub fn gm_beamformer_set_steering(h: *mut GmBeamformer, beam: u32, s: *const Complex32) -> c_int;
+    /// static mode: P M fixed weights [P][L][A] for every later block (synchronous); null: back to the adaptive rule
+    pub fn gm_beamformer_set_weights(h: *mut GmBeamformer, w: *const Complex32) -> c_int;
+    /// device buffers [cap_blocks][M][M] and [cap_blocks][P][M] that every later gm_beamformer_process_dev fills from word 0
+    pub fn gm_beamformer_capture(h: *mut GmBeamformer, d_r: *mut c_void, d_w: *mut c_void, cap_blocks: usize) -> c_int;
+    pub fn gm_beamformer_process_dev(h: *mut GmBeamformer, d_in: *const c_void, fmt: c_int, n_in: usize, d_out: *mut c_void,
+                                     out_stride: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gm_beamformer_process(h: *mut GmBeamformer, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32,
+                                 out_stride: usize, n_out: *mut usize, r: *mut Complex32, w: *mut Complex32, cap_blocks: usize) -> c_int;
     // do_tracking.rs:118-158, 311-327
     pub fn gm_trk_create(cfg: *const GmTrkCfg, out: *mut *mut GmTrk) -> c_int;
     pub fn gm_trk_destroy(t: *mut GmTrk) -> c_int;
