@@ -3404,6 +3404,37 @@ int gm_trk_last_timing(gm_trk* t, float* ms_total, uint32_t* launches) {
     return GM_OK;
 }
 
+// Diagnostic: the tracking loop's scalar device math on caller-supplied arguments (trk_debug_math_kernel; ops in gnss_mi355x.h).
+// Host buffers, synchronous: H2D, one kernel on the NULL stream, D2H.  Not part of the reference API.
+int gm_debug_math(int op, const float* x, size_t n, float p0, float p1, float p2, uint32_t* out0, uint32_t* out1) {
+    if (!x || !out0 || !out1) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (op < 0 || op > 10) return set_err(GM_ERR_OUT_OF_RANGE, "op must be 0..10");
+    if (n > (size_t(1) << 24)) return set_err(GM_ERR_OUT_OF_RANGE, "n must be at most 2^24");
+    (void)p2;                                              // reserved: no op reads a third parameter
+    const bool two = op == 7 || op == 8;                   // p0 = fs, p1 = len
+    const bool one = op == 4 || op == 5 || op == 9 || op == 10 || two;
+    if (one && !(p0 > 0.0f && p0 < 3.0e38f)) return set_err(GM_ERR_OUT_OF_RANGE, "p0 (divisor / fs / len) must be positive and finite");
+    if (two && !(p1 > 0.0f && p1 < 3.0e38f)) return set_err(GM_ERR_OUT_OF_RANGE, "p1 (len) must be positive and finite");
+    if (op == 10 && !(p0 >= 1.0f && p0 <= 16777216.0f && p0 == float(int(p0)))) return set_err(GM_ERR_OUT_OF_RANGE, "len must be an integer in 1..2^24");
+    if (int rc = ensure_device(g_device)) return rc;
+    if (!n) return GM_OK;
+    const float inv = op == 7 ? 1.0f / p1 : (one ? 1.0f / p0 : 0.0f);      // RN(1 / divisor), as fill_trk_derived forms it
+    float* dx = nullptr;
+    uint32_t* dout = nullptr;
+    HIPC(hipMalloc(&dx, n * 4));
+    hipError_t e = hipMalloc(&dout, n * 8);
+    if (e == hipSuccess) e = hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        gm::launch_trk_debug_math(nullptr, op, dx, uint32_t(n), p0, p1, inv, dout, dout + n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out0, dout, n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out1, dout + n, n * 4, hipMemcpyDeviceToHost);
+    hipFree(dx); hipFree(dout);
+    if (e != hipSuccess) return hip_fail(e, "gm_debug_math");
+    return GM_OK;
+}
+
 }  // extern "C"
 
 // ====================================================================== digital front-end

@@ -331,6 +331,8 @@ hipError_t trk_persistent_lds_need(const TrkDevCfg&, int device, size_t* need, s
 int trk_persistent_granule_stride(int G);      // granules per arm in the exchange block of the persistent kernel (16 for G <= 16)
 void launch_trk_results_to_host(hipStream_t, const void* d_src, void* h_dst_pinned, size_t bytes, const void* d_src2 = nullptr, void* h_dst2_pinned = nullptr,
                                 size_t bytes2 = 0);
+// gm_debug_math: one lane per argument through the tracking loop's scalar helpers (trk_kernels.hip); inv = RN(1 / divisor) of ops 4, 5, 7
+void launch_trk_debug_math(hipStream_t, int op, const float* d_x, uint32_t n, float p0, float p1, float inv, uint32_t* d_out0, uint32_t* d_out1);
 void launch_trk_persistent(hipStream_t, const TrkDevCfg&, const int8_t* d_codes, gm_trk_state* d_states,
                            const cf* ring, uint64_t mask, uint64_t head, int G, int packed, int epochs, uint32_t tag_base,
                            unsigned long long* d_xchg, gm_trk_out* d_outs, uint8_t* d_processed, uint8_t* d_lost,

@@ -10,7 +10,11 @@
 // in glibc's order (compile with -ffp-contract=off; divisions are IEEE), so loop state stays bit-identical.
 // tests/cpu/test_libm.cpp checks it against the host's atanf on 2^26 arguments, bit for bit.
 //
-// Host/device portable on purpose (same idea as fft_core.h): g++ validates it without a GPU.
+// Host/device portable on purpose (same idea as fft_core.h): g++ validates it without a GPU.  That run executes no device
+// instruction; what the DEVICE makes of these functions (__fdiv_rn, the sqrt lowering, denormals, rintf, the f64 FMAs and 64-bit
+// products of sincosf_glibc, ocml's fmodf behind fmod_bounded, -ffp-contract=off in trk_kernels.hip) is checked by
+// tests/test_gpu_device_math.py: every function below through gm_debug_math, over every branch, word for word against this
+// header's host evaluation (tests/cpu/libm_host.cpp).
 #pragma once
 #include <cstdint>
 #include <cstring>

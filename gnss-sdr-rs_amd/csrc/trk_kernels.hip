@@ -81,17 +81,21 @@ template <bool FAST> __device__ __forceinline__ float fmod_code(float t, float l
 // get_ca_chip's index (:275): `(phase.floor() as usize) % 1023` — the cast saturates, so a negative
 // phase (late arm just after the code wraps) reads chip 0 in FAITHFUL mode; FIXED mode wraps.
 // phase = chip_idx +- spacing with |chip_idx| < len and spacing < len (checked at gm_trk_create), so
-// one conditional subtraction replaces the modulo.
+// conditional subtractions replace the modulo.  One downward would do for the tracker's own phases (the f32 sum of two values below
+// len cannot reach 2 len); there are two each way so that the index equals the reference's `% len` on all of [-2 len, 3 len), which
+// is what tests/test_gpu_device_math.py holds it to on [-len - 2, 2 len + 2] without having to argue about the caller.
 __device__ __forceinline__ int chip_index(float phase, int len, int mode) {
     const float f = floorf(phase);
     if (mode == GM_CODE_INDEX_FAITHFUL) {
         if (!(f > 0.0f)) return 0;
-        const int i = int(f);
+        int i = int(f);
+        i = i >= len ? i - len : i;
         return i >= len ? i - len : i;
     }
     int i = int(f);
     if (i < 0) i += len;
     if (i < 0) i += len;
+    i = i >= len ? i - len : i;
     return i >= len ? i - len : i;
 }
 
@@ -101,7 +105,8 @@ __device__ __forceinline__ float loop_filter_update(float dt_over_tau1, float ta
     return d_err * dt_over_tau1 + (d_err - err) * tau2_over_tau1;
 }
 
-// (div_const and fmod_bounded: gm_libm.h, host/device portable and checked on the CPU by tests/cpu/test_libm.cpp)
+// (div_const and fmod_bounded: gm_libm.h, host/device portable and checked on the CPU by tests/cpu/test_libm.cpp; on the device,
+// with the helpers of this file, by tests/test_gpu_device_math.py through trk_debug_math_kernel below)
 
 // generate_ca_code_samples(..).len() = round(fs / (code_rate / len))  (ca_code.rs:13-16)
 __device__ __forceinline__ uint64_t samples_per_code(float fs, float code_rate, float lenf) {
@@ -1748,6 +1753,49 @@ void launch_trk_results_to_host(hipStream_t st, const void* d_src, void* h_dst_p
     const int blocks = int(wg < 64 ? wg : 64);
     hipLaunchKernelGGL(trk_results_to_host_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const uint32_t*>(d_src),
                        static_cast<uint32_t*>(h_dst_pinned), words, static_cast<const uint32_t*>(d_src2), static_cast<uint32_t*>(h_dst2_pinned), words2);
+}
+
+// ---- gm_debug_math: the scalar helpers above and gm_libm.h's functions, one argument per lane, results as raw words ------------------
+// A diagnostic that lives HERE so that it is compiled with this file's flags (-ffp-contract=off, correctly rounded divide / sqrt) and
+// calls the file-local helpers as the tracking kernels do; tests/test_gpu_device_math.py compares its words with the host evaluation of
+// the same header.  p0..p2 and inv are kernel arguments, hence wave-uniform: fmod_bounded's fallback reads its divisor through
+// readfirstlane.  Op numbers: gnss_mi355x.h.
+__global__ __launch_bounds__(256) void trk_debug_math_kernel(int op, const float* __restrict__ xs, uint32_t n, float p0, float p1, float inv,
+                                                             uint32_t* __restrict__ out0, uint32_t* __restrict__ out1) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float x = xs[i];
+    uint32_t w0 = 0, w1 = 0;
+    float a = 0.0f, b = 0.0f;
+    switch (op) {
+        case 0: w0 = f32_bits(atanf_glibc(x)); break;
+        case 1: sincosf_glibc(x, a, b); w0 = f32_bits(a); w1 = f32_bits(b); break;
+        case 2: sincos_cw(x, a, b); w0 = f32_bits(a); w1 = f32_bits(b); break;
+        case 3: sincos_f32_via_f64(x, a, b); w0 = f32_bits(a); w1 = f32_bits(b); break;
+        case 4: w0 = f32_bits(div_const(x, p0, inv)); w1 = f32_bits(div_rn(x, p0)); break;
+        case 5: w0 = f32_bits(fmod_bounded(x, p0, inv)); break;
+        case 6: w0 = f32_bits(sqrt_rn(x)); break;
+        case 7: {
+            TrkDevCfg cfg{};                     // the three fields samples_per_code(cfg, .) reads
+            cfg.fs = p0; cfg.code_len_f = p1; cfg.inv_len = inv;
+            w0 = uint32_t(samples_per_code(p0, x, p1));
+            w1 = uint32_t(samples_per_code(cfg, x));
+            break;
+        }
+        case 8: spc_rate_bounds(p0, p1, x, a, b); w0 = f32_bits(a); w1 = f32_bits(b); break;
+        case 9: w0 = f32_bits(fmod_code<true>(x, p0)); w1 = f32_bits(fmod_code<false>(x, p0)); break;
+        case 10:
+            w0 = uint32_t(chip_index(x, int(p0), GM_CODE_INDEX_FAITHFUL));
+            w1 = uint32_t(chip_index(x, int(p0), GM_CODE_INDEX_FIXED));
+            break;
+        default: break;
+    }
+    out0[i] = w0;
+    out1[i] = w1;
+}
+void launch_trk_debug_math(hipStream_t st, int op, const float* d_x, uint32_t n, float p0, float p1, float inv, uint32_t* d_out0, uint32_t* d_out1) {
+    if (!n) return;
+    hipLaunchKernelGGL(trk_debug_math_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, op, d_x, n, p0, p1, inv, d_out0, d_out1);
 }
 
 // ---- gm_trk_bank: the correlator bank at tracked states, a section of its own that uses the helpers above ----------------------------

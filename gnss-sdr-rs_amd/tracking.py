@@ -118,6 +118,16 @@ def bank_plan(fs, taps, offsets_hz=(0.0,), n_states=1, code_rate=0.0, code_len=0
     return out.as_dict()
 
 
+def debug_math(op, x, p0=0.0, p1=0.0, p2=0.0):
+    """gm_debug_math: the tracking loop's scalar device math (op numbers in gnss_mi355x.h) evaluated on the device for every element
+    of the f32 array x -> (out0, out1), uint32 words."""
+    _lib.init(_lib._initialised or 0)
+    xs = np.ascontiguousarray(x, np.float32)
+    o0, o1 = np.zeros(xs.size, np.uint32), np.zeros(xs.size, np.uint32)
+    check(lib().gm_debug_math(int(op), _p(xs), xs.size, float(p0), float(p1), float(p2), _p(o0), _p(o1)), "gm_debug_math")
+    return o0, o1
+
+
 class TrackingManager:
     """TrackingManager::new (:336-348): n channels in one handle; process_channels' rayon fan-out
     (:364-371) becomes update_all()."""

@@ -1458,6 +1458,25 @@ int gm_trk_set_stream(gm_trk *t, void *hip_stream);
 int gm_trk_debug_stamps(gm_trk *t, uint32_t cap, long long *out);
 int gm_trk_enable_timing(gm_trk *t, int on);
 int gm_trk_last_timing(gm_trk *t, float *ms_correlate_total, uint32_t *launches);
+/* Diagnostic (additive, ABI 9; not in the reference): the tracking loop's scalar device math, evaluated ON THE DEVICE for n caller-supplied
+ * arguments, one per lane of 256-lane workgroups, by a kernel compiled with the tracking kernels (tests/test_gpu_device_math.py holds
+ * the words against the host evaluation of csrc/gm_libm.h).  x, out0, out1: host arrays of n elements (n <= 2^24); results are raw
+ * 32-bit words, 0 where an op has one result only.  p0 / p1 are uniform over the call; p2 is reserved.  RN(1/y) is formed on the host.
+ *   op  out0 | out1                                                             parameters
+ *    0  atanf_glibc(x)
+ *    1  sincosf_glibc(x): sin | cos
+ *    2  sincos_cw(x): sin | cos
+ *    3  sincos_f32_via_f64(x): sin | cos
+ *    4  div_const(x, y, RN(1/y)) | div_rn(x, y)                                 p0 = y
+ *    5  fmod_bounded(x, y, RN(1/y))                                             p0 = y
+ *    6  sqrt_rn(x)
+ *    7  samples_per_code(fs, x, len) | samples_per_code(cfg, x), low 32 bits    p0 = fs, p1 = len
+ *    8  spc_rate_bounds(fs, len, x): lo | hi                                    p0 = fs, p1 = len
+ *    9  fmod_code<true>(x, len) | fmod_code<false>(x, len)                      p0 = len
+ *   10  chip_index(x, len, FAITHFUL) | chip_index(x, len, FIXED)                p0 = len (an integer, 1..2^24)
+ * GM_ERR_INVALID_ARG: a null array; GM_ERR_OUT_OF_RANGE: op, n, or a parameter an op reads that is not positive and finite;
+ * GM_ERR_NO_DEVICE without a device. */
+int gm_debug_math(int op, const float *x, size_t n, float p0, float p1, float p2, uint32_t *out0, uint32_t *out1);
 
 /* ------------------------------------------------------------------ Correlator bank at tracked states (additive, ABI 9)
  * T taps x F carrier offsets of one code period at caller-supplied tracking states, formed with the tracker's own per-sample

@@ -93,6 +93,15 @@ def test_null_handles_are_refused_not_dereferenced(gm):
     forms = (C.c_uint32 * 3)(9, 9, 9)
     assert L.gm_frontend_debug_forms(None, forms) == -1 and list(forms) == [9, 9, 9]
     assert b"null pointer" in L.gm_last_error()
+    # the device-math probe (an additive export): null arrays, then op and n out of range — all refused before a device is needed
+    xs, w0, w1 = (C.c_float * 4)(), (C.c_uint32 * 4)(9, 9, 9, 9), (C.c_uint32 * 4)(9, 9, 9, 9)
+    for a, b, c in ((None, w0, w1), (xs, None, w1), (xs, w0, None)):
+        assert L.gm_debug_math(0, a, 4, 0.0, 0.0, 0.0, b, c) == -1 and b"null pointer" in L.gm_last_error()
+    assert L.gm_debug_math(11, xs, 4, 0.0, 0.0, 0.0, w0, w1) == -5 and L.gm_debug_math(-1, xs, 4, 0.0, 0.0, 0.0, w0, w1) == -5
+    assert L.gm_debug_math(0, xs, (1 << 24) + 1, 0.0, 0.0, 0.0, w0, w1) == -5
+    assert L.gm_debug_math(5, xs, 4, 0.0, 0.0, 0.0, w0, w1) == -5 and L.gm_debug_math(8, xs, 4, 4.0e6, float("nan"), 0.0, w0, w1) == -5
+    assert L.gm_debug_math(10, xs, 4, 1023.5, 0.0, 0.0, w0, w1) == -5
+    assert list(w0) == [9, 9, 9, 9] and list(w1) == [9, 9, 9, 9]
 
 
 def test_ca_table_and_resampler_host(gm, oracle):
@@ -196,7 +205,9 @@ def test_device_atanf_restatement_matches_host_libm_bit_for_bit():
     """tests/cpu/test_libm.cpp: gm::atanf_glibc (csrc/gm_libm.h, what the tracking epilogue runs on the device for
     f32::atan of do_tracking.rs:280) equals this host's atanf on 8.7e7 arguments, bit for bit; gm::sincosf_glibc (what
     gm_trk_cfg.strict_libm runs for `phase.cos()` / `phase.sin()`, :234-235) equals this host's sinf AND cosf on 1.0e8
-    arguments (every 127th bit pattern, the carrier's operating range, the range boundaries), bit for bit."""
+    arguments (every 127th bit pattern, the carrier's operating range, the range boundaries), bit for bit.
+    This is g++ running the host/device-portable header: no device instruction executes here.  That the DEVICE's evaluation of the
+    same functions equals the host's, word for word over every branch, is tests/test_gpu_device_math.py (gm_debug_math)."""
     import subprocess
     import tempfile
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
