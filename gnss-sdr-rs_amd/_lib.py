@@ -76,6 +76,14 @@ class AcqLocalOut(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ArrayRowInfo(C.Structure):
+    """gm_array_row_info (24 bytes): what gm_array_row_solve reports beside the row"""
+    _fields_ = [("lambda1", C.c_double), ("lambda2", C.c_double), ("ref_index", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class AcqCancelCand(C.Structure):
     """gm_acq_cancel_cand (32 bytes): a found satellite for gm_acq_cancel"""
     _fields_ = [("worker", C.c_uint32), ("reserved", C.c_uint32), ("carrier_hz", C.c_double), ("code_phase", C.c_double),
@@ -258,6 +266,9 @@ SIGNATURES = {
     "gm_acq_local_search": (_i, [_vp, _vp, _i, _vp, _u32, C.POINTER(AcqLocalCfg), _vp, _vp, _vp]),
     "gm_acq_local_plan": (_i, [_u32, _u32, C.POINTER(AcqLocalCfg), _f, _u32, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32),
                            C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gm_acq_array_prompts": (_i, [_vp, _vp, _i, _u32, _u32, _vp, _u32, _vp]),
+    "gm_acq_array_plan": (_i, [_u32, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
+    "gm_array_row_solve": (_i, [_u32, _u32, _vp, _vp, _sz, _f, _vp, C.POINTER(ArrayRowInfo)]),
     "gm_acq_cancel": (_i, [_vp, _vp, _i, _vp, _u32, _vp, _vp, _vp, _u32]),
     "gm_acq_cancel_plan": (_i, [C.c_uint64, _u32, C.c_double, C.c_double, C.POINTER(_u32), _vp, _u32]),
     "gm_acq_enable_timing": (_i, [_vp, _i]),

@@ -6,7 +6,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import AcqCancelCand, AcqCancelOut, AcqCand, AcqCfg, AcqLocalCfg, AcqLocalOut, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
+from ._lib import AcqCancelCand, AcqCancelOut, AcqCand, AcqCfg, AcqLocalCfg, AcqLocalOut, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, ArrayRowInfo, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
 
 PRN_SEARCH_ACQUISITION_TOTAL = 32      # do_acquisition.rs:22
 FREQ_SEARCH_ACQUISITION_HZ = 14e3      # :20
@@ -177,6 +177,50 @@ def local_plan(coherent_periods, n_integrations, fs, fft_size, table_freq, bin=0
                                   _p(tf) if tf.size else None, int(bin), C.byref(w), C.byref(j), C.byref(g), C.byref(z), C.byref(hs),
                                   C.byref(st)), "gm_acq_local_plan")
     return dict(n_lags=w.value, span_periods=j.value, n_groups=g.value, n_freq=z.value, half_span_hz=hs.value, step_hz=st.value)
+
+
+def array_plan(coherent_periods, n_integrations, n_antennas, taps=1):
+    """gm_acq_array_plan: the argument rules of array_prompts (n_antennas 2 .. 8, taps 1 .. 8, n_antennas * taps <= 32; GmError
+    INVALID_ARG) -> dict(periods = R_u = max(1, coherent_periods) * n_integrations, words_per_cand = R_u * taps * n_antennas).  Host only."""
+    r, w = C.c_uint32(0), C.c_uint32(0)
+    check(lib().gm_acq_array_plan(int(coherent_periods), int(n_integrations), int(n_antennas), int(taps), C.byref(r), C.byref(w)),
+          "gm_acq_array_plan")
+    return dict(periods=r.value, words_per_cand=w.value)
+
+
+def solve_row(z, R=None, loading=0.0):
+    """gm_array_row_solve for one cell: z complex64 [n, m] prompt vectors (array_prompts' [R_u, L, A] of a candidate goes in as it
+    comes out), R complex64 [n_blocks, m, m] or [m, m] as Stap.capture / Beamformer.capture write it, or None: the identity.
+    -> (row complex64 [m], dict(lambda1, lambda2, ref_index)).  Host only, float64 inside; the library judges nothing."""
+    z = np.ascontiguousarray(z, np.complex64)
+    if z.ndim < 2:
+        raise ValueError("z must be [n, m] or [n, L, A]")
+    z = z.reshape(z.shape[0], -1)
+    n, m = z.shape
+    Rp, nb = None, 0
+    if R is not None:
+        R = np.ascontiguousarray(R, np.complex64)
+        if R.size % (m * m) or R.shape[-2:] != (m, m):
+            raise ValueError("R must be [n_blocks, m, m] with m = %d" % m)
+        nb, Rp = R.size // (m * m), _p(R)
+    row = np.zeros(m, np.complex64)
+    info = ArrayRowInfo()
+    check(lib().gm_array_row_solve(m, n, _p(z) if z.size else None, Rp, nb, float(loading), _p(row), C.byref(info)), "gm_array_row_solve")
+    return row, info.as_dict()
+
+
+def solve_rows(z, R=None, loading=0.0):
+    """solve_row for every candidate of array_prompts' result: z complex64 [n_cands, R_u, L, A] -> (rows complex64 [n_cands, L, A],
+    list of dict(lambda1, lambda2, ref_index)); R as solve_row takes it, shared by the candidates."""
+    z = np.ascontiguousarray(z, np.complex64)
+    if z.ndim != 4:
+        raise ValueError("z must be [n_cands, R_u, L, A]")
+    rows, infos = np.zeros((z.shape[0],) + z.shape[2:], np.complex64), []
+    for c in range(z.shape[0]):
+        row, info = solve_row(z[c], R, loading)
+        rows[c] = row.reshape(z.shape[2:])
+        infos.append(info)
+    return rows, infos
 
 
 def cancel_plan(dwell_samples, fft_size, code_phase, period_samples=0.0):
@@ -470,6 +514,22 @@ class AcquisitionEngine:
                 d["surface"] = s[i].copy()
             ret.append(d)
         return ret
+
+    def array_prompts(self, cands, samples, n_antennas, taps=1, fmt=FMT_C32):
+        """Space-time prompts of an antenna array at known cells (gm_acq_array_prompts): every antenna and every tap delay of the
+        interleaved stream against each candidate's replica, one vector a code period.  `samples`: a device pointer to dwell_samples
+        TIME samples of n_antennas interleaved elements each (what Nuller / Stap / Beamformer take), FMT_C32 or FMT_I8_IQ; read only.
+        A candidate is local_search's dict.  -> complex64 [n_cands, R_u, taps, n_antennas], R_u = max(1, K) * n_integrations; solve_rows
+        turns it into constraint rows.  The library makes no detection decision."""
+        n = len(cands)
+        cs = (AcqCand * max(n, 1))()
+        for i, c in enumerate(cands):
+            cs[i] = AcqCand(int(c["worker"]), int(c["doppler_bin"]), int(c["code_phase_samples"]), int(c.get("offset_periods", 0)))
+        plan = array_plan(self.K, self.M, n_antennas, taps)
+        z = np.zeros((max(n, 1), plan["periods"], int(taps), int(n_antennas)), np.complex64)
+        check(lib().gm_acq_array_prompts(self._h, C.c_void_p(samples) if samples else None, int(fmt), int(n_antennas), int(taps),
+                                         C.cast(cs, C.c_void_p), n, _p(z)), "gm_acq_array_prompts")
+        return z[:n]
 
     def cancel(self, cands, out_ptr, samples=None, fmt=FMT_C32, want_amps=False):
         """Subtract found satellites from a dwell (gm_acq_cancel): one complex amplitude per signal code period and satellite is

@@ -466,6 +466,11 @@ struct gm_acq {
         void* d_block = nullptr;
         size_t bytes = 0;
     } local;
+    // space-time prompts of an antenna array at known cells (gm_acq_array_prompts): one device block (the candidates and z), grown like local's
+    struct Array {
+        void* d_block = nullptr;
+        size_t bytes = 0;
+    } array;
     // subtracting found satellites from a dwell (gm_acq_cancel): one device block (candidate constants, the segment tables o and b, the
     // amplitudes), grown like local's, and a device copy of the raw chip rows [P][code_len], uploaded at the first call
     struct Cancel {
@@ -805,6 +810,7 @@ int gm_acq_destroy(gm_acq* a) {
     hipFree(a->fine.d_peak_pow); hipFree(a->fine.d_peak_idx);
     hipFree(a->refine.d_block);
     hipFree(a->local.d_block);
+    hipFree(a->array.d_block);
     hipFree(a->cancel.d_block); hipFree(a->cancel.d_chips);
     if (a->device >= 0) hipSetDevice(a->device);
     hipFree(a->d_tw_mix);
@@ -2031,6 +2037,16 @@ int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const 
     return GM_OK;
 }
 
+// the rules of a known cell (gm_acq_cand), shared by gm_acq_local_search and gm_acq_array_prompts
+static int acq_cand_rules(const gm_acq* a, const gm_acq_cand& c) {
+    if (c.worker >= a->P) return set_err(GM_ERR_INVALID_ARG, "candidate.worker outside the handle's workers");
+    if (c.doppler_bin < 0 || uint32_t(c.doppler_bin) >= a->D) return set_err(GM_ERR_INVALID_ARG, "candidate.doppler_bin outside the handle's bins");
+    if (c.code_phase_samples >= a->N) return set_err(GM_ERR_INVALID_ARG, "candidate.code_phase_samples >= fft_size");
+    if (c.offset_periods > (a->edge.H ? a->edge.o_max : 0u))
+        return set_err(GM_ERR_INVALID_ARG, "candidate.offset_periods above the edge search's last offset (0 without an edge search)");
+    return GM_OK;
+}
+
 int gm_acq_local_search(gm_acq* a, const void* d_samples, int fmt, const gm_acq_cand* cands, uint32_t n_cands,
                         const gm_acq_local_cfg* cfg, gm_acq_local_out* out, gm_c32* prompts, float* surface) {
     if (!a || !cands || !out) return set_err(GM_ERR_INVALID_ARG, "null pointer");
@@ -2045,12 +2061,8 @@ int gm_acq_local_search(gm_acq* a, const void* d_samples, int fmt, const gm_acq_
     if (int rc = local_rules(a->cfg.coherent_periods, a->M, cfg, fs, N, D, a->table_freq.data(), 0, common, L)) return rc;
     std::vector<RefinePlan> plans(n_cands);
     for (uint32_t c = 0; c < n_cands; ++c) {
-        if (cands[c].worker >= a->P) return set_err(GM_ERR_INVALID_ARG, "candidate.worker outside the handle's workers");
+        if (int rc = acq_cand_rules(a, cands[c])) return rc;
         const int32_t d = cands[c].doppler_bin;
-        if (d < 0 || uint32_t(d) >= D) return set_err(GM_ERR_INVALID_ARG, "candidate.doppler_bin outside the handle's bins");
-        if (cands[c].code_phase_samples >= N) return set_err(GM_ERR_INVALID_ARG, "candidate.code_phase_samples >= fft_size");
-        if (cands[c].offset_periods > (a->edge.H ? a->edge.o_max : 0u))
-            return set_err(GM_ERR_INVALID_ARG, "candidate.offset_periods above the edge search's last offset (0 without an edge search)");
         uint32_t l = 0;
         if (int rc = local_rules(a->cfg.coherent_periods, a->M, cfg, fs, N, D, a->table_freq.data(), uint32_t(d), plans[c], l)) return rc;
     }
@@ -2163,6 +2175,241 @@ int gm_acq_local_search(gm_acq* a, const void* d_samples, int fmt, const gm_acq_
         }
         r.doppler_bin = d; r.offset_periods = o; r.span_periods = J; r.n_groups = G; r.n_freq = Z; r.n_lags = W;
     }
+    return GM_OK;
+}
+
+// ---------------------------------------------------------------- beam rows from the array's own correlations (additive entries, ABI 9)
+// the argument rules of gm_acq_array_plan / gm_acq_array_prompts (gnss_mi355x.h states them)
+static int array_rules(uint32_t coherent_periods, uint32_t M, uint32_t A, uint32_t L, uint32_t& R_u, uint32_t& words) {
+    const uint32_t K = coherent_periods > 1 ? coherent_periods : 1;
+    if (K > uint32_t(gm::GM_COHERENT_MAX)) return set_err(GM_ERR_INVALID_ARG, "coherent_periods > 32");
+    if (!M) return set_err(GM_ERR_INVALID_ARG, "n_integrations is required");
+    if (A < 2 || A > uint32_t(gm::NL_A_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_antennas must be 2 .. 8");
+    if (L < 1 || L > uint32_t(gm::ST_L_MAX)) return set_err(GM_ERR_INVALID_ARG, "taps must be 1 .. 8");
+    if (A * L > uint32_t(gm::ST_M_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_antennas * taps must not exceed 32");
+    const uint64_t r = uint64_t(K) * M, wds = r * A * L;
+    if (wds > 0xFFFFFFFFull) return set_err(GM_ERR_INVALID_ARG, "periods * taps * n_antennas does not fit 32 bits");
+    R_u = uint32_t(r); words = uint32_t(wds);
+    return GM_OK;
+}
+
+int gm_acq_array_plan(uint32_t coherent_periods, uint32_t n_integrations, uint32_t n_antennas, uint32_t taps, uint32_t* periods,
+                      uint32_t* words_per_cand) {
+    uint32_t R_u = 0, words = 0;
+    if (int rc = array_rules(coherent_periods, n_integrations, n_antennas, taps, R_u, words)) return rc;
+    if (periods) *periods = R_u;
+    if (words_per_cand) *words_per_cand = words;
+    return GM_OK;
+}
+
+int gm_acq_array_prompts(gm_acq* a, const void* d_samples, int fmt, uint32_t n_antennas, uint32_t taps, const gm_acq_cand* cands,
+                         uint32_t n_cands, gm_c32* z) {
+    if (!a || !d_samples || !cands || !z) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "the array stream is GM_FMT_C32 or GM_FMT_I8_IQ");
+    // every argument is checked before anything runs or is written
+    uint32_t R_u = 0, words = 0;
+    if (int rc = array_rules(a->K, a->M, n_antennas, taps, R_u, words)) return rc;
+    if (n_cands > 1024u) return set_err(GM_ERR_INVALID_ARG, "n_cands > 1024");
+    for (uint32_t c = 0; c < n_cands; ++c)
+        if (int rc = acq_cand_rules(a, cands[c])) return rc;
+    if (!n_cands) return GM_OK;
+    if (int rc = ensure_device(a->device)) return rc;
+    if (int rc = acq_flush_decision(a)) return rc;
+    // the block: [cands | z], each part 256-byte aligned
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t z_bytes = size_t(n_cands) * words * 8;
+    const size_t o_cand = 0, o_z = o_cand + up(size_t(n_cands) * sizeof(gm::RefineSat)), total = o_z + up(z_bytes);
+    gm_acq::Array& ar = a->array;
+    if (total > ar.bytes) {                 // the new block before the old one goes: a failure leaves the handle as it was
+        void* blk = nullptr;
+        if (hipMalloc(&blk, total) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(GM_ERR_NOMEM, "the array-prompts block does not fit (gnss_mi355x.h states the formula); the handle is as it was");
+        }
+        if (hipError_t e = hipStreamSynchronize(a->stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
+        hipFree(ar.d_block);
+        ar.d_block = blk; ar.bytes = total;
+    }
+    char* const base = static_cast<char*>(ar.d_block);
+    std::vector<gm::RefineSat> cs(n_cands);
+    for (uint32_t c = 0; c < n_cands; ++c)
+        cs[c] = gm::RefineSat{cands[c].worker, cands[c].code_phase_samples, uint32_t(cands[c].doppler_bin), cands[c].offset_periods};
+    HIPC(hipMemcpyAsync(base + o_cand, cs.data(), size_t(n_cands) * sizeof(gm::RefineSat), hipMemcpyHostToDevice, a->stream));
+    gm::ArrayArgs aa{};
+    aa.samples = d_samples; aa.fmt = fmt;
+    aa.starts = a->drift.on ? a->drift.d_starts : nullptr; aa.R = a->drift.on ? a->drift.R : 0u;
+    aa.tables = a->d_tables; aa.code_samples = a->d_code_samples;
+    aa.cands = reinterpret_cast<const gm::RefineSat*>(base + o_cand); aa.n_cands = n_cands;
+    aa.N = a->N; aa.R_u = R_u; aa.A = n_antennas; aa.L = taps;
+    aa.z = reinterpret_cast<cf*>(base + o_z);
+    gm::launch_array(a->stream, aa);
+    HIPC(hipGetLastError());
+    // the caller's array has the block's layout: filled directly, after every check and the launch have passed
+    HIPC(hipMemcpyAsync(z, base + o_z, z_bytes, hipMemcpyDeviceToHost, a->stream));
+    HIPC(hipStreamSynchronize(a->stream));
+    return GM_OK;
+}
+
+// gm_array_row_solve: gnss_mi355x.h states the nine steps; all f64, host only
+namespace {
+struct zc { double re, im; };
+// cyclic Hermitian Jacobi on Q [m][m] (both triangles kept), V the accumulated rotations: Q <- J^H Q J, V <- V J, until the
+// off-diagonal energy is below 1e-30 of the whole (or 64 sweeps)
+void hermitian_jacobi(uint32_t m, std::vector<zc>& Q, std::vector<zc>& V) {
+    for (uint32_t i = 0; i < m * m; ++i) V[i] = zc{0.0, 0.0};
+    for (uint32_t i = 0; i < m; ++i) V[i * m + i].re = 1.0;
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        double off = 0.0, all = 0.0;
+        for (uint32_t p = 0; p < m; ++p)
+            for (uint32_t q = 0; q < m; ++q) {
+                const double e = Q[p * m + q].re * Q[p * m + q].re + Q[p * m + q].im * Q[p * m + q].im;
+                all += e;
+                if (p != q) off += e;
+            }
+        if (!(off > 1e-30 * all)) break;
+        for (uint32_t p = 0; p + 1 < m; ++p)
+            for (uint32_t q = p + 1; q < m; ++q) {
+                const zc b = Q[p * m + q];
+                const double g = ::hypot(b.re, b.im);
+                if (g == 0.0) continue;
+                const double app = Q[p * m + p].re, aqq = Q[q * m + q].re;
+                // b = g e^{j phi}: the 2 x 2 block [[app, b], [conj b, aqq]] is diagonalised by J = [[c, s e^{j phi}], [-s e^{-j phi}, c]]
+                const double tau = (aqq - app) / (2.0 * g);
+                const double t = (tau >= 0.0 ? 1.0 : -1.0) / (::fabs(tau) + ::sqrt(1.0 + tau * tau));
+                const double c = 1.0 / ::sqrt(1.0 + t * t), s = t * c;
+                const zc e{b.re / g, b.im / g};                           // e^{j phi}
+                const zc se{s * e.re, s * e.im};                          // s e^{j phi}
+                // columns: X[:, p] <- c X[:, p] - conj(se) X[:, q];  X[:, q] <- se X[:, p] + c X[:, q]   (X = Q, then V)
+                auto cols = [&](std::vector<zc>& X) {
+                    for (uint32_t k = 0; k < m; ++k) {
+                        const zc xp = X[k * m + p], xq = X[k * m + q];
+                        X[k * m + p] = zc{c * xp.re - (se.re * xq.re + se.im * xq.im), c * xp.im - (se.re * xq.im - se.im * xq.re)};
+                        X[k * m + q] = zc{se.re * xp.re - se.im * xp.im + c * xq.re, se.re * xp.im + se.im * xp.re + c * xq.im};
+                    }
+                };
+                cols(Q);
+                // rows (J^H from the left): X[p, :] <- c X[p, :] - se X[q, :];  X[q, :] <- conj(se) X[p, :] + c X[q, :]
+                for (uint32_t k = 0; k < m; ++k) {
+                    const zc xp = Q[p * m + k], xq = Q[q * m + k];
+                    Q[p * m + k] = zc{c * xp.re - (se.re * xq.re - se.im * xq.im), c * xp.im - (se.re * xq.im + se.im * xq.re)};
+                    Q[q * m + k] = zc{se.re * xp.re + se.im * xp.im + c * xq.re, se.re * xp.im - se.im * xp.re + c * xq.im};
+                }
+                Q[p * m + q] = zc{0.0, 0.0}; Q[q * m + p] = zc{0.0, 0.0};
+                Q[p * m + p].im = 0.0; Q[q * m + q].im = 0.0;
+                cols(V);
+            }
+    }
+}
+}  // namespace
+
+int gm_array_row_solve(uint32_t m, uint32_t n, const gm_c32* z, const gm_c32* R, size_t n_blocks, float loading, gm_c32* row,
+                       gm_array_row_info* info) {
+    if (!z || !row || !info) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (m < 2 || m > uint32_t(gm::ST_M_MAX)) return set_err(GM_ERR_INVALID_ARG, "m must be 2 .. 32");
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "n = 0: no prompt vector");
+    if (R && !n_blocks) return set_err(GM_ERR_INVALID_ARG, "R without blocks");
+    double load = 1e-4;
+    if (loading != 0.0f) {
+        if (!(loading >= 1e-6f && loading <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "loading must be 0 or lie in [1e-6, 1]");   // (NaN fails too)
+        load = double(loading);
+    }
+    const size_t mm = size_t(m) * m;
+    for (size_t i = 0; i < size_t(n) * m; ++i)
+        if (!std::isfinite(z[i].re) || !std::isfinite(z[i].im)) return set_err(GM_ERR_INVALID_ARG, "a prompt word is not finite");
+    // 1. Rs, from the upper triangles
+    std::vector<zc> Rs(mm, zc{0.0, 0.0});
+    if (R) {
+        for (size_t b = 0; b < n_blocks; ++b)
+            for (uint32_t p = 0; p < m; ++p)
+                for (uint32_t q = p; q < m; ++q) {
+                    const gm_c32 v = R[b * mm + size_t(p) * m + q];
+                    if (!std::isfinite(v.re) || !std::isfinite(v.im)) return set_err(GM_ERR_INVALID_ARG, "a word of R is not finite");
+                    Rs[p * m + q].re += double(v.re);
+                    if (p != q) Rs[p * m + q].im += double(v.im);
+                }
+    } else {
+        for (uint32_t p = 0; p < m; ++p) Rs[p * m + p].re = 1.0;
+    }
+    // 2. the loading
+    double tr = 0.0;
+    for (uint32_t p = 0; p < m; ++p) tr += Rs[p * m + p].re;
+    if (!(tr > 0.0) || !std::isfinite(tr)) return set_err(GM_ERR_INVALID_ARG, "the trace of R is not positive and finite");
+    const double dl = load * (tr / double(m));
+    // 3. Cholesky, Rl = C C^H, left-looking, columns ascending; Rl[i][j] for i >= j is conj(Rs[j][i])
+    std::vector<zc> Cf(mm, zc{0.0, 0.0});
+    for (uint32_t j = 0; j < m; ++j) {
+        double pj = Rs[j * m + j].re + dl;
+        for (uint32_t k = 0; k < j; ++k) pj -= Cf[j * m + k].re * Cf[j * m + k].re + Cf[j * m + k].im * Cf[j * m + k].im;
+        if (!(pj > 0.0) || !std::isfinite(pj)) return set_err(GM_ERR_INVALID_ARG, "a Cholesky pivot is not positive and finite");
+        const double d = ::sqrt(pj);
+        Cf[j * m + j] = zc{d, 0.0};
+        for (uint32_t i = j + 1; i < m; ++i) {
+            double xr = Rs[j * m + i].re, xi = -Rs[j * m + i].im;
+            for (uint32_t k = 0; k < j; ++k) {                            // - C[i][k] conj(C[j][k])
+                const zc ci = Cf[i * m + k], cj = Cf[j * m + k];
+                xr -= ci.re * cj.re + ci.im * cj.im;
+                xi -= ci.im * cj.re - ci.re * cj.im;
+            }
+            Cf[i * m + j] = zc{xr / d, xi / d};
+        }
+    }
+    // 4. zt_i = C^-1 z_i (forward substitution), Q = sum_i zt_i zt_i^H
+    std::vector<zc> Q(mm, zc{0.0, 0.0}), V(mm), zt(m);
+    for (uint32_t i = 0; i < n; ++i) {
+        for (uint32_t p = 0; p < m; ++p) {
+            double xr = double(z[size_t(i) * m + p].re), xi = double(z[size_t(i) * m + p].im);
+            for (uint32_t k = 0; k < p; ++k) {
+                const zc c = Cf[p * m + k];
+                xr -= c.re * zt[k].re - c.im * zt[k].im;
+                xi -= c.re * zt[k].im + c.im * zt[k].re;
+            }
+            zt[p] = zc{xr / Cf[p * m + p].re, xi / Cf[p * m + p].re};
+        }
+        for (uint32_t p = 0; p < m; ++p)
+            for (uint32_t q = 0; q < m; ++q) {                            // zt[p] conj(zt[q])
+                Q[p * m + q].re += zt[p].re * zt[q].re + zt[p].im * zt[q].im;
+                Q[p * m + q].im += zt[p].im * zt[q].re - zt[p].re * zt[q].im;
+            }
+    }
+    // 5. the two largest eigenvalues and the first eigenvector
+    hermitian_jacobi(m, Q, V);
+    uint32_t i1 = 0;
+    for (uint32_t p = 1; p < m; ++p)
+        if (Q[p * m + p].re > Q[i1 * m + i1].re) i1 = p;
+    const double lambda1 = Q[i1 * m + i1].re;
+    double lambda2 = -1.0;
+    for (uint32_t p = 0; p < m; ++p)
+        if (p != i1 && Q[p * m + p].re > lambda2) lambda2 = Q[p * m + p].re;
+    if (lambda2 < 0.0) lambda2 = 0.0;
+    if (!(lambda1 > 0.0) || !std::isfinite(lambda1)) return set_err(GM_ERR_INVALID_ARG, "lambda1 is not greater than 0");
+    // 6. s = C v
+    std::vector<zc> s(m);
+    for (uint32_t p = 0; p < m; ++p) {
+        double xr = 0.0, xi = 0.0;
+        for (uint32_t k = 0; k <= p; ++k) {
+            const zc c = Cf[p * m + k], v = V[k * m + i1];
+            xr += c.re * v.re - c.im * v.im;
+            xi += c.re * v.im + c.im * v.re;
+        }
+        s[p] = zc{xr, xi};
+    }
+    // 7. the word of largest modulus real and positive;  8. s^H s = m;  9. one rounding to f32
+    uint32_t ref = 0;
+    double best = -1.0, e = 0.0;
+    for (uint32_t p = 0; p < m; ++p) {
+        const double a2 = s[p].re * s[p].re + s[p].im * s[p].im;
+        e += a2;
+        if (a2 > best) { best = a2; ref = p; }
+    }
+    if (!(best > 0.0) || !std::isfinite(e)) return set_err(GM_ERR_INVALID_ARG, "the row came out zero or not finite");
+    const double g = ::sqrt(best), scale = ::sqrt(double(m) / e);
+    const zc rot{s[ref].re / g, -s[ref].im / g};                          // conj of the word's phase
+    for (uint32_t p = 0; p < m; ++p) {
+        row[p].re = float((s[p].re * rot.re - s[p].im * rot.im) * scale);
+        row[p].im = float((s[p].re * rot.im + s[p].im * rot.re) * scale);
+    }
+    row[ref].im = 0.0f;
+    info->lambda1 = lambda1; info->lambda2 = lambda2; info->ref_index = ref; info->reserved = 0;
     return GM_OK;
 }
 

@@ -101,6 +101,20 @@ struct LocalArgs {
 };
 void launch_local(hipStream_t, const LocalArgs&);
 
+// Space-time prompts of an antenna array at known cells (gm_acq_array_prompts, acq_array.hip): one kernel on grid (R_u, n_cands), every
+// time sample of [s - (L - 1), s + N) read once with its A words, against ref[n] = tab[d][n] c_w[(n - cp) mod N].  A candidate is a
+// RefineSat.  gnss_mi355x.h states the definition and the summation order.
+struct ArrayArgs {
+    const void* samples; int fmt;          // the caller's interleaved dwell: time sample t, antenna a at element t A + a (c32 or int8 IQ)
+    const uint64_t* starts; uint32_t R;    // as RefineArgs (in TIME samples)
+    const cf* tables;
+    const int8_t* code_samples;
+    const RefineSat* cands; uint32_t n_cands;
+    uint32_t N, R_u, A, L;                 // A in 2 .. 8, L in 1 .. 8, A L <= 32
+    cf* z;                                 // [n_cands][R_u][L][A]
+};
+void launch_array(hipStream_t, const ArrayArgs&);
+
 // Subtracting found satellites from a dwell (gm_acq_cancel, acq_cancel.hip): the amplitude kernel on grid (q_max, n_cands) sums one
 // signal code period of one candidate per workgroup, the subtraction is one pass over the dwell.  The tables are [n_cands][stride],
 // stride >= q_max + 1: o and b hold Q + 1 entries of a candidate, amps Q.

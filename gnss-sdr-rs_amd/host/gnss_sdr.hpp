@@ -86,7 +86,7 @@ public:
 // `workers.par_iter_mut()...search_satellite(...)` (:268-271, :302-313).
 class AcquisitionEngine {
     gm_acq* h_ = nullptr;
-    uint32_t n_prn_ = 0;
+    uint32_t n_prn_ = 0, coherent_periods_ = 1, n_integrations_ = 0;     // (what gm_acq_array_plan sizes array_prompts' words from)
 public:
     AcquisitionEngine(float fs, float f_if, uint32_t fft_size, const std::vector<float>& doppler_hz,
                       const std::vector<uint8_t>& prn_ids, uint32_t n_integrations = 10, float threshold = 7.0f,
@@ -98,7 +98,7 @@ public:
         c.fs = fs; c.f_if = f_if; c.fft_size = fft_size; c.n_integrations = n_integrations;
         c.n_bins = uint32_t(doppler_hz.size()); c.doppler_hz = doppler_hz.data();
         c.n_prn = uint32_t(prn_ids.size()); c.prn_ids = prn_ids.data(); c.threshold = threshold;
-        n_prn_ = c.n_prn;
+        n_prn_ = c.n_prn; coherent_periods_ = c.coherent_periods; n_integrations_ = c.n_integrations;
         check(gm_acq_create(&c, &h_), "AcquisitionEngine::new");
     }
     // caller-built tables, as search_satellite receives them (:160-161)
@@ -115,7 +115,7 @@ public:
         c.fs = fs; c.fft_size = fft_size; c.n_integrations = n_integrations; c.n_bins = uint32_t(tables.size());
         c.tables = flat.data(); c.table_freq = freq.data(); c.n_prn = uint32_t(prn_ids.size()); c.prn_ids = prn_ids.data();
         c.any_length = any_length ? 1 : 0;
-        n_prn_ = c.n_prn;
+        n_prn_ = c.n_prn; coherent_periods_ = c.coherent_periods; n_integrations_ = c.n_integrations;
         check(gm_acq_create(&c, &h_), "AcquisitionEngine::new");
     }
     ~AcquisitionEngine() { gm_acq_destroy(h_); }
@@ -179,6 +179,19 @@ public:
         check(gm_acq_local_search(h_, d_samples, fmt, cands.data(), uint32_t(cands.size()), &cfg, out.data(), nullptr, nullptr), "local_search");
         return out;
     }
+    // Space-time prompts of an antenna array at known cells (gm_acq_array_prompts): every antenna and tap delay of the interleaved
+    // stream at d_samples (dwell_samples() TIME samples of n_antennas elements, read only) against each candidate's replica ->
+    // [cands][R_u][taps][n_antennas] words, R_u from gm_acq_array_plan.  solve_row turns a candidate's words into a constraint row.
+    std::vector<gm_c32> array_prompts(const std::vector<gm_acq_cand>& cands, const void* d_samples, uint32_t n_antennas, uint32_t taps = 1,
+                                      int fmt = GM_FMT_C32, uint32_t* periods = nullptr) {
+        uint32_t r = 0, words = 0;
+        check(gm_acq_array_plan(coherent_periods_, n_integrations_, n_antennas, taps, &r, &words), "array_plan");
+        std::vector<gm_c32> z(std::max<size_t>(cands.size(), 1) * words);
+        check(gm_acq_array_prompts(h_, d_samples, fmt, n_antennas, taps, cands.data(), uint32_t(cands.size()), z.data()), "array_prompts");
+        z.resize(cands.size() * words);
+        if (periods) *periods = r;
+        return z;
+    }
     // Subtracting found satellites from a dwell (gm_acq_cancel): one amplitude per signal code period and candidate is estimated from
     // the input (the snapshot of the last search when d_samples is null, else any dwell of dwell_samples() samples, read only) and
     // the dwell minus the replicas is written as c32 to d_out, which every search entry takes as a dwell (d_out may be the c32 input
@@ -228,6 +241,19 @@ public:
         return out;
     }
 };
+
+// A constraint row from one cell's prompt vectors (gm_array_row_solve, host only): z is [n][m] (a candidate's words of
+// AcquisitionEngine::array_prompts: n = R_u, m = taps * n_antennas), R the captured Gram blocks [n_blocks][m][m] of a Stap or a
+// Beamformer (empty: the identity), loading 0 -> 1e-4.  -> the row [m]; info->lambda1 / info->lambda2 is the estimate's quality, which
+// the caller judges.
+inline std::vector<gm_c32> solve_row(uint32_t m, const std::vector<gm_c32>& z, const std::vector<gm_c32>& R = {}, float loading = 0.0f,
+                                     gm_array_row_info* info = nullptr) {
+    std::vector<gm_c32> row(m);
+    gm_array_row_info local{};
+    check(gm_array_row_solve(m, m ? uint32_t(z.size() / m) : 0u, z.data(), R.empty() ? nullptr : R.data(),
+                             m ? R.size() / (size_t(m) * m) : 0, loading, row.data(), info ? info : &local), "solve_row");
+    return row;
+}
 
 // AcquisitionWorker::new(prn, fft_size, freq_sampling_hz) / search_satellite (:130-226): one PRN per object.
 class AcquisitionWorker {

@@ -579,6 +579,89 @@ int gm_acq_local_search(gm_acq *a, const void *d_samples /* NULL: the last searc
 int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const gm_acq_local_cfg *cfg, float fs, uint32_t fft_size,
                       uint32_t n_bins, const float *table_freq, uint32_t bin, uint32_t *n_lags, uint32_t *span_periods,
                       uint32_t *n_groups, uint32_t *n_freq, double *half_span_hz, double *step_hz);
+/* ---- Beam rows from the array's own correlations.  A gm_beamformer handle (below) wants one constraint row [L][A] per satellite, and a real
+ * receiver knows neither its array's geometry nor its cable phases.  Once a search behind the e_0 beam has found a satellite, its row can
+ * be estimated from the array stream itself: correlate EVERY antenna and EVERY tap delay with the satellite's replica at the found cell
+ * (gm_acq_array_prompts: one vector z_i of M = A L words per code period, in which the satellite is 30 dB up and has rank one), whiten
+ * the z_i with the Gram matrix the beamformer already captures, take the principal eigenvector and un-whiten it (gm_array_row_solve).
+ * Data bits cancel in z z^H; the array response, the cable phases and the code's autocorrelation across the taps are in the estimate.
+ * A spatial-only estimate (A words in tap 0 of an L > 1 handle) and an estimate without the whitening both fail on the jammed scenes of
+ * tests/array_probe_model.py: the prompts must be space-time and R must be the beamformer's own [M][M] matrix.
+ *
+ * gm_acq_array_prompts.  d_samples is ONE interleaved stream of A antennas, gm_nuller's / gm_stap's / gm_beamformer's layout: x_a[t] is
+ * element t * A + a, t a TIME sample; a device pointer to gm_acq_dwell_samples(handle) time samples of A elements each, ready on the
+ * handle's stream, GM_FMT_C32 or GM_FMT_I8_IQ (GM_FMT_I8_REAL is refused; int8 -128 is -128.0f), aligned to its ELEMENT size only (8
+ * or 2 bytes: A = 3 int8 puts period starts on odd 2-byte boundaries).  It is only read and does not become the snapshot.
+ * N = fft_size, A = n_antennas in 2 .. 8, L = taps in 1 .. 8, A L <= 32 (gm_stap's limits), R_u = max(1, coherent_periods) *
+ * n_integrations.  For candidate c = (worker w, bin d, code phase cp, offset o: gm_acq_local_search's candidate and its rules, an edge
+ * search allowing any o up to its last offset, else o = 0), period i < R_u, tap l < L, antenna a < A:
+ *     ref[n]        = tab[d][n] * c_w[(n - cp) mod N]        the handle's mix table (gm_acq_tables) and sampled replica; c_w is +-1,
+ *                                                            so both components of ref are exact
+ *     z[c][i][l][a] = sum_{n<N} x_a[s[d][o+i] + n - l] * ref[n]
+ *   s[d][.] are the handle's period starts in TIME samples, exactly as gm_acq_refine_doppler and gm_acq_local_search take them:
+ *   (o + i) N without the code-drift compensation, gm_acq_code_drift_starts' table with it.  A time index below 0 reads as ZERO (and
+ *   the word in front of the buffer is not touched): gm_stap's zero halo at the start of a stream, so with s = 0 tap l's sum misses its
+ *   first l terms exactly as gm_stap's stacked samples do.  A dwell cut from the MIDDLE of a stream therefore differs from gm_stap's
+ *   snapshots in the first L - 1 time samples of period 0 only; every later period reads its L - 1 predecessors from the dwell.
+ *   At L = 1, z[c][i][0][a] is gm_acq_local_search's prompt (lag_half_window = 0) of antenna a's de-interleaved stream, up to the order
+ *   of the sum.
+ *   THE ORDER, f32.  With u = n - l the time sample relative to s, u in [-(L-1), N): lane j of 256 owns the time samples u = -(L-1) + j,
+ *   -(L-1) + j + 256, ... (< N, and s + u >= 0), takes them in ascending u, and for each, l ascending and a ascending inside, adds the
+ *   term of ref[u + l] (terms with u + l outside [0, N) are skipped: ref is zero there) into its own sum of (l, a), from +0, as
+ *       re = fmaf(x.re, ref.re, re);  re = fmaf(-x.im, ref.im, re);  im = fmaf(x.re, ref.im, im);  im = fmaf(x.im, ref.re, im).
+ *   Then S[j] = S[j] + S[j + d] for d = 32, 16, 8, 4, 2, 1 inside each group of 64 lanes, the group's sum being its S[0]; then
+ *   z = ((G0 + G1) + G2) + G3 over the four groups.  No floating-point atomics: a candidate's words depend on the candidate and the
+ *   samples alone, not on what else is in the call, not on the pointer's alignment and not on repetition.  Each component passes
+ *   through at most 2 ceil((N + L - 1) / 256) + 9 roundings, so a word is within about (N / 128 + 12) 2^-24 sum_n |x_a[s + n - l]| of the
+ *   exact sum.
+ *   Synchronous, on the handle's stream, like gm_acq_local_search; runs a pending deferred decision first; changes no metric, choice,
+ *   result or snapshot word.  z is a HOST array [n_cands][R_u][L][A] (gm_acq_array_plan gives R_u and R_u L A).
+ *   GM_ERR_INVALID_ARG, all checked before anything runs or is written: a null handle (no device is touched), d_samples, cands or z; fmt
+ *   not GM_FMT_C32 or GM_FMT_I8_IQ; A, L or A L outside the limits; n_cands > 1024; gm_acq_local_search's candidate rules (worker,
+ *   doppler_bin, code_phase_samples, offset_periods).  n_cands = 0: GM_OK, nothing is written.
+ *   Kernel (csrc/acq_array.hip): one 256-lane workgroup per (period, candidate); every time sample of [s - (L-1), s + N) and every table
+ *   word is read once; a tile's 1024 ref words plus the L - 1 halo sit in LDS; a lane keeps its M complex sums in registers; a time
+ *   sample's A words are loaded together with the widest loads (up to 16 bytes) its address allows, element by element where not.
+ *   Device memory: one block of n_cands * (8 R_u L A + 16) bytes, built at the first call and grown when a call needs more — the new
+ *   block is allocated before the old one goes (GM_ERR_NOMEM leaves the handle as it was); gm_acq_destroy releases it.
+ *   Cost: R_u (N + L - 1) A element reads and R_u N table reads per candidate, 4 R_u N A L multiply-adds.
+ *
+ * gm_array_row_solve.  Host only, f64, no device.  z: n prompt vectors of m words ([n][m]; for one candidate of gm_acq_array_prompts
+ * n = R_u, m = L A, as written).  R: n_blocks matrices [m][m] as gm_stap_capture / gm_beamformer_capture write them, or NULL: the
+ * identity (n_blocks is ignored).  loading: 0 -> 1e-4, else in [1e-6, 1].
+ *   1. Rs = the sum of the blocks in ascending order; only the UPPER triangle (p <= q) is read, the lower is its conjugate, the
+ *      diagonal's imaginary part is taken as 0.
+ *   2. tr = sum_p Re Rs[p][p] (p ascending);  Rl = Rs + loading * (tr / m) * I.
+ *   3. Cholesky, Rl = C C^H, C lower triangular with a real positive diagonal.
+ *   4. zt_i = C^-1 z_i;  Q = sum_i zt_i zt_i^H (i ascending).
+ *   5. lambda1 >= lambda2: the two largest eigenvalues of Q, v the unit eigenvector of lambda1 (cyclic Hermitian Jacobi until the
+ *      off-diagonal energy is below 1e-30 of the whole; lambda2 is reported as 0 where it comes out negative).
+ *   6. s = C v.
+ *   7. s is rotated so that its word of largest modulus, at ref_index (the lowest index on ties), is real and positive.
+ *   8. s is scaled so that s^H s = m.
+ *   9. Each word is rounded once to f32: row[0 .. m).
+ *   v is defined up to a phase, which step 7 fixes; the row is as well defined as lambda1 is separated from lambda2.
+ *   info: lambda1, lambda2, ref_index.  THE LIBRARY DECIDES NOTHING: a caller reads lambda1 / lambda2 as the quality of the estimate
+ *   (the satellite's rank-one term over the largest whitened residual).
+ *   GM_ERR_INVALID_ARG with row and info untouched: m outside 2 .. 32; n = 0; a NULL z, row or info; R non-NULL with n_blocks = 0; a z
+ *   or R word read that is not finite; loading outside its range or not a number; tr <= 0 or not finite; a Cholesky pivot that is not
+ *   positive and finite; lambda1 not greater than 0.
+ *
+ * The sequence: gm_beamformer with the row e_0 and gm_beamformer_capture; gm_acq_search_dev on plane 0; gm_acq_array_prompts at the
+ * found cells on the beamformer's own input; gm_array_row_solve per cell with the captured R; gm_beamformer_set_steering, or a new
+ * handle with the rows.
+ * Not built: per-antenna prompts from the tracker (the array form of gm_trk_bank); a loop that re-steers by itself; several constraints
+ * on one beam (LCMV); ring writers; any detection or quality decision; wiring into receiver_harness.cpp or bench.py.
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct { double lambda1, lambda2; uint32_t ref_index; uint32_t reserved; } gm_array_row_info;   /* 24 bytes; reserved = 0 */
+int gm_acq_array_prompts(gm_acq *a, const void *d_samples, int fmt, uint32_t n_antennas, uint32_t taps, const gm_acq_cand *cands,
+                         uint32_t n_cands, gm_c32 *z /* [n_cands][R_u][L][A], host */);
+/* host only, no device: the limits on A, L and A L, coherent_periods <= 32 and n_integrations >= 1 (and R_u L A below 2^32);
+ * *periods = R_u, *words_per_cand = R_u L A (either may be NULL) */
+int gm_acq_array_plan(uint32_t coherent_periods, uint32_t n_integrations, uint32_t n_antennas, uint32_t taps, uint32_t *periods,
+                      uint32_t *words_per_cand);
+int gm_array_row_solve(uint32_t m, uint32_t n, const gm_c32 *z /* [n][m] */, const gm_c32 *R /* [n_blocks][m][m] or NULL */,
+                       size_t n_blocks, float loading /* 0 -> 1e-4; else [1e-6, 1] */, gm_c32 *row /* [m] */, gm_array_row_info *info);
 /* ---- Subtracting found satellites from a dwell.  C/A codes isolate about 24 dB: a strong satellite's cross-correlation peaks stand
  * above a satellite 24 dB weaker in every other PRN's plane.  gm_acq_cancel writes the dwell with the named satellites' signals
  * subtracted, as c32, into a second device buffer, which every search entry takes as a dwell.  The expected sequence is: search,

@@ -102,6 +102,10 @@ pub struct GmAcqLocalOut {          // gm_acq_local_out (88 bytes)
     pub doppler_bin: u32, pub offset_periods: u32, pub span_periods: u32, pub n_groups: u32, pub n_freq: u32, pub n_lags: u32,
 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmArrayRowInfo {         // gm_array_row_info (24 bytes): lambda1 / lambda2 is the estimate's quality; the caller judges
+    pub lambda1: f64, pub lambda2: f64, pub ref_index: u32, pub reserved: u32,
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct GmAcqCancelCand {        // gm_acq_cancel_cand (32 bytes): a found satellite for gm_acq_cancel
     pub worker: u32, pub reserved: u32,
     pub carrier_hz: f64,             // IF + Doppler: GmAcqLocalOut::carrier_hz
@@ -252,6 +256,14 @@ extern "C" {
     pub fn gm_acq_local_plan(coherent_periods: u32, n_integrations: u32, cfg: *const GmAcqLocalCfg, fs: f32, fft_size: u32,
                              n_bins: u32, table_freq: *const f32, bin: u32, n_lags: *mut u32, span_periods: *mut u32,
                              n_groups: *mut u32, n_freq: *mut u32, half_span_hz: *mut f64, step_hz: *mut f64) -> c_int;
+    // beam rows from the array's own correlations (additive entries, ABI stays 9): every antenna and tap delay of an interleaved array
+    // stream against a candidate's replica, z = [n_cands][R_u][taps][n_antennas] on the host; then a row per cell on the host in f64
+    pub fn gm_acq_array_prompts(a: *mut GmAcq, d_samples: *const c_void, fmt: c_int, n_antennas: u32, taps: u32,
+                                cands: *const GmAcqCand, n_cands: u32, z: *mut Complex32) -> c_int;
+    pub fn gm_acq_array_plan(coherent_periods: u32, n_integrations: u32, n_antennas: u32, taps: u32, periods: *mut u32,
+                             words_per_cand: *mut u32) -> c_int;
+    pub fn gm_array_row_solve(m: u32, n: u32, z: *const Complex32, r: *const Complex32, n_blocks: usize, loading: f32,
+                              row: *mut Complex32, info: *mut GmArrayRowInfo) -> c_int;
     // subtracting found satellites from a dwell (additive entries, ABI stays 9): one amplitude per signal code period and candidate,
     // estimated from the input; the output is c32 in device memory; d_samples null: the snapshot of the last search
     pub fn gm_acq_cancel(a: *mut GmAcq, d_samples: *const c_void, fmt: c_int, cands: *const GmAcqCancelCand, n_cands: u32,

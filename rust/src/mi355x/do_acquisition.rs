@@ -108,7 +108,7 @@ impl AcquisitionWorker {
 }
 impl Drop for AcquisitionWorker { fn drop(&mut self) { if !self.h.is_null() { unsafe { gm_acq_destroy(self.h); } } } }
 
-pub struct AcquisitionEngine { h: *mut GmAcq, n_prn: usize }   // replaces Vec<AcquisitionWorker> in run() (:268-271)
+pub struct AcquisitionEngine { h: *mut GmAcq, n_prn: usize, n_int: usize }   // replaces Vec<AcquisitionWorker> in run() (:268-271)
 unsafe impl Send for AcquisitionEngine {}
 
 impl AcquisitionEngine {
@@ -122,7 +122,7 @@ impl AcquisitionEngine {
                 coherent_periods: 1 };   // one code period per transform, as the reference (:174-193)
         let mut h = std::ptr::null_mut();
         if unsafe { gm_acq_create(&cfg, &mut h) } != 0 { return Err(AcqError); }
-        Ok(Self { h, n_prn: prn_ids.len() })
+        Ok(Self { h, n_prn: prn_ids.len(), n_int })
     }
     /// Not in the reference: on an engine built with coherent_periods >= 2, search `offsets` (ascending, in code periods) for where
     /// the coherent groups start, with an optional secondary row of +-1 (e.g. BeiDou's NH20); a dwell then takes
@@ -161,6 +161,33 @@ impl AcquisitionEngine {
         if unsafe { gm_acq_local_search(self.h, ptr, fmt, cands.as_ptr(), cands.len() as u32, cfg, out.as_mut_ptr(),
                                         std::ptr::null_mut(), std::ptr::null_mut()) } != 0 { return Err(AcqError); }
         Ok(out)
+    }
+    /// Not in the reference: the space-time prompts of an antenna array at known cells — every antenna and tap delay of the interleaved
+    /// stream at `d_samples` (device memory, `dwell_samples` TIME samples of `n_antennas` elements each, read only) against every
+    /// candidate's replica.  -> [cands][periods][taps][n_antennas] words and `periods`.  `solve_row` turns a candidate's words into a
+    /// beamformer row.  No detection decision is made.
+    pub fn array_prompts(&mut self, cands: &[GmAcqCand], d_samples: (*const std::os::raw::c_void, i32), n_antennas: u32, taps: u32)
+                         -> Result<(Vec<Complex32>, u32), AcqError> {
+        let (mut periods, mut words) = (0u32, 0u32);
+        if unsafe { gm_acq_array_plan(1, self.n_int as u32, n_antennas, taps, &mut periods, &mut words) } != 0 { return Err(AcqError); }
+        let mut z = vec![Complex32::new(0.0, 0.0); cands.len().max(1) * words as usize];
+        if unsafe { gm_acq_array_prompts(self.h, d_samples.0, d_samples.1, n_antennas, taps, cands.as_ptr(), cands.len() as u32,
+                                         z.as_mut_ptr()) } != 0 { return Err(AcqError); }
+        z.truncate(cands.len() * words as usize);
+        Ok((z, periods))
+    }
+    /// Not in the reference: a constraint row from one cell's prompt vectors `z` ([n][m]) and the Gram blocks `r` ([blocks][m][m]) a
+    /// beamformer captured (None: the identity), on the host in f64; loading 0 is 1e-4.  info.lambda1 / info.lambda2 is the estimate's
+    /// quality, which the caller judges.
+    pub fn solve_row(m: u32, z: &[Complex32], r: Option<&[Complex32]>, loading: f32) -> Result<(Vec<Complex32>, GmArrayRowInfo), AcqError> {
+        if m == 0 || z.len() % m as usize != 0 { return Err(AcqError); }
+        let mut row = vec![Complex32::new(0.0, 0.0); m as usize];
+        let mut info = GmArrayRowInfo::default();
+        let (rp, nb) = r.map_or((std::ptr::null(), 0usize), |v| (v.as_ptr(), v.len() / (m as usize * m as usize)));
+        if unsafe { gm_array_row_solve(m, (z.len() / m as usize) as u32, z.as_ptr(), rp, nb, loading, row.as_mut_ptr(), &mut info) } != 0 {
+            return Err(AcqError);
+        }
+        Ok((row, info))
     }
     /// Not in the reference: subtract found satellites from a dwell — one amplitude per signal code period and candidate is estimated
     /// from the input (the snapshot of the LAST search when `d_samples` is None, else any dwell in device memory, read only) and the
