@@ -518,6 +518,11 @@ static int acq_set_mask(gm_acq* a, uint64_t mask) {
     return GM_OK;
 }
 
+// decide_kernel stages a code's 3 * n_bins words in dynamic LDS (launch_decide: 12 bytes per bin of the 64 KB one workgroup may ask for):
+// every entry that reaches it with a caller's n_bins refuses more on the host instead of handing the runtime a launch it rejects
+static_assert(size_t(GM_ACQ_DECIDE_MAX_BINS) * 12 <= 65536 && size_t(GM_ACQ_DECIDE_MAX_BINS + 1) * 12 > 65536, "the limit the header states");
+static const char* const DECIDE_BINS_MSG = "n_bins above GM_ACQ_DECIDE_MAX_BINS = 5461 (the decision stages 12 bytes per bin in 64 KB of LDS)";
+
 static int acq_flush_decision(gm_acq* a) {
     if (a->dec_deferred) {
         a->dec_deferred = false;
@@ -1317,6 +1322,7 @@ int gm_acq_prepare_dev(gm_acq* a, const void* d_samples, int fmt, void* ready_st
 
 int gm_acq_decide_dev(gm_acq* a, const void* d_metrics, uint32_t n_prn, const uint8_t* prn_ids, uint64_t local_tail) {
     if (!a || !n_prn) return set_err(GM_ERR_INVALID_ARG, "null handle / n_prn == 0");
+    if (a->D > GM_ACQ_DECIDE_MAX_BINS) return set_err(GM_ERR_OUT_OF_RANGE, DECIDE_BINS_MSG);
     if (int rc = ensure_device(a->device)) return rc;
     if (int rc = acq_flush_decision(a)) return rc;
     if (int rc = acq_reserve_results(a, n_prn)) return rc;
@@ -5903,6 +5909,9 @@ int gm_acq_decide_planes_dev(const float* d_max, const uint32_t* d_argmax, const
                              void* hip_stream) {
     if (!d_max || !d_argmax || !d_sum || !d_prn_ids || !d_table_freq || !d_results || !d_found || !n_prn || !n_bins || fft_size < 2)
         return set_err(GM_ERR_INVALID_ARG, "null buffer or zero dimension");
+    if (n_bins > GM_ACQ_DECIDE_MAX_BINS) return set_err(GM_ERR_OUT_OF_RANGE, DECIDE_BINS_MSG);
+    if (threshold == 0.0f) threshold = 7.0f;             // gm_acq_cfg's and gm_acq_decide_host's defaults
+    if (!(code_rate > 0.0f)) code_rate = CA_RATE;
     if (int rc = ensure_device(g_device)) return rc;
     gm::DecideArgs da;
     da.mmax = d_max; da.margmax = d_argmax; da.msum = d_sum;

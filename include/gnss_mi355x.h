@@ -301,7 +301,12 @@ int gm_grid_assemble_dev(const void *d_gathered, uint32_t nranks, uint32_t p_max
 /* gm_acq_decide_dev without a handle: the reference's decision (do_acquisition.rs:195-238) for `n_prn` codes of ONE
  * family from device-resident planes (each [n_prn][n_bins]; e.g. a family's rows inside gm_grid_assemble_dev's output),
  * d_prn_ids / d_table_freq device arrays, results into caller-owned device arrays.  decision_mode: gm_decision_mode.
- * Asynchronous on hip_stream. */
+ * Asynchronous on hip_stream.
+ * Defaults, the ones of gm_acq_cfg and gm_acq_decide_host: threshold == 0 -> 7.0; code_rate <= 0 (or not a number) -> the
+ * C/A rate 1.023e6.
+ * n_bins <= GM_ACQ_DECIDE_MAX_BINS: one workgroup stages a code's 3 * n_bins words (12 bytes per bin) in the 64 KB of
+ * dynamic LDS it may ask for.  Above: GM_ERR_OUT_OF_RANGE, nothing launched, nothing written. */
+#define GM_ACQ_DECIDE_MAX_BINS 5461u   /* 65536 / 12 */
 int gm_acq_decide_planes_dev(const float *d_max, const uint32_t *d_argmax, const float *d_sum, uint32_t n_prn,
                              uint32_t n_bins, const uint8_t *d_prn_ids, const float *d_table_freq, uint32_t fft_size,
                              float fs, float code_rate, float threshold, int decision_mode, uint64_t local_tail,
@@ -309,11 +314,16 @@ int gm_acq_decide_planes_dev(const float *d_max, const uint32_t *d_argmax, const
 
 /* Replay the reference's decision (running best + ratio test + early exit) on the GPU from a metrics
  * block laid out as above for `n_prn` workers (e.g. an all-gathered one).  prn_ids: host [n_prn].
- * Asynchronous; results land in an internal device buffer read back by gm_acq_fetch_results. */
+ * Asynchronous; results land in an internal device buffer read back by gm_acq_fetch_results.
+ * Threshold and code rate are the handle's (gm_acq_cfg, its defaults applied at gm_acq_create: threshold 0 -> 7.0, code_rate
+ * <= 0 -> the C/A rate).  A handle of more than GM_ACQ_DECIDE_MAX_BINS Doppler bins: GM_ERR_OUT_OF_RANGE, nothing launched
+ * (gm_acq_search and gm_acq_search_ring, which decide through this entry, return the same). */
 int gm_acq_decide_dev(gm_acq *a, const void *d_metrics, uint32_t n_prn, const uint8_t *prn_ids,
                       uint64_t local_tail);
 int gm_acq_fetch_results(gm_acq *a, uint32_t n_prn, gm_acq_result *results, uint8_t *found); /* syncs */
-/* The same decision replay on host-resident metrics ([n_prn][n_bins] planes), no device involved. */
+/* The same decision replay on host-resident metrics ([n_prn][n_bins] planes), no device involved.  threshold == 0 -> 7.0;
+ * code_rate <= 0 (or not a number) -> the C/A rate 1.023e6, as in gm_acq_decide_planes_dev.  A sequential scan: no limit on
+ * n_bins. */
 int gm_acq_decide_host(const float *max, const uint32_t *argmax, const float *sum, const float *table_freq,
                        uint32_t n_prn, uint32_t n_bins, const uint8_t *prn_ids, uint32_t fft_size, float fs,
                        float code_rate, float threshold, uint64_t local_tail, gm_acq_result *results,
