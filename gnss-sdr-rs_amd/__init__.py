@@ -23,3 +23,7 @@ from .channelizer import Channelizer  # noqa: F401
 from .nuller import Nuller  # noqa: F401
 from .stap import Stap  # noqa: F401
 from .beamformer import Beamformer  # noqa: F401
+from . import tracking  # noqa: F401
+# per-antenna prompts of an array stream at tracked states: TrackingManager.array_prompts, and tracking.array_plan under a name that
+# does not collide with acquisition.array_plan
+from .tracking import TrackingManager, array_plan as trk_array_plan  # noqa: F401

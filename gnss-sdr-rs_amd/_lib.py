@@ -197,6 +197,19 @@ class TrkBankPlanOut(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TrkArrayCfg(C.Structure):
+    """gm_trk_array_cfg (32 bytes): A antennas, L taps, the code tap in chips"""
+    _fields_ = [("n_antennas", C.c_uint32), ("taps", C.c_uint32), ("tap_chips", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class TrkArrayPlanOut(C.Structure):
+    """gm_trk_array_plan_out (32 bytes)"""
+    _fields_ = [("words_per_record", C.c_uint32), ("out_words", C.c_uint64), ("samples", C.c_uint64), ("slices", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 FMT_C32, FMT_I8_IQ, FMT_I8_REAL = 0, 1, 2
 CODE_INDEX_FAITHFUL, CODE_INDEX_FIXED = 0, 1
 
@@ -414,6 +427,8 @@ SIGNATURES = {
     "gm_trk_bank_plan": (_i, [C.POINTER(TrkCfg), C.POINTER(TrkBankCfg), _u32, C.POINTER(TrkBankPlanOut)]),
     "gm_trk_bank": (_i, [_vp, _vp, _vp, _u32, C.POINTER(TrkBankCfg), _vp, _vp]),
     "gm_trk_bank_samples": (_i, [_vp, C.POINTER(TrkState), _vp, _sz, C.POINTER(TrkBankCfg), _vp]),
+    "gm_trk_array_plan": (_i, [C.POINTER(TrkCfg), C.POINTER(TrkArrayCfg), _u32, C.POINTER(TrkArrayPlanOut)]),
+    "gm_trk_array_prompts": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _u32, C.POINTER(TrkArrayCfg), _vp, _vp]),
 }
 
 _lib = None

@@ -2898,6 +2898,8 @@ struct gm_trk {
     uint64_t next_ticket = 1;
     // gm_trk_bank: one device block per call shape, [records | taps | offsets | out | done | partials] (trk_bank_run), grown on demand
     uint8_t* d_bank = nullptr; size_t bank_cap = 0;
+    // gm_trk_array_prompts: one device block per call shape, [records | z | done | partials], grown on demand
+    uint8_t* d_array = nullptr; size_t array_cap = 0;
 };
 
 static int trk_check_error(gm_trk* t);
@@ -2956,7 +2958,7 @@ int gm_trk_destroy(gm_trk* t) {
     if (!t) return GM_OK;
     if (t->device >= 0) hipSetDevice(t->device);
     hipFree(t->d_codes); hipFree(t->d_states); hipFree(t->d_partials); hipFree(t->d_ready); hipFree(t->d_scratch); hipFree(t->d_terms);
-    hipFree(t->d_res); hipFree(t->d_bank);
+    hipFree(t->d_res); hipFree(t->d_bank); hipFree(t->d_array);
     if (t->h_res) hipHostFree(t->h_res);
     for (auto& k : t->tk) if (k.done) hipEventDestroy(k.done);
     if (t->tk_block) hipHostFree(t->tk_block);
@@ -3351,6 +3353,28 @@ static int trk_bank_run(gm_trk* t, std::vector<gm::TrkBankRec>& recs, const gm_t
     return GM_OK;
 }
 
+// ---- gm_trk_array_prompts: per-antenna, per-tap prompts of an array stream at caller-supplied records (gnss_mi355x.h states the
+// definition and the limits) -- gm_trk_array_plan's argument rules, shared by the device entry
+static int trk_array_rules(float fs, bool custom_codes, uint32_t n_codes, uint32_t code_len, const gm_trk_array_cfg* cfg, uint32_t n_states) {
+    if (!cfg) return set_err(GM_ERR_INVALID_ARG, "null array cfg");
+    if (!(fs > 0) || !std::isfinite(fs)) return set_err(GM_ERR_INVALID_ARG, "fs is required");
+    if (custom_codes && (!n_codes || !code_len)) return set_err(GM_ERR_INVALID_ARG, "n_codes/code_len required");
+    for (uint32_t v : cfg->reserved)
+        if (v) return set_err(GM_ERR_INVALID_ARG, "gm_trk_array_cfg.reserved must be 0");
+    if (!std::isfinite(cfg->tap_chips)) return set_err(GM_ERR_INVALID_ARG, "tap_chips is not finite");
+    // the chip row shares the workgroup's 64 KB of LDS with the slice's ref image (33 KB, trk_array.hip)
+    if (custom_codes && code_len > 16384) return set_err(GM_ERR_OUT_OF_RANGE, "the array prompts serve codes of at most 16384 chips");
+    if (cfg->n_antennas < uint32_t(gm::GM_TRK_ARRAY_MIN_ANTENNAS) || cfg->n_antennas > uint32_t(gm::GM_TRK_ARRAY_MAX_ANTENNAS))
+        return set_err(GM_ERR_OUT_OF_RANGE, "n_antennas must be in 2 .. 8");
+    if (cfg->taps < 1 || cfg->taps > uint32_t(gm::GM_TRK_ARRAY_MAX_TAPS)) return set_err(GM_ERR_OUT_OF_RANGE, "taps must be in 1 .. 8");
+    if (cfg->n_antennas * cfg->taps > uint32_t(gm::GM_TRK_ARRAY_MAX_WORDS)) return set_err(GM_ERR_OUT_OF_RANGE, "n_antennas * taps must be at most 32");
+    if (n_states < 1 || n_states > uint32_t(gm::GM_TRK_ARRAY_MAX_STATES)) return set_err(GM_ERR_OUT_OF_RANGE, "n_states must be in 1 .. 1024");
+    const float half_len = 0.5f * float(custom_codes ? code_len : 1023u);
+    if (fabsf(cfg->tap_chips) > 64.0f || !(fabsf(cfg->tap_chips) < half_len))
+        return set_err(GM_ERR_OUT_OF_RANGE, "|tap_chips| must be at most 64 chips and below code_len / 2");
+    return GM_OK;
+}
+
 extern "C" {
 
 int gm_trk_bank_plan(const gm_trk_cfg* trk, const gm_trk_bank_cfg* cfg, uint32_t n_states, gm_trk_bank_plan_out* out) {
@@ -3419,6 +3443,87 @@ int gm_trk_bank_samples(gm_trk* t, const gm_trk_state* state, const gm_c32* samp
     std::vector<gm::TrkBankRec> recs(1);
     recs[0].st = *state; recs[0].n = uint32_t(n); recs[0].run = 1; recs[0].slices = 0; recs[0].poff = 0;
     return trk_bank_run(t, recs, cfg, F, t->d_scratch, ~0ull, 1, out, nullptr);
+}
+
+int gm_trk_array_plan(const gm_trk_cfg* trk, const gm_trk_array_cfg* cfg, uint32_t n_states, gm_trk_array_plan_out* out) {
+    if (!trk) return set_err(GM_ERR_INVALID_ARG, "null tracking cfg");
+    if (int rc = trk_array_rules(trk->fs, trk->codes != nullptr, trk->n_codes, trk->code_len, cfg, n_states)) return rc;
+    if (!out) return GM_OK;
+    memset(out, 0, sizeof(*out));
+    out->words_per_record = cfg->taps * cfg->n_antennas;
+    out->out_words = uint64_t(n_states) * out->words_per_record;
+    uint32_t n = 0;
+    const bool ok = trk_bank_samples_per_code(trk->fs, trk->nominal_code_rate > 0 ? trk->nominal_code_rate : CA_RATE,
+                                              trk->codes ? float(trk->code_len) : 1023.0f, n);
+    out->samples = n;
+    out->slices = ok ? (n + gm::GM_TRK_ARRAY_SLICE - 1) / gm::GM_TRK_ARRAY_SLICE : 0;
+    return GM_OK;
+}
+
+int gm_trk_array_prompts(gm_trk* t, const void* d_samples, int fmt, uint64_t first_index, uint64_t n_time, const gm_trk_state* states,
+                         uint32_t n_states, const gm_trk_array_cfg* cfg, gm_c32* z, uint8_t* done) {
+    if (!t || !d_samples || !z) return set_err(GM_ERR_INVALID_ARG, "null handle, samples or z");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "fmt must be GM_FMT_C32 or GM_FMT_I8_IQ");
+    if (!states && n_states != t->C) return set_err(GM_ERR_INVALID_ARG, "states NULL: n_states must be n_channels");
+    if (int rc = trk_array_rules(t->dc.fs, !t->dc.gps_ca, uint32_t(t->dc.n_codes), uint32_t(t->dc.code_len), cfg, n_states)) return rc;
+    constexpr uint64_t INDEX_MAX = 1ull << 62;
+    if (first_index >= INDEX_MAX || n_time >= INDEX_MAX || first_index + n_time >= INDEX_MAX)
+        return set_err(GM_ERR_OUT_OF_RANGE, "first_index + n_time must be below 2^62");
+    if (int rc = ensure_device(t->device)) return rc;
+    const uint32_t R = n_states, A = cfg->n_antennas, L = cfg->taps, M = A * L;
+    std::vector<gm::TrkBankRec> recs(R);
+    if (states) {
+        for (uint32_t r = 0; r < R; ++r) recs[r].st = states[r];
+    } else {        // the handle's own channels as they stand
+        std::vector<gm_trk_state> own(t->C);
+        if (int rc = gm_trk_get_states(t, own.data())) return rc;
+        for (uint32_t r = 0; r < R; ++r) recs[r].st = own[r];
+    }
+    // which records run: the kernel reads the time samples [max(0, s - (L-1)), s + n) of a record that does, and nothing else
+    const uint64_t H = L - 1;
+    uint64_t total = 0;
+    uint32_t max_slices = 0;
+    for (auto& r : recs) {
+        const gm_trk_state& s = r.st;
+        const int row = trk_bank_row(t, s);
+        bool run = s.active && row >= 0 && row < t->dc.n_codes && trk_bank_samples_per_code(t->dc.fs, s.code_rate, t->dc.code_len_f, r.n);
+        const uint64_t start = s.next_sample_index;
+        if (run) run = (start > H ? start - H : 0) >= first_index;                                // the halo is not in front of the buffer
+        if (run) run = start - first_index <= n_time && uint64_t(r.n) <= n_time - (start - first_index);      // s + n <= first_index + n_time
+        r.run = run ? 1 : 0;
+        if (!run) r.n = 0;
+        r.slices = run ? (r.n + gm::GM_TRK_ARRAY_SLICE - 1) / gm::GM_TRK_ARRAY_SLICE : 0;
+        r.poff = uint32_t(total);
+        total += r.slices;                              // at most 1024 x 2^19: no wrap
+        if (r.slices > max_slices) max_slices = r.slices;
+    }
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_recs = 0, o_z = o_recs + up(R * sizeof(gm::TrkBankRec)), o_done = o_z + up(size_t(R) * M * 8), o_part = o_done + up(R),
+                 bytes = o_part + up(size_t(total) * M * 8);
+    if (bytes > t->array_cap) {
+        HIPC(hipStreamSynchronize(t->stream));
+        hipFree(t->d_array); t->d_array = nullptr; t->array_cap = 0;
+        if (hipMalloc(&t->d_array, bytes) != hipSuccess) { (void)hipGetLastError(); t->d_array = nullptr; return set_err(GM_ERR_NOMEM, "gm_trk_array_prompts: device block"); }
+        t->array_cap = bytes;
+    }
+    uint8_t* d = t->d_array;
+    HIPC(hipMemcpyAsync(d + o_recs, recs.data(), R * sizeof(gm::TrkBankRec), hipMemcpyHostToDevice, t->stream));
+    gm::TrkArrayArgs a;
+    a.recs = reinterpret_cast<const gm::TrkBankRec*>(d + o_recs);
+    a.samples = d_samples; a.first_index = first_index;
+    a.fmt = fmt; a.A = int(A); a.L = int(L); a.tau = cfg->tap_chips;
+    a.partials = reinterpret_cast<cf*>(d + o_part);
+    gm::launch_trk_array(t->stream, t->dc, t->d_codes, a, int(R), max_slices, reinterpret_cast<gm_c32*>(d + o_z), d + o_done);
+    HIPC(hipGetLastError());
+    // the results land in host blocks of the call's own and reach the caller's only once everything has succeeded
+    std::vector<gm_c32> h_z(size_t(R) * M);
+    std::vector<uint8_t> h_done(R);
+    HIPC(hipMemcpyAsync(h_z.data(), d + o_z, h_z.size() * 8, hipMemcpyDeviceToHost, t->stream));
+    HIPC(hipMemcpyAsync(h_done.data(), d + o_done, R, hipMemcpyDeviceToHost, t->stream));
+    HIPC(hipStreamSynchronize(t->stream));
+    memcpy(z, h_z.data(), h_z.size() * 8);
+    if (done) memcpy(done, h_done.data(), R);
+    return GM_OK;
 }
 
 // The persistent kernel's workgroups wait for one another, so its whole grid must be resident at once: ONE persistent

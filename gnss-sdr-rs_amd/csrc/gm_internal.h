@@ -370,6 +370,24 @@ int trk_bank_tap_group(int n_taps);     // taps per workgroup: the smallest of 1
 void launch_trk_bank(hipStream_t, const TrkDevCfg&, const int8_t* d_codes, const TrkBankArgs&, int n_records, uint32_t max_slices,
                      gm_c32* d_out, uint8_t* d_done);
 
+// gm_trk_array_prompts (trk_array.hip, a section of trk_kernels.hip): per-antenna, per-tap prompts of an interleaved array stream at
+// caller-supplied records.  The host decides which records run (gnss_mi355x.h lists what skips one: among them any record whose time
+// samples [max(0, s - (L-1)), s + n) do not lie inside the buffer) and hands the kernel n, the slice count ceil(n / 4096) and the
+// record's first partial in a TrkBankRec; nothing of a record is written.
+constexpr int GM_TRK_ARRAY_MIN_ANTENNAS = 2, GM_TRK_ARRAY_MAX_ANTENNAS = 8, GM_TRK_ARRAY_MAX_TAPS = 8, GM_TRK_ARRAY_MAX_WORDS = 32,
+              GM_TRK_ARRAY_MAX_STATES = 1024;
+constexpr uint32_t GM_TRK_ARRAY_SLICE = 4096;
+struct TrkArrayArgs {
+    const TrkBankRec* recs;      // [n_records]
+    const void* samples;         // time sample first_index of the interleaved stream, fmt's elements
+    uint64_t first_index;
+    int fmt, A, L;               // GM_FMT_C32 or GM_FMT_I8_IQ
+    float tau;                   // the code tap, chips
+    cf* partials;                // [sum of slices][L][A]
+};
+void launch_trk_array(hipStream_t, const TrkDevCfg&, const int8_t* d_codes, const TrkArrayArgs&, int n_records, uint32_t max_slices,
+                      gm_c32* d_z, uint8_t* d_done);
+
 // ---------------------------------------------------------------- digital front-end (fe_kernels.hip)
 struct FeState { float phase_accumulator; float bias_re[8]; float bias_im[8]; };   // NcoLut.phase_accumulator, DcRemoverSimd.bias_*
 struct FrontendArgs {

@@ -1801,4 +1801,7 @@ void launch_trk_debug_math(hipStream_t st, int op, const float* d_x, uint32_t n,
 // ---- gm_trk_bank: the correlator bank at tracked states, a section of its own that uses the helpers above ----------------------------
 #include "trk_bank.hip"
 
+// ---- gm_trk_array_prompts: per-antenna prompts of an array stream at tracked states, a section of its own like the bank ------------------
+#include "trk_array.hip"
+
 }  // namespace gm

@@ -896,6 +896,29 @@ public:
         check(gm_trk_bank_plan(&trk, &c, n_states, &p), "TrackingManager::bank_plan");
         return p;
     }
+    // gm_trk_array_prompts: one code period of an interleaved array stream on the device (d_samples: time sample first_index, n_time
+    // time samples of n_antennas elements of fmt, written before the call) against the tracker's replica at tracking records, every
+    // antenna and tap delay at once; nothing is advanced.  records NULL: the handle's own channels as they stand.  -> [R][L][A], the
+    // word order gm_array_row_solve takes; done: [R] flags, 0 for a skipped record (whose words are zeros)
+    std::vector<Complex32> array_prompts(const void* d_samples, int fmt, uint64_t first_index, uint64_t n_time, uint32_t n_antennas,
+                                         uint32_t taps = 1, float tap_chips = 0.0f, const std::vector<gm_trk_state>* records = nullptr,
+                                         std::vector<uint8_t>* done = nullptr) {
+        const uint32_t r = records ? uint32_t(records->size()) : n_;
+        gm_trk_array_cfg c{}; c.n_antennas = n_antennas; c.taps = taps; c.tap_chips = tap_chips;
+        std::vector<Complex32> z(size_t(r) * taps * n_antennas);
+        if (done) done->assign(r, 0);
+        check(gm_trk_array_prompts(h_, d_samples, fmt, first_index, n_time, records ? records->data() : nullptr, r, &c,
+                                   reinterpret_cast<gm_c32*>(z.data()), done ? done->data() : nullptr), "TrackingManager::array_prompts");
+        return z;
+    }
+    // gm_trk_array_plan (host only): the argument rules and the sizes of an array_prompts call for a tracking configuration
+    static gm_trk_array_plan_out array_plan(const gm_trk_cfg& trk, uint32_t n_antennas, uint32_t taps = 1, float tap_chips = 0.0f,
+                                            uint32_t n_states = 1) {
+        gm_trk_array_cfg c{}; c.n_antennas = n_antennas; c.taps = taps; c.tap_chips = tap_chips;
+        gm_trk_array_plan_out p{};
+        check(gm_trk_array_plan(&trk, &c, n_states, &p), "TrackingManager::array_plan");
+        return p;
+    }
 private:
     std::map<uint64_t, uint32_t> pending_;      // ticket -> its pass count
 };

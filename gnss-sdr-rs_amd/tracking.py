@@ -118,6 +118,28 @@ def bank_plan(fs, taps, offsets_hz=(0.0,), n_states=1, code_rate=0.0, code_len=0
     return out.as_dict()
 
 
+def _array_cfg(n_antennas, taps, tap_chips):
+    cfg = _lib.TrkArrayCfg()
+    cfg.n_antennas, cfg.taps, cfg.tap_chips = int(n_antennas), int(taps), float(tap_chips)
+    return cfg
+
+
+def array_plan(fs, n_antennas, taps=1, tap_chips=0.0, n_states=1, code_rate=0.0, code_len=0):
+    """gm_trk_array_plan (host only, no device): the argument rules of the per-antenna prompts at tracked states and the sizes of a
+    call -> dict(words_per_record, out_words, samples, slices).  code_rate 0: 1.023e6; code_len 0: the C/A code's 1023, else the chips
+    per period of a custom table.  Raises GmError where the library refuses."""
+    trk = TrkCfg()
+    trk.fs, trk.n_channels, trk.nominal_code_rate = fs, 1, code_rate
+    dummy = np.ones(max(int(code_len), 1), np.int8)
+    if code_len:
+        trk.codes, trk.n_codes, trk.code_len = dummy.ctypes.data, 1, int(code_len)
+    cfg = _array_cfg(n_antennas, taps, tap_chips)
+    out = _lib.TrkArrayPlanOut()
+    check(lib().gm_trk_array_plan(C.byref(trk), C.byref(cfg), int(n_states), C.byref(out)), "gm_trk_array_plan")
+    del dummy
+    return out.as_dict()
+
+
 def debug_math(op, x, p0=0.0, p1=0.0, p2=0.0):
     """gm_debug_math: the tracking loop's scalar device math (op numbers in gnss_mi355x.h) evaluated on the device for every element
     of the f32 array x -> (out0, out1), uint32 words."""
@@ -234,6 +256,21 @@ class TrackingManager:
               "gm_trk_bank")
         del keep
         return out, done
+
+    def array_prompts(self, samples_ptr, n_time, n_antennas, taps=1, states=None, first_index=0, tap_chips=0.0, fmt=_lib.FMT_C32):
+        """gm_trk_array_prompts: one code period of an interleaved array stream on the device (samples_ptr: time sample first_index,
+        n_time time samples of n_antennas elements, FMT_C32 or FMT_I8_IQ, written before the call) against the tracker's replica at
+        tracking states, every antenna and tap delay at once; nothing is advanced.  states None: the handle's own channels as they
+        stand, else a list of TrkState records.  -> (z complex64 [R, L, A], done uint8 [R]); a skipped record has done 0 and zeros."""
+        cfg = _array_cfg(n_antennas, taps, tap_chips)
+        R = self.n_channels if states is None else len(states)
+        arr = None if states is None else (TrkState * max(R, 1))(*states)
+        z = np.zeros((R, int(taps), int(n_antennas)), np.complex64)
+        done = np.zeros(R, np.uint8)
+        check(lib().gm_trk_array_prompts(self._h, C.c_void_p(samples_ptr), int(fmt), int(first_index), int(n_time),
+                                         None if arr is None else C.cast(arr, C.c_void_p), R, C.byref(cfg), _p(z), _p(done)),
+              "gm_trk_array_prompts")
+        return z, done
 
     def update_all_dev(self, ring, epochs):
         check(lib().gm_trk_update_all_dev(self._h, ring._h, int(epochs)), "gm_trk_update_all_dev")

@@ -48,6 +48,7 @@ extern "C" {
                               and the lag window x fine Doppler at known cells — gm_acq_local_search, gm_acq_local_plan;
                               and subtracting found satellites from a dwell — gm_acq_cancel, gm_acq_cancel_plan;
                               and the correlator bank at tracked states — gm_trk_bank_plan, gm_trk_bank, gm_trk_bank_samples;
+                              and per-antenna prompts of an array stream at tracked states — gm_trk_array_plan, gm_trk_array_prompts;
                               8: gm_acq_cfg.any_length, gm_acq_plan_info;
                               7: gm_trk_collect hands over the channel states, gm_trk_get_states / gm_trk_set_states,
                               gm_ring_get_enqueued_head (round 6); 6: gm_acq_prepare_dev returns a token (round 5) */
@@ -662,6 +663,7 @@ int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const 
  * handle with the rows.
  * Not built: per-antenna prompts from the tracker (the array form of gm_trk_bank); a loop that re-steers by itself; several constraints
  * on one beam (LCMV); ring writers; any detection or quality decision; wiring into receiver_harness.cpp or bench.py.
+ * (Since then the first item has been built: gm_trk_array_prompts, "Per-antenna prompts at tracked states" below.)
  * (ABI 9, additive: a caller detects the feature by the symbol) */
 typedef struct { double lambda1, lambda2; uint32_t ref_index; uint32_t reserved; } gm_array_row_info;   /* 24 bytes; reserved = 0 */
 int gm_acq_array_prompts(gm_acq *a, const void *d_samples, int fmt, uint32_t n_antennas, uint32_t taps, const gm_acq_cand *cands,
@@ -1633,6 +1635,75 @@ int gm_trk_bank(gm_trk *t, gm_ring *ring, const gm_trk_state *states, uint32_t n
  * rule of gm_trk_correlate: GM_ERR_OUT_OF_RANGE otherwise, and for a code row outside the table.  Like gm_trk_correlate it runs
  * whatever `active` says.  out: [F][T]. */
 int gm_trk_bank_samples(gm_trk *t, const gm_trk_state *state, const gm_c32 *samples, size_t n, const gm_trk_bank_cfg *cfg, gm_c32 *out);
+
+/* ------------------------------------------------------------------ Per-antenna prompts at tracked states (additive, ABI 9)
+ * The array form of gm_trk_bank: one code period of an INTERLEAVED antenna-array stream correlated with the tracker's replica at
+ * caller-supplied tracking states, every antenna and every tap delay at once — the [L][A] words gm_array_row_solve takes, refreshed
+ * from a tracked channel instead of from a new search (the first item the section "Beam rows from the array's own correlations" above
+ * lists as not built).  The tracker's state goes in and [L][A] words come out; nothing is advanced.
+ *
+ * A record is a gm_trk_state, as for gm_trk_bank: a copy of a channel or anything the caller made up.  For record r:
+ *   n = round(fs / (code_rate / code_len)).
+ *   s = next_sample_index, a 64-bit TIME index.
+ *   tau = cfg->tap_chips.
+ *   x_a[t] is element (t - first_index) * A + a of an interleaved device buffer.  The buffer holds n_time time samples from absolute
+ *   time first_index, in the layout gm_nuller, gm_stap, gm_beamformer and gm_acq_array_prompts take.
+ *
+ *     phase_i = carrier_phase + fl(fl(fl(2 pi) * carrier_freq) * i) / fs        gm_trk_bank's expression at df = 0
+ *     c[i]    = (code_phase + i * (code_rate / fs)) mod code_len                as correlate_sample forms it
+ *     ref[i]  = (cos phase_i, -sin phase_i) * chip(fl(c[i] + tau))              chip = +-1 (x BOC sign): an exact sign flip
+ *     z[r][l][a] = sum_{i < n} x_a[s + i - l] * ref[i]                          l < L, a < A
+ *
+ * Helpers: chip(), the division by fs and the sine and cosine are the helpers gm_trk_bank uses (the exact fast forms where the epoch
+ * allows them, the f64-reduced sine and cosine), with glibc's forms on a strict_libm handle.
+ * Product: the complex product is four explicit fmaf, in the order gm_acq_array_prompts writes them:
+ *     re = fma(xr, rr, re);  re = fma(-xi, ri, re);  im = fma(xr, ri, im);  im = fma(xi, rr, im)
+ * THE ORDER, f32.  strict_sum_order is IGNORED.  The sum is a tree, a function of n and L alone.  Seen from the samples, time sample
+ * u = i - l (u in [-(L-1), n)) meets ref[u .. u + L - 1].  The time samples are cut into ceil(n / 4096) slices: slice k holds u in
+ * [4096 k, 4096 (k + 1)) below n, and slice 0 holds the L - 1 halo samples u < 0 as well.  Within a slice lane j of 256 takes, in this
+ * order, the halo sample u = j - (L-1) (slice 0 and j < L - 1 only), then u = 4096 k + j + 256 m for m = 0 .. 15; for each time sample
+ * it adds the taps l = 0 .. L-1 (a halo sample: l = -u .. L-1), one product above per tap, into its own sum per (l, a).  The 64 lanes of a wave add by
+ * the butterfly v += v[lane xor d], d = 32, 16, 8, 4, 2, 1; the four waves add in ascending order ((w0 + w1) + w2) + w3; the slices
+ * add in ascending order.  There are no floating-point atomics.  A record's words therefore do not depend on what else is in the call,
+ * on repetition, or on where the buffer starts.
+ * Agreement with gm_trk_bank: at L = 1, antenna a's word agrees with gm_trk_bank on the de-interleaved antenna (T = 1 tap tau, F = 1)
+ * within the tracking tolerance of 1e-5 of the envelope.  It is NOT bit for bit: the bank rounds x * w (two products and a difference
+ * per component) before the chip and sums in another order; this entry multiplies the sample by the finished ref word inside the fma.
+ * NOTHING IS ADVANCED: no record is written and no channel state, loop filter or lock counter moves.
+ *
+ * Time samples and the halo: a time index below 0 reads as ZERO (gm_stap's halo), which can happen only when s < L - 1.  A record is
+ * SKIPPED — done[r] = 0, its words zeros, the call succeeds — when active == 0; when its code row is outside the table; when n is 0 or
+ * >= 2^31; when s + n > first_index + n_time; when max(0, s - (L-1)) < first_index, that is, part of its halo lies in front of the
+ * buffer.  The library never reads outside [d_samples, d_samples + n_time * A elements).
+ *
+ * Formats: GM_FMT_C32 or GM_FMT_I8_IQ, aligned to the element only (8 or 2 bytes); int8 -128 is -128.0f.  GM_FMT_I8_REAL is refused.
+ * Limits, all checked before anything runs (gm_trk_array_plan holds those of cfg and n_states; the device entry calls the same code):
+ * a NULL handle, d_samples, cfg or z, a tap_chips that is not finite, a format other than the two above, a reserved word that is not
+ * zero, states NULL with n_states != n_channels: GM_ERR_INVALID_ARG; n_antennas outside 2 .. 8, taps outside 1 .. 8, n_antennas * taps
+ * above 32, n_states outside 1 .. 1024, |tap_chips| above 64 or not below code_len / 2, a custom code of more than 16384 chips (the chip
+ * row shares the workgroup's LDS with the slice's ref image), first_index + n_time not below 2^62: GM_ERR_OUT_OF_RANGE.  A refusal
+ * leaves z and done untouched.
+ * Out of scope: a loop that re-steers by itself; propagating a state over several epochs inside the call; carrier offsets or several
+ * code taps per call; an array ring; a _dev / caller's-stream form; any detection or quality decision. */
+typedef struct {
+    uint32_t n_antennas, taps;     /* A, L */
+    float tap_chips;               /* tau, chips */
+    uint32_t reserved[5];          /* zeros */
+} gm_trk_array_cfg;
+typedef struct {
+    uint32_t words_per_record;     /* L * A */
+    uint64_t out_words;            /* n_states * L * A gm_c32 words */
+    uint64_t samples;              /* n for gm_trk_cfg.nominal_code_rate (0 -> 1.023e6) and code_len (no codes: 1023) */
+    uint32_t slices;               /* ceil(n / 4096); 0 where a record with this n would be skipped */
+} gm_trk_array_plan_out;
+/* host only, no device: the argument rules above, and the sizes of a call.  Of `trk` it reads fs, codes / code_len (the chips per
+ * period) and nominal_code_rate (the code_rate n is reported for).  out may be NULL. */
+int gm_trk_array_plan(const gm_trk_cfg *trk, const gm_trk_array_cfg *cfg, uint32_t n_states, gm_trk_array_plan_out *out);
+/* Synchronous, on the handle's stream.  The caller HAS FINISHED WRITING d_samples before the call (the library orders nothing against
+ * the buffer's writer).  states NULL: the handle's own channels as they stand, n_states = n_channels.  z: [n_states][L][A], host
+ * memory, the word order gm_array_row_solve takes; done: [n_states] or NULL. */
+int gm_trk_array_prompts(gm_trk *t, const void *d_samples, int fmt, uint64_t first_index, uint64_t n_time, const gm_trk_state *states,
+                         uint32_t n_states, const gm_trk_array_cfg *cfg, gm_c32 *z, uint8_t *done);
 
 /* ------------------------------------------------------------------ Bit sync + nav-bit accumulation
  * src/decoding.rs:8,40-227 (legacy file outside the reference's module tree): 20-bin histogram of prompt-I sign

@@ -160,6 +160,20 @@ pub struct GmTrkBankPlanOut {       // gm_trk_bank_plan_out (32 bytes)
     pub tap_groups: u32,             // ceil(T / 16)
 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmTrkArrayCfg {          // gm_trk_array_cfg (32 bytes): per-antenna prompts of an array stream at tracked states
+    pub n_antennas: u32,             // A: 2 .. 8
+    pub taps: u32,                   // L: 1 .. 8, A * L <= 32
+    pub tap_chips: f32,              // the code tap tau, chips: |tau| <= 64 and < code_len / 2
+    pub reserved: [u32; 5],          // must be 0
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmTrkArrayPlanOut {      // gm_trk_array_plan_out (32 bytes)
+    pub words_per_record: u32,       // L * A
+    pub out_words: u64,              // n_states * L * A complex words
+    pub samples: u64,                // n for the configuration's nominal code rate
+    pub slices: u32,                 // ceil(n / 4096)
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct GmDdcCfg {               // gm_ddc_cfg (40 bytes; zeros in the filter fields: the defaults)
     pub mix_cycles_per_sample: f64,  // f_mix / fs_in: the frequency brought to 0, cycles per input sample; any finite value
     pub up: u32, pub down: u32,      // as GmResamplerCfg, field by field
@@ -460,6 +474,14 @@ extern "C" {
                        out: *mut Complex32, done: *mut u8) -> c_int;
     pub fn gm_trk_bank_samples(t: *mut GmTrk, state: *const GmTrkState, s: *const Complex32, n: usize, cfg: *const GmTrkBankCfg,
                                out: *mut Complex32) -> c_int;
+    /// per-antenna prompts at tracked states: one code period of an interleaved array stream on the device (n_time time samples from
+    /// absolute time first_index, fmt 0 = c32 or 1 = int8 IQ, written before the call) against the tracker's replica per record, every
+    /// antenna and tap delay at once, nothing advanced (states null: the handle's own channels, n_states = n_channels;
+    /// z: [n_states][L][A], host, the word order gm_array_row_solve takes; done: [n_states] or null)
+    pub fn gm_trk_array_plan(trk: *const GmTrkCfg, cfg: *const GmTrkArrayCfg, n_states: u32, out: *mut GmTrkArrayPlanOut) -> c_int;
+    pub fn gm_trk_array_prompts(t: *mut GmTrk, d_samples: *const c_void, fmt: c_int, first_index: u64, n_time: u64,
+                                states: *const GmTrkState, n_states: u32, cfg: *const GmTrkArrayCfg, z: *mut Complex32,
+                                done: *mut u8) -> c_int;
     // fft.rs:5-56
     pub fn gm_fft_c2c_f32(n: usize, dir: c_int, inout: *mut Complex32, batch: usize) -> c_int;
     pub fn gm_fft_power_spectrum_f32(n: usize, inout: *mut Complex32, power: *mut f32) -> c_int;

@@ -393,6 +393,26 @@ impl TrackingManager {
         (out, done)
     }
 
+    /// Per-antenna prompts at tracked states (gm_trk_array_prompts): one code period of an interleaved array stream on the device
+    /// (`d_samples`: time sample `first_index`, `n_time` time samples of `n_antennas` elements, `fmt` 0 = c32 or 1 = int8 IQ, written
+    /// before the call) against the tracker's replica at `records` — None: the handle's channels as they stand —, every antenna and
+    /// each of `taps` tap delays at once.  Nothing is advanced.  -> (z [R][L][A], done [R]); a skipped record has done 0 and zeros.
+    /// Not part of the reference.
+    pub fn array_prompts(&mut self, d_samples: *const std::ffi::c_void, fmt: i32, first_index: u64, n_time: u64, n_antennas: u32,
+                         taps: u32, tap_chips: f32, records: Option<&[GmTrkState]>) -> (Vec<Complex32>, Vec<u8>) {
+        self.collect_ready(true);                                        // nothing in flight moves a record under the call
+        self.push_dirty();
+        let r = records.map_or(self.channels.len(), |s| s.len());
+        let cfg = GmTrkArrayCfg { n_antennas, taps, tap_chips, reserved: [0; 5] };
+        let (mut z, mut done): (Vec<Complex32>, Vec<u8>) = (Vec::new(), Vec::new());        // (a caller's look, not the loop: it allocates)
+        z.resize(r * (taps as usize) * (n_antennas as usize), Complex32::new(0.0, 0.0));
+        done.resize(r, 0u8);
+        let st = unsafe { gm_trk_array_prompts(self.h, d_samples, fmt, first_index, n_time, records.map_or(std::ptr::null(), |s| s.as_ptr()),
+                                               r as u32, &cfg, z.as_mut_ptr(), done.as_mut_ptr()) };
+        assert_eq!(st, 0, "gm_trk_array_prompts: {}", last_error());
+        (z, done)
+    }
+
     fn next_tracking_index(&self) -> usize {                             // :373-381 on the PLANNED positions (= the fields when nothing is in flight)
         (0..self.channels.len()).filter(|i| self.channels[*i].is_active())
             .map(|i| self.planned_index(i) + self.channels[i].num_samples_per_code).min().unwrap_or(0)
