@@ -424,6 +424,7 @@ SIGNATURES = {
     "gm_trk_enable_timing": (_i, [_vp, _i]),
     "gm_trk_last_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_u32)]),
     "gm_debug_math": (_i, [_i, _vp, _sz, _f, _f, _f, _vp, _vp]),
+    "gm_debug_fft_four_step": (_i, [_u32, _u32, _i, _vp, _sz]),
     "gm_trk_bank_plan": (_i, [C.POINTER(TrkCfg), C.POINTER(TrkBankCfg), _u32, C.POINTER(TrkBankPlanOut)]),
     "gm_trk_bank": (_i, [_vp, _vp, _vp, _u32, C.POINTER(TrkBankCfg), _vp, _vp]),
     "gm_trk_bank_samples": (_i, [_vp, C.POINTER(TrkState), _vp, _sz, C.POINTER(TrkBankCfg), _vp]),

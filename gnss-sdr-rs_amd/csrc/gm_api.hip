@@ -651,21 +651,25 @@ int gm_apply_doppler_shift(const gm_c32* samples, const gm_c32* table, gm_c32* o
 // ---------------------------------------------------------------- FFT<T> / RealFFT<T>
 int gm_fft_supported_sizes(uint32_t* sizes, int cap) { return gm::list_plans(sizes, cap); }
 
-// power-of-two lengths above one LDS buffer: L = N1 * N2, both in-LDS power-of-two plans (N1 >= N2, as balanced as they come)
+// the in-LDS plan of a length, decided on the size_t value: nothing above 16384 has one (int(n) of 2^32 + 256 is 256)
+static const gm::PlanOps* plan_for(size_t n) { return n <= 16384 ? gm::find_plan(int(n)) : nullptr; }
+
+// power-of-two lengths above one LDS buffer: L = N1 * N2, both in-LDS power-of-two plans.  The loop takes the SMALLEST N2 in 256, 512, ...
+// with N1 = L / N2 >= N2 a plan of at most 16384: N2 = 256 up to 2^22, then 16384 x 512 ... 16384 x 16384 (32768 = 256 x 128: none)
 static bool pow2_split(size_t n, const gm::PlanOps** p1, const gm::PlanOps** p2) {
     if (n < 2 || (n & (n - 1)) || n > (size_t(1) << 28)) return false;
     for (size_t n2 = 256; n2 * n2 <= n || n2 <= 16384; n2 *= 2) {
         if (n % n2) continue;
         const size_t n1 = n / n2;
         if (n1 < n2) break;
-        const gm::PlanOps *a = n1 <= 16384 ? gm::find_plan(int(n1)) : nullptr, *b = gm::find_plan(int(n2));
+        const gm::PlanOps *a = plan_for(n1), *b = plan_for(n2);
         if (a && b && a->big_cols && b->big_rows) { *p1 = a; *p2 = b; return true; }
     }
     return false;
 }
-static int fft_run_big(size_t n, int dir, cf* d_data, size_t batch, hipStream_t st) {
-    const gm::PlanOps *p1 = nullptr, *p2 = nullptr;
-    if (!pow2_split(n, &p1, &p2)) return set_err(GM_ERR_UNSUPPORTED_N, "no in-LDS FFT plan for this length");
+// the four-step transform of length p1->n * p2->n on `batch` device arrays: columns by p1 (grid p2->n), rows by p2 (grid p1->n)
+static int fft_run_four_step(const gm::PlanOps* p1, const gm::PlanOps* p2, int dir, cf* d_data, size_t batch, hipStream_t st) {
+    const size_t n = size_t(p1->n) * size_t(p2->n);
     std::vector<cf> t1(size_t(p1->tw_total) + 1), t2(size_t(p2->tw_total) + 1);
     p1->fill_tw(t1.data(), dir != 0);
     p2->fill_tw(t2.data(), dir != 0);
@@ -683,9 +687,14 @@ static int fft_run_big(size_t n, int dir, cf* d_data, size_t batch, hipStream_t 
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return done(set_err(GM_ERR_HIP, "long FFT kernels"));
     return done(GM_OK);
 }
+static int fft_run_big(size_t n, int dir, cf* d_data, size_t batch, hipStream_t st) {
+    const gm::PlanOps *p1 = nullptr, *p2 = nullptr;
+    if (!pow2_split(n, &p1, &p2)) return set_err(GM_ERR_UNSUPPORTED_N, "no in-LDS FFT plan for this length");
+    return fft_run_four_step(p1, p2, dir, d_data, batch, st);
+}
 
 static int fft_run(size_t n, int dir, cf* d_data, size_t batch, hipStream_t st) {
-    const gm::PlanOps* pl = gm::find_plan(int(n));
+    const gm::PlanOps* pl = plan_for(n);
     if (!pl) return fft_run_big(n, dir, d_data, batch, st);
     std::vector<cf> tw(size_t(pl->tw_total) + 1);
     pl->fill_tw(tw.data(), dir != 0);
@@ -699,6 +708,22 @@ static int fft_run(size_t n, int dir, cf* d_data, size_t batch, hipStream_t st) 
     return GM_OK;
 }
 
+// Bluestein's transform length for n: the smallest power of two L >= max(256, 2n - 1) that has a transform (32768 = 256 x 128 has no
+// two in-LDS factors: 65536 then); 0 where there is none (n above 2^23, decided before 2n is formed)
+static size_t bluestein_len(size_t n) {
+    if (n > (size_t(1) << 23)) return 0;
+    size_t L = 256;
+    while (L < 2 * n - 1) L *= 2;
+    const gm::PlanOps *p1 = nullptr, *p2 = nullptr;
+    while (L <= (size_t(1) << 24) && !plan_for(L) && !pow2_split(L, &p1, &p2)) L *= 2;
+    return L <= (size_t(1) << 24) ? L : 0;
+}
+// a length FFT<T> serves: an in-LDS plan, a four-step pair, or Bluestein on one of the two
+static bool fft_len_supported(size_t n) {
+    const gm::PlanOps *p1 = nullptr, *p2 = nullptr;
+    return plan_for(n) || pow2_split(n, &p1, &p2) || bluestein_len(n);
+}
+
 // FFT<T>::new is generic over the length (src/fft.rs:10-19: rustfft plans any N).  Lengths without an in-LDS plan go
 // through Bluestein's chirp-z identity on the smallest power-of-two plan L >= 2N - 1:
 //   X[k] = c[k] * sum_n (x[n] c[n]) conj(c[k - n]),   c[n] = exp(-j pi n^2 / N)   (phase from n^2 mod 2N: exact in integers)
@@ -706,14 +731,8 @@ static int fft_run(size_t n, int dir, cf* d_data, size_t batch, hipStream_t st) 
 // device; the three O(N) chirp products are host loops (this entry takes and returns host buffers).  L up to 2^24 (N <= 2^23):
 // powers of two above one LDS buffer run as a four-step transform (fft_run_big).
 static int fft_bluestein(size_t n, int dir, gm_c32* inout, size_t batch) {
-    size_t L = 256;
-    while (L < 2 * n - 1) L *= 2;
-    {   // the next power of two that has a transform (32768 = 256 x 128 has no two in-LDS factors: 65536 then)
-        const gm::PlanOps *p1 = nullptr, *p2 = nullptr;
-        while (L <= (size_t(1) << 24) && !gm::find_plan(int(L)) && !pow2_split(L, &p1, &p2)) L *= 2;
-        if (L > (size_t(1) << 24))
-            return set_err(GM_ERR_UNSUPPORTED_N, "length above 2^23: no FFT plan (Bluestein needs a power of two >= 2N - 1, at most 2^24)");
-    }
+    const size_t L = bluestein_len(n);
+    if (!L) return set_err(GM_ERR_UNSUPPORTED_N, "length above 2^23: no FFT plan (Bluestein needs a power of two >= 2N - 1, at most 2^24)");
     std::vector<cf> c(n), b(L, gm::cf_make(0.f, 0.f));
     for (size_t i = 0; i < n; ++i) {
         const double a = M_PI * double((uint64_t(i) * i) % (2 * n)) / double(n);
@@ -757,7 +776,7 @@ int gm_fft_c2c_f32(size_t n, int dir, gm_c32* inout, size_t batch) {
     if (int rc = ensure_device(g_device)) return rc;
     {
         const gm::PlanOps *p1 = nullptr, *p2 = nullptr;
-        if (!gm::find_plan(int(n)) && !pow2_split(n, &p1, &p2)) return fft_bluestein(n, dir, inout, batch);
+        if (!plan_for(n) && !pow2_split(n, &p1, &p2)) return fft_bluestein(n, dir, inout, batch);
     }
     cf* d = nullptr;
     HIPC(hipMalloc(&d, n * batch * 8));
@@ -772,7 +791,7 @@ int gm_fft_power_spectrum_f32(size_t n, gm_c32* inout, float* power) {
     if (!inout || !power || !n) return set_err(GM_ERR_INVALID_ARG, "null or empty");
     if (int rc = ensure_device(g_device)) return rc;
     const gm::PlanOps *pp1 = nullptr, *pp2 = nullptr;
-    if (!gm::find_plan(int(n)) && !pow2_split(n, &pp1, &pp2)) {            // any other length: Bluestein, then |X|^2 on the host
+    if (!plan_for(n) && !pow2_split(n, &pp1, &pp2)) {            // any other length: Bluestein, then |X|^2 on the host
         if (int rc = fft_bluestein(n, 0, inout, 1)) return rc;
         for (size_t i = 0; i < n; ++i) power[i] = inout[i].re * inout[i].re + inout[i].im * inout[i].im;   // norm_sqr (fft.rs:28)
         return GM_OK;
@@ -793,10 +812,29 @@ int gm_fft_power_spectrum_f32(size_t n, gm_c32* inout, float* power) {
 
 int gm_rfft_f32(size_t n, const float* in, gm_c32* out) {
     if (!in || !out || !n) return set_err(GM_ERR_INVALID_ARG, "null or empty");
+    if (!fft_len_supported(n)) return set_err(GM_ERR_UNSUPPORTED_N, "no FFT plan for this length");   // before n words are read
     std::vector<gm_c32> buf(n);
     for (size_t i = 0; i < n; ++i) { buf[i].re = in[i]; buf[i].im = 0.0f; }
     const int rc = gm_fft_c2c_f32(n, 0, buf.data(), 1);
     if (!rc) memcpy(out, buf.data(), (n / 2 + 1) * sizeof(gm_c32));
+    return rc;
+}
+
+// Diagnostic: the four-step transform of a NAMED factor pair (the public entries reach only the pairs pow2_split chooses)
+int gm_debug_fft_four_step(uint32_t n1, uint32_t n2, int dir, gm_c32* inout, size_t batch) {
+    if (!inout || !batch) return set_err(GM_ERR_INVALID_ARG, "null or empty");
+    const gm::PlanOps *p1 = plan_for(n1), *p2 = plan_for(n2);
+    if (!p1 || !p2 || !p1->big_cols || !p2->big_rows)
+        return set_err(GM_ERR_UNSUPPORTED_N, "both factors must be power-of-two in-LDS plans");
+    if (batch > (size_t(1) << 31) / (size_t(n1) * n2)) return set_err(GM_ERR_OUT_OF_RANGE, "more than 2^31 points in one call");
+    if (int rc = ensure_device(g_device)) return rc;
+    const size_t bytes = size_t(n1) * n2 * batch * 8;                    // n1 * n2 <= 2^28
+    cf* d = nullptr;
+    HIPC(hipMalloc(&d, bytes));
+    int rc = hipMemcpy(d, inout, bytes, hipMemcpyHostToDevice) == hipSuccess ? GM_OK : set_err(GM_ERR_HIP, "hipMemcpy");
+    if (!rc) rc = fft_run_four_step(p1, p2, dir, d, batch, nullptr);
+    if (!rc && hipMemcpy(inout, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_err(GM_ERR_HIP, "hipMemcpy");
+    hipFree(d);
     return rc;
 }
 

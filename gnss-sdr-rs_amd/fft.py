@@ -17,6 +17,15 @@ def supported_sizes():
     return [int(x) for x in buf[:n]]
 
 
+def four_step(n1, n2, x, inverse=False):
+    """gm_debug_fft_four_step (a test entry): the four-step transform of length n1 * n2 by the column kernel of n1's plan and the row
+    kernel of n2's, in place on `x` (complex64 array of n1 * n2, or batch * n1 * n2) and returns it"""
+    assert x.dtype == np.complex64 and x.flags.c_contiguous and x.size and x.size % (int(n1) * int(n2)) == 0
+    _lib.init(_lib._initialised or 0)
+    check(lib().gm_debug_fft_four_step(int(n1), int(n2), 1 if inverse else 0, _p(x), x.size // (int(n1) * int(n2))), "fft.four_step")
+    return x
+
+
 class FFT:
     def __init__(self, len):
         self.len = int(len)

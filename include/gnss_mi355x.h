@@ -1572,6 +1572,14 @@ int gm_trk_last_timing(gm_trk *t, float *ms_correlate_total, uint32_t *launches)
  * GM_ERR_INVALID_ARG: a null array; GM_ERR_OUT_OF_RANGE: op, n, or a parameter an op reads that is not positive and finite;
  * GM_ERR_NO_DEVICE without a device. */
 int gm_debug_math(int op, const float *x, size_t n, float p0, float p1, float p2, uint32_t *out0, uint32_t *out1);
+/* Diagnostic (additive, ABI 9; not in the reference; a test entry): the four-step transform of length n1 * n2 with the factor pair NAMED,
+ * in place on `batch` host arrays of n1 * n2 values: the column kernel of n1's plan on a grid of n2 workgroups, then the row kernel of
+ * n2's plan on a grid of n1 — the code gm_fft_c2c_f32 runs for a power of two above 16384, which reaches only the pair its own rule
+ * picks (N2 = 256 up to 2^22 points; a row plan of 2048 or more first at 2^25).  tests/test_gpu_fft_paths.py runs every column and
+ * row kernel through it at 2^16 .. 2^22 points.  n1 < n2 is accepted.  dir: 0 forward, otherwise inverse (not normalised).
+ * GM_ERR_INVALID_ARG: a null array or batch == 0; GM_ERR_UNSUPPORTED_N: a factor that is not one of the power-of-two in-LDS plans
+ * (256 .. 16384), decided before the array is read; GM_ERR_OUT_OF_RANGE: n1 * n2 * batch above 2^31; GM_ERR_NO_DEVICE without a device. */
+int gm_debug_fft_four_step(uint32_t n1, uint32_t n2, int dir, gm_c32 *inout, size_t batch);
 
 /* ------------------------------------------------------------------ Correlator bank at tracked states (additive, ABI 9)
  * T taps x F carrier offsets of one code period at caller-supplied tracking states, formed with the tracker's own per-sample

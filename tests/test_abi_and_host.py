@@ -102,6 +102,17 @@ def test_null_handles_are_refused_not_dereferenced(gm):
     assert L.gm_debug_math(5, xs, 4, 0.0, 0.0, 0.0, w0, w1) == -5 and L.gm_debug_math(8, xs, 4, 4.0e6, float("nan"), 0.0, w0, w1) == -5
     assert L.gm_debug_math(10, xs, 4, 1023.5, 0.0, 0.0, w0, w1) == -5
     assert list(w0) == [9, 9, 9, 9] and list(w1) == [9, 9, 9, 9]
+    # the named four-step transform (an additive export): a null array, batch 0, a factor that is no power-of-two in-LDS plan, and
+    # too many points — all refused before a device is needed and before the one-word array is read
+    one = (C.c_float * 2)(9.0, 9.0)
+    assert L.gm_debug_fft_four_step(256, 256, 0, None, 1) == -1 and L.gm_debug_fft_four_step(256, 256, 0, one, 0) == -1
+    for n1, n2 in ((128, 256), (256, 128), (8000, 256), (256, 16368), (384, 256), (32768, 16384), (0, 256), (256, 0), (1 << 31, 2)):
+        assert L.gm_debug_fft_four_step(n1, n2, 0, one, 1) == -2 and b"power-of-two in-LDS plans" in L.gm_last_error(), (n1, n2)
+    assert L.gm_debug_fft_four_step(16384, 16384, 1, one, 9) == -5
+    # a length whose low 32 bits alone name a plan is no plan: gm_rfft_f32 decides that on the size_t value, before n words are read
+    for n in ((1 << 32) + 256, (1 << 32) + 8000, (1 << 23) + 1, (1 << 63) + 100):
+        assert L.gm_rfft_f32(n, one, one) == -2, n
+    assert list(one) == [9.0, 9.0]
 
 
 def test_ca_table_and_resampler_host(gm, oracle):
