@@ -9,9 +9,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BeamformerCfg, check, lib
-from .nuller import _array
-from .resample import _p
+from ._lib import BeamformerCfg
+from ._stage import ArrayStage, _p, array_plan
 
 
 def _rows(n_antennas, taps, steering):
@@ -34,58 +33,28 @@ def plan(n_antennas, taps, steering, block=0, loading=0.0, inputs_so_far=0, n_in
     """gm_beamformer_plan (host only, no device): the argument rules, the defaults and the number of outputs PER BEAM that n_in more
     time samples deliver to a stream that has taken inputs_so_far."""
     c, keep = _cfg(n_antennas, taps, steering, block, loading)
-    b, ld, n = C.c_uint32(0), C.c_float(0), C.c_uint64(0)
-    check(lib().gm_beamformer_plan(C.byref(c), int(inputs_so_far), int(n_in), C.byref(b), C.byref(ld), C.byref(n)), "gm_beamformer_plan")
-    return dict(block=b.value, loading=ld.value, n_out=n.value)
+    return array_plan("beamformer", c, inputs_so_far, n_in)
 
 
-class Beamformer:
+class Beamformer(ArrayStage):
+    """process(x, want_blocks=False): x [n, A] complex64 or [n, A, 2] int8 -> complex64 [P, n_out]: this call's outputs, a row a beam
+    (synchronous); with want_blocks (y, R [blocks, M, M], w [blocks, P, M]): the words each of the call's blocks was combined with (R is
+    zeros in static mode).  capture(d_R, d_w, cap_blocks): device buffers [cap_blocks][M][M] and [cap_blocks][P][M]."""
+    _NAME = "beamformer"
+
     def __init__(self, n_antennas, taps, steering, block=0, loading=0.0, device=None):
         _lib.init(device if device is not None else (_lib._initialised or 0))
         p = plan(n_antennas, taps, steering, block, loading)
         c, keep = _cfg(n_antennas, taps, steering, block, loading)
         self.n_antennas, self.taps, self.block, self.loading = int(n_antennas), int(taps), p["block"], p["loading"]
-        self.n_weights = self.n_antennas * self.taps
-        self.n_beams = keep.shape[0]
-        h = C.c_void_p()
-        check(lib().gm_beamformer_create(C.byref(c), C.byref(h)), "gm_beamformer_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gm_beamformer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):      # (at interpreter shutdown the module globals close() uses may be gone already)
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def process(self, x, want_blocks=False):
-        """x: [n, A] complex64 or [n, A, 2] int8 -> complex64 [P, n_out]: this call's outputs, a row a beam (synchronous); with
-        want_blocks (y, R [blocks, M, M], w [blocks, P, M]): the words each of the call's blocks was combined with (R is zeros in
-        static mode)"""
-        M, P = self.n_weights, self.n_beams
-        x, n, fmt = _array(x, self.n_antennas)
-        cap = n + self.block
-        out = np.zeros((P, cap), np.complex64)
-        got = C.c_size_t(0)
-        if not want_blocks:
-            check(lib().gm_beamformer_process(self._h, _p(x), fmt, n, _p(out), cap, C.byref(got), None, None, 0), "gm_beamformer_process")
-            return out[:, :got.value].copy()
-        nb = cap // self.block
-        R, w = np.zeros((nb, M, M), np.complex64), np.zeros((nb, P, M), np.complex64)
-        check(lib().gm_beamformer_process(self._h, _p(x), fmt, n, _p(out), cap, C.byref(got), _p(R), _p(w), nb), "gm_beamformer_process")
-        nb = got.value // self.block
-        return out[:, :got.value].copy(), R[:nb].copy(), w[:nb].copy()
+        self.n_weights = self._M = self.n_antennas * self.taps
+        self.n_beams = self._P = keep.shape[0]
+        self._open(c)
 
     def process_dev(self, d_in, fmt, n_in, d_out, out_stride, stream=None):
         """device pointers, n_in time samples; beam p's outputs at d_out + p * out_stride complex64 words; asynchronous on `stream`
         (None: the handle's own); returns the outputs written per beam"""
-        got = C.c_size_t(0)
-        check(lib().gm_beamformer_process_dev(self._h, d_in, fmt, n_in, d_out, out_stride, C.byref(got), stream), "gm_beamformer_process_dev")
-        return got.value
+        return super().process_dev(d_in, fmt, n_in, d_out, out_stride, stream)
 
     def set_steering(self, beam, s):
         """beam `beam`'s new row of M = taps * n_antennas words [taps][n_antennas], for every block a later call finishes; waits for
@@ -93,32 +62,16 @@ class Beamformer:
         s = np.ascontiguousarray(np.asarray(s).astype(np.complex64)).reshape(-1)
         if s.shape != (self.n_weights,):
             raise ValueError("s: taps * n_antennas complex words")
-        check(lib().gm_beamformer_set_steering(self._h, int(beam), _p(s)), "gm_beamformer_set_steering")
+        self._call("set_steering", int(beam), _p(s))
 
     def set_weights(self, w=None):
         """[P][M] fixed complex weights for every later block (static mode, synchronous); None: back to the adaptive rule"""
-        if w is None:
-            check(lib().gm_beamformer_set_weights(self._h, None), "gm_beamformer_set_weights")
-            return
-        w = np.ascontiguousarray(np.asarray(w).astype(np.complex64)).reshape(-1)
-        if w.shape != (self.n_beams * self.n_weights,):
-            raise ValueError("w: beams * taps * n_antennas complex words")
-        check(lib().gm_beamformer_set_weights(self._h, _p(w)), "gm_beamformer_set_weights")
-
-    def capture(self, d_R=None, d_w=None, cap_blocks=0):
-        """device buffers [cap_blocks][M][M] and [cap_blocks][P][M] complex64 that every later process_dev fills from word 0"""
-        check(lib().gm_beamformer_capture(self._h, d_R, d_w, int(cap_blocks)), "gm_beamformer_capture")
-
-    def reset(self, input_index=0):
-        check(lib().gm_beamformer_reset(self._h, int(input_index)), "gm_beamformer_reset")
+        self._set_flat_weights(w, self.n_beams * self.n_weights, "w: beams * taps * n_antennas complex words")
 
     def stats(self):
         """time samples taken, outputs delivered per beam, blocks finished and, per beam, the blocks that took the fallback weights
         since the creation or the last reset (synchronises)"""
         i, o, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         f = (C.c_uint64 * self.n_beams)()
-        check(lib().gm_beamformer_stats(self._h, C.byref(i), C.byref(o), C.byref(b), f), "gm_beamformer_stats")
+        self._call("stats", C.byref(i), C.byref(o), C.byref(b), f)
         return dict(inputs=i.value, outputs=o.value, blocks=b.value, fallbacks=list(f))
-
-    def synchronize(self):
-        check(lib().gm_beamformer_synchronize(self._h), "gm_beamformer_synchronize")

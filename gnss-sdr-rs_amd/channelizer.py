@@ -8,7 +8,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import ChannelizerCfg, check, lib
-from .resample import _p, _samples
+from ._stage import Stage, _p
+from .resample import _samples
 
 _KEYS = ("taps_per_branch", "cutoff", "kaiser_beta", "blank_threshold")
 
@@ -58,7 +59,9 @@ def glonass_code():
     return chips
 
 
-class Channelizer:
+class Channelizer(Stage):
+    _NAME = "channelizer"
+
     def __init__(self, n_channels, decim, channels=None, device=None, **cfg):
         unknown = set(cfg) - set(_KEYS)
         if unknown:
@@ -69,20 +72,7 @@ class Channelizer:
         self.n_channels, self.decim = int(n_channels), int(decim)
         self.channels = [int(k) for k in channels] if channels is not None else list(range(self.n_channels))
         self.taps_per_branch, self.n_taps = p["taps_per_branch"], p["n_taps"]
-        h = C.c_void_p()
-        check(lib().gm_channelizer_create(C.byref(c), C.byref(h)), "gm_channelizer_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gm_channelizer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):      # (at interpreter shutdown the module globals close() uses may be gone already)
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(c)
 
     def process(self, samples):
         """samples: complex64 array, or int8 array of interleaved I/Q -> complex64 [C, n]: this call's outputs, a row per listed
@@ -91,31 +81,22 @@ class Channelizer:
         cap = n // self.decim + 2                                      # a call never delivers more than n / D + 1
         out = np.zeros((len(self.channels), cap), np.complex64)
         got = C.c_size_t(0)
-        check(lib().gm_channelizer_process(self._h, _p(s), fmt, n, _p(out), cap, C.byref(got)), "gm_channelizer_process")
+        self._call("process", _p(s), fmt, n, _p(out), cap, C.byref(got))
         return out[:, :got.value].copy()
 
     def process_dev(self, d_in, fmt, n_in, d_out, out_stride, out_cap, stream=None):
         """device pointers; d_out is [C][out_stride] complex64; asynchronous on `stream` (None: the handle's own); returns the number
         of outputs written to every plane"""
         got = C.c_size_t(0)
-        check(lib().gm_channelizer_process_dev(self._h, d_in, fmt, n_in, d_out, out_stride, out_cap, C.byref(got), stream),
-              "gm_channelizer_process_dev")
+        self._call("process_dev", d_in, fmt, n_in, d_out, out_stride, out_cap, C.byref(got), stream)
         return got.value
-
-    def reset(self, input_index=0):
-        check(lib().gm_channelizer_reset(self._h, int(input_index)), "gm_channelizer_reset")
 
     def taps(self):
         """the L float32 words the device uses"""
         taps = np.zeros(self.n_taps, np.float32)
-        check(lib().gm_channelizer_taps(self._h, _p(taps)), "gm_channelizer_taps")
+        self._call("taps", _p(taps))
         return taps
 
     def stats(self):
         """inputs taken, outputs delivered per channel, inputs blanked since the creation or the last reset (synchronises)"""
-        i, o, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        check(lib().gm_channelizer_stats(self._h, C.byref(i), C.byref(o), C.byref(b)), "gm_channelizer_stats")
-        return dict(inputs=i.value, outputs=o.value, blanked=b.value)
-
-    def synchronize(self):
-        check(lib().gm_channelizer_synchronize(self._h), "gm_channelizer_synchronize")
+        return self._counters("inputs", "outputs", "blanked")

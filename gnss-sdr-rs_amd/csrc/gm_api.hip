@@ -4140,8 +4140,18 @@ int gm_frontend_write_ring(gm_frontend* f, gm_ring* r, const void* samples, size
 // A stage turns a stream of inputs into a stream of outputs call by call, whatever the cuts: a history of the last inputs travels between
 // calls in two device buffers used alternately, and the counters say where in the stream the next call starts.  Each handle inherits
 // this state and adds its plan, its tables, `*_count` (outputs of the next n inputs) and `*_launch` (that kernel's argument block).
+// The antenna-array stages (gm_nuller, gm_stap, gm_beamformer) inherit it through ArrayStage, further down: blocks of B time samples of
+// A elements each, per block a matrix R and weights w that a call can hand back.  ArrayStage owns what the three share (the count, the
+// format verdict, the block / loading / steering-row rules, the capture, the two process bodies, the common argument fields), and
+// each handle adds its plan, its `*_launch` and whatever only it keeps.
 namespace {
 constexpr uint64_t RS_INDEX_MAX = 1ull << 62;
+// every gm_*_plan entry: a stream of inputs_so_far, then n_in more, ends at or below 2^62
+int stage_check_span(uint64_t inputs_so_far, uint64_t n_in) {
+    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
+        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    return GM_OK;
+}
 
 struct StreamStage {
     int device = -1;
@@ -4395,8 +4405,7 @@ int gm_resampler_plan(const gm_resampler_cfg* cfg, uint64_t inputs_so_far, uint6
                       uint32_t* taps, uint32_t* n_phases, uint64_t* n_out) {
     ResamplerPlan p;
     if (int rc = resampler_rules(cfg, p)) return rc;
-    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (int rc = stage_check_span(inputs_so_far, n_in)) return rc;
     if (up_reduced) *up_reduced = p.up;
     if (down_reduced) *down_reduced = p.down;
     if (taps) *taps = p.T;
@@ -4582,8 +4591,7 @@ int gm_excisor_plan(const gm_excisor_cfg* cfg, uint64_t inputs_so_far, uint64_t 
                     float* threshold_factor, uint64_t* n_out) {
     ExcisorPlan p;
     if (int rc = excisor_rules(cfg, p)) return rc;
-    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (int rc = stage_check_span(inputs_so_far, n_in)) return rc;
     if (block) *block = p.B;
     if (guard_bins) *guard_bins = p.guard;
     if (threshold_factor) *threshold_factor = p.factor;
@@ -4946,8 +4954,7 @@ int gm_ddc_plan(const gm_ddc_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, ui
                 uint32_t* taps, uint32_t* n_phases, uint64_t* phase_inc, uint64_t* n_out) {
     DdcPlan p;
     if (int rc = ddc_rules(cfg, p)) return rc;
-    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (int rc = stage_check_span(inputs_so_far, n_in)) return rc;
     if (up_reduced) *up_reduced = p.rs.up;
     if (down_reduced) *down_reduced = p.rs.down;
     if (taps) *taps = p.rs.T;
@@ -5174,8 +5181,7 @@ int gm_channelizer_plan(const gm_channelizer_cfg* cfg, uint64_t inputs_so_far, u
                         uint32_t* taps_per_branch, uint32_t* n_taps, uint64_t* n_out) {
     ChannelizerPlan p;
     if (int rc = channelizer_rules(cfg, p)) return rc;
-    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
+    if (int rc = stage_check_span(inputs_so_far, n_in)) return rc;
     if (n_out_channels) *n_out_channels = p.C;
     if (taps_per_branch) *taps_per_branch = p.P;
     if (n_taps) *n_taps = p.L;
@@ -5277,6 +5283,169 @@ int gm_glonass_code(int8_t* out) {
 
 }  // extern "C"
 
+// ====================================================================== antenna-array stages: what gm_nuller, gm_stap and gm_beamformer share
+// A stream of time samples of A interleaved elements, cut into blocks of B: total_out(T) = B * (T div B).  Per finished block the kernels
+// form a matrix R (r_words) and weights w (w_words: a row per output plane), which a call can hand back: process_dev to the device
+// buffers the caller armed with *_capture, process to host arrays through the handle's own d_blk.  A handle derives from ArrayStage, sets
+// these numbers in its create (array_shape) and supplies `*_launch(handle, stream, d_in, fmt, n_in, out, out_stride, n_out, cap_R, cap_w)`:
+// its kernels' argument block, the shared fields filled by array_fill_args.
+namespace {
+struct ArrayStage : StreamStage {
+    std::string fmt_err, plan_entry;        // the format verdict; the entry that gives the output count
+    uint32_t A = 0, B = 0;                  // elements per time sample; time samples per block
+    size_t r_words = 0, w_words = 0;        // words of R and of w per block
+    uint32_t planes = 1;                    // output planes (the rows of w)
+    float loading = 0.0f;
+    bool fixed = false;                     // static mode
+    cf* cap_R = nullptr; cf* cap_w = nullptr; size_t cap_blocks = 0;     // the caller's capture (device)
+    cf* d_blk = nullptr; size_t blk_cap = 0;                             // blocks; the host-buffer entry's own capture: [blk_cap][r_words] then [blk_cap][w_words]
+};
+
+void array_shape(ArrayStage* n, const char* name, uint32_t A, uint32_t B, float loading, size_t r_words, size_t w_words, uint32_t planes = 1) {
+    n->fmt_err = std::string(name) + " input is interleaved c32 or int8 IQ";
+    n->plan_entry = std::string("gm_") + name + "_plan";
+    n->A = A; n->B = B; n->loading = loading; n->r_words = r_words; n->w_words = w_words; n->planes = planes;
+}
+void array_destroy(ArrayStage* n) {
+    stage_destroy(n);
+    hipFree(n->d_blk);
+}
+
+// ---- the argument rules
+bool array_finite(const gm_c32* v, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i].re) || !std::isfinite(v[i].im)) return false;
+    return true;
+}
+// the block length (0: 1024) and the diagonal loading (0: 1e-4)
+int array_block_rules(uint32_t block, float loading, uint32_t* B, float* resolved) {
+    *B = block ? block : 1024;
+    if (*B < 256 || *B > 16384 || (*B & (*B - 1))) return set_err(GM_ERR_INVALID_ARG, "block: a power of two in 256 .. 16384, 0 for the default");
+    if (!std::isfinite(loading)) return set_err(GM_ERR_INVALID_ARG, "loading must be finite");
+    if (loading != 0.0f && !(loading >= 1e-6f && loading <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "loading: [1e-6, 1], 0 for the default");
+    *resolved = loading == 0.0f ? 1e-4f : loading;
+    return GM_OK;
+}
+// one steering row: n finite words, not all zero (`zero_err`: the entry's words for that)
+int array_row_rules(const gm_c32* s, uint32_t n, const char* zero_err) {
+    if (!array_finite(s, n)) return set_err(GM_ERR_INVALID_ARG, "steering must be finite");
+    bool any = false;
+    for (uint32_t i = 0; i < n; ++i) any = any || s[i].re != 0.0f || s[i].im != 0.0f;
+    if (!any) return set_err(GM_ERR_INVALID_ARG, zero_err);
+    return GM_OK;
+}
+// gm_nuller's and gm_stap's steering vector of n words: e_0 where the cfg has none
+int array_steering_rules(const gm_c32* s, uint32_t n, cf* dst, uint32_t dst_words) {
+    for (uint32_t i = 0; i < dst_words; ++i) dst[i] = gm::cf_make(i == 0 ? 1.0f : 0.0f, 0.0f);
+    if (!s) return GM_OK;
+    if (int rc = array_row_rules(s, n, "steering is all zero")) return rc;
+    for (uint32_t i = 0; i < n; ++i) dst[i] = gm::cf_make(s[i].re, s[i].im);
+    return GM_OK;
+}
+
+// ---- the counts
+// total_out(T) = B * (T div B)
+uint64_t array_total_out(uint32_t B, uint64_t T) { return T / B * B; }
+uint64_t array_count(const ArrayStage* n, uint64_t n_in) {
+    const uint64_t T = n->base + n->inputs;
+    return array_total_out(n->B, T + n_in) - array_total_out(n->B, T);
+}
+// the gm_*_plan entries behind their rules
+int array_plan(uint32_t B, float resolved, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, float* loading, uint64_t* n_out) {
+    if (int rc = stage_check_span(inputs_so_far, n_in)) return rc;
+    if (block) *block = B;
+    if (loading) *loading = resolved;
+    if (n_out) *n_out = array_total_out(B, inputs_so_far + n_in) - array_total_out(B, inputs_so_far);
+    return GM_OK;
+}
+int array_stats(ArrayStage* n, uint64_t* inputs, uint64_t* outputs, uint64_t* blocks, uint64_t* blanked) {
+    if (int rc = stage_stats(n, inputs, outputs, blanked)) return rc;
+    if (blocks) *blocks = n->outputs / n->B;
+    return GM_OK;
+}
+
+// ---- a call
+// the fields that NullerArgs, StapArgs and BeamArgs have in common
+template <class Args>
+void array_fill_args(Args& a, const ArrayStage* n, const void* d_in, uint64_t n_in, cf* out, uint64_t n_out, cf* cap_R, cf* cap_w) {
+    const uint64_t T = n->base + n->inputs;
+    a.in = d_in; a.n_in = n_in;
+    a.hist_in = static_cast<const cf*>(n->d_hist[n->cur]); a.hist_out = static_cast<cf*>(n->d_hist[n->cur ^ 1]);
+    a.A = n->A; a.B = n->B;
+    a.pending = uint32_t(T % n->B); a.pending_out = uint32_t((T + n_in) % n->B);
+    a.n_blocks = n_out / n->B;
+    a.out = out; a.cap_R = cap_R; a.cap_w = cap_w;
+    a.loading = n->loading; a.adaptive = n->fixed ? 0 : 1;
+}
+int array_check_call(const ArrayStage* n, int fmt, const void* in, size_t n_in, const void* out, size_t out_cap, uint64_t* cnt) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    const char* fmt_err = fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? n->fmt_err.c_str() : nullptr;
+    return stage_check_call(n, array_count, fmt_err, in, n_in, out, out_cap, n->plan_entry.c_str(), cnt);
+}
+size_t array_in_bytes(const ArrayStage* n, int fmt, size_t n_in) { return n_in * n->A * (fmt == GM_FMT_C32 ? 8 : 2); }
+
+int array_capture(ArrayStage* n, void* d_R, void* d_w, size_t cap_blocks) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if ((d_R == nullptr) != (d_w == nullptr)) return set_err(GM_ERR_INVALID_ARG, "d_R and d_w: both or neither");
+    if ((d_R == nullptr) != (cap_blocks == 0)) return set_err(GM_ERR_INVALID_ARG, "cap_blocks: 0 exactly where the pointers are null");
+    n->cap_R = static_cast<cf*>(d_R); n->cap_w = static_cast<cf*>(d_w); n->cap_blocks = cap_blocks;
+    return GM_OK;
+}
+// the fixed weights of gm_nuller and gm_stap live in the handle (w[w_words]) and travel in the argument block
+template <class H>
+int array_set_host_weights(H* n, const gm_c32* w) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!w) { n->fixed = false; return GM_OK; }
+    if (!array_finite(w, n->w_words)) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
+    for (size_t i = 0; i < n->w_words; ++i) n->w[i] = gm::cf_make(w[i].re, w[i].im);
+    n->fixed = true;
+    return GM_OK;
+}
+
+// The device entries.  Plane p's outputs start at d_out + p * out_cap: a plane's room is its stride, a count above it is out of range,
+// and the planes together, (planes - 1) * out_cap + count words, may not lie over the inputs.
+template <class H, class Launch>
+int array_process_dev(H* n, Launch launch, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out, void* stream) {
+    uint64_t cnt = 0;
+    if (int rc = array_check_call(n, fmt, d_in, n_in, d_out, out_cap, &cnt)) return rc;
+    if (n->cap_w && cnt / n->B > n->cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "the capture is smaller than the call's blocks");
+    if (cnt)
+        if (int rc = stage_check_overlap(d_in, array_in_bytes(n, fmt, n_in), d_out, uint64_t(n->planes - 1) * out_cap + cnt)) return rc;
+    if (n_out) *n_out = size_t(cnt);
+    if (!n_in) return GM_OK;
+    if (int rc = ensure_device(n->device)) return rc;
+    return launch(n, stream ? static_cast<hipStream_t>(stream) : n->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), out_cap, cnt, n->cap_R, n->cap_w);
+}
+// The host-buffer entries: R and w (either may be null) take the words of the call's blocks, `cap_blocks` the room in each.  R is not
+// written in static mode.  Plane p is delivered at out + p * out_cap.
+template <class H, class Launch>
+int array_process(H* n, Launch launch, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out, gm_c32* R, gm_c32* w,
+                  size_t cap_blocks) {
+    uint64_t cnt = 0;
+    if (int rc = array_check_call(n, fmt, in, n_in, out, out_cap, &cnt)) return rc;
+    const uint64_t blocks = cnt / n->B;
+    const bool want = (R || w) && blocks;
+    if ((R || w) && blocks > cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "cap_blocks below the call's blocks");
+    if (want && n->blk_cap < blocks) {
+        if (int rc = ensure_device(n->device)) return rc;
+        if (int rc = stage_sync(n)) return rc;
+        hipFree(n->d_blk); n->d_blk = nullptr; n->blk_cap = 0;
+        HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_blk), size_t(blocks) * (n->r_words + n->w_words) * sizeof(cf)));
+        n->blk_cap = size_t(blocks);
+    }
+    cf* d_R = want ? n->d_blk : nullptr;
+    cf* d_w = want ? n->d_blk + n->blk_cap * n->r_words : nullptr;
+    if (int rc = stage_process(n, in, array_in_bytes(n, fmt, n_in), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
+            return launch(n, st, d_in, fmt, n_in, d_out, cnt, cnt, d_R, d_w);
+        }, n->planes, out_cap)) return rc;
+    if (want) {      // stage_process has waited for the kernels
+        if (R && !n->fixed) HIPC(hipMemcpy(R, d_R, size_t(blocks) * n->r_words * sizeof(cf), hipMemcpyDeviceToHost));
+        if (w) HIPC(hipMemcpy(w, d_w, size_t(blocks) * n->w_words * sizeof(cf), hipMemcpyDeviceToHost));
+    }
+    return GM_OK;
+}
+}  // namespace
+
 // ====================================================================== adaptive spatial nulling of an antenna array (gm_nuller)
 // gnss_mi355x.h states the definition; tests/nuller_model.py restates it in float64.
 namespace {
@@ -5286,69 +5455,30 @@ struct NullerPlan {
     cf s[gm::NL_A_MAX] = {};
 };
 
-bool nuller_finite(const gm_c32* v, uint32_t n) {
-    for (uint32_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i].re) || !std::isfinite(v[i].im)) return false;
-    return true;
-}
-
 int nuller_rules(const gm_nuller_cfg* c, NullerPlan& p) {
     if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
     if (c->reserved) return set_err(GM_ERR_INVALID_ARG, "gm_nuller_cfg.reserved must be 0");
     if (c->n_antennas < 2 || c->n_antennas > uint32_t(gm::NL_A_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_antennas: 2 .. 8");
-    const uint32_t B = c->block ? c->block : 1024;
-    if (B < 256 || B > 16384 || (B & (B - 1))) return set_err(GM_ERR_INVALID_ARG, "block: a power of two in 256 .. 16384, 0 for the default");
-    if (!std::isfinite(c->loading)) return set_err(GM_ERR_INVALID_ARG, "loading must be finite");
-    if (c->loading != 0.0f && !(c->loading >= 1e-6f && c->loading <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "loading: [1e-6, 1], 0 for the default");
-    p.A = c->n_antennas; p.B = B; p.loading = c->loading == 0.0f ? 1e-4f : c->loading;
-    for (uint32_t i = 0; i < uint32_t(gm::NL_A_MAX); ++i) p.s[i] = gm::cf_make(i == 0 ? 1.0f : 0.0f, 0.0f);
-    if (c->steering) {
-        if (!nuller_finite(c->steering, p.A)) return set_err(GM_ERR_INVALID_ARG, "steering must be finite");
-        bool any = false;
-        for (uint32_t i = 0; i < p.A; ++i) {
-            p.s[i] = gm::cf_make(c->steering[i].re, c->steering[i].im);
-            any = any || c->steering[i].re != 0.0f || c->steering[i].im != 0.0f;
-        }
-        if (!any) return set_err(GM_ERR_INVALID_ARG, "steering is all zero");
-    }
-    return GM_OK;
+    if (int rc = array_block_rules(c->block, c->loading, &p.B, &p.loading)) return rc;
+    p.A = c->n_antennas;
+    return array_steering_rules(c->steering, p.A, p.s, uint32_t(gm::NL_A_MAX));
 }
-
-// total_out(T) = B * (T div B)
-uint64_t nuller_total_out(const NullerPlan& p, uint64_t T) { return T / p.B * p.B; }
 }  // namespace
 
-struct gm_nuller : StreamStage {            // history: the converted time samples of the unfinished block (cf [B][A])
+struct gm_nuller : ArrayStage {             // history: the converted time samples of the unfinished block (cf [B][A]); R is [A][A], w is [A]
     NullerPlan plan;
-    bool fixed = false;                     // static mode
     cf w[gm::NL_A_MAX] = {};
-    cf* cap_R = nullptr; cf* cap_w = nullptr; size_t cap_blocks = 0;     // the caller's capture (device)
-    cf* d_blk = nullptr; size_t blk_cap = 0;                             // blocks; the host-buffer entry's own capture: [blk_cap][A][A] then [blk_cap][A]
 };
 
 // one call's kernels on `st`; the caller has checked every argument; n_in > 0
-static int nuller_launch(gm_nuller* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t n_out, cf* cap_R, cf* cap_w) {
-    const NullerPlan& p = n->plan;
-    const uint64_t T = n->base + n->inputs;
+static int nuller_launch(gm_nuller* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t, uint64_t n_out, cf* cap_R,
+                         cf* cap_w) {
     gm::NullerArgs a{};
-    a.in = d_in; a.n_in = n_in;
-    a.hist_in = static_cast<const cf*>(n->d_hist[n->cur]); a.hist_out = static_cast<cf*>(n->d_hist[n->cur ^ 1]);
-    a.A = p.A; a.B = p.B;
-    a.pending = uint32_t(T % p.B); a.pending_out = uint32_t((T + n_in) % p.B);
-    a.n_blocks = n_out / p.B;
-    a.out = out; a.cap_R = cap_R; a.cap_w = cap_w;
-    a.loading = p.loading; a.adaptive = n->fixed ? 0 : 1;
-    a.in_wide = reinterpret_cast<uintptr_t>(d_in) % gm::nuller_in_align(p.A, fmt) == 0 ? 1 : 0;
-    for (int i = 0; i < gm::NL_A_MAX; ++i) { a.s[i] = p.s[i]; a.w[i] = n->w[i]; }
+    array_fill_args(a, n, d_in, n_in, out, n_out, cap_R, cap_w);
+    a.in_wide = reinterpret_cast<uintptr_t>(d_in) % gm::nuller_in_align(n->A, fmt) == 0 ? 1 : 0;
+    for (int i = 0; i < gm::NL_A_MAX; ++i) { a.s[i] = n->plan.s[i]; a.w[i] = n->w[i]; }
     gm::launch_nuller(st, a, fmt);
     return stage_launched(n, st, n_in, n_out);
-}
-static uint64_t nuller_count(const gm_nuller* n, uint64_t n_in) {
-    const uint64_t T = n->base + n->inputs;
-    return nuller_total_out(n->plan, T + n_in) - nuller_total_out(n->plan, T);
-}
-static const char* nuller_fmt_err(int fmt) {
-    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "nuller input is interleaved c32 or int8 IQ" : nullptr;
 }
 
 extern "C" {
@@ -5356,12 +5486,7 @@ extern "C" {
 int gm_nuller_plan(const gm_nuller_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, float* loading, uint64_t* n_out) {
     NullerPlan p;
     if (int rc = nuller_rules(cfg, p)) return rc;
-    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
-    if (block) *block = p.B;
-    if (loading) *loading = p.loading;
-    if (n_out) *n_out = nuller_total_out(p, inputs_so_far + n_in) - nuller_total_out(p, inputs_so_far);
-    return GM_OK;
+    return array_plan(p.B, p.loading, inputs_so_far, n_in, block, loading, n_out);
 }
 
 int gm_nuller_create(const gm_nuller_cfg* cfg, gm_nuller** out) {
@@ -5372,6 +5497,7 @@ int gm_nuller_create(const gm_nuller_cfg* cfg, gm_nuller** out) {
     if (int rc = ensure_device(g_device)) return rc;
     gm_nuller* n = new gm_nuller;
     n->device = g_device; n->plan = p;
+    array_shape(n, "nuller", p.A, p.B, p.loading, size_t(p.A) * p.A, p.A);
     hipError_t e = stage_create(n, size_t(p.B) * p.A * sizeof(cf));
     if (e != hipSuccess) { gm_nuller_destroy(n); return hip_fail(e, "gm_nuller_create"); }
     *out = n;
@@ -5380,8 +5506,7 @@ int gm_nuller_create(const gm_nuller_cfg* cfg, gm_nuller** out) {
 
 int gm_nuller_destroy(gm_nuller* n) {
     if (!n) return GM_OK;
-    stage_destroy(n);
-    hipFree(n->d_blk);
+    array_destroy(n);
     delete n;
     return GM_OK;
 }
@@ -5391,66 +5516,22 @@ int gm_nuller_reset(gm_nuller* n, uint64_t input_index) {
 }
 
 int gm_nuller_stats(gm_nuller* n, uint64_t* inputs, uint64_t* outputs, uint64_t* blocks) {
-    if (int rc = stage_stats(n, inputs, outputs, nullptr)) return rc;
-    if (blocks) *blocks = n->outputs / n->plan.B;
-    return GM_OK;
+    return array_stats(n, inputs, outputs, blocks, nullptr);
 }
 
 int gm_nuller_synchronize(gm_nuller* n) { return stage_synchronize(n); }
 
-int gm_nuller_set_weights(gm_nuller* n, const gm_c32* w) {
-    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (!w) { n->fixed = false; return GM_OK; }
-    if (!nuller_finite(w, n->plan.A)) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
-    for (uint32_t i = 0; i < n->plan.A; ++i) n->w[i] = gm::cf_make(w[i].re, w[i].im);
-    n->fixed = true;
-    return GM_OK;
-}
+int gm_nuller_set_weights(gm_nuller* n, const gm_c32* w) { return array_set_host_weights(n, w); }
 
-int gm_nuller_capture(gm_nuller* n, void* d_R, void* d_w, size_t cap_blocks) {
-    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if ((d_R == nullptr) != (d_w == nullptr)) return set_err(GM_ERR_INVALID_ARG, "d_R and d_w: both or neither");
-    if ((d_R == nullptr) != (cap_blocks == 0)) return set_err(GM_ERR_INVALID_ARG, "cap_blocks: 0 exactly where the pointers are null");
-    n->cap_R = static_cast<cf*>(d_R); n->cap_w = static_cast<cf*>(d_w); n->cap_blocks = cap_blocks;
-    return GM_OK;
-}
+int gm_nuller_capture(gm_nuller* n, void* d_R, void* d_w, size_t cap_blocks) { return array_capture(n, d_R, d_w, cap_blocks); }
 
 int gm_nuller_process_dev(gm_nuller* n, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out, void* stream) {
-    uint64_t cnt = 0;
-    if (int rc = stage_check_call(n, nuller_count, nuller_fmt_err(fmt), d_in, n_in, d_out, out_cap, "gm_nuller_plan", &cnt)) return rc;
-    if (n->cap_w && cnt / n->plan.B > n->cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "the capture is smaller than the call's blocks");
-    if (int rc = stage_check_overlap(d_in, n_in * n->plan.A * (fmt == GM_FMT_C32 ? 8 : 2), d_out, cnt)) return rc;
-    if (n_out) *n_out = size_t(cnt);
-    if (!n_in) return GM_OK;
-    if (int rc = ensure_device(n->device)) return rc;
-    return nuller_launch(n, stream ? static_cast<hipStream_t>(stream) : n->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), cnt, n->cap_R, n->cap_w);
+    return array_process_dev(n, nuller_launch, d_in, fmt, n_in, d_out, out_cap, n_out, stream);
 }
 
 int gm_nuller_process(gm_nuller* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out, gm_c32* R, gm_c32* w,
                       size_t cap_blocks) {
-    uint64_t cnt = 0;
-    if (int rc = stage_check_call(n, nuller_count, nuller_fmt_err(fmt), in, n_in, out, out_cap, "gm_nuller_plan", &cnt)) return rc;
-    const uint64_t blocks = cnt / n->plan.B;
-    const bool want = (R || w) && blocks;
-    if ((R || w) && blocks > cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "cap_blocks below the call's blocks");
-    const size_t AA = size_t(n->plan.A) * n->plan.A, A = n->plan.A;
-    if (want && n->blk_cap < blocks) {
-        if (int rc = ensure_device(n->device)) return rc;
-        if (int rc = stage_sync(n)) return rc;
-        hipFree(n->d_blk); n->d_blk = nullptr; n->blk_cap = 0;
-        HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_blk), size_t(blocks) * (AA + A) * sizeof(cf)));
-        n->blk_cap = size_t(blocks);
-    }
-    cf* d_R = want ? n->d_blk : nullptr;
-    cf* d_w = want ? n->d_blk + n->blk_cap * AA : nullptr;
-    if (int rc = stage_process(n, in, n_in * A * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
-            return nuller_launch(n, st, d_in, fmt, n_in, d_out, cnt, d_R, d_w);
-        })) return rc;
-    if (want) {      // stage_process has waited for the kernels
-        if (R && !n->fixed) HIPC(hipMemcpy(R, d_R, size_t(blocks) * AA * sizeof(cf), hipMemcpyDeviceToHost));
-        if (w) HIPC(hipMemcpy(w, d_w, size_t(blocks) * A * sizeof(cf), hipMemcpyDeviceToHost));
-    }
-    return GM_OK;
+    return array_process(n, nuller_launch, in, fmt, n_in, out, out_cap, n_out, R, w, cap_blocks);
 }
 
 }  // extern "C"
@@ -5470,59 +5551,29 @@ int stap_rules(const gm_stap_cfg* c, StapPlan& p) {
     if (c->n_antennas < 2 || c->n_antennas > uint32_t(gm::NL_A_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_antennas: 2 .. 8");
     if (c->taps < 1 || c->taps > uint32_t(gm::ST_L_MAX)) return set_err(GM_ERR_INVALID_ARG, "taps: 1 .. 8");
     if (c->n_antennas * c->taps > uint32_t(gm::ST_M_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_antennas * taps: at most 32");
-    const uint32_t B = c->block ? c->block : 1024;
-    if (B < 256 || B > 16384 || (B & (B - 1))) return set_err(GM_ERR_INVALID_ARG, "block: a power of two in 256 .. 16384, 0 for the default");
-    if (!std::isfinite(c->loading)) return set_err(GM_ERR_INVALID_ARG, "loading must be finite");
-    if (c->loading != 0.0f && !(c->loading >= 1e-6f && c->loading <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "loading: [1e-6, 1], 0 for the default");
-    p.A = c->n_antennas; p.L = c->taps; p.M = p.A * p.L; p.B = B; p.loading = c->loading == 0.0f ? 1e-4f : c->loading;
-    for (uint32_t i = 0; i < uint32_t(gm::ST_M_MAX); ++i) p.s[i] = gm::cf_make(i == 0 ? 1.0f : 0.0f, 0.0f);
-    if (c->steering) {
-        if (!nuller_finite(c->steering, p.M)) return set_err(GM_ERR_INVALID_ARG, "steering must be finite");
-        bool any = false;
-        for (uint32_t i = 0; i < p.M; ++i) {
-            p.s[i] = gm::cf_make(c->steering[i].re, c->steering[i].im);
-            any = any || c->steering[i].re != 0.0f || c->steering[i].im != 0.0f;
-        }
-        if (!any) return set_err(GM_ERR_INVALID_ARG, "steering is all zero");
-    }
-    return GM_OK;
+    if (int rc = array_block_rules(c->block, c->loading, &p.B, &p.loading)) return rc;
+    p.A = c->n_antennas; p.L = c->taps; p.M = p.A * p.L;
+    return array_steering_rules(c->steering, p.M, p.s, uint32_t(gm::ST_M_MAX));
 }
-
-// total_out(T) = B * (T div B)
-uint64_t stap_total_out(const StapPlan& p, uint64_t T) { return T / p.B * p.B; }
+// the history both tap stages keep: the L - 1 converted time samples in front of the unfinished block, then that block's (cf [L - 1 + B][A])
+size_t stap_hist_bytes(const StapPlan& p) { return (size_t(p.B) + p.L - 1) * p.A * sizeof(cf); }
 }  // namespace
 
-struct gm_stap : StreamStage {              // history: the L - 1 converted time samples in front of the unfinished block, then that
-    StapPlan plan;                          // block's (cf [L - 1 + B][A]); d_blanked counts the fallback blocks
-    bool fixed = false;                     // static mode
+struct gm_stap : ArrayStage {               // history: stap_hist_bytes; d_blanked counts the fallback blocks; R is [M][M], w is [M]
+    StapPlan plan;
     cf w[gm::ST_M_MAX] = {};
-    cf* cap_R = nullptr; cf* cap_w = nullptr; size_t cap_blocks = 0;     // the caller's capture (device)
-    cf* d_blk = nullptr; size_t blk_cap = 0;                             // blocks; the host-buffer entry's own capture: [blk_cap][M][M] then [blk_cap][M]
 };
 
 // one call's kernels on `st`; the caller has checked every argument; n_in > 0
-static int stap_launch(gm_stap* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t n_out, cf* cap_R, cf* cap_w) {
-    const StapPlan& p = n->plan;
-    const uint64_t T = n->base + n->inputs;
+static int stap_launch(gm_stap* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t, uint64_t n_out, cf* cap_R,
+                       cf* cap_w) {
     gm::StapArgs a{};
-    a.in = d_in; a.n_in = n_in; a.fmt = fmt;
-    a.hist_in = static_cast<const cf*>(n->d_hist[n->cur]); a.hist_out = static_cast<cf*>(n->d_hist[n->cur ^ 1]);
-    a.A = p.A; a.L = p.L; a.B = p.B;
-    a.pending = uint32_t(T % p.B); a.pending_out = uint32_t((T + n_in) % p.B);
-    a.n_blocks = n_out / p.B;
-    a.out = out; a.cap_R = cap_R; a.cap_w = cap_w;
-    a.loading = p.loading; a.adaptive = n->fixed ? 0 : 1;
+    array_fill_args(a, n, d_in, n_in, out, n_out, cap_R, cap_w);
+    a.fmt = fmt; a.L = n->plan.L;
     a.fallbacks = n->d_blanked;
-    for (int i = 0; i < gm::ST_M_MAX; ++i) { a.s[i] = p.s[i]; a.w[i] = n->w[i]; }
+    for (int i = 0; i < gm::ST_M_MAX; ++i) { a.s[i] = n->plan.s[i]; a.w[i] = n->w[i]; }
     gm::launch_stap(st, a);
     return stage_launched(n, st, n_in, n_out);
-}
-static uint64_t stap_count(const gm_stap* n, uint64_t n_in) {
-    const uint64_t T = n->base + n->inputs;
-    return stap_total_out(n->plan, T + n_in) - stap_total_out(n->plan, T);
-}
-static const char* stap_fmt_err(int fmt) {
-    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "stap input is interleaved c32 or int8 IQ" : nullptr;
 }
 
 extern "C" {
@@ -5530,12 +5581,7 @@ extern "C" {
 int gm_stap_plan(const gm_stap_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, float* loading, uint64_t* n_out) {
     StapPlan p;
     if (int rc = stap_rules(cfg, p)) return rc;
-    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
-    if (block) *block = p.B;
-    if (loading) *loading = p.loading;
-    if (n_out) *n_out = stap_total_out(p, inputs_so_far + n_in) - stap_total_out(p, inputs_so_far);
-    return GM_OK;
+    return array_plan(p.B, p.loading, inputs_so_far, n_in, block, loading, n_out);
 }
 
 int gm_stap_create(const gm_stap_cfg* cfg, gm_stap** out) {
@@ -5546,7 +5592,8 @@ int gm_stap_create(const gm_stap_cfg* cfg, gm_stap** out) {
     if (int rc = ensure_device(g_device)) return rc;
     gm_stap* n = new gm_stap;
     n->device = g_device; n->plan = p;
-    hipError_t e = stage_create(n, (size_t(p.B) + p.L - 1) * p.A * sizeof(cf));
+    array_shape(n, "stap", p.A, p.B, p.loading, size_t(p.M) * p.M, p.M);
+    hipError_t e = stage_create(n, stap_hist_bytes(p));
     if (e != hipSuccess) { gm_stap_destroy(n); return hip_fail(e, "gm_stap_create"); }
     *out = n;
     return GM_OK;
@@ -5554,8 +5601,7 @@ int gm_stap_create(const gm_stap_cfg* cfg, gm_stap** out) {
 
 int gm_stap_destroy(gm_stap* n) {
     if (!n) return GM_OK;
-    stage_destroy(n);
-    hipFree(n->d_blk);
+    array_destroy(n);
     delete n;
     return GM_OK;
 }
@@ -5565,66 +5611,22 @@ int gm_stap_reset(gm_stap* n, uint64_t input_index) {
 }
 
 int gm_stap_stats(gm_stap* n, uint64_t* inputs, uint64_t* outputs, uint64_t* blocks, uint64_t* fallback_blocks) {
-    if (int rc = stage_stats(n, inputs, outputs, fallback_blocks)) return rc;
-    if (blocks) *blocks = n->outputs / n->plan.B;
-    return GM_OK;
+    return array_stats(n, inputs, outputs, blocks, fallback_blocks);
 }
 
 int gm_stap_synchronize(gm_stap* n) { return stage_synchronize(n); }
 
-int gm_stap_set_weights(gm_stap* n, const gm_c32* w) {
-    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if (!w) { n->fixed = false; return GM_OK; }
-    if (!nuller_finite(w, n->plan.M)) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
-    for (uint32_t i = 0; i < n->plan.M; ++i) n->w[i] = gm::cf_make(w[i].re, w[i].im);
-    n->fixed = true;
-    return GM_OK;
-}
+int gm_stap_set_weights(gm_stap* n, const gm_c32* w) { return array_set_host_weights(n, w); }
 
-int gm_stap_capture(gm_stap* n, void* d_R, void* d_w, size_t cap_blocks) {
-    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if ((d_R == nullptr) != (d_w == nullptr)) return set_err(GM_ERR_INVALID_ARG, "d_R and d_w: both or neither");
-    if ((d_R == nullptr) != (cap_blocks == 0)) return set_err(GM_ERR_INVALID_ARG, "cap_blocks: 0 exactly where the pointers are null");
-    n->cap_R = static_cast<cf*>(d_R); n->cap_w = static_cast<cf*>(d_w); n->cap_blocks = cap_blocks;
-    return GM_OK;
-}
+int gm_stap_capture(gm_stap* n, void* d_R, void* d_w, size_t cap_blocks) { return array_capture(n, d_R, d_w, cap_blocks); }
 
 int gm_stap_process_dev(gm_stap* n, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_cap, size_t* n_out, void* stream) {
-    uint64_t cnt = 0;
-    if (int rc = stage_check_call(n, stap_count, stap_fmt_err(fmt), d_in, n_in, d_out, out_cap, "gm_stap_plan", &cnt)) return rc;
-    if (n->cap_w && cnt / n->plan.B > n->cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "the capture is smaller than the call's blocks");
-    if (int rc = stage_check_overlap(d_in, n_in * n->plan.A * (fmt == GM_FMT_C32 ? 8 : 2), d_out, cnt)) return rc;
-    if (n_out) *n_out = size_t(cnt);
-    if (!n_in) return GM_OK;
-    if (int rc = ensure_device(n->device)) return rc;
-    return stap_launch(n, stream ? static_cast<hipStream_t>(stream) : n->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), cnt, n->cap_R, n->cap_w);
+    return array_process_dev(n, stap_launch, d_in, fmt, n_in, d_out, out_cap, n_out, stream);
 }
 
 int gm_stap_process(gm_stap* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_cap, size_t* n_out, gm_c32* R, gm_c32* w,
                     size_t cap_blocks) {
-    uint64_t cnt = 0;
-    if (int rc = stage_check_call(n, stap_count, stap_fmt_err(fmt), in, n_in, out, out_cap, "gm_stap_plan", &cnt)) return rc;
-    const uint64_t blocks = cnt / n->plan.B;
-    const bool want = (R || w) && blocks;
-    if ((R || w) && blocks > cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "cap_blocks below the call's blocks");
-    const size_t M = n->plan.M, MM = M * M, A = n->plan.A;
-    if (want && n->blk_cap < blocks) {
-        if (int rc = ensure_device(n->device)) return rc;
-        if (int rc = stage_sync(n)) return rc;
-        hipFree(n->d_blk); n->d_blk = nullptr; n->blk_cap = 0;
-        HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_blk), size_t(blocks) * (MM + M) * sizeof(cf)));
-        n->blk_cap = size_t(blocks);
-    }
-    cf* d_R = want ? n->d_blk : nullptr;
-    cf* d_w = want ? n->d_blk + n->blk_cap * MM : nullptr;
-    if (int rc = stage_process(n, in, n_in * A * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
-            return stap_launch(n, st, d_in, fmt, n_in, d_out, cnt, d_R, d_w);
-        })) return rc;
-    if (want) {      // stage_process has waited for the kernels
-        if (R && !n->fixed) HIPC(hipMemcpy(R, d_R, size_t(blocks) * MM * sizeof(cf), hipMemcpyDeviceToHost));
-        if (w) HIPC(hipMemcpy(w, d_w, size_t(blocks) * M * sizeof(cf), hipMemcpyDeviceToHost));
-    }
-    return GM_OK;
+    return array_process(n, stap_launch, in, fmt, n_in, out, out_cap, n_out, R, w, cap_blocks);
 }
 
 }  // extern "C"
@@ -5637,15 +5639,6 @@ struct BeamPlan {
     uint32_t P = 0;
 };
 
-// one constraint row: M finite words, not all zero
-int beam_row_rules(const gm_c32* s, uint32_t M) {
-    if (!nuller_finite(s, M)) return set_err(GM_ERR_INVALID_ARG, "steering must be finite");
-    bool any = false;
-    for (uint32_t i = 0; i < M; ++i) any = any || s[i].re != 0.0f || s[i].im != 0.0f;
-    if (!any) return set_err(GM_ERR_INVALID_ARG, "a steering row is all zero");
-    return GM_OK;
-}
-
 int beam_rules(const gm_beamformer_cfg* c, BeamPlan& p) {
     if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
     if (c->reserved || c->reserved32) return set_err(GM_ERR_INVALID_ARG, "gm_beamformer_cfg.reserved32 and reserved must be 0");
@@ -5655,44 +5648,28 @@ int beam_rules(const gm_beamformer_cfg* c, BeamPlan& p) {
     if (c->n_beams < 1 || c->n_beams > uint32_t(gm::BM_P_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_beams: 1 .. 16");
     if (!c->steering) return set_err(GM_ERR_INVALID_ARG, "steering is required: n_beams rows of taps * n_antennas words");
     for (uint32_t b = 0; b < c->n_beams; ++b)
-        if (int rc = beam_row_rules(c->steering + size_t(b) * p.st.M, p.st.M)) return rc;
+        if (int rc = array_row_rules(c->steering + size_t(b) * p.st.M, p.st.M, "a steering row is all zero")) return rc;
     p.P = c->n_beams;
     return GM_OK;
 }
 }  // namespace
 
-struct gm_beamformer : StreamStage {        // history: gm_stap's (cf [L - 1 + B][A]); d_blanked is not used, the counters are per beam
+struct gm_beamformer : ArrayStage {         // history: gm_stap's; d_blanked is not used, the counters are per beam; R is [M][M], w is [P][M]
     BeamPlan plan;
-    bool fixed = false;                     // static mode
-    cf* d_s = nullptr; cf* d_w = nullptr;   // [P][M] each: the constraint rows, the fixed weights
+    cf* d_s = nullptr; cf* d_w = nullptr;   // [P][M] each: the constraint rows, the fixed weights (too many words for the argument block)
     unsigned long long* d_fb = nullptr;     // [P] fallback counters
-    cf* cap_R = nullptr; cf* cap_w = nullptr; size_t cap_blocks = 0;     // the caller's capture (device)
-    cf* d_blk = nullptr; size_t blk_cap = 0;                             // blocks; the host-buffer entry's own capture: [blk_cap][M][M] then [blk_cap][P][M]
 };
 
 // one call's kernels on `st`; the caller has checked every argument; n_in > 0
 static int beam_launch(gm_beamformer* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t out_stride, uint64_t n_out,
                        cf* cap_R, cf* cap_w) {
-    const StapPlan& p = n->plan.st;
-    const uint64_t T = n->base + n->inputs;
     gm::BeamArgs a{};
-    a.in = d_in; a.n_in = n_in; a.fmt = fmt;
-    a.hist_in = static_cast<const cf*>(n->d_hist[n->cur]); a.hist_out = static_cast<cf*>(n->d_hist[n->cur ^ 1]);
-    a.A = p.A; a.L = p.L; a.B = p.B; a.P = n->plan.P;
-    a.pending = uint32_t(T % p.B); a.pending_out = uint32_t((T + n_in) % p.B);
-    a.n_blocks = n_out / p.B;
-    a.out = out; a.out_stride = out_stride; a.cap_R = cap_R; a.cap_w = cap_w;
-    a.loading = p.loading; a.adaptive = n->fixed ? 0 : 1;
+    array_fill_args(a, n, d_in, n_in, out, n_out, cap_R, cap_w);
+    a.fmt = fmt; a.L = n->plan.st.L; a.P = n->plan.P;
+    a.out_stride = out_stride;
     a.fallbacks = n->d_fb; a.s = n->d_s; a.w = n->d_w;
     gm::launch_beam(st, a);
     return stage_launched(n, st, n_in, n_out);
-}
-static uint64_t beam_count(const gm_beamformer* n, uint64_t n_in) {
-    const uint64_t T = n->base + n->inputs;
-    return stap_total_out(n->plan.st, T + n_in) - stap_total_out(n->plan.st, T);
-}
-static const char* beam_fmt_err(int fmt) {
-    return fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ ? "beamformer input is interleaved c32 or int8 IQ" : nullptr;
 }
 // the words of the handle that kernels read are replaced only when no call of the handle is in flight, on any stream
 static int beam_install(gm_beamformer* n, cf* d_dst, const gm_c32* src, size_t words) {
@@ -5707,12 +5684,7 @@ extern "C" {
 int gm_beamformer_plan(const gm_beamformer_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, float* loading, uint64_t* n_out) {
     BeamPlan p;
     if (int rc = beam_rules(cfg, p)) return rc;
-    if (inputs_so_far > RS_INDEX_MAX || n_in > RS_INDEX_MAX || inputs_so_far + n_in > RS_INDEX_MAX)
-        return set_err(GM_ERR_INVALID_ARG, "inputs_so_far + n_in above 2^62");
-    if (block) *block = p.st.B;
-    if (loading) *loading = p.st.loading;
-    if (n_out) *n_out = stap_total_out(p.st, inputs_so_far + n_in) - stap_total_out(p.st, inputs_so_far);
-    return GM_OK;
+    return array_plan(p.st.B, p.st.loading, inputs_so_far, n_in, block, loading, n_out);
 }
 
 int gm_beamformer_create(const gm_beamformer_cfg* cfg, gm_beamformer** out) {
@@ -5723,6 +5695,7 @@ int gm_beamformer_create(const gm_beamformer_cfg* cfg, gm_beamformer** out) {
     if (int rc = ensure_device(g_device)) return rc;
     gm_beamformer* n = new gm_beamformer;
     n->device = g_device; n->plan = p;
+    array_shape(n, "beamformer", p.st.A, p.st.B, p.st.loading, size_t(p.st.M) * p.st.M, size_t(p.P) * p.st.M, p.P);
     const size_t words = size_t(gm::BM_P_MAX) * gm::ST_M_MAX;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&n->d_s), words * sizeof(cf));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&n->d_w), words * sizeof(cf));
@@ -5731,7 +5704,7 @@ int gm_beamformer_create(const gm_beamformer_cfg* cfg, gm_beamformer** out) {
     if (e == hipSuccess) e = hipMemset(n->d_w, 0, words * sizeof(cf));
     if (e == hipSuccess) e = hipMemset(n->d_fb, 0, gm::BM_P_MAX * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemcpy(n->d_s, cfg->steering, size_t(p.P) * p.st.M * sizeof(cf), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = stage_create(n, (size_t(p.st.B) + p.st.L - 1) * p.st.A * sizeof(cf));
+    if (e == hipSuccess) e = stage_create(n, stap_hist_bytes(p.st));
     if (e != hipSuccess) { gm_beamformer_destroy(n); return hip_fail(e, "gm_beamformer_create"); }
     *out = n;
     return GM_OK;
@@ -5739,8 +5712,8 @@ int gm_beamformer_create(const gm_beamformer_cfg* cfg, gm_beamformer** out) {
 
 int gm_beamformer_destroy(gm_beamformer* n) {
     if (!n) return GM_OK;
-    stage_destroy(n);
-    hipFree(n->d_blk); hipFree(n->d_s); hipFree(n->d_w); hipFree(n->d_fb);
+    array_destroy(n);
+    hipFree(n->d_s); hipFree(n->d_w); hipFree(n->d_fb);
     delete n;
     return GM_OK;
 }
@@ -5750,8 +5723,7 @@ int gm_beamformer_reset(gm_beamformer* n, uint64_t input_index) {
 }
 
 int gm_beamformer_stats(gm_beamformer* n, uint64_t* inputs, uint64_t* outputs, uint64_t* blocks, uint64_t* fallbacks) {
-    if (int rc = stage_stats(n, inputs, outputs, nullptr)) return rc;
-    if (blocks) *blocks = n->outputs / n->plan.st.B;
+    if (int rc = array_stats(n, inputs, outputs, blocks, nullptr)) return rc;
     if (fallbacks) {
         unsigned long long fb[gm::BM_P_MAX] = {};
         HIPC(hipMemcpy(fb, n->d_fb, n->plan.P * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -5766,69 +5738,29 @@ int gm_beamformer_set_steering(gm_beamformer* n, uint32_t beam, const gm_c32* s)
     if (!n || !s) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (beam >= n->plan.P) return set_err(GM_ERR_INVALID_ARG, "beam: below n_beams");
     const uint32_t M = n->plan.st.M;
-    if (int rc = beam_row_rules(s, M)) return rc;
+    if (int rc = array_row_rules(s, M, "a steering row is all zero")) return rc;
     return beam_install(n, n->d_s + size_t(beam) * M, s, M);
 }
 
 int gm_beamformer_set_weights(gm_beamformer* n, const gm_c32* w) {
     if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
     if (!w) { n->fixed = false; return GM_OK; }
-    const size_t words = size_t(n->plan.P) * n->plan.st.M;
-    if (!nuller_finite(w, uint32_t(words))) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
-    if (int rc = beam_install(n, n->d_w, w, words)) return rc;
+    if (!array_finite(w, n->w_words)) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
+    if (int rc = beam_install(n, n->d_w, w, n->w_words)) return rc;
     n->fixed = true;
     return GM_OK;
 }
 
-int gm_beamformer_capture(gm_beamformer* n, void* d_R, void* d_w, size_t cap_blocks) {
-    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
-    if ((d_R == nullptr) != (d_w == nullptr)) return set_err(GM_ERR_INVALID_ARG, "d_R and d_w: both or neither");
-    if ((d_R == nullptr) != (cap_blocks == 0)) return set_err(GM_ERR_INVALID_ARG, "cap_blocks: 0 exactly where the pointers are null");
-    n->cap_R = static_cast<cf*>(d_R); n->cap_w = static_cast<cf*>(d_w); n->cap_blocks = cap_blocks;
-    return GM_OK;
-}
+int gm_beamformer_capture(gm_beamformer* n, void* d_R, void* d_w, size_t cap_blocks) { return array_capture(n, d_R, d_w, cap_blocks); }
 
 int gm_beamformer_process_dev(gm_beamformer* n, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_stride, size_t* n_out,
                               void* stream) {
-    uint64_t cnt = 0;      // (a plane's room is its stride: a count above it is out of range)
-    if (int rc = stage_check_call(n, beam_count, beam_fmt_err(fmt), d_in, n_in, d_out, out_stride, "gm_beamformer_plan", &cnt)) return rc;
-    const StapPlan& p = n->plan.st;
-    if (n->cap_w && cnt / p.B > n->cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "the capture is smaller than the call's blocks");
-    if (cnt)
-        if (int rc = stage_check_overlap(d_in, n_in * p.A * (fmt == GM_FMT_C32 ? 8 : 2), d_out, uint64_t(n->plan.P - 1) * out_stride + cnt)) return rc;
-    if (n_out) *n_out = size_t(cnt);
-    if (!n_in) return GM_OK;
-    if (int rc = ensure_device(n->device)) return rc;
-    return beam_launch(n, stream ? static_cast<hipStream_t>(stream) : n->stream, d_in, fmt, n_in, static_cast<cf*>(d_out), out_stride, cnt,
-                       n->cap_R, n->cap_w);
+    return array_process_dev(n, beam_launch, d_in, fmt, n_in, d_out, out_stride, n_out, stream);
 }
 
 int gm_beamformer_process(gm_beamformer* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_stride, size_t* n_out, gm_c32* R,
                           gm_c32* w, size_t cap_blocks) {
-    uint64_t cnt = 0;
-    if (int rc = stage_check_call(n, beam_count, beam_fmt_err(fmt), in, n_in, out, out_stride, "gm_beamformer_plan", &cnt)) return rc;
-    const StapPlan& p = n->plan.st;
-    const uint64_t blocks = cnt / p.B;
-    const bool want = (R || w) && blocks;
-    if ((R || w) && blocks > cap_blocks) return set_err(GM_ERR_OUT_OF_RANGE, "cap_blocks below the call's blocks");
-    const size_t M = p.M, MM = M * M, PM = size_t(n->plan.P) * M, A = p.A;
-    if (want && n->blk_cap < blocks) {
-        if (int rc = ensure_device(n->device)) return rc;
-        if (int rc = stage_sync(n)) return rc;
-        hipFree(n->d_blk); n->d_blk = nullptr; n->blk_cap = 0;
-        HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_blk), size_t(blocks) * (MM + PM) * sizeof(cf)));
-        n->blk_cap = size_t(blocks);
-    }
-    cf* d_R = want ? n->d_blk : nullptr;
-    cf* d_w = want ? n->d_blk + n->blk_cap * MM : nullptr;
-    if (int rc = stage_process(n, in, n_in * A * (fmt == GM_FMT_C32 ? 8 : 2), out, cnt, n_out, [&](hipStream_t st, const void* d_in, cf* d_out) {
-            return beam_launch(n, st, d_in, fmt, n_in, d_out, cnt, cnt, d_R, d_w);
-        }, n->plan.P, out_stride)) return rc;
-    if (want) {      // stage_process has waited for the kernels
-        if (R && !n->fixed) HIPC(hipMemcpy(R, d_R, size_t(blocks) * MM * sizeof(cf), hipMemcpyDeviceToHost));
-        if (w) HIPC(hipMemcpy(w, d_w, size_t(blocks) * PM * sizeof(cf), hipMemcpyDeviceToHost));
-    }
-    return GM_OK;
+    return array_process(n, beam_launch, in, fmt, n_in, out, out_stride, n_out, R, w, cap_blocks);
 }
 
 }  // extern "C"

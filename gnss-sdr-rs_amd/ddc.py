@@ -9,13 +9,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import DdcCfg, check, lib
+from ._stage import Stage, _p
 
 _KEYS = ("taps", "n_phases", "cutoff", "kaiser_beta", "blank_threshold")
 TABLE_WORDS = 4096
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _cfg(mix_cycles_per_sample, up, down, taps=0, n_phases=0, cutoff=0.0, kaiser_beta=0.0, blank_threshold=0.0):
@@ -41,7 +38,9 @@ def phasor_tables():
     return whi, wlo
 
 
-class Ddc:
+class Ddc(Stage):
+    _NAME = "ddc"
+
     def __init__(self, mix_cycles_per_sample, up, down, device=None, **cfg):
         unknown = set(cfg) - set(_KEYS)
         if unknown:
@@ -51,9 +50,7 @@ class Ddc:
         p = plan(mix_cycles_per_sample, up, down, **cfg)
         self.up, self.down, self.n_taps, self.n_phases, self.phase_inc = p["up"], p["down"], p["taps"], p["n_phases"], p["phase_inc"]
         self.mix_cycles_per_sample = float(mix_cycles_per_sample)
-        h = C.c_void_p()
-        check(lib().gm_ddc_create(C.byref(self._cfg), C.byref(h)), "gm_ddc_create")
-        self._h = h
+        self._open(self._cfg)
 
     @classmethod
     def from_rates(cls, fs_in, fs_out, f_mix_hz, device=None, max_denominator=1 << 24, **cfg):
@@ -62,30 +59,19 @@ class Ddc:
         ratio = (Fraction(fs_out) / Fraction(fs_in)).limit_denominator(max_denominator)
         return cls(float(Fraction(f_mix_hz) / Fraction(fs_in)), ratio.numerator, ratio.denominator, device=device, **cfg)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gm_ddc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):      # (at interpreter shutdown the module globals close() uses may be gone already)
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def process(self, samples):
         """samples: int8 array of real samples -> complex64 array of this call's outputs (synchronous)."""
         s = np.ascontiguousarray(samples, np.int8).reshape(-1)
         out = np.zeros(s.size * self.up // self.down + 2, np.complex64)     # a call never delivers more than n * up / down + 1
         got = C.c_size_t(0)
-        check(lib().gm_ddc_process(self._h, _p(s), s.size, _p(out), out.size, C.byref(got)), "gm_ddc_process")
+        self._call("process", _p(s), s.size, _p(out), out.size, C.byref(got))
         return out[:got.value].copy()
 
     def process_dev(self, d_in, n_in, d_out, out_cap, stream=None):
         """device pointers (d_in at any byte address); asynchronous on `stream` (None: the handle's own); returns the number of outputs
         written to d_out"""
         got = C.c_size_t(0)
-        check(lib().gm_ddc_process_dev(self._h, d_in, n_in, d_out, out_cap, C.byref(got), stream), "gm_ddc_process_dev")
+        self._call("process_dev", d_in, n_in, d_out, out_cap, C.byref(got), stream)
         return got.value
 
     def write_ring(self, ring, block, excisor=None, resampler=None):
@@ -93,26 +79,17 @@ class Ddc:
         ring (gm_ddc_write_ring): ring indices count the last stage's outputs, and the outputs enqueued are returned."""
         s = np.ascontiguousarray(block, np.int8).reshape(-1)
         total = C.c_uint64(0)
-        check(lib().gm_ddc_write_ring(self._h, excisor._h if excisor is not None else None,
-                                      resampler._h if resampler is not None else None, ring._h, _p(s), s.size, C.byref(total)),
-              "gm_ddc_write_ring")
+        self._call("write_ring", excisor._h if excisor is not None else None, resampler._h if resampler is not None else None,
+                   ring._h, _p(s), s.size, C.byref(total))
         return total.value
-
-    def reset(self, input_index=0):
-        check(lib().gm_ddc_reset(self._h, int(input_index)), "gm_ddc_reset")
 
     def tables(self):
         """the words the device uses: the [n_phases + 1][taps] float32 filter table, and the complex64 phasor tables Whi and Wlo"""
         table = np.zeros((self.n_phases + 1, self.n_taps), np.float32)
         whi, wlo = np.zeros(TABLE_WORDS, np.complex64), np.zeros(TABLE_WORDS, np.complex64)
-        check(lib().gm_ddc_tables(self._h, _p(table), _p(whi), _p(wlo)), "gm_ddc_tables")
+        self._call("tables", _p(table), _p(whi), _p(wlo))
         return table, whi, wlo
 
     def stats(self):
         """inputs taken, outputs delivered, inputs blanked since the creation or the last reset (synchronises)"""
-        i, o, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        check(lib().gm_ddc_stats(self._h, C.byref(i), C.byref(o), C.byref(b)), "gm_ddc_stats")
-        return dict(inputs=i.value, outputs=o.value, blanked=b.value)
-
-    def synchronize(self):
-        check(lib().gm_ddc_synchronize(self._h), "gm_ddc_synchronize")
+        return self._counters("inputs", "outputs", "blanked")

@@ -8,12 +8,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMT_C32, FMT_I8_IQ, ExcisorBlockCfg, ExcisorCfg, check, lib
+from ._stage import Stage, _p
 
 _KEYS = ("guard_bins", "threshold_factor", "blank_threshold")
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 _HIP = None
@@ -74,7 +71,9 @@ def _samples(samples):
     return s, s.size, FMT_C32
 
 
-class Excisor:
+class Excisor(Stage):
+    _NAME = "excisor"
+
     def __init__(self, block=0, device=None, **cfg):
         unknown = set(cfg) - set(_KEYS)
         if unknown:
@@ -85,44 +84,34 @@ class Excisor:
         p = plan(block, **cfg)
         self.block, self.guard_bins, self.threshold_factor = p["block"], p["guard_bins"], p["threshold_factor"]
         self._d_adapt, self._adapt_cap, self._base = None, 0, 0
-        h = C.c_void_p()
-        check(lib().gm_excisor_create(C.byref(self._cfg), C.byref(h)), "gm_excisor_create")
-        self._h = h
+        self._open(self._cfg)
 
     def close(self):
-        if getattr(self, "_h", None):
-            lib().gm_excisor_destroy(self._h)
-            self._h = None
+        super().close()
         if getattr(self, "_d_adapt", None):
             _hip().hipFree(self._d_adapt)
             self._d_adapt = None
-
-    def __del__(self):      # (at interpreter shutdown the module globals close() uses may be gone already)
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_block_adapt(self, threshold_factor=0.0, guard_bins=0):
         """the block-adapt mode on (a mask per block, decided on the device between the two transforms; 0 -> factor 16) or, with
         set_block_adapt(None), off; returns self"""
         if threshold_factor is None:
-            check(lib().gm_excisor_set_block_adapt(self._h, None), "gm_excisor_set_block_adapt")
+            self._call("set_block_adapt", None)
         else:
             c = _block_cfg(threshold_factor, guard_bins)
-            check(lib().gm_excisor_set_block_adapt(self._h, C.byref(c)), "gm_excisor_set_block_adapt")
+            self._call("set_block_adapt", C.byref(c))
         return self
 
     def block_stats(self):
         """the block-adapt counters since the creation or the last reset (synchronises)"""
         v = [C.c_uint64(0) for _ in range(4)]
-        check(lib().gm_excisor_block_stats(self._h, *[C.byref(c) for c in v]), "gm_excisor_block_stats")
+        self._call("block_stats", *[C.byref(c) for c in v])
         return dict(zip(("blocks", "blocks_flagged", "bins_flagged", "bins_zeroed"), (c.value for c in v)))
 
     def block_capture(self, d_power=None, d_mask=None, cap_blocks=0):
         """arms a capture of the power words (f32 [cap_blocks][block]) and masks (u8 [cap_blocks][block]) of every later process_dev
         into device buffers; both None disarms it"""
-        check(lib().gm_excisor_block_capture(self._h, d_power, d_mask, int(cap_blocks)), "gm_excisor_block_capture")
+        self._call("block_capture", d_power, d_mask, int(cap_blocks))
 
     def _process_blocks(self, s, n, fmt):
         """process(want_blocks=True): process_dev with a capture armed on plain device buffers of this call's own"""
@@ -166,18 +155,18 @@ class Excisor:
             return self._process_blocks(s, n, fmt)
         out = np.zeros(n + self.block, np.complex64)                    # a call never delivers more than n + H
         got = C.c_size_t(0)
-        check(lib().gm_excisor_process(self._h, _p(s), fmt, n, _p(out), out.size, C.byref(got)), "gm_excisor_process")
+        self._call("process", _p(s), fmt, n, _p(out), out.size, C.byref(got))
         return out[:got.value].copy()
 
     def process_dev(self, d_in, fmt, n_in, d_out, out_cap, stream=None):
         """device pointers; asynchronous on `stream` (None: the handle's own); returns the number of outputs written to d_out"""
         got = C.c_size_t(0)
-        check(lib().gm_excisor_process_dev(self._h, d_in, fmt, n_in, d_out, out_cap, C.byref(got), stream), "gm_excisor_process_dev")
+        self._call("process_dev", d_in, fmt, n_in, d_out, out_cap, C.byref(got), stream)
         return got.value
 
     def adapt_dev(self, d_in, fmt, n, stream=None):
         """the adaptive step on n samples in device memory: periodogram, median, mask, gains; enqueued, no host wait"""
-        check(lib().gm_excisor_adapt_dev(self._h, d_in, fmt, n, stream), "gm_excisor_adapt_dev")
+        self._call("adapt_dev", d_in, fmt, n, stream)
 
     def adapt(self, samples):
         """the adaptive step on host samples (copied to a device buffer the object keeps, then adapt_dev on the handle's stream)"""
@@ -200,33 +189,28 @@ class Excisor:
         g = np.ascontiguousarray(gains, np.float32)
         if g.shape != (self.block,):
             raise ValueError("gains: %d values" % self.block)
-        check(lib().gm_excisor_set_gains(self._h, _p(g)), "gm_excisor_set_gains")
+        self._call("set_gains", _p(g))
 
     def gains(self):
         g = np.zeros(self.block, np.float32)
-        check(lib().gm_excisor_gains(self._h, _p(g)), "gm_excisor_gains")
+        self._call("gains", _p(g))
         return g
 
     def psd(self):
         """the last adapt's words: dict of P [block] float32, median, n_flagged, n_zeroed (synchronises)"""
         P = np.zeros(self.block, np.float32)
         med, nf, nz = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
-        check(lib().gm_excisor_psd(self._h, _p(P), C.byref(med), C.byref(nf), C.byref(nz)), "gm_excisor_psd")
+        self._call("psd", _p(P), C.byref(med), C.byref(nf), C.byref(nz))
         return dict(P=P, median=np.float32(med.value), n_flagged=nf.value, n_zeroed=nz.value)
 
     def reset(self, input_index=0):
-        check(lib().gm_excisor_reset(self._h, int(input_index)), "gm_excisor_reset")
+        super().reset(input_index)
         self._base = int(input_index)
 
     def stats(self):
         """inputs taken, outputs delivered, inputs blanked since the creation or the last reset (synchronises)"""
-        i, o, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        check(lib().gm_excisor_stats(self._h, C.byref(i), C.byref(o), C.byref(b)), "gm_excisor_stats")
-        return dict(inputs=i.value, outputs=o.value, blanked=b.value)
+        return self._counters("inputs", "outputs", "blanked")
 
     def windows(self):
         """the float32 analysis and synthesis window words the device uses"""
         return windows(self.block, **self._settings)
-
-    def synchronize(self):
-        check(lib().gm_excisor_synchronize(self._h), "gm_excisor_synchronize")

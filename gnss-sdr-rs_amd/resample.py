@@ -9,12 +9,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMT_C32, FMT_I8_IQ, ResamplerCfg, check, lib
+from ._stage import Stage, _p
 
 _KEYS = ("taps", "n_phases", "cutoff", "kaiser_beta", "blank_threshold")
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _cfg(up, down, taps=0, n_phases=0, cutoff=0.0, kaiser_beta=0.0, blank_threshold=0.0):
@@ -48,7 +45,9 @@ def _samples(samples):
     return s, s.size, FMT_C32
 
 
-class Resampler:
+class Resampler(Stage):
+    _NAME = "resampler"
+
     def __init__(self, up, down, device=None, **cfg):
         unknown = set(cfg) - set(_KEYS)
         if unknown:
@@ -57,9 +56,7 @@ class Resampler:
         self._cfg = _cfg(up, down, **cfg)
         p = plan(up, down, **cfg)
         self.up, self.down, self.n_taps, self.n_phases = p["up"], p["down"], p["taps"], p["n_phases"]
-        h = C.c_void_p()
-        check(lib().gm_resampler_create(C.byref(self._cfg), C.byref(h)), "gm_resampler_create")
-        self._h = h
+        self._open(self._cfg)
 
     @classmethod
     def from_rates(cls, fs_in, fs_out, device=None, max_denominator=1 << 24, **cfg):
@@ -68,46 +65,26 @@ class Resampler:
         ratio = (Fraction(fs_out) / Fraction(fs_in)).limit_denominator(max_denominator)
         return cls(ratio.numerator, ratio.denominator, device=device, **cfg)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gm_resampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):      # (at interpreter shutdown the module globals close() uses may be gone already)
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def process(self, samples):
         """samples: complex64 array, or int8 array of interleaved I/Q -> complex64 array of this call's outputs (synchronous)."""
         s, n, fmt = _samples(samples)
         out = np.zeros(n * self.up // self.down + 2, np.complex64)      # a call never delivers more than n * up / down + 1
         got = C.c_size_t(0)
-        check(lib().gm_resampler_process(self._h, _p(s), fmt, n, _p(out), out.size, C.byref(got)), "gm_resampler_process")
+        self._call("process", _p(s), fmt, n, _p(out), out.size, C.byref(got))
         return out[:got.value].copy()
 
     def process_dev(self, d_in, fmt, n_in, d_out, out_cap, stream=None):
         """device pointers; asynchronous on `stream` (None: the handle's own); returns the number of outputs written to d_out"""
         got = C.c_size_t(0)
-        check(lib().gm_resampler_process_dev(self._h, d_in, fmt, n_in, d_out, out_cap, C.byref(got), stream),
-              "gm_resampler_process_dev")
+        self._call("process_dev", d_in, fmt, n_in, d_out, out_cap, C.byref(got), stream)
         return got.value
-
-    def reset(self, input_index=0):
-        check(lib().gm_resampler_reset(self._h, int(input_index)), "gm_resampler_reset")
 
     def taps(self):
         """the [n_phases + 1][taps] float32 words the device uses"""
         table = np.zeros((self.n_phases + 1, self.n_taps), np.float32)
-        check(lib().gm_resampler_taps(self._h, _p(table)), "gm_resampler_taps")
+        self._call("taps", _p(table))
         return table
 
     def stats(self):
         """inputs taken, outputs delivered, inputs blanked since the creation or the last reset (synchronises)"""
-        i, o, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        check(lib().gm_resampler_stats(self._h, C.byref(i), C.byref(o), C.byref(b)), "gm_resampler_stats")
-        return dict(inputs=i.value, outputs=o.value, blanked=b.value)
-
-    def synchronize(self):
-        check(lib().gm_resampler_synchronize(self._h), "gm_resampler_synchronize")
+        return self._counters("inputs", "outputs", "blanked")
