@@ -18,6 +18,14 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _cand_array(cands):
+    """the gm_acq_cand array of local_search's candidate dicts (one spare entry for an empty list: the pointer is never null)"""
+    cs = (AcqCand * max(len(cands), 1))()
+    for i, c in enumerate(cands):
+        cs[i] = AcqCand(int(c["worker"]), int(c["doppler_bin"]), int(c["code_phase_samples"]), int(c.get("offset_periods", 0)))
+    return cs
+
+
 def generate_ca_code_samples(prn, code_rate, f_sampling):
     """utilities::ca_code::generate_ca_code_samples (ca_code.rs:12-27)"""
     n = C.c_size_t(0)
@@ -489,9 +497,7 @@ class AcquisitionEngine:
         n_freq, n_lags); with want_prompts `prompts` (complex64 [n_lags][span_periods * n_groups]), with want_surface `surface`
         (float32 [n_lags][n_freq]).  The library makes no detection decision."""
         n = len(cands)
-        cs = (AcqCand * max(n, 1))()
-        for i, c in enumerate(cands):
-            cs[i] = AcqCand(int(c["worker"]), int(c["doppler_bin"]), int(c["code_phase_samples"]), int(c.get("offset_periods", 0)))
+        cs = _cand_array(cands)
         cfg = AcqLocalCfg(int(lag_half_window), int(span_periods), int(n_freq), float(half_span_hz))
         out = (AcqLocalOut * max(n, 1))()
         z = s = None
@@ -522,9 +528,7 @@ class AcquisitionEngine:
         A candidate is local_search's dict.  -> complex64 [n_cands, R_u, taps, n_antennas], R_u = max(1, K) * n_integrations; solve_rows
         turns it into constraint rows.  The library makes no detection decision."""
         n = len(cands)
-        cs = (AcqCand * max(n, 1))()
-        for i, c in enumerate(cands):
-            cs[i] = AcqCand(int(c["worker"]), int(c["doppler_bin"]), int(c["code_phase_samples"]), int(c.get("offset_periods", 0)))
+        cs = _cand_array(cands)
         plan = array_plan(self.K, self.M, n_antennas, taps)
         z = np.zeros((max(n, 1), plan["periods"], int(taps), int(n_antennas)), np.complex64)
         check(lib().gm_acq_array_prompts(self._h, C.c_void_p(samples) if samples else None, int(fmt), int(n_antennas), int(taps),

@@ -338,6 +338,44 @@ static int ring_write_blocks(gm_ring* r, const void* samples, size_t n, size_t b
     return GM_OK;
 }
 
+// ====================================================================== per-call device blocks: what the known-cell entries share
+// gm_acq_refine_doppler, gm_acq_local_search, gm_acq_array_prompts, gm_acq_cancel, gm_trk_bank and gm_trk_array_prompts each run a small
+// kernel at cells the caller names and return host results synchronously.  Each keeps ONE grow-only device block on its handle and
+// carves it per call.  Here: the block, the carve, and the two pieces of host arithmetic more than one of them uses.  What needs a
+// handle's fields sits in front of the entries that use it ("known cells on gm_acq", "known records on gm_trk").
+// An entry supplies its rules, its carve, its launch and its result loop.
+static size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
+struct CallBlock {
+    void* d = nullptr;
+    size_t bytes = 0;
+    // room for `total` bytes: the new block before the old one goes, so a failure leaves the handle as it was
+    int reserve(hipStream_t stream, size_t total, const char* nomem_text) {
+        if (total <= bytes) return GM_OK;
+        void* blk = nullptr;
+        if (hipMalloc(&blk, total) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(GM_ERR_NOMEM, nomem_text);
+        }
+        if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
+        hipFree(d);
+        d = blk; bytes = total;
+        return GM_OK;
+    }
+    void release() { hipFree(d); d = nullptr; bytes = 0; }
+};
+// the parts of a block in the order they are taken, each 256-byte aligned; `end` is the block's size so far
+struct Carve {
+    size_t end = 0;
+    size_t take(size_t b) { const size_t at = end; end += round256(b); return at; }
+};
+static size_t fmt_bytes(int fmt) { return fmt == GM_FMT_C32 ? 8 : (fmt == GM_FMT_I8_IQ ? 2 : 1); }     // per sample, of the three formats
+// the vertex of the parabola through (-1, y0), (0, y1), (1, y2), in grid steps, f64; 0 where y1 is no strict maximum; clamped to half a step
+static double parabola_offset(double y0, double y1, double y2) {
+    const double den = y0 - 2.0 * y1 + y2;
+    const double x = den < 0.0 ? 0.5 * (y0 - y2) / den : 0.0;
+    return x > 0.5 ? 0.5 : (x < -0.5 ? -0.5 : x);
+}
+
 // ====================================================================== acquisition handle
 struct gm_acq {
     int device = -1;
@@ -455,29 +493,11 @@ struct gm_acq {
         float *d_mean = nullptr, *d_rowmax = nullptr, *d_peak_pow = nullptr;
         uint32_t *d_rowarg = nullptr, *d_sat_worker = nullptr, *d_sat_cp = nullptr, *d_peak_idx = nullptr;
     } fine;
-    // fine Doppler from per-period prompts (gm_acq_refine_doppler): one lazily built device block, carved per call into the satellite
-    // list, the prompts, the period times, the per-satellite centre and step, the spectra and the peaks; grown when a call needs more
-    struct Refine {
-        void* d_block = nullptr;
-        size_t bytes = 0;
-    } refine;
-    // lag window x fine Doppler at known cells (gm_acq_local_search): one device block of its own, carved per call and grown like refine's
-    struct Local {
-        void* d_block = nullptr;
-        size_t bytes = 0;
-    } local;
-    // space-time prompts of an antenna array at known cells (gm_acq_array_prompts): one device block (the candidates and z), grown like local's
-    struct Array {
-        void* d_block = nullptr;
-        size_t bytes = 0;
-    } array;
-    // subtracting found satellites from a dwell (gm_acq_cancel): one device block (candidate constants, the segment tables o and b, the
-    // amplitudes), grown like local's, and a device copy of the raw chip rows [P][code_len], uploaded at the first call
-    struct Cancel {
-        void* d_block = nullptr;
-        size_t bytes = 0;
-        int8_t* d_chips = nullptr;
-    } cancel;
+    // the known-cell entries' device blocks, one each: gm_acq_refine_doppler (the satellite list, the prompts, the period times, the
+    // per-satellite centre and step, the spectra and the peaks), gm_acq_local_search, gm_acq_array_prompts (the candidates and z) and
+    // gm_acq_cancel (candidate constants, the segment tables o and b, the amplitudes)
+    CallBlock refine, local, array, cancel;
+    int8_t* d_cancel_chips = nullptr;      // gm_acq_cancel: a device copy of the raw chip rows [P][code_len], uploaded at the first call
 };
 
 // the fused single-LDS-buffer kernels (acq_kernels.hip): neither a composite nor an any-length size
@@ -554,6 +574,73 @@ static int acq_reserve_results(gm_acq* a, uint32_t n) {
     a->d_prn_ids = ids;
     a->results_cap = n;
     return GM_OK;
+}
+
+// ---------------------------------------------------------------- known cells on gm_acq: what gm_acq_refine_doppler, gm_acq_local_search,
+// gm_acq_array_prompts and gm_acq_cancel share beyond CallBlock and Carve
+namespace {
+struct RefinePlan { uint32_t J = 0, G = 0, Z = 0; double half_span = 0.0, step = 0.0; };
+// the fine-Doppler grid of a cell list: host copies the result loops read, and where the kernels find them
+struct CellGrid { std::vector<double> t, fc, step; const double *d_t = nullptr, *d_fc = nullptr, *d_step = nullptr; };
+}
+// these samples, or the snapshot of the last search
+static int acq_call_input(const gm_acq* a, const void* d_samples, int fmt, const void** in, int* in_fmt) {
+    if (d_samples) {
+        if (fmt < GM_FMT_C32 || fmt > GM_FMT_I8_REAL) return set_err(GM_ERR_INVALID_ARG, "bad sample format");
+    } else if (!a->last_samples) return set_err(GM_ERR_INVALID_ARG, "no search has run on this handle yet");
+    *in = d_samples ? d_samples : a->last_samples;
+    *in_fmt = d_samples ? fmt : a->last_fmt;
+    return GM_OK;
+}
+// the rules of a known cell (gm_acq_cand), shared by gm_acq_local_search and gm_acq_array_prompts
+static int acq_cand_rules(const gm_acq* a, const gm_acq_cand& c) {
+    if (c.worker >= a->P) return set_err(GM_ERR_INVALID_ARG, "candidate.worker outside the handle's workers");
+    if (c.doppler_bin < 0 || uint32_t(c.doppler_bin) >= a->D) return set_err(GM_ERR_INVALID_ARG, "candidate.doppler_bin outside the handle's bins");
+    if (c.code_phase_samples >= a->N) return set_err(GM_ERR_INVALID_ARG, "candidate.code_phase_samples >= fft_size");
+    if (c.offset_periods > (a->edge.H ? a->edge.o_max : 0u))
+        return set_err(GM_ERR_INVALID_ARG, "candidate.offset_periods above the edge search's last offset (0 without an edge search)");
+    return GM_OK;
+}
+static gm::RefineSat acq_cand_cell(const gm_acq_cand& c) {
+    return gm::RefineSat{c.worker, c.code_phase_samples, uint32_t(c.doppler_bin), c.offset_periods};
+}
+// the period times of every group of every cell (f64, relative to the group's first period: whole samples over fs; the code-drift
+// starts while they are on) and the cells' centre frequencies, beside the caller's g.step; all three uploaded to d_t, d_fc, d_step
+static int acq_cell_grid(const gm_acq* a, const std::vector<gm::RefineSat>& cells, uint32_t J, uint32_t G, char* d_t, char* d_fc, char* d_step,
+                         CellGrid& g) {
+    const uint32_t S = uint32_t(cells.size()), R_u = J * G, N = a->N;
+    const double fs = double(a->cfg.fs);
+    g.t.resize(size_t(S) * R_u); g.fc.resize(S);
+    for (uint32_t i = 0; i < S; ++i) {
+        const uint32_t d = cells[i].bin, o = cells[i].offset;
+        g.fc[i] = double(a->table_freq[d]);
+        for (uint32_t gi = 0; gi < G; ++gi)
+            for (uint32_t k = 0; k < J; ++k) {
+                const uint32_t q0 = o + gi * J, q = q0 + k;
+                const uint64_t s0 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q0] : uint64_t(q0) * N;
+                const uint64_t s1 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q] : uint64_t(q) * N;
+                g.t[size_t(i) * R_u + gi * J + k] = double(s1 - s0) / fs;
+            }
+    }
+    HIPC(hipMemcpyAsync(d_t, g.t.data(), g.t.size() * 8, hipMemcpyHostToDevice, a->stream));
+    HIPC(hipMemcpyAsync(d_fc, g.fc.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
+    HIPC(hipMemcpyAsync(d_step, g.step.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
+    g.d_t = reinterpret_cast<const double*>(d_t); g.d_fc = reinterpret_cast<const double*>(d_fc);
+    g.d_step = reinterpret_cast<const double*>(d_step);
+    return GM_OK;
+}
+// the fields gm::RefineArgs, gm::LocalArgs and gm::ArrayArgs share ...
+template <class Args> static void acq_cell_args(Args& g, const gm_acq* a, const void* in, int in_fmt, uint32_t R_u) {
+    g.samples = in; g.fmt = in_fmt;
+    g.starts = a->drift.on ? a->drift.d_starts : nullptr; g.R = a->drift.on ? a->drift.R : 0u;
+    g.tables = a->d_tables; g.code_samples = a->d_code_samples;
+    g.N = a->N; g.R_u = R_u;
+}
+// ... and those of the two with a fine-Doppler grid
+template <class Args> static void acq_grid_args(Args& g, const gm_acq* a, const RefinePlan& p, cf* z, const CellGrid& cg) {
+    g.J = p.J; g.G = p.G; g.Z = p.Z;
+    g.neg = (a->K >= 2 && a->edge.H) ? a->edge.neg : 0u;
+    g.z = z; g.t = cg.d_t; g.fc = cg.d_fc; g.step = cg.d_step;
 }
 
 extern "C" {
@@ -851,10 +938,7 @@ int gm_acq_destroy(gm_acq* a) {
     hipFree(a->fine.d_chips); hipFree(a->fine.d_tw1); hipFree(a->fine.d_tw2); hipFree(a->fine.d_B); hipFree(a->fine.d_mean);
     hipFree(a->fine.d_rowmax); hipFree(a->fine.d_rowarg); hipFree(a->fine.d_sat_worker); hipFree(a->fine.d_sat_cp);
     hipFree(a->fine.d_peak_pow); hipFree(a->fine.d_peak_idx);
-    hipFree(a->refine.d_block);
-    hipFree(a->local.d_block);
-    hipFree(a->array.d_block);
-    hipFree(a->cancel.d_block); hipFree(a->cancel.d_chips);
+    a->refine.release(); a->local.release(); a->array.release(); a->cancel.release(); hipFree(a->d_cancel_chips);
     if (a->device >= 0) hipSetDevice(a->device);
     hipFree(a->d_tw_mix);
     hipFree(a->d_tables); hipFree(a->d_tw_fwd); hipFree(a->d_tw_inv); hipFree(a->d_code_fft); hipFree(a->d_code_fft_paired); hipFree(a->d_order);
@@ -1436,7 +1520,7 @@ int gm_acq_search(gm_acq* a, const void* samples, size_t n_samples, int fmt, uin
                                             : a->edge.H ? "samples_chunk shorter than (coherent_periods*num_integrations + the last edge offset)*fft_size"
                                                       : "samples_chunk shorter than coherent_periods*num_integrations*fft_size");
     if (int rc = ensure_device(a->device)) return rc;
-    const size_t bps = fmt == GM_FMT_C32 ? 8 : (fmt == GM_FMT_I8_IQ ? 2 : 1);
+    const size_t bps = fmt_bytes(fmt);
     if (int rc = acq_set_mask(a, prn_mask)) return rc;
     HIPC(hipMemcpyAsync(a->d_samples, samples, need * bps, hipMemcpyHostToDevice, a->stream));   // (a pinned staging block of the handle's own: measured, no gain)
     if (int rc = gm_acq_search_dev(a, a->d_samples, fmt, nullptr)) return rc;
@@ -1524,7 +1608,7 @@ int gm_acq_finer_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t*
     std::vector<uint32_t> passes;
     for (uint32_t p = 0; p < n_prn; ++p)
         if (found[p] && std::find(passes.begin(), passes.end(), off[p]) == passes.end()) passes.push_back(off[p]);
-    const size_t bps = a->last_fmt == GM_FMT_C32 ? 8 : (a->last_fmt == GM_FMT_I8_IQ ? 2 : 1);
+    const size_t bps = fmt_bytes(a->last_fmt);
     // (not compensated: the code is stripped over K*M contiguous periods from period o* on; a drift dwell of periods shorter than
     //  fft_size ends before them — checked for the largest offset before any pass runs, so no output is half filled)
     if (a->drift.on && !passes.empty() &&
@@ -1892,9 +1976,6 @@ int gm_acq_code_drift_phasors(gm_acq* a, uint32_t h, gm_c32* out) {
 }
 
 // ---------------------------------------------------------------- fine Doppler from per-period prompts (additive entries, ABI 9)
-namespace {
-struct RefinePlan { uint32_t J = 0, G = 0, Z = 0; double half_span = 0.0, step = 0.0; };
-}
 // the argument rules of gm_acq_refine_plan / gm_acq_refine_doppler and what a call uses for `bin` (gnss_mi355x.h states them)
 static int refine_rules(uint32_t coherent_periods, uint32_t M, const gm_acq_refine_cfg* cfg, double fs, uint32_t N, uint32_t D,
                         const float* table_freq, uint32_t bin, RefinePlan& o) {
@@ -1949,7 +2030,9 @@ int gm_acq_refine_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t
                           gm_acq_refine_out* out, gm_c32* prompts, float* spectrum) {
     if (!a || !results || !found || !out) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (n_prn > a->P) return set_err(GM_ERR_INVALID_ARG, "n_prn exceeds the handle's workers");
-    if (!a->last_samples) return set_err(GM_ERR_INVALID_ARG, "no search has run on this handle yet");
+    const void* in = nullptr;
+    int in_fmt = 0;
+    if (int rc = acq_call_input(a, nullptr, 0, &in, &in_fmt)) return rc;          // the snapshot of the last search
     const uint32_t N = a->N, D = a->D;
     const double fs = double(a->cfg.fs);
     // every argument is checked before anything runs or is written
@@ -1973,52 +2056,29 @@ int gm_acq_refine_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t
     if (a->edge.H)
         if (int rc = gm_acq_result_offsets(a, results, found, n_prn, off.data())) return rc;
     // the block: [sats | z | t | fc | step | spectrum | peak values | peak indices], every part 256-byte aligned
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_sat = 0, o_z = o_sat + up(size_t(S) * sizeof(gm::RefineSat)), o_t = o_z + up(size_t(S) * R_u * 8),
-                 o_fc = o_t + up(size_t(S) * R_u * 8), o_step = o_fc + up(size_t(S) * 8), o_spec = o_step + up(size_t(S) * 8),
-                 o_pv = o_spec + up(size_t(S) * Z * 4), o_pi = o_pv + up(size_t(S) * 4), total = o_pi + up(size_t(S) * 4);
-    gm_acq::Refine& rf = a->refine;
-    if (total > rf.bytes) {                 // the new block before the old one goes: a failure leaves the handle as it was
-        void* blk = nullptr;
-        if (hipMalloc(&blk, total) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(GM_ERR_NOMEM, "the fine-Doppler block does not fit (gnss_mi355x.h states the formula); the handle is as it was");
-        }
-        if (hipError_t e = hipStreamSynchronize(a->stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
-        hipFree(rf.d_block);
-        rf.d_block = blk; rf.bytes = total;
-    }
-    char* const base = static_cast<char*>(rf.d_block);
-    // host side of the block's inputs: the satellite list, the period times of every group (f64, relative to the group's first
-    // period: whole samples over fs), the centre frequency and the grid step
+    Carve cv;
+    const size_t o_sat = cv.take(size_t(S) * sizeof(gm::RefineSat)), o_z = cv.take(size_t(S) * R_u * 8), o_t = cv.take(size_t(S) * R_u * 8),
+                 o_fc = cv.take(size_t(S) * 8), o_step = cv.take(size_t(S) * 8), o_spec = cv.take(size_t(S) * Z * 4),
+                 o_pv = cv.take(size_t(S) * 4), o_pi = cv.take(size_t(S) * 4);
+    if (int rc = a->refine.reserve(a->stream, cv.end,
+                                   "the fine-Doppler block does not fit (gnss_mi355x.h states the formula); the handle is as it was"))
+        return rc;
+    char* const base = static_cast<char*>(a->refine.d);
+    // host side of the block's inputs: the satellite list, and the grid of its cells
     std::vector<gm::RefineSat> sats(S);
-    std::vector<double> t(size_t(S) * R_u), fc(S), step(S);
+    CellGrid cg;
+    cg.step.resize(S);
     for (uint32_t i = 0; i < S; ++i) {
-        const uint32_t p = list[i], d = uint32_t(results[p].doppler_bin), o = off[p];
-        sats[i] = gm::RefineSat{p, uint32_t(results[p].code_phase_samples), d, o};
-        fc[i] = double(a->table_freq[d]);
-        step[i] = plans[p].step;
-        for (uint32_t g = 0; g < G; ++g)
-            for (uint32_t k = 0; k < J; ++k) {
-                const uint32_t q0 = o + g * J, q = q0 + k;
-                const uint64_t s0 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q0] : uint64_t(q0) * N;
-                const uint64_t s1 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q] : uint64_t(q) * N;
-                t[size_t(i) * R_u + g * J + k] = double(s1 - s0) / fs;
-            }
+        const uint32_t p = list[i];
+        sats[i] = gm::RefineSat{p, uint32_t(results[p].code_phase_samples), uint32_t(results[p].doppler_bin), off[p]};
+        cg.step[i] = plans[p].step;
     }
     HIPC(hipMemcpyAsync(base + o_sat, sats.data(), size_t(S) * sizeof(gm::RefineSat), hipMemcpyHostToDevice, a->stream));
-    HIPC(hipMemcpyAsync(base + o_t, t.data(), t.size() * 8, hipMemcpyHostToDevice, a->stream));
-    HIPC(hipMemcpyAsync(base + o_fc, fc.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
-    HIPC(hipMemcpyAsync(base + o_step, step.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
+    if (int rc = acq_cell_grid(a, sats, J, G, base + o_t, base + o_fc, base + o_step, cg)) return rc;
     gm::RefineArgs ra{};
-    ra.samples = a->last_samples; ra.fmt = a->last_fmt;
-    ra.starts = a->drift.on ? a->drift.d_starts : nullptr; ra.R = a->drift.on ? a->drift.R : 0u;
-    ra.tables = a->d_tables; ra.code_samples = a->d_code_samples;
+    acq_cell_args(ra, a, in, in_fmt, R_u);
+    acq_grid_args(ra, a, common, reinterpret_cast<cf*>(base + o_z), cg);
     ra.sats = reinterpret_cast<const gm::RefineSat*>(base + o_sat); ra.n_sats = S;
-    ra.N = N; ra.R_u = R_u; ra.J = J; ra.G = G; ra.Z = Z;
-    ra.neg = (a->K >= 2 && a->edge.H) ? a->edge.neg : 0u;
-    ra.z = reinterpret_cast<cf*>(base + o_z); ra.t = reinterpret_cast<const double*>(base + o_t);
-    ra.fc = reinterpret_cast<const double*>(base + o_fc); ra.step = reinterpret_cast<const double*>(base + o_step);
     ra.spectrum = reinterpret_cast<float*>(base + o_spec);
     ra.peak_val = reinterpret_cast<float*>(base + o_pv); ra.peak_idx = reinterpret_cast<uint32_t*>(base + o_pi);
     gm::launch_refine(a->stream, ra);
@@ -2036,15 +2096,10 @@ int gm_acq_refine_doppler(gm_acq* a, const gm_acq_result* results, const uint8_t
         const uint32_t pk = pi[i] < Z ? pi[i] : (Z - 1) / 2;      // (no comparable value at all, e.g. samples that are not numbers: the centre)
         gm_acq_refine_out& r = out[p];
         r.at_edge = (pk == 0 || pk == Z - 1) ? 1u : 0u;
-        double delta = (double(pk) - double((Z - 1) / 2)) * step[i];
-        if (!r.at_edge) {                   // three-point parabola through the peak and its neighbours, f64
-            const double y0 = sp[pk - 1], y1 = sp[pk], y2 = sp[pk + 1], den = y0 - 2.0 * y1 + y2;
-            double x = den < 0.0 ? 0.5 * (y0 - y2) / den : 0.0;
-            x = x > 0.5 ? 0.5 : (x < -0.5 ? -0.5 : x);
-            delta += x * step[i];
-        }
-        r.carrier_hz = fc[i] + delta;
-        r.delta_hz = float(delta); r.step_hz = float(step[i]); r.half_span_hz = float(plans[p].half_span);
+        double delta = (double(pk) - double((Z - 1) / 2)) * cg.step[i];
+        if (!r.at_edge) delta += parabola_offset(sp[pk - 1], sp[pk], sp[pk + 1]) * cg.step[i];     // through the peak and its neighbours
+        r.carrier_hz = cg.fc[i] + delta;
+        r.delta_hz = float(delta); r.step_hz = float(cg.step[i]); r.half_span_hz = float(plans[p].half_span);
         r.peak_power = sp[pk]; r.center_power = sp[(Z - 1) / 2];
         r.peak_index = pk;
         r.doppler_bin = sats[i].bin; r.offset_periods = sats[i].offset; r.span_periods = J; r.n_groups = G; r.n_freq = Z;
@@ -2081,22 +2136,12 @@ int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const 
     return GM_OK;
 }
 
-// the rules of a known cell (gm_acq_cand), shared by gm_acq_local_search and gm_acq_array_prompts
-static int acq_cand_rules(const gm_acq* a, const gm_acq_cand& c) {
-    if (c.worker >= a->P) return set_err(GM_ERR_INVALID_ARG, "candidate.worker outside the handle's workers");
-    if (c.doppler_bin < 0 || uint32_t(c.doppler_bin) >= a->D) return set_err(GM_ERR_INVALID_ARG, "candidate.doppler_bin outside the handle's bins");
-    if (c.code_phase_samples >= a->N) return set_err(GM_ERR_INVALID_ARG, "candidate.code_phase_samples >= fft_size");
-    if (c.offset_periods > (a->edge.H ? a->edge.o_max : 0u))
-        return set_err(GM_ERR_INVALID_ARG, "candidate.offset_periods above the edge search's last offset (0 without an edge search)");
-    return GM_OK;
-}
-
 int gm_acq_local_search(gm_acq* a, const void* d_samples, int fmt, const gm_acq_cand* cands, uint32_t n_cands,
                         const gm_acq_local_cfg* cfg, gm_acq_local_out* out, gm_c32* prompts, float* surface) {
     if (!a || !cands || !out) return set_err(GM_ERR_INVALID_ARG, "null pointer");
-    if (d_samples) {
-        if (fmt < GM_FMT_C32 || fmt > GM_FMT_I8_REAL) return set_err(GM_ERR_INVALID_ARG, "bad sample format");
-    } else if (!a->last_samples) return set_err(GM_ERR_INVALID_ARG, "no search has run on this handle yet");
+    const void* in = nullptr;
+    int in_fmt = 0;
+    if (int rc = acq_call_input(a, d_samples, fmt, &in, &in_fmt)) return rc;
     const uint32_t N = a->N, D = a->D;
     const double fs = double(a->cfg.fs);
     // every argument is checked before anything runs or is written
@@ -2116,54 +2161,30 @@ int gm_acq_local_search(gm_acq* a, const void* d_samples, int fmt, const gm_acq_
     const uint32_t S = n_cands, W = 2 * L + 1, J = common.J, G = common.G, Z = common.Z, R_u = J * G;
     const size_t rows = size_t(S) * W;
     // the block: [cands | z | t | fc | step | surface | row maxima | row indices | row sums | picks], every part 256-byte aligned
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_cand = 0, o_z = o_cand + up(size_t(S) * sizeof(gm::RefineSat)), o_t = o_z + up(rows * R_u * 8),
-                 o_fc = o_t + up(size_t(S) * R_u * 8), o_step = o_fc + up(size_t(S) * 8), o_surf = o_step + up(size_t(S) * 8),
-                 o_rv = o_surf + up(rows * Z * 4), o_ri = o_rv + up(rows * 4), o_rs = o_ri + up(rows * 4), o_pk = o_rs + up(rows * 8),
-                 total = o_pk + up(size_t(S) * sizeof(gm::LocalPick));
-    gm_acq::Local& lc = a->local;
-    if (total > lc.bytes) {                 // the new block before the old one goes: a failure leaves the handle as it was
-        void* blk = nullptr;
-        if (hipMalloc(&blk, total) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(GM_ERR_NOMEM, "the local-search block does not fit (gnss_mi355x.h states the formula); the handle is as it was");
-        }
-        if (hipError_t e = hipStreamSynchronize(a->stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
-        hipFree(lc.d_block);
-        lc.d_block = blk; lc.bytes = total;
-    }
-    char* const base = static_cast<char*>(lc.d_block);
-    // host side of the block's inputs, as gm_acq_refine_doppler forms them: the period times of every group (f64, relative to the
-    // group's first period: whole samples over fs), the centre frequency and the grid step
+    Carve cv;
+    const size_t o_cand = cv.take(size_t(S) * sizeof(gm::RefineSat)), o_z = cv.take(rows * R_u * 8), o_t = cv.take(size_t(S) * R_u * 8),
+                 o_fc = cv.take(size_t(S) * 8), o_step = cv.take(size_t(S) * 8), o_surf = cv.take(rows * Z * 4), o_rv = cv.take(rows * 4),
+                 o_ri = cv.take(rows * 4), o_rs = cv.take(rows * 8), o_pk = cv.take(size_t(S) * sizeof(gm::LocalPick));
+    if (int rc = a->local.reserve(a->stream, cv.end,
+                                  "the local-search block does not fit (gnss_mi355x.h states the formula); the handle is as it was"))
+        return rc;
+    char* const base = static_cast<char*>(a->local.d);
+    // host side of the block's inputs: the candidates, and the grid of their cells
     std::vector<gm::RefineSat> cs(S);
-    std::vector<double> t(size_t(S) * R_u), fc(S), step(S);
+    CellGrid cg;
+    cg.step.resize(S);
     for (uint32_t c = 0; c < S; ++c) {
-        const uint32_t d = uint32_t(cands[c].doppler_bin), o = cands[c].offset_periods;
-        cs[c] = gm::RefineSat{cands[c].worker, cands[c].code_phase_samples, d, o};
-        fc[c] = double(a->table_freq[d]);
-        step[c] = plans[c].step;
-        for (uint32_t g = 0; g < G; ++g)
-            for (uint32_t k = 0; k < J; ++k) {
-                const uint32_t q0 = o + g * J, q = q0 + k;
-                const uint64_t s0 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q0] : uint64_t(q0) * N;
-                const uint64_t s1 = a->drift.on ? a->drift.starts[size_t(d) * a->drift.R + q] : uint64_t(q) * N;
-                t[size_t(c) * R_u + g * J + k] = double(s1 - s0) / fs;
-            }
+        cs[c] = acq_cand_cell(cands[c]);
+        cg.step[c] = plans[c].step;
     }
     HIPC(hipMemcpyAsync(base + o_cand, cs.data(), size_t(S) * sizeof(gm::RefineSat), hipMemcpyHostToDevice, a->stream));
-    HIPC(hipMemcpyAsync(base + o_t, t.data(), t.size() * 8, hipMemcpyHostToDevice, a->stream));
-    HIPC(hipMemcpyAsync(base + o_fc, fc.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
-    HIPC(hipMemcpyAsync(base + o_step, step.data(), size_t(S) * 8, hipMemcpyHostToDevice, a->stream));
+    if (int rc = acq_cell_grid(a, cs, J, G, base + o_t, base + o_fc, base + o_step, cg)) return rc;
     gm::LocalArgs la{};
-    la.samples = d_samples ? d_samples : a->last_samples; la.fmt = d_samples ? fmt : a->last_fmt;
-    la.starts = a->drift.on ? a->drift.d_starts : nullptr; la.R = a->drift.on ? a->drift.R : 0u;
-    la.tables = a->d_tables; la.code_samples = a->d_code_samples;
+    acq_cell_args(la, a, in, in_fmt, R_u);
+    acq_grid_args(la, a, common, reinterpret_cast<cf*>(base + o_z), cg);
     la.cands = reinterpret_cast<const gm::RefineSat*>(base + o_cand); la.n_cands = S;
-    la.N = N; la.R_u = R_u; la.J = J; la.G = G; la.Z = Z; la.L = L;
-    la.neg = (a->K >= 2 && a->edge.H) ? a->edge.neg : 0u;
+    la.L = L;
     la.guard = uint32_t(::ceil(fs / double(a->code_rate))) + 1u;
-    la.z = reinterpret_cast<cf*>(base + o_z); la.t = reinterpret_cast<const double*>(base + o_t);
-    la.fc = reinterpret_cast<const double*>(base + o_fc); la.step = reinterpret_cast<const double*>(base + o_step);
     la.surface = reinterpret_cast<float*>(base + o_surf);
     la.row_val = reinterpret_cast<float*>(base + o_rv); la.row_idx = reinterpret_cast<uint32_t*>(base + o_ri);
     la.row_sum = reinterpret_cast<double*>(base + o_rs); la.picks = reinterpret_cast<gm::LocalPick*>(base + o_pk);
@@ -2180,15 +2201,10 @@ int gm_acq_local_search(gm_acq* a, const void* d_samples, int fmt, const gm_acq_
         const uint32_t d = cs[c].bin, o = cs[c].offset, ls = p.l < W ? p.l : L, js = p.j < Z ? p.j : (Z - 1) / 2;
         gm_acq_local_out& r = out[c];
         r.freq_at_edge = (js == 0 || js == Z - 1) ? 1u : 0u;
-        double delta = (double(js) - double((Z - 1) / 2)) * step[c];
-        if (!r.freq_at_edge) {              // gm_acq_refine_doppler's three-point parabola along j, f64
-            const double y0 = p.s_jm, y1 = p.s0, y2 = p.s_jp, den = y0 - 2.0 * y1 + y2;
-            double x = den < 0.0 ? 0.5 * (y0 - y2) / den : 0.0;
-            x = x > 0.5 ? 0.5 : (x < -0.5 ? -0.5 : x);
-            delta += x * step[c];
-        }
-        r.carrier_hz = fc[c] + delta;
-        r.delta_hz = float(delta); r.step_hz = float(step[c]); r.half_span_hz = float(plans[c].half_span);
+        double delta = (double(js) - double((Z - 1) / 2)) * cg.step[c];
+        if (!r.freq_at_edge) delta += parabola_offset(p.s_jm, p.s0, p.s_jp) * cg.step[c];         // along j
+        r.carrier_hz = cg.fc[c] + delta;
+        r.delta_hz = float(delta); r.step_hz = float(cg.step[c]); r.half_span_hz = float(plans[c].half_span);
         r.peak_power = p.s0;
         r.floor_power = p.n_floor ? float(p.floor_sum / (double(p.n_floor) * double(Z))) : 0.0f;
         r.n_floor = p.n_floor;
@@ -2260,31 +2276,20 @@ int gm_acq_array_prompts(gm_acq* a, const void* d_samples, int fmt, uint32_t n_a
     if (int rc = ensure_device(a->device)) return rc;
     if (int rc = acq_flush_decision(a)) return rc;
     // the block: [cands | z], each part 256-byte aligned
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t z_bytes = size_t(n_cands) * words * 8;
-    const size_t o_cand = 0, o_z = o_cand + up(size_t(n_cands) * sizeof(gm::RefineSat)), total = o_z + up(z_bytes);
-    gm_acq::Array& ar = a->array;
-    if (total > ar.bytes) {                 // the new block before the old one goes: a failure leaves the handle as it was
-        void* blk = nullptr;
-        if (hipMalloc(&blk, total) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(GM_ERR_NOMEM, "the array-prompts block does not fit (gnss_mi355x.h states the formula); the handle is as it was");
-        }
-        if (hipError_t e = hipStreamSynchronize(a->stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
-        hipFree(ar.d_block);
-        ar.d_block = blk; ar.bytes = total;
-    }
-    char* const base = static_cast<char*>(ar.d_block);
+    Carve cv;
+    const size_t o_cand = cv.take(size_t(n_cands) * sizeof(gm::RefineSat)), o_z = cv.take(z_bytes);
+    if (int rc = a->array.reserve(a->stream, cv.end,
+                                  "the array-prompts block does not fit (gnss_mi355x.h states the formula); the handle is as it was"))
+        return rc;
+    char* const base = static_cast<char*>(a->array.d);
     std::vector<gm::RefineSat> cs(n_cands);
-    for (uint32_t c = 0; c < n_cands; ++c)
-        cs[c] = gm::RefineSat{cands[c].worker, cands[c].code_phase_samples, uint32_t(cands[c].doppler_bin), cands[c].offset_periods};
+    for (uint32_t c = 0; c < n_cands; ++c) cs[c] = acq_cand_cell(cands[c]);
     HIPC(hipMemcpyAsync(base + o_cand, cs.data(), size_t(n_cands) * sizeof(gm::RefineSat), hipMemcpyHostToDevice, a->stream));
     gm::ArrayArgs aa{};
-    aa.samples = d_samples; aa.fmt = fmt;
-    aa.starts = a->drift.on ? a->drift.d_starts : nullptr; aa.R = a->drift.on ? a->drift.R : 0u;
-    aa.tables = a->d_tables; aa.code_samples = a->d_code_samples;
+    acq_cell_args(aa, a, d_samples, fmt, R_u);
     aa.cands = reinterpret_cast<const gm::RefineSat*>(base + o_cand); aa.n_cands = n_cands;
-    aa.N = a->N; aa.R_u = R_u; aa.A = n_antennas; aa.L = taps;
+    aa.A = n_antennas; aa.L = taps;
     aa.z = reinterpret_cast<cf*>(base + o_z);
     gm::launch_array(a->stream, aa);
     HIPC(hipGetLastError());
@@ -2503,17 +2508,15 @@ int gm_acq_cancel(gm_acq* a, const void* d_samples, int fmt, const gm_acq_cancel
                   gm_acq_cancel_out* out, gm_c32* amps, uint32_t amps_stride) {
     if (!a || (!cands && n_cands) || !d_out) return set_err(GM_ERR_INVALID_ARG, "null pointer");
     if (n_cands > 64) return set_err(GM_ERR_INVALID_ARG, "more than 64 candidates");
-    if (d_samples) {
-        if (fmt < GM_FMT_C32 || fmt > GM_FMT_I8_REAL) return set_err(GM_ERR_INVALID_ARG, "bad sample format");
-    } else if (!a->last_samples) return set_err(GM_ERR_INVALID_ARG, "no search has run on this handle yet");
-    const void* const in = d_samples ? d_samples : a->last_samples;
-    const int in_fmt = d_samples ? fmt : a->last_fmt;
+    const void* in = nullptr;
+    int in_fmt = 0;
+    if (int rc = acq_call_input(a, d_samples, fmt, &in, &in_fmt)) return rc;
     const uint32_t N = a->N;
     const uint64_t D = acq_dwell_samples(a);
     const double fs = double(a->cfg.fs);
     // every argument is checked before anything runs or is written
     {   // the output may be the c32 input itself (in place); any other overlap of the two ranges is refused
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + D * (in_fmt == GM_FMT_C32 ? 8u : (in_fmt == GM_FMT_I8_IQ ? 2u : 1u));
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + D * fmt_bytes(in_fmt);
         const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + D * 8u;
         if (!(o0 == i0 && in_fmt == GM_FMT_C32) && o0 < i1 && i0 < o1)
             return set_err(GM_ERR_INVALID_ARG, "d_out overlaps the input (only d_out == the c32 input itself is allowed)");
@@ -2532,8 +2535,7 @@ int gm_acq_cancel(gm_acq* a, const void* d_samples, int fmt, const gm_acq_cancel
     if (amps && amps_stride < q_max) return set_err(GM_ERR_INVALID_ARG, "amps_stride below the largest n_segments");
     if (int rc = ensure_device(a->device)) return rc;
     if (int rc = acq_flush_decision(a)) return rc;
-    gm_acq::Cancel& cn = a->cancel;
-    if (!cn.d_chips) {
+    if (!a->d_cancel_chips) {
         int8_t* chips = nullptr;
         if (hipMalloc(&chips, a->chips.size()) != hipSuccess) {
             (void)hipGetLastError();
@@ -2543,25 +2545,17 @@ int gm_acq_cancel(gm_acq* a, const void* d_samples, int fmt, const gm_acq_cancel
             hipFree(chips);
             return hip_fail(e, "hipMemcpy");
         }
-        cn.d_chips = chips;
+        a->d_cancel_chips = chips;
     }
     // the block: [candidate constants | o | b | amplitudes], every part 256-byte aligned; the tables are [n_cands][stride]
     const uint32_t S = n_cands, stride = q_max + 1;
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t cells = size_t(S) * stride;
-    const size_t o_cand = 0, o_o = o_cand + up(size_t(S) * sizeof(gm::CancelCand)), o_b = o_o + up(cells * 8), o_a = o_b + up(cells * 8),
-                 total = o_a + up(cells * 8) + 256;
-    if (total > cn.bytes) {                 // the new block before the old one goes: a failure leaves the handle as it was
-        void* blk = nullptr;
-        if (hipMalloc(&blk, total) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(GM_ERR_NOMEM, "the cancellation block does not fit (gnss_mi355x.h states the formula); the handle is as it was");
-        }
-        if (hipError_t e = hipStreamSynchronize(a->stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
-        hipFree(cn.d_block);
-        cn.d_block = blk; cn.bytes = total;
-    }
-    char* const base = static_cast<char*>(cn.d_block);
+    Carve cv;
+    const size_t o_cand = cv.take(size_t(S) * sizeof(gm::CancelCand)), o_o = cv.take(cells * 8), o_b = cv.take(cells * 8), o_a = cv.take(cells * 8);
+    if (int rc = a->cancel.reserve(a->stream, cv.end + 256,          // (the block ends 256 bytes behind the amplitudes)
+                                   "the cancellation block does not fit (gnss_mi355x.h states the formula); the handle is as it was"))
+        return rc;
+    char* const base = static_cast<char*>(a->cancel.d);
     std::vector<gm::CancelCand> cs(S);
     std::vector<double> o(cells, 0.0);
     std::vector<uint64_t> b(cells, D);
@@ -2581,7 +2575,7 @@ int gm_acq_cancel(gm_acq* a, const void* d_samples, int fmt, const gm_acq_cancel
     ca.samples = in; ca.fmt = in_fmt; ca.D = D;
     ca.cands = reinterpret_cast<const gm::CancelCand*>(base + o_cand); ca.n_cands = S; ca.q_max = q_max; ca.stride = stride;
     ca.o = reinterpret_cast<const double*>(base + o_o); ca.b = reinterpret_cast<const uint64_t*>(base + o_b);
-    ca.chips = cn.d_chips;
+    ca.chips = a->d_cancel_chips;
     ca.amps = reinterpret_cast<cf*>(base + o_a); ca.out = static_cast<cf*>(d_out);
     gm::launch_cancel(a->stream, ca);
     HIPC(hipGetLastError());
@@ -2934,10 +2928,9 @@ struct gm_trk {
     uint8_t* tk_block = nullptr;          // ONE pinned allocation cut into the TICKETS slots (a pinned allocation costs ~1 ms: not per slot, not in a receiver's loop)
     size_t tk_cap = 0;                    // bytes per slot
     uint64_t next_ticket = 1;
-    // gm_trk_bank: one device block per call shape, [records | taps | offsets | out | done | partials] (trk_bank_run), grown on demand
-    uint8_t* d_bank = nullptr; size_t bank_cap = 0;
-    // gm_trk_array_prompts: one device block per call shape, [records | z | done | partials], grown on demand
-    uint8_t* d_array = nullptr; size_t array_cap = 0;
+    // the known-record entries' device blocks: gm_trk_bank's [records | taps | offsets | out | done | partials] (trk_bank_run) and
+    // gm_trk_array_prompts' [records | z | done | partials]
+    CallBlock bank, array;
 };
 
 static int trk_check_error(gm_trk* t);
@@ -2996,7 +2989,7 @@ int gm_trk_destroy(gm_trk* t) {
     if (!t) return GM_OK;
     if (t->device >= 0) hipSetDevice(t->device);
     hipFree(t->d_codes); hipFree(t->d_states); hipFree(t->d_partials); hipFree(t->d_ready); hipFree(t->d_scratch); hipFree(t->d_terms);
-    hipFree(t->d_res); hipFree(t->d_bank); hipFree(t->d_array);
+    hipFree(t->d_res); t->bank.release(); t->array.release();
     if (t->h_res) hipHostFree(t->h_res);
     for (auto& k : t->tk) if (k.done) hipEventDestroy(k.done);
     if (t->tk_block) hipHostFree(t->tk_block);
@@ -3304,12 +3297,75 @@ int gm_trk_do_work(gm_trk* t, uint32_t ch, const gm_c32* samples, size_t n, gm_t
 }  // extern "C"
 
 // ---- gm_trk_bank: taps x carrier offsets at caller-supplied records (gnss_mi355x.h states the definition and the limits) -------------
+// ---- known records on gm_trk: what gm_trk_bank and gm_trk_array_prompts share beyond CallBlock and Carve ---------------------------------
+// the rules both plans begin with
+static int trk_call_rules(const void* cfg, const char* null_cfg_text, float fs, bool custom_codes, uint32_t n_codes, uint32_t code_len) {
+    if (!cfg) return set_err(GM_ERR_INVALID_ARG, null_cfg_text);
+    if (!(fs > 0) || !std::isfinite(fs)) return set_err(GM_ERR_INVALID_ARG, "fs is required");
+    if (custom_codes && (!n_codes || !code_len)) return set_err(GM_ERR_INVALID_ARG, "n_codes/code_len required");
+    return GM_OK;
+}
+static int trk_call_states_rule(const gm_trk* t, const gm_trk_state* states, uint32_t n_states) {
+    if (!states && n_states != t->C) return set_err(GM_ERR_INVALID_ARG, "states NULL: n_states must be n_channels");
+    return GM_OK;
+}
+// n = round(fs / (code_rate / code_len)) as the tracker forms it (trk_kernels.hip samples_per_code); false: a record with this n is skipped
+static bool trk_bank_samples_per_code(float fs, float code_rate, float lenf, uint32_t& n) {
+    const float v = roundf(fs / (code_rate / lenf));
+    n = 0;
+    if (!(v > 0.0f) || !(v < 2147483648.0f)) return false;
+    n = uint32_t(v);
+    return true;
+}
+static int trk_bank_row(const gm_trk* t, const gm_trk_state& s) {      // trk_kernels.hip code_row
+    return t->dc.gps_ca ? (t->dc.code_index_mode == GM_CODE_INDEX_FAITHFUL ? int(s.prn) : int(s.prn) - 1) : int(s.prn) - 1;
+}
+// the records of a call, from `states` or the handle's own channels as they stand: n, and run = active with a code row and a sample
+// count; the caller's window gate may clear run
+static int trk_call_records(gm_trk* t, const gm_trk_state* states, uint32_t n_states, std::vector<gm::TrkBankRec>& recs) {
+    recs.assign(n_states, gm::TrkBankRec{});
+    if (states) {
+        for (uint32_t r = 0; r < n_states; ++r) recs[r].st = states[r];
+    } else {
+        std::vector<gm_trk_state> own(t->C);
+        if (int rc = gm_trk_get_states(t, own.data())) return rc;
+        for (uint32_t r = 0; r < n_states; ++r) recs[r].st = own[r];
+    }
+    for (auto& r : recs) {
+        const int row = trk_bank_row(t, r.st);
+        r.run = (r.st.active && row >= 0 && row < t->dc.n_codes && trk_bank_samples_per_code(t->dc.fs, r.st.code_rate, t->dc.code_len_f, r.n)) ? 1 : 0;
+    }
+    return GM_OK;
+}
+// slices of `slice` samples and the first partial of every record (none, and n = 0, for a record that does not run)
+static int trk_call_slices(std::vector<gm::TrkBankRec>& recs, uint32_t slice, uint64_t& total, uint32_t& max_slices) {
+    total = 0; max_slices = 0;
+    for (auto& r : recs) {
+        if (!r.run) r.n = 0;
+        r.slices = r.run ? (r.n + slice - 1) / slice : 0;
+        if (total + r.slices > 0xffffffffull) return set_err(GM_ERR_NOMEM, "the call's partial sums exceed 2^32 slices");
+        r.poff = uint32_t(total);
+        total += r.slices;
+        if (r.slices > max_slices) max_slices = r.slices;
+    }
+    return GM_OK;
+}
+// the results land in host blocks of the call's own and reach the caller's only once everything has succeeded
+static int trk_call_finish(gm_trk* t, const uint8_t* d_words, size_t n_words, const uint8_t* d_done, uint32_t R, gm_c32* out, uint8_t* done) {
+    std::vector<gm_c32> h_out(n_words);
+    std::vector<uint8_t> h_done(R);
+    HIPC(hipMemcpyAsync(h_out.data(), d_words, n_words * 8, hipMemcpyDeviceToHost, t->stream));
+    HIPC(hipMemcpyAsync(h_done.data(), d_done, R, hipMemcpyDeviceToHost, t->stream));
+    HIPC(hipStreamSynchronize(t->stream));
+    memcpy(out, h_out.data(), n_words * 8);
+    if (done) memcpy(done, h_done.data(), R);
+    return GM_OK;
+}
+
 // gm_trk_bank_plan's argument rules, shared by the device entries; F: the effective number of offsets
 static int trk_bank_rules(float fs, bool custom_codes, uint32_t n_codes, uint32_t code_len, const gm_trk_bank_cfg* cfg, uint32_t n_states,
                           uint32_t& F) {
-    if (!cfg) return set_err(GM_ERR_INVALID_ARG, "null bank cfg");
-    if (!(fs > 0) || !std::isfinite(fs)) return set_err(GM_ERR_INVALID_ARG, "fs is required");
-    if (custom_codes && (!n_codes || !code_len)) return set_err(GM_ERR_INVALID_ARG, "n_codes/code_len required");
+    if (int rc = trk_call_rules(cfg, "null bank cfg", fs, custom_codes, n_codes, code_len)) return rc;
     // the chip row shares the workgroup's 64 KB of LDS with the slice's samples and sign words (44 KB, trk_bank.hip)
     if (custom_codes && code_len > 16384) return set_err(GM_ERR_OUT_OF_RANGE, "the bank serves codes of at most 16384 chips");
     if (!cfg->taps_chips) return set_err(GM_ERR_INVALID_ARG, "null taps_chips");
@@ -3332,43 +3388,21 @@ static int trk_bank_rules(float fs, bool custom_codes, uint32_t n_codes, uint32_
     }
     return GM_OK;
 }
-// n = round(fs / (code_rate / code_len)) as the tracker forms it (trk_kernels.hip samples_per_code); false: a record with this n is skipped
-static bool trk_bank_samples_per_code(float fs, float code_rate, float lenf, uint32_t& n) {
-    const float v = roundf(fs / (code_rate / lenf));
-    n = 0;
-    if (!(v > 0.0f) || !(v < 2147483648.0f)) return false;
-    n = uint32_t(v);
-    return true;
-}
-static int trk_bank_row(const gm_trk* t, const gm_trk_state& s) {      // trk_kernels.hip code_row
-    return t->dc.gps_ca ? (t->dc.code_index_mode == GM_CODE_INDEX_FAITHFUL ? int(s.prn) : int(s.prn) - 1) : int(s.prn) - 1;
-}
 // the launch and the copies of both forms: recs carry st, n and run; slices and partial offsets are filled in here
 static int trk_bank_run(gm_trk* t, std::vector<gm::TrkBankRec>& recs, const gm_trk_bank_cfg* cfg, uint32_t F, const cf* base, uint64_t mask,
                         int linear, gm_c32* out, uint8_t* done) {
     const uint32_t R = uint32_t(recs.size()), T = cfg->n_taps;
     uint64_t total = 0;
     uint32_t max_slices = 0;
-    for (auto& r : recs) {
-        r.slices = r.run ? (r.n + gm::GM_TRK_BANK_SLICE - 1) / gm::GM_TRK_BANK_SLICE : 0;
-        if (total + r.slices > 0xffffffffull) return set_err(GM_ERR_NOMEM, "the call's partial sums exceed 2^32 slices");
-        r.poff = uint32_t(total);
-        total += r.slices;
-        if (r.slices > max_slices) max_slices = r.slices;
-    }
+    if (int rc = trk_call_slices(recs, gm::GM_TRK_BANK_SLICE, total, max_slices)) return rc;
     std::vector<float> offs(F, 0.0f);
     for (uint32_t k = 0; k < cfg->n_offsets; ++k) offs[k] = cfg->offsets_hz[k];
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t words = size_t(F) * T;
-    const size_t o_recs = 0, o_taps = o_recs + up(R * sizeof(gm::TrkBankRec)), o_offs = o_taps + up(T * 4), o_out = o_offs + up(F * 4),
-                 o_done = o_out + up(R * words * 8), o_part = o_done + up(R), bytes = o_part + up(size_t(total) * words * 8);
-    if (bytes > t->bank_cap) {
-        HIPC(hipStreamSynchronize(t->stream));
-        hipFree(t->d_bank); t->d_bank = nullptr; t->bank_cap = 0;
-        if (hipMalloc(&t->d_bank, bytes) != hipSuccess) { (void)hipGetLastError(); t->d_bank = nullptr; return set_err(GM_ERR_NOMEM, "gm_trk_bank: device block"); }
-        t->bank_cap = bytes;
-    }
-    uint8_t* d = t->d_bank;
+    Carve cv;
+    const size_t o_recs = cv.take(R * sizeof(gm::TrkBankRec)), o_taps = cv.take(T * 4), o_offs = cv.take(F * 4), o_out = cv.take(R * words * 8),
+                 o_done = cv.take(R), o_part = cv.take(size_t(total) * words * 8);
+    if (int rc = t->bank.reserve(t->stream, cv.end, "gm_trk_bank: device block")) return rc;
+    uint8_t* d = static_cast<uint8_t*>(t->bank.d);
     HIPC(hipMemcpyAsync(d + o_recs, recs.data(), R * sizeof(gm::TrkBankRec), hipMemcpyHostToDevice, t->stream));
     HIPC(hipMemcpyAsync(d + o_taps, cfg->taps_chips, T * 4, hipMemcpyHostToDevice, t->stream));
     HIPC(hipMemcpyAsync(d + o_offs, offs.data(), F * 4, hipMemcpyHostToDevice, t->stream));
@@ -3380,23 +3414,13 @@ static int trk_bank_run(gm_trk* t, std::vector<gm::TrkBankRec>& recs, const gm_t
     a.partials = reinterpret_cast<float*>(d + o_part);
     gm::launch_trk_bank(t->stream, t->dc, t->d_codes, a, int(R), max_slices, reinterpret_cast<gm_c32*>(d + o_out), d + o_done);
     HIPC(hipGetLastError());
-    // the results land in host blocks of the call's own and reach the caller's only once everything has succeeded
-    std::vector<gm_c32> h_out(size_t(R) * words);
-    std::vector<uint8_t> h_done(R);
-    HIPC(hipMemcpyAsync(h_out.data(), d + o_out, h_out.size() * 8, hipMemcpyDeviceToHost, t->stream));
-    HIPC(hipMemcpyAsync(h_done.data(), d + o_done, R, hipMemcpyDeviceToHost, t->stream));
-    HIPC(hipStreamSynchronize(t->stream));
-    memcpy(out, h_out.data(), h_out.size() * 8);
-    if (done) memcpy(done, h_done.data(), R);
-    return GM_OK;
+    return trk_call_finish(t, d + o_out, size_t(R) * words, d + o_done, R, out, done);
 }
 
 // ---- gm_trk_array_prompts: per-antenna, per-tap prompts of an array stream at caller-supplied records (gnss_mi355x.h states the
 // definition and the limits) -- gm_trk_array_plan's argument rules, shared by the device entry
 static int trk_array_rules(float fs, bool custom_codes, uint32_t n_codes, uint32_t code_len, const gm_trk_array_cfg* cfg, uint32_t n_states) {
-    if (!cfg) return set_err(GM_ERR_INVALID_ARG, "null array cfg");
-    if (!(fs > 0) || !std::isfinite(fs)) return set_err(GM_ERR_INVALID_ARG, "fs is required");
-    if (custom_codes && (!n_codes || !code_len)) return set_err(GM_ERR_INVALID_ARG, "n_codes/code_len required");
+    if (int rc = trk_call_rules(cfg, "null array cfg", fs, custom_codes, n_codes, code_len)) return rc;
     for (uint32_t v : cfg->reserved)
         if (v) return set_err(GM_ERR_INVALID_ARG, "gm_trk_array_cfg.reserved must be 0");
     if (!std::isfinite(cfg->tap_chips)) return set_err(GM_ERR_INVALID_ARG, "tap_chips is not finite");
@@ -3436,28 +3460,18 @@ int gm_trk_bank(gm_trk* t, gm_ring* ring, const gm_trk_state* states, uint32_t n
                 uint8_t* done) {
     if (!t || !ring || !out) return set_err(GM_ERR_INVALID_ARG, "null handle, ring or out");
     if (t->device != ring->device) return set_err(GM_ERR_INVALID_ARG, "ring lives on another device");
-    if (!states && n_states != t->C) return set_err(GM_ERR_INVALID_ARG, "states NULL: n_states must be n_channels");
+    if (int rc = trk_call_states_rule(t, states, n_states)) return rc;
     uint32_t F = 0;
     if (int rc = trk_bank_rules(t->dc.fs, !t->dc.gps_ca, uint32_t(t->dc.n_codes), uint32_t(t->dc.code_len), cfg, n_states, F)) return rc;
     if (int rc = ensure_device(t->device)) return rc;
-    std::vector<gm::TrkBankRec> recs(n_states);
-    if (states) {
-        for (uint32_t r = 0; r < n_states; ++r) recs[r].st = states[r];
-    } else {        // the handle's own channels as they stand
-        std::vector<gm_trk_state> own(t->C);
-        if (int rc = gm_trk_get_states(t, own.data())) return rc;
-        for (uint32_t r = 0; r < n_states; ++r) recs[r].st = own[r];
-    }
+    std::vector<gm::TrkBankRec> recs;
+    if (int rc = trk_call_records(t, states, n_states, recs)) return rc;
     ring_refresh_head(ring);
     const uint64_t head = ring->head.load(std::memory_order_acquire);      // the PUBLISHED head, as gm_trk_update_all reads it
     for (auto& r : recs) {
-        const gm_trk_state& s = r.st;
-        const int row = trk_bank_row(t, s);
-        bool run = s.active && row >= 0 && row < t->dc.n_codes && trk_bank_samples_per_code(t->dc.fs, s.code_rate, t->dc.code_len_f, r.n);
-        if (run) run = int64_t(head - (s.next_sample_index + r.n)) >= 0;      // the tracker's gate (:170-172)
-        if (run) run = head - s.next_sample_index <= uint64_t(ring->size);   // the epoch's first sample is still in the ring
-        r.run = run ? 1 : 0; r.slices = 0; r.poff = 0;
-        if (!run) r.n = 0;
+        const uint64_t start = r.st.next_sample_index;
+        if (r.run && int64_t(head - (start + r.n)) < 0) r.run = 0;            // the tracker's gate (:170-172)
+        if (r.run && head - start > uint64_t(ring->size)) r.run = 0;          // the epoch's first sample is no longer in the ring
     }
     return trk_bank_run(t, recs, cfg, F, ring->d_buf, ring->mask, 0, out, done);
 }
@@ -3502,49 +3516,30 @@ int gm_trk_array_prompts(gm_trk* t, const void* d_samples, int fmt, uint64_t fir
                          uint32_t n_states, const gm_trk_array_cfg* cfg, gm_c32* z, uint8_t* done) {
     if (!t || !d_samples || !z) return set_err(GM_ERR_INVALID_ARG, "null handle, samples or z");
     if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "fmt must be GM_FMT_C32 or GM_FMT_I8_IQ");
-    if (!states && n_states != t->C) return set_err(GM_ERR_INVALID_ARG, "states NULL: n_states must be n_channels");
+    if (int rc = trk_call_states_rule(t, states, n_states)) return rc;
     if (int rc = trk_array_rules(t->dc.fs, !t->dc.gps_ca, uint32_t(t->dc.n_codes), uint32_t(t->dc.code_len), cfg, n_states)) return rc;
     constexpr uint64_t INDEX_MAX = 1ull << 62;
     if (first_index >= INDEX_MAX || n_time >= INDEX_MAX || first_index + n_time >= INDEX_MAX)
         return set_err(GM_ERR_OUT_OF_RANGE, "first_index + n_time must be below 2^62");
     if (int rc = ensure_device(t->device)) return rc;
     const uint32_t R = n_states, A = cfg->n_antennas, L = cfg->taps, M = A * L;
-    std::vector<gm::TrkBankRec> recs(R);
-    if (states) {
-        for (uint32_t r = 0; r < R; ++r) recs[r].st = states[r];
-    } else {        // the handle's own channels as they stand
-        std::vector<gm_trk_state> own(t->C);
-        if (int rc = gm_trk_get_states(t, own.data())) return rc;
-        for (uint32_t r = 0; r < R; ++r) recs[r].st = own[r];
-    }
+    std::vector<gm::TrkBankRec> recs;
+    if (int rc = trk_call_records(t, states, n_states, recs)) return rc;
     // which records run: the kernel reads the time samples [max(0, s - (L-1)), s + n) of a record that does, and nothing else
     const uint64_t H = L - 1;
+    for (auto& r : recs) {
+        const uint64_t start = r.st.next_sample_index;
+        if (r.run && (start > H ? start - H : 0) < first_index) r.run = 0;                          // the halo is in front of the buffer
+        if (r.run && !(start - first_index <= n_time && uint64_t(r.n) <= n_time - (start - first_index))) r.run = 0;   // s + n > first_index + n_time
+    }
     uint64_t total = 0;
     uint32_t max_slices = 0;
-    for (auto& r : recs) {
-        const gm_trk_state& s = r.st;
-        const int row = trk_bank_row(t, s);
-        bool run = s.active && row >= 0 && row < t->dc.n_codes && trk_bank_samples_per_code(t->dc.fs, s.code_rate, t->dc.code_len_f, r.n);
-        const uint64_t start = s.next_sample_index;
-        if (run) run = (start > H ? start - H : 0) >= first_index;                                // the halo is not in front of the buffer
-        if (run) run = start - first_index <= n_time && uint64_t(r.n) <= n_time - (start - first_index);      // s + n <= first_index + n_time
-        r.run = run ? 1 : 0;
-        if (!run) r.n = 0;
-        r.slices = run ? (r.n + gm::GM_TRK_ARRAY_SLICE - 1) / gm::GM_TRK_ARRAY_SLICE : 0;
-        r.poff = uint32_t(total);
-        total += r.slices;                              // at most 1024 x 2^19: no wrap
-        if (r.slices > max_slices) max_slices = r.slices;
-    }
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_recs = 0, o_z = o_recs + up(R * sizeof(gm::TrkBankRec)), o_done = o_z + up(size_t(R) * M * 8), o_part = o_done + up(R),
-                 bytes = o_part + up(size_t(total) * M * 8);
-    if (bytes > t->array_cap) {
-        HIPC(hipStreamSynchronize(t->stream));
-        hipFree(t->d_array); t->d_array = nullptr; t->array_cap = 0;
-        if (hipMalloc(&t->d_array, bytes) != hipSuccess) { (void)hipGetLastError(); t->d_array = nullptr; return set_err(GM_ERR_NOMEM, "gm_trk_array_prompts: device block"); }
-        t->array_cap = bytes;
-    }
-    uint8_t* d = t->d_array;
+    if (int rc = trk_call_slices(recs, gm::GM_TRK_ARRAY_SLICE, total, max_slices)) return rc;      // (at most 1024 x 2^19 slices: never refused)
+    Carve cv;
+    const size_t o_recs = cv.take(R * sizeof(gm::TrkBankRec)), o_z = cv.take(size_t(R) * M * 8), o_done = cv.take(R),
+                 o_part = cv.take(size_t(total) * M * 8);
+    if (int rc = t->array.reserve(t->stream, cv.end, "gm_trk_array_prompts: device block")) return rc;
+    uint8_t* d = static_cast<uint8_t*>(t->array.d);
     HIPC(hipMemcpyAsync(d + o_recs, recs.data(), R * sizeof(gm::TrkBankRec), hipMemcpyHostToDevice, t->stream));
     gm::TrkArrayArgs a;
     a.recs = reinterpret_cast<const gm::TrkBankRec*>(d + o_recs);
@@ -3553,15 +3548,7 @@ int gm_trk_array_prompts(gm_trk* t, const void* d_samples, int fmt, uint64_t fir
     a.partials = reinterpret_cast<cf*>(d + o_part);
     gm::launch_trk_array(t->stream, t->dc, t->d_codes, a, int(R), max_slices, reinterpret_cast<gm_c32*>(d + o_z), d + o_done);
     HIPC(hipGetLastError());
-    // the results land in host blocks of the call's own and reach the caller's only once everything has succeeded
-    std::vector<gm_c32> h_z(size_t(R) * M);
-    std::vector<uint8_t> h_done(R);
-    HIPC(hipMemcpyAsync(h_z.data(), d + o_z, h_z.size() * 8, hipMemcpyDeviceToHost, t->stream));
-    HIPC(hipMemcpyAsync(h_done.data(), d + o_done, R, hipMemcpyDeviceToHost, t->stream));
-    HIPC(hipStreamSynchronize(t->stream));
-    memcpy(z, h_z.data(), h_z.size() * 8);
-    if (done) memcpy(done, h_done.data(), R);
-    return GM_OK;
+    return trk_call_finish(t, d + o_z, size_t(R) * M, d + o_done, R, z, done);
 }
 
 // The persistent kernel's workgroups wait for one another, so its whole grid must be resident at once: ONE persistent
@@ -3637,7 +3624,7 @@ static int trk_reserve_tickets(gm_trk* t, size_t bytes) {
     for (const auto& k : t->tk)
         if (k.in_flight) return set_err(GM_ERR_OUT_OF_RANGE, "a larger max_epochs than the result slots hold: collect the tickets in flight first");
     if (t->tk_block) { hipHostFree(t->tk_block); t->tk_block = nullptr; t->tk_cap = 0; }
-    const size_t per = (bytes + 255) & ~size_t(255);
+    const size_t per = round256(bytes);
     HIPC(hipHostMalloc(reinterpret_cast<void**>(&t->tk_block), per * gm_trk::TICKETS, hipHostMallocDefault));
     t->tk_cap = per;
     for (int i = 0; i < gm_trk::TICKETS; ++i) {
