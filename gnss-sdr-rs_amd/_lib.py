@@ -84,6 +84,12 @@ class ArrayRowInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class ArraySolveCfg(C.Structure):
+    """gm_array_solve_cfg (56 bytes): the shape of one gm_array_rows_solve_dev call; zero strides are the dense [n_rows][n][m]"""
+    _fields_ = [("m", C.c_uint32), ("n", C.c_uint32), ("n_rows", C.c_uint32), ("n_blocks", C.c_uint32), ("row_stride", C.c_uint64),
+                ("vec_stride", C.c_uint64), ("loading", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 class AcqCancelCand(C.Structure):
     """gm_acq_cancel_cand (32 bytes): a found satellite for gm_acq_cancel"""
     _fields_ = [("worker", C.c_uint32), ("reserved", C.c_uint32), ("carrier_hz", C.c_double), ("code_phase", C.c_double),
@@ -282,6 +288,8 @@ SIGNATURES = {
     "gm_acq_array_prompts": (_i, [_vp, _vp, _i, _u32, _u32, _vp, _u32, _vp]),
     "gm_acq_array_plan": (_i, [_u32, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "gm_array_row_solve": (_i, [_u32, _u32, _vp, _vp, _sz, _f, _vp, C.POINTER(ArrayRowInfo)]),
+    "gm_array_solve_plan": (_i, [C.POINTER(ArraySolveCfg), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_array_rows_solve_dev": (_i, [C.POINTER(ArraySolveCfg), _vp, _vp, _vp, _vp, _vp]),
     "gm_acq_cancel": (_i, [_vp, _vp, _i, _vp, _u32, _vp, _vp, _vp, _u32]),
     "gm_acq_cancel_plan": (_i, [C.c_uint64, _u32, C.c_double, C.c_double, C.POINTER(_u32), _vp, _u32]),
     "gm_acq_enable_timing": (_i, [_vp, _i]),
@@ -397,6 +405,7 @@ SIGNATURES = {
     "gm_beamformer_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "gm_beamformer_synchronize": (_i, [_vp]),
     "gm_beamformer_set_steering": (_i, [_vp, _u32, _vp]),
+    "gm_beamformer_set_steering_dev": (_i, [_vp, _u32, _u32, _vp, _vp, _f, _vp, _vp]),
     "gm_beamformer_set_weights": (_i, [_vp, _vp]),
     "gm_beamformer_capture": (_i, [_vp, _vp, _vp, _sz]),
     "gm_beamformer_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
@@ -430,6 +439,7 @@ SIGNATURES = {
     "gm_trk_bank_samples": (_i, [_vp, C.POINTER(TrkState), _vp, _sz, C.POINTER(TrkBankCfg), _vp]),
     "gm_trk_array_plan": (_i, [C.POINTER(TrkCfg), C.POINTER(TrkArrayCfg), _u32, C.POINTER(TrkArrayPlanOut)]),
     "gm_trk_array_prompts": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _u32, C.POINTER(TrkArrayCfg), _vp, _vp]),
+    "gm_trk_array_prompts_dev": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _u32, C.POINTER(TrkArrayCfg), _vp, _vp, _vp]),
 }
 
 _lib = None

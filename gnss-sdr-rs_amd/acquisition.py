@@ -6,7 +6,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import AcqCancelCand, AcqCancelOut, AcqCand, AcqCfg, AcqLocalCfg, AcqLocalOut, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, ArrayRowInfo, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
+from ._lib import AcqCancelCand, AcqCancelOut, AcqCand, AcqCfg, AcqLocalCfg, AcqLocalOut, AcqPlan, AcqRefineCfg, AcqRefineOut, AcqResult, ArrayRowInfo, ArraySolveCfg, FMT_C32, FMT_I8_IQ, FMT_I8_REAL, check, lib
 
 PRN_SEARCH_ACQUISITION_TOTAL = 32      # do_acquisition.rs:22
 FREQ_SEARCH_ACQUISITION_HZ = 14e3      # :20
@@ -215,6 +215,29 @@ def solve_row(z, R=None, loading=0.0):
     info = ArrayRowInfo()
     check(lib().gm_array_row_solve(m, n, _p(z) if z.size else None, Rp, nb, float(loading), _p(row), C.byref(info)), "gm_array_row_solve")
     return row, info.as_dict()
+
+
+def _solve_cfg(m, n, n_rows, n_blocks, row_stride, vec_stride, loading):
+    return ArraySolveCfg(int(m), int(n), int(n_rows), int(n_blocks), int(row_stride), int(vec_stride), float(loading))
+
+
+def solve_plan(m, n, n_rows, n_blocks=0, row_stride=0, vec_stride=0, loading=0.0):
+    """gm_array_solve_plan: the argument rules of solve_rows_dev (GmError INVALID_ARG) -> dict(z_words, R_words, row_words): the
+    complex64 words the call reads at d_z and d_R and writes at d_rows.  Host only."""
+    cfg = _solve_cfg(m, n, n_rows, n_blocks, row_stride, vec_stride, loading)
+    z, r, w = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().gm_array_solve_plan(C.byref(cfg), C.byref(z), C.byref(r), C.byref(w)), "gm_array_solve_plan")
+    return dict(z_words=z.value, R_words=r.value, row_words=w.value)
+
+
+def solve_rows_dev(m, n, n_rows, d_z, d_rows, d_info, d_R=None, n_blocks=0, row_stride=0, vec_stride=0, loading=0.0, stream=None):
+    """gm_array_rows_solve_dev: solve_row for n_rows rows in one launch on the device, asynchronously on `stream` (None: the null
+    stream).  Device pointers: d_z (vector i of row p at d_z + p * row_stride + i * vec_stride complex64 words; 0, 0: the dense
+    [n_rows, n, m]), d_R [n_blocks, m, m] or None with n_blocks = 0, d_rows complex64 [n_rows, m], d_info [n_rows] ArrayRowInfo whose
+    `reserved` holds the row's status (0: solved)."""
+    cfg = _solve_cfg(m, n, n_rows, n_blocks, row_stride, vec_stride, loading)
+    check(lib().gm_array_rows_solve_dev(C.byref(cfg), C.c_void_p(d_z), C.c_void_p(d_R), C.c_void_p(d_rows), C.c_void_p(d_info),
+                                        C.c_void_p(stream)), "gm_array_rows_solve_dev")
 
 
 def solve_rows(z, R=None, loading=0.0):

@@ -64,6 +64,14 @@ class Beamformer(ArrayStage):
             raise ValueError("s: taps * n_antennas complex words")
         self._call("set_steering", int(beam), _p(s))
 
+    def set_steering_dev(self, first_beam, n_rows, d_rows, d_info=None, min_ratio=0.0, d_installed=None, stream=None):
+        """gm_beamformer_set_steering_dev: rows [n_rows][M] complex64 in DEVICE memory (solve_rows_dev's d_rows) into beams first_beam
+        .. first_beam + n_rows - 1 by a kernel on `stream` (None: the handle's own), ordered like a process_dev call, no host wait.
+        A row is installed where it is finite and not all zero and, with d_info (solve_rows_dev's), its status is 0 and lambda1 >=
+        min_ratio * lambda2; d_installed: device uint8 [n_rows], 1 where installed."""
+        self._call("set_steering_dev", int(first_beam), int(n_rows), C.c_void_p(d_rows), C.c_void_p(d_info), float(min_ratio),
+                   C.c_void_p(d_installed), C.c_void_p(stream))
+
     def set_weights(self, w=None):
         """[P][M] fixed complex weights for every later block (static mode, synchronous); None: back to the adaptive rule"""
         self._set_flat_weights(w, self.n_beams * self.n_weights, "w: beams * taps * n_antennas complex words")

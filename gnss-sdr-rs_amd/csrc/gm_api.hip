@@ -356,7 +356,8 @@ struct CallBlock {
             (void)hipGetLastError();
             return set_err(GM_ERR_NOMEM, nomem_text);
         }
-        if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
+        if (d)                                 // (nothing can be in flight on a block that does not exist yet)
+            if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) { hipFree(blk); return hip_fail(e, "hipStreamSynchronize"); }
         hipFree(d);
         d = blk; bytes = total;
         return GM_OK;
@@ -2931,6 +2932,15 @@ struct gm_trk {
     // the known-record entries' device blocks: gm_trk_bank's [records | taps | offsets | out | done | partials] (trk_bank_run) and
     // gm_trk_array_prompts' [records | z | done | partials]
     CallBlock bank, array;
+    // gm_trk_array_prompts_dev shares `array` with the synchronous entry: the stream the last array call of either kind went to (a call
+    // on another stream waits for it on the host first, stage_join's rule), and the pinned copies of the records that calls still in
+    // flight read: ONE pinned allocation cut into ARRAY_SLOTS equal slots of the largest call's records (1024), taken in turn; a slot
+    // is taken again once the event behind its copy has passed
+    hipStream_t array_last = nullptr;
+    static constexpr int ARRAY_SLOTS = 16;
+    uint8_t* array_recs = nullptr;        // [ARRAY_SLOTS][GM_TRK_ARRAY_MAX_STATES] TrkBankRec, built at the first device call
+    hipEvent_t array_ev[ARRAY_SLOTS] = {};
+    uint32_t array_next = 0;
 };
 
 static int trk_check_error(gm_trk* t);
@@ -2989,6 +2999,9 @@ int gm_trk_destroy(gm_trk* t) {
     if (!t) return GM_OK;
     if (t->device >= 0) hipSetDevice(t->device);
     hipFree(t->d_codes); hipFree(t->d_states); hipFree(t->d_partials); hipFree(t->d_ready); hipFree(t->d_scratch); hipFree(t->d_terms);
+    if (t->array_last) hipStreamSynchronize(t->array_last);
+    for (auto& e : t->array_ev) if (e) hipEventDestroy(e);
+    if (t->array_recs) hipHostFree(t->array_recs);
     hipFree(t->d_res); t->bank.release(); t->array.release();
     if (t->h_res) hipHostFree(t->h_res);
     for (auto& k : t->tk) if (k.done) hipEventDestroy(k.done);
@@ -3437,6 +3450,49 @@ static int trk_array_rules(float fs, bool custom_codes, uint32_t n_codes, uint32
     return GM_OK;
 }
 
+// what the synchronous and the device entry share behind their own pointer checks: the handle's rules and the index rule
+static int trk_array_call_rules(const gm_trk* t, uint64_t first_index, uint64_t n_time, const gm_trk_array_cfg* cfg, uint32_t n_states) {
+    if (int rc = trk_array_rules(t->dc.fs, !t->dc.gps_ca, uint32_t(t->dc.n_codes), uint32_t(t->dc.code_len), cfg, n_states)) return rc;
+    constexpr uint64_t INDEX_MAX = 1ull << 62;
+    if (first_index >= INDEX_MAX || n_time >= INDEX_MAX || first_index + n_time >= INDEX_MAX)
+        return set_err(GM_ERR_OUT_OF_RANGE, "first_index + n_time must be below 2^62");
+    return GM_OK;
+}
+// before array work on `st`: the last array call of the handle, where it went to another stream, has run (stage_join's rule)
+static int trk_array_join(gm_trk* t, hipStream_t st) {
+    if (t->array_last && t->array_last != st) HIPC(hipStreamSynchronize(t->array_last));
+    return GM_OK;
+}
+// which records run, their slices, and the block [records | z | done | partials] with room for them; the caller has joined `st`
+struct TrkArrayCall { size_t o_recs = 0, o_z = 0, o_done = 0, o_part = 0; uint32_t max_slices = 0; };
+static int trk_array_carve(gm_trk* t, hipStream_t st, std::vector<gm::TrkBankRec>& recs, uint64_t first_index, uint64_t n_time,
+                           const gm_trk_array_cfg* cfg, TrkArrayCall& c) {
+    const uint32_t R = uint32_t(recs.size()), M = cfg->n_antennas * cfg->taps;
+    // the kernel reads the time samples [max(0, s - (L-1)), s + n) of a record that runs, and nothing else
+    const uint64_t H = cfg->taps - 1;
+    for (auto& r : recs) {
+        const uint64_t start = r.st.next_sample_index;
+        if (r.run && (start > H ? start - H : 0) < first_index) r.run = 0;                          // the halo is in front of the buffer
+        if (r.run && !(start - first_index <= n_time && uint64_t(r.n) <= n_time - (start - first_index))) r.run = 0;   // s + n > first_index + n_time
+    }
+    uint64_t total = 0;
+    if (int rc = trk_call_slices(recs, gm::GM_TRK_ARRAY_SLICE, total, c.max_slices)) return rc;    // (at most 1024 x 2^19 slices: never refused)
+    Carve cv;
+    c.o_recs = cv.take(R * sizeof(gm::TrkBankRec)); c.o_z = cv.take(size_t(R) * M * 8); c.o_done = cv.take(R);
+    c.o_part = cv.take(size_t(total) * M * 8);
+    return t->array.reserve(st, cv.end, "gm_trk_array_prompts: device block");
+}
+static void trk_array_launch(gm_trk* t, hipStream_t st, const void* d_samples, int fmt, uint64_t first_index, const gm_trk_array_cfg* cfg,
+                             const TrkArrayCall& c, uint32_t R, gm_c32* d_z, uint8_t* d_done) {
+    uint8_t* d = static_cast<uint8_t*>(t->array.d);
+    gm::TrkArrayArgs a;
+    a.recs = reinterpret_cast<const gm::TrkBankRec*>(d + c.o_recs);
+    a.samples = d_samples; a.first_index = first_index;
+    a.fmt = fmt; a.A = int(cfg->n_antennas); a.L = int(cfg->taps); a.tau = cfg->tap_chips;
+    a.partials = reinterpret_cast<cf*>(d + c.o_part);
+    gm::launch_trk_array(st, t->dc, t->d_codes, a, int(R), c.max_slices, d_z, d_done);
+}
+
 extern "C" {
 
 int gm_trk_bank_plan(const gm_trk_cfg* trk, const gm_trk_bank_cfg* cfg, uint32_t n_states, gm_trk_bank_plan_out* out) {
@@ -3517,38 +3573,20 @@ int gm_trk_array_prompts(gm_trk* t, const void* d_samples, int fmt, uint64_t fir
     if (!t || !d_samples || !z) return set_err(GM_ERR_INVALID_ARG, "null handle, samples or z");
     if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "fmt must be GM_FMT_C32 or GM_FMT_I8_IQ");
     if (int rc = trk_call_states_rule(t, states, n_states)) return rc;
-    if (int rc = trk_array_rules(t->dc.fs, !t->dc.gps_ca, uint32_t(t->dc.n_codes), uint32_t(t->dc.code_len), cfg, n_states)) return rc;
-    constexpr uint64_t INDEX_MAX = 1ull << 62;
-    if (first_index >= INDEX_MAX || n_time >= INDEX_MAX || first_index + n_time >= INDEX_MAX)
-        return set_err(GM_ERR_OUT_OF_RANGE, "first_index + n_time must be below 2^62");
+    if (int rc = trk_array_call_rules(t, first_index, n_time, cfg, n_states)) return rc;
     if (int rc = ensure_device(t->device)) return rc;
-    const uint32_t R = n_states, A = cfg->n_antennas, L = cfg->taps, M = A * L;
+    if (int rc = trk_array_join(t, t->stream)) return rc;
+    const uint32_t R = n_states, M = cfg->n_antennas * cfg->taps;
     std::vector<gm::TrkBankRec> recs;
     if (int rc = trk_call_records(t, states, n_states, recs)) return rc;
-    // which records run: the kernel reads the time samples [max(0, s - (L-1)), s + n) of a record that does, and nothing else
-    const uint64_t H = L - 1;
-    for (auto& r : recs) {
-        const uint64_t start = r.st.next_sample_index;
-        if (r.run && (start > H ? start - H : 0) < first_index) r.run = 0;                          // the halo is in front of the buffer
-        if (r.run && !(start - first_index <= n_time && uint64_t(r.n) <= n_time - (start - first_index))) r.run = 0;   // s + n > first_index + n_time
-    }
-    uint64_t total = 0;
-    uint32_t max_slices = 0;
-    if (int rc = trk_call_slices(recs, gm::GM_TRK_ARRAY_SLICE, total, max_slices)) return rc;      // (at most 1024 x 2^19 slices: never refused)
-    Carve cv;
-    const size_t o_recs = cv.take(R * sizeof(gm::TrkBankRec)), o_z = cv.take(size_t(R) * M * 8), o_done = cv.take(R),
-                 o_part = cv.take(size_t(total) * M * 8);
-    if (int rc = t->array.reserve(t->stream, cv.end, "gm_trk_array_prompts: device block")) return rc;
+    TrkArrayCall c;
+    if (int rc = trk_array_carve(t, t->stream, recs, first_index, n_time, cfg, c)) return rc;
     uint8_t* d = static_cast<uint8_t*>(t->array.d);
-    HIPC(hipMemcpyAsync(d + o_recs, recs.data(), R * sizeof(gm::TrkBankRec), hipMemcpyHostToDevice, t->stream));
-    gm::TrkArrayArgs a;
-    a.recs = reinterpret_cast<const gm::TrkBankRec*>(d + o_recs);
-    a.samples = d_samples; a.first_index = first_index;
-    a.fmt = fmt; a.A = int(A); a.L = int(L); a.tau = cfg->tap_chips;
-    a.partials = reinterpret_cast<cf*>(d + o_part);
-    gm::launch_trk_array(t->stream, t->dc, t->d_codes, a, int(R), max_slices, reinterpret_cast<gm_c32*>(d + o_z), d + o_done);
+    HIPC(hipMemcpyAsync(d + c.o_recs, recs.data(), R * sizeof(gm::TrkBankRec), hipMemcpyHostToDevice, t->stream));
+    trk_array_launch(t, t->stream, d_samples, fmt, first_index, cfg, c, R, reinterpret_cast<gm_c32*>(d + c.o_z), d + c.o_done);
     HIPC(hipGetLastError());
-    return trk_call_finish(t, d + o_z, size_t(R) * M, d + o_done, R, z, done);
+    t->array_last = t->stream;
+    return trk_call_finish(t, d + c.o_z, size_t(R) * M, d + c.o_done, R, z, done);
 }
 
 // The persistent kernel's workgroups wait for one another, so its whole grid must be resident at once: ONE persistent
@@ -5748,6 +5786,136 @@ int gm_beamformer_process_dev(gm_beamformer* n, const void* d_in, int fmt, size_
 int gm_beamformer_process(gm_beamformer* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_stride, size_t* n_out, gm_c32* R,
                           gm_c32* w, size_t cap_blocks) {
     return array_process(n, beam_launch, in, fmt, n_in, out, out_stride, n_out, R, w, cap_blocks);
+}
+
+}  // extern "C"
+
+// ====================================================================== re-steering on the device (additive entries, ABI 9)
+// gnss_mi355x.h states the contracts.  Three entries that enqueue and return: the tracker's array prompts into device buffers, the
+// batched row solver (array_solve.hip), and the install of its rows into a beamformer's steering words.  Together with
+// gm_beamformer_process_dev they put a whole update behind the block it belongs to, on one stream, with no host wait.
+namespace {
+// gm_array_solve_plan's rules; the resolved loading and strides, and the extents in c32 words
+struct SolvePlan { double load = 1e-4; uint64_t row_stride = 0, vec_stride = 0, z_words = 0, R_words = 0, row_words = 0; };
+int solve_rules(const gm_array_solve_cfg* c, SolvePlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    for (uint32_t v : c->reserved)
+        if (v) return set_err(GM_ERR_INVALID_ARG, "gm_array_solve_cfg.reserved must be 0");
+    if (c->m < 2 || c->m > uint32_t(gm::ST_M_MAX)) return set_err(GM_ERR_INVALID_ARG, "m must be 2 .. 32");
+    if (c->n < 1 || c->n > 4096) return set_err(GM_ERR_INVALID_ARG, "n must be 1 .. 4096");
+    if (c->n_rows < 1 || c->n_rows > 1024) return set_err(GM_ERR_INVALID_ARG, "n_rows must be 1 .. 1024");
+    if (c->n_blocks > (1u << 20)) return set_err(GM_ERR_INVALID_ARG, "n_blocks must be at most 2^20");
+    if ((c->row_stride == 0) != (c->vec_stride == 0)) return set_err(GM_ERR_INVALID_ARG, "row_stride and vec_stride: both 0 or neither");
+    p.row_stride = c->row_stride ? c->row_stride : uint64_t(c->n) * c->m;
+    p.vec_stride = c->vec_stride ? c->vec_stride : uint64_t(c->m);
+    if (p.vec_stride < c->m || p.row_stride < c->m) return set_err(GM_ERR_INVALID_ARG, "row_stride and vec_stride must be at least m");
+    if (p.vec_stride > (1ull << 40) || p.row_stride > (1ull << 40)) return set_err(GM_ERR_INVALID_ARG, "row_stride and vec_stride must be at most 2^40");
+    if (c->loading != 0.0f) {
+        if (!(c->loading >= 1e-6f && c->loading <= 1.0f)) return set_err(GM_ERR_INVALID_ARG, "loading must be 0 or lie in [1e-6, 1]");   // (NaN fails too)
+        p.load = double(c->loading);
+    }
+    p.z_words = uint64_t(c->n_rows - 1) * p.row_stride + uint64_t(c->n - 1) * p.vec_stride + c->m;
+    p.R_words = uint64_t(c->n_blocks) * c->m * c->m;
+    p.row_words = uint64_t(c->n_rows) * c->m;
+    return GM_OK;
+}
+// the next pinned slot for a call's records and the event to record behind their copy; a caller ARRAY_SLOTS calls ahead of its
+// stream waits here for the oldest copy
+int trk_array_slot(gm_trk* t, void** h, hipEvent_t* ev) {
+    constexpr size_t slot_bytes = size_t(gm::GM_TRK_ARRAY_MAX_STATES) * sizeof(gm::TrkBankRec);
+    if (!t->array_recs) {
+        void* blk = nullptr;
+        HIPC(hipHostMalloc(&blk, slot_bytes * gm_trk::ARRAY_SLOTS, hipHostMallocDefault));
+        for (auto& e : t->array_ev)
+            if (hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming); rc != hipSuccess) {
+                for (auto& d : t->array_ev) { if (d) hipEventDestroy(d); d = nullptr; }
+                hipHostFree(blk);
+                return hip_fail(rc, "hipEventCreate");
+            }
+        t->array_recs = static_cast<uint8_t*>(blk);
+    }
+    const uint32_t k = t->array_next % gm_trk::ARRAY_SLOTS;
+    HIPC(hipEventSynchronize(t->array_ev[k]));                // (returns at once for an event never recorded or already passed)
+    *h = t->array_recs + slot_bytes * k; *ev = t->array_ev[k];
+    ++t->array_next;
+    return GM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gm_trk_array_prompts_dev(gm_trk* t, const void* d_samples, int fmt, uint64_t first_index, uint64_t n_time, const gm_trk_state* states,
+                             uint32_t n_states, const gm_trk_array_cfg* cfg, void* d_z, void* d_done, void* stream) {
+    if (!t || !d_samples || !d_z || !d_done) return set_err(GM_ERR_INVALID_ARG, "null handle, samples, d_z or d_done");
+    if (fmt != GM_FMT_C32 && fmt != GM_FMT_I8_IQ) return set_err(GM_ERR_INVALID_ARG, "fmt must be GM_FMT_C32 or GM_FMT_I8_IQ");
+    if (!states) return set_err(GM_ERR_INVALID_ARG, "states NULL: the handle's own channels live on the device (take them from gm_trk_collect)");
+    if (int rc = trk_array_call_rules(t, first_index, n_time, cfg, n_states)) return rc;
+    const uint32_t R = n_states, M = cfg->n_antennas * cfg->taps;
+    if (n_time <= (1ull << 40))
+        if (stage_check_overlap(d_samples, size_t(n_time) * cfg->n_antennas * fmt_bytes(fmt), d_z, uint64_t(R) * M))
+            return set_err(GM_ERR_INVALID_ARG, "d_z overlaps the samples");
+    if (int rc = ensure_device(t->device)) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : t->stream;
+    if (int rc = trk_array_join(t, st)) return rc;
+    std::vector<gm::TrkBankRec> recs;
+    if (int rc = trk_call_records(t, states, n_states, recs)) return rc;
+    TrkArrayCall c;
+    if (int rc = trk_array_carve(t, st, recs, first_index, n_time, cfg, c)) return rc;
+    void* h_recs = nullptr;
+    hipEvent_t copied = nullptr;
+    if (int rc = trk_array_slot(t, &h_recs, &copied)) return rc;
+    memcpy(h_recs, recs.data(), R * sizeof(gm::TrkBankRec));
+    uint8_t* d = static_cast<uint8_t*>(t->array.d);
+    HIPC(hipMemcpyAsync(d + c.o_recs, h_recs, R * sizeof(gm::TrkBankRec), hipMemcpyHostToDevice, st));
+    HIPC(hipEventRecord(copied, st));
+    trk_array_launch(t, st, d_samples, fmt, first_index, cfg, c, R, static_cast<gm_c32*>(d_z), static_cast<uint8_t*>(d_done));
+    HIPC(hipGetLastError());
+    t->array_last = st;
+    return GM_OK;
+}
+
+int gm_array_solve_plan(const gm_array_solve_cfg* cfg, uint64_t* z_words, uint64_t* R_words, uint64_t* row_words) {
+    SolvePlan p;
+    if (int rc = solve_rules(cfg, p)) return rc;
+    if (z_words) *z_words = p.z_words;
+    if (R_words) *R_words = p.R_words;
+    if (row_words) *row_words = p.row_words;
+    return GM_OK;
+}
+
+int gm_array_rows_solve_dev(const gm_array_solve_cfg* cfg, const void* d_z, const void* d_R, void* d_rows, void* d_info, void* stream) {
+    SolvePlan p;
+    if (int rc = solve_rules(cfg, p)) return rc;
+    if (!d_z || !d_rows || !d_info) return set_err(GM_ERR_INVALID_ARG, "null d_z, d_rows or d_info");
+    if ((d_R == nullptr) != (cfg->n_blocks == 0)) return set_err(GM_ERR_INVALID_ARG, "n_blocks: 0 exactly where d_R is null");
+    if (int rc = ensure_device(g_device)) return rc;
+    gm::ArraySolveArgs a{};
+    a.z = static_cast<const cf*>(d_z); a.R = static_cast<const cf*>(d_R);
+    a.rows = static_cast<cf*>(d_rows); a.info = d_info;
+    a.row_stride = p.row_stride; a.vec_stride = p.vec_stride;
+    a.m = cfg->m; a.n = cfg->n; a.n_rows = cfg->n_rows; a.n_blocks = cfg->n_blocks;
+    a.load = p.load;
+    gm::launch_array_solve(static_cast<hipStream_t>(stream), a);
+    HIPC(hipGetLastError());
+    return GM_OK;
+}
+
+int gm_beamformer_set_steering_dev(gm_beamformer* n, uint32_t first_beam, uint32_t n_rows, const void* d_rows, const void* d_info,
+                                   float min_ratio, void* d_installed, void* stream) {
+    if (!n || !d_rows) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (!n_rows) return set_err(GM_ERR_INVALID_ARG, "n_rows = 0");
+    if (first_beam >= n->plan.P || n_rows > n->plan.P - first_beam) return set_err(GM_ERR_INVALID_ARG, "first_beam + n_rows: at most n_beams");
+    if (!std::isfinite(min_ratio) || min_ratio < 0.0f) return set_err(GM_ERR_INVALID_ARG, "min_ratio must be finite and not negative");
+    if (int rc = ensure_device(n->device)) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : n->stream;
+    if (int rc = stage_join(n, st)) return rc;                // a call in flight elsewhere reads the old rows
+    gm::BeamInstallArgs a{};
+    a.rows = static_cast<const cf*>(d_rows); a.info = d_info; a.s = n->d_s; a.installed = static_cast<uint8_t*>(d_installed);
+    a.M = n->plan.st.M; a.first_beam = first_beam; a.n_rows = n_rows; a.min_ratio = min_ratio;
+    gm::launch_beam_install(st, a);
+    HIPC(hipGetLastError());
+    n->last_stream = st;
+    return GM_OK;
 }
 
 }  // extern "C"

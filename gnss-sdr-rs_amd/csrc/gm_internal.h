@@ -569,6 +569,30 @@ struct BeamArgs {
 };
 void launch_beam(hipStream_t, const BeamArgs&);
 
+// ---------------------------------------------------------------- re-steering on the device (array_solve.hip)
+// gm_array_rows_solve_dev: gm_array_row_solve's nine steps for n_rows rows, f64, one workgroup a row; the host has checked every limit
+// (gm_array_solve_plan) and every pointer.  Vector i of row p: the m words at z + p * row_stride + i * vec_stride.
+struct ArraySolveArgs {
+    const cf* z;
+    const cf* R;                           // [n_blocks][m][m], only the upper triangles are read; null: the identity
+    cf* rows;                              // [n_rows][m]
+    void* info;                            // [n_rows] gm_array_row_info, the status in `reserved`
+    uint64_t row_stride, vec_stride;       // c32 words
+    uint32_t m, n, n_rows, n_blocks;
+    double load;                           // the resolved loading
+};
+void launch_array_solve(hipStream_t, const ArraySolveArgs&);
+// gm_beamformer_set_steering_dev: row p of `rows` into s[first_beam + p] where it is finite, not all zero and passes the gate
+struct BeamInstallArgs {
+    const cf* rows;                        // [n_rows][M]
+    const void* info;                      // [n_rows] gm_array_row_info or null
+    cf* s;                                 // the handle's constraint rows [P][M]
+    uint8_t* installed;                    // [n_rows] or null
+    uint32_t M, first_beam, n_rows;
+    float min_ratio;
+};
+void launch_beam_install(hipStream_t, const BeamInstallArgs&);
+
 // ---------------------------------------------------------------- narrowband interference excision (excise_kernels.hip)
 // gnss_mi355x.h states the definition.  One call = one launch of the output kernel (a workgroup per tile of G segments of H = B / 2
 // outputs) and one of the state kernel (the next history of 3H blanked inputs, the blanked count).  The host hands over where the

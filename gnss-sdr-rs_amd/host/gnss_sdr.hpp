@@ -255,6 +255,20 @@ inline std::vector<gm_c32> solve_row(uint32_t m, const std::vector<gm_c32>& z, c
     return row;
 }
 
+// Re-steering on the device.  solve_plan (gm_array_solve_plan, host only): the argument rules of solve_rows_dev and the c32 words it
+// reads at d_z and d_R and writes at d_rows.  solve_rows_dev (gm_array_rows_solve_dev): solve_row for cfg.n_rows rows in one launch,
+// asynchronous on `stream` (null: the null stream); vector i of row p at d_z + p * row_stride + i * vec_stride words (0, 0: the dense
+// [n_rows][n][m]); d_R null with n_blocks = 0: the identity; d_info[p].reserved is row p's status, 0: solved.
+struct SolveExtents { uint64_t z_words, R_words, row_words; };
+inline SolveExtents solve_plan(const gm_array_solve_cfg& cfg) {
+    SolveExtents e{};
+    check(gm_array_solve_plan(&cfg, &e.z_words, &e.R_words, &e.row_words), "solve_plan");
+    return e;
+}
+inline void solve_rows_dev(const gm_array_solve_cfg& cfg, const void* d_z, const void* d_R, void* d_rows, void* d_info, void* stream = nullptr) {
+    check(gm_array_rows_solve_dev(&cfg, d_z, d_R, d_rows, d_info, stream), "solve_rows_dev");
+}
+
 // AcquisitionWorker::new(prn, fft_size, freq_sampling_hz) / search_satellite (:130-226): one PRN per object.
 class AcquisitionWorker {
     uint8_t prn_; uint32_t fft_size_; float fs_;
@@ -691,6 +705,13 @@ public:
         if (s.size() != weights()) check(GM_ERR_INVALID_ARG, "Beamformer::set_steering (taps * n_antennas words)");
         check(gm_beamformer_set_steering(h_, beam, reinterpret_cast<const gm_c32*>(s.data())), "Beamformer::set_steering");
     }
+    // gm_beamformer_set_steering_dev: n_rows rows [n_rows][M] in DEVICE memory (solve_rows_dev's) into beams first_beam .., by a kernel on
+    // `stream` (null: the handle's own), ordered like a process_dev call, no host wait.  A row is installed where it is finite, not all
+    // zero and, with d_info, has status 0 and lambda1 >= min_ratio * lambda2; d_installed: [n_rows] bytes on the device or null
+    void set_steering_dev(uint32_t first_beam, uint32_t n_rows, const void* d_rows, const void* d_info = nullptr, float min_ratio = 0.0f,
+                          void* d_installed = nullptr, void* stream = nullptr) {
+        check(gm_beamformer_set_steering_dev(h_, first_beam, n_rows, d_rows, d_info, min_ratio, d_installed, stream), "Beamformer::set_steering_dev");
+    }
     // fixed weights [beams][M] for every later block (static mode, synchronous); empty: back to the adaptive rule
     void set_weights(const std::vector<Complex32>& w) {
         if (!w.empty() && w.size() != size_t(beams_) * weights()) check(GM_ERR_INVALID_ARG, "Beamformer::set_weights (beams * taps * n_antennas words)");
@@ -910,6 +931,14 @@ public:
         check(gm_trk_array_prompts(h_, d_samples, fmt, first_index, n_time, records ? records->data() : nullptr, r, &c,
                                    reinterpret_cast<gm_c32*>(z.data()), done ? done->data() : nullptr), "TrackingManager::array_prompts");
         return z;
+    }
+    // gm_trk_array_prompts_dev: array_prompts' words into device buffers (d_z [R][L][A] c32, d_done [R] bytes), asynchronous on `stream`
+    // (null: the handle's own), no host wait; the records are required (the states a collect handed over) and read before the return
+    void array_prompts_dev(const void* d_samples, int fmt, uint64_t first_index, uint64_t n_time, uint32_t n_antennas, uint32_t taps,
+                           float tap_chips, const std::vector<gm_trk_state>& records, void* d_z, void* d_done, void* stream = nullptr) {
+        gm_trk_array_cfg c{}; c.n_antennas = n_antennas; c.taps = taps; c.tap_chips = tap_chips;
+        check(gm_trk_array_prompts_dev(h_, d_samples, fmt, first_index, n_time, records.data(), uint32_t(records.size()), &c, d_z, d_done,
+                                       stream), "TrackingManager::array_prompts_dev");
     }
     // gm_trk_array_plan (host only): the argument rules and the sizes of an array_prompts call for a tracking configuration
     static gm_trk_array_plan_out array_plan(const gm_trk_cfg& trk, uint32_t n_antennas, uint32_t taps = 1, float tap_chips = 0.0f,

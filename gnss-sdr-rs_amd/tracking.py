@@ -272,6 +272,19 @@ class TrackingManager:
               "gm_trk_array_prompts")
         return z, done
 
+    def array_prompts_dev(self, samples_ptr, n_time, n_antennas, states, d_z, d_done, taps=1, first_index=0, tap_chips=0.0,
+                          fmt=_lib.FMT_C32, stream=None):
+        """gm_trk_array_prompts_dev: array_prompts' words into device buffers (d_z: complex64 [R, L, A], d_done: uint8 [R]; device
+        pointers), asynchronously on `stream` (None: the handle's own), with no host wait.  states: a list of TrkState records, read
+        before the call returns (required: take them from collect(..., with_states=True))."""
+        cfg = _array_cfg(n_antennas, taps, tap_chips)
+        R = 0 if states is None else len(states)
+        arr = None if states is None else (TrkState * max(R, 1))(*states)
+        check(lib().gm_trk_array_prompts_dev(self._h, C.c_void_p(samples_ptr), int(fmt), int(first_index), int(n_time),
+                                             None if arr is None else C.cast(arr, C.c_void_p), R, C.byref(cfg), C.c_void_p(d_z),
+                                             C.c_void_p(d_done), C.c_void_p(stream)),
+              "gm_trk_array_prompts_dev")
+
     def update_all_dev(self, ring, epochs):
         check(lib().gm_trk_update_all_dev(self._h, ring._h, int(epochs)), "gm_trk_update_all_dev")
 

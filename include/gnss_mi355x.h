@@ -664,8 +664,12 @@ int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const 
  * Not built: per-antenna prompts from the tracker (the array form of gm_trk_bank); a loop that re-steers by itself; several constraints
  * on one beam (LCMV); ring writers; any detection or quality decision; wiring into receiver_harness.cpp or bench.py.
  * (Since then the first item has been built: gm_trk_array_prompts, "Per-antenna prompts at tracked states" below.)
+ * (And the second, as far as a library that decides nothing can build it: "Re-steering on the device" below, the three entries
+ * gm_trk_array_prompts_dev, gm_array_rows_solve_dev and gm_beamformer_set_steering_dev that put one update on a stream with no host wait.)
  * (ABI 9, additive: a caller detects the feature by the symbol) */
-typedef struct { double lambda1, lambda2; uint32_t ref_index; uint32_t reserved; } gm_array_row_info;   /* 24 bytes; reserved = 0 */
+/* 24 bytes.  reserved: gm_array_row_solve writes 0; gm_array_rows_solve_dev writes the row's STATUS there (0: solved; 1 .. 6: see
+ * "Re-steering on the device") */
+typedef struct { double lambda1, lambda2; uint32_t ref_index; uint32_t reserved; } gm_array_row_info;
 int gm_acq_array_prompts(gm_acq *a, const void *d_samples, int fmt, uint32_t n_antennas, uint32_t taps, const gm_acq_cand *cands,
                          uint32_t n_cands, gm_c32 *z /* [n_cands][R_u][L][A], host */);
 /* host only, no device: the limits on A, L and A L, coherent_periods <= 32 and n_integrations >= 1 (and R_u L A below 2^32);
@@ -674,6 +678,71 @@ int gm_acq_array_plan(uint32_t coherent_periods, uint32_t n_integrations, uint32
                       uint32_t *words_per_cand);
 int gm_array_row_solve(uint32_t m, uint32_t n, const gm_c32 *z /* [n][m] */, const gm_c32 *R /* [n_blocks][m][m] or NULL */,
                        size_t n_blocks, float loading /* 0 -> 1e-4; else [1e-6, 1] */, gm_c32 *row /* [m] */, gm_array_row_info *info);
+/* ---- Re-steering on the device.  A receiver that follows its satellites across the sky, or past a moving jammer, refreshes its beam
+ * rows every few code periods.  With the entries above that is three host waits an update: gm_trk_array_prompts delivers to the host,
+ * gm_array_row_solve is host f64 one row a call, gm_beamformer_set_steering drains the handle once per beam.  The three entries here
+ * enqueue and return; with gm_beamformer_process_dev on the same stream the whole update sits behind the block it belongs to:
+ *     states from gm_trk_collect (no synchronisation) -> gm_trk_array_prompts_dev into slot e of a history of prompts
+ *     every few epochs: gm_array_rows_solve_dev (history, the captured R) -> gm_beamformer_set_steering_dev -> the next process_dev
+ * THE LIBRARY DECIDES NOTHING but what the caller's min_ratio says: when to re-steer and how much history are the caller's.
+ *
+ * gm_trk_array_prompts_dev ("Per-antenna prompts at tracked states" below states the words): gm_trk_array_prompts' two kernels, rules,
+ * order of refusals and skipped records, the result in DEVICE buffers, asynchronously on `stream` (NULL: the handle's own).  d_z
+ * [n_states][L][A] c32 and d_done [n_states] u8 are word for word what the synchronous entry returns for the same arguments.
+ *   states is a HOST array, read before the call returns; NULL is GM_ERR_INVALID_ARG (the handle's own channels live on the device
+ *   and reading them needs a wait: take the states from gm_trk_collect).  A NULL d_z or d_done, and a d_z lying over the sample
+ *   buffer, are refused likewise; a refused call enqueues nothing.
+ *   The handle's per-call device block is shared with the synchronous entry, and calls of the two entries on one handle take effect in
+ *   the order issued: a call that goes to a stream other than the last array call's first waits ON THE HOST for that call (the
+ *   streaming stages' rule); growing the block waits for what is in flight before the old block goes.  A caller that keeps one stream
+ *   and one shape never waits.  The records travel through pinned host blocks of the handle's (one allocation at the first call; at most 16 calls
+ *   ahead of the stream: the 17th waits for the oldest copy).
+ *
+ * gm_array_rows_solve_dev: steps 1 to 9 of gm_array_row_solve above for n_rows rows in one launch, f64, on `stream` (NULL: the null
+ * stream; there is no handle).  Vector i of row p is the m words at d_z + p * row_stride + i * vec_stride (c32 words): the defaults
+ * (0, 0 -> n m and m) are gm_acq_array_prompts' [n_cands][R_u][m]; a history [n][P][m] of gm_trk_array_prompts_dev calls, one per
+ * epoch, is row_stride = m, vec_stride = P m.  A skipped record's zeros add nothing to Q.  d_R: n_blocks captured matrices shared by
+ * all rows, or NULL with n_blocks = 0: the identity.  Only the upper triangles are read; the blocks are summed in ascending order, so
+ * Rs, C and Q are gm_array_row_solve's bit for bit.  The eigenproblem is a PARALLEL-ORDER cyclic Jacobi: the m indices (and an idle
+ * one where m is odd) are paired by a round-robin tournament, player m' - 1 fixed, step r of m' - 1 pairing (r, m' - 1) and
+ * ((r + k) mod (m' - 1), (r - k) mod (m' - 1)); the pairs of a step are disjoint, each pair's rotation is formed by
+ * gm_array_row_solve's formulas from the current Q, the column rotations of Q and V are applied, then the row rotations of Q.  The
+ * stopping rule is the host's (off-diagonal energy below 1e-30 of the whole, at most 64 sweeps).  This is a different but fixed
+ * rotation order: lambda1, lambda2 and the row equal the host entry's up to f64 rounding, not bit for bit.
+ *   STATUS.  What gm_array_row_solve refuses after looking at the data is here a per-row status in d_info[p].reserved, the first that
+ *   applies: 1 a z word of the row is not finite; 2 a word of R that is read is not finite; 3 tr is not positive and finite; 4 a
+ *   Cholesky pivot is not positive and finite; 5 lambda1 is not greater than 0; 6 the row came out zero or not finite.  Such a row
+ *   gets all-zero words, lambda1 = lambda2 = 0 and ref_index = 0; the other rows of the call are not affected, bit for bit.
+ *   A row's words depend on that row's vectors, R and the cfg alone: not on n_rows, not on the row's place in the call, not on
+ *   repetition.  No floating-point atomics.
+ *   gm_array_solve_plan (host only, no device) states every argument rule: m in 2 .. 32, n in 1 .. 4096, n_rows in 1 .. 1024,
+ *   n_blocks at most 2^20, the strides both 0 or both at least m (and at most 2^40), loading 0 or in [1e-6, 1], reserved 0; and the
+ *   extents in c32 words: *z_words = (n_rows - 1) row_stride + (n - 1) vec_stride + m read at d_z, *R_words = n_blocks m m read at
+ *   d_R, *row_words = n_rows m written at d_rows (n_rows gm_array_row_info at d_info).  Any of the three may be NULL.
+ *   gm_array_rows_solve_dev checks through the same function, then: a NULL d_z, d_rows or d_info; d_R NULL exactly where n_blocks
+ *   is 0.  GM_ERR_INVALID_ARG, before anything is launched, nothing touched.
+ *   Kernel (csrc/array_solve.hip): one 256-lane workgroup a row, no word between workgroups, no spin wait, every loop bounded by a
+ *   checked argument or the 64 sweeps; Rs / C, Q and V stay in LDS in f64 (50688 bytes).  With 16 or fewer rows most of the device
+ *   idles on purpose: a latency path beside the streaming kernels.
+ *
+ * gm_beamformer_set_steering_dev (the beamformer's section below states what a steering row is): a small kernel on `stream` (NULL:
+ * the handle's own) copies row p of d_rows [n_rows][M] into the steering words of beam first_beam + p where every word of the row is
+ * finite, the row is not all zero (gm_beamformer_set_steering's rules) and, with d_info, the row's status is 0 and lambda1 >=
+ * min_ratio * lambda2 (min_ratio: the caller's policy; 0: no gate).  Otherwise the beam keeps its row.  d_installed[p] (or NULL) is
+ * 1 or 0 accordingly.  Ordered like a process_dev call: it applies to every block finished by a call issued later, blocks of earlier
+ * calls keep the old words; no host wait but the streaming stages' when `stream` differs from the last call's.
+ * gm_beamformer_capture's w words show the effect.  GM_ERR_INVALID_ARG, nothing enqueued: a NULL handle or d_rows; n_rows = 0;
+ * first_beam + n_rows > n_beams; min_ratio negative or not finite.
+ * (ABI 9, additive: a caller detects the feature by the symbols) */
+typedef struct {
+    uint32_t m, n, n_rows, n_blocks;   /* m = L A in 2..32; n vectors a row, 1..4096; n_rows 1..1024; n_blocks 0 (R = identity) .. 2^20 */
+    uint64_t row_stride, vec_stride;   /* c32 words between rows / between a row's vectors in d_z; 0, 0 -> n m and m ([n_rows][n][m]) */
+    float    loading;                  /* gm_array_row_solve's: 0 -> 1e-4, else [1e-6, 1] */
+    uint32_t reserved[5];              /* 0 */
+} gm_array_solve_cfg;                  /* 56 bytes */
+int gm_array_solve_plan(const gm_array_solve_cfg *cfg, uint64_t *z_words, uint64_t *R_words, uint64_t *row_words);
+int gm_array_rows_solve_dev(const gm_array_solve_cfg *cfg, const void *d_z, const void *d_R /* [n_blocks][m][m] c32 or NULL */,
+                            void *d_rows /* [n_rows][m] c32 */, void *d_info /* [n_rows] gm_array_row_info */, void *stream);
 /* ---- Subtracting found satellites from a dwell.  C/A codes isolate about 24 dB: a strong satellite's cross-correlation peaks stand
  * above a satellite 24 dB weaker in every other PRN's plane.  gm_acq_cancel writes the dwell with the named satellites' signals
  * subtracted, as c32, into a second device buffer, which every search entry takes as a dwell.  The expected sequence is: search,
@@ -1406,6 +1475,12 @@ int gm_beamformer_synchronize(gm_beamformer *h);
 /* s: the M words [L][A] of beam `beam`'s new row (finite, not all zero; beam >= P, a bad row or a NULL: GM_ERR_INVALID_ARG with
  * nothing changed).  Synchronous, see "Moving beams". */
 int gm_beamformer_set_steering(gm_beamformer *h, uint32_t beam, const gm_c32 *s);
+/* n_rows rows from DEVICE memory into beams first_beam .. first_beam + n_rows - 1, by a kernel on `stream` (NULL: the handle's own),
+ * ordered like a process_dev call; no host wait.  "Re-steering on the device" above states the gate (d_info, min_ratio), d_installed
+ * and the refusals. */
+int gm_beamformer_set_steering_dev(gm_beamformer *h, uint32_t first_beam, uint32_t n_rows, const void *d_rows /* [n_rows][M] c32 */,
+                                   const void *d_info /* [n_rows] gm_array_row_info or NULL */, float min_ratio,
+                                   void *d_installed /* [n_rows] u8 or NULL */, void *stream);
 /* w: P M finite c32 words [P][L][A] used for every later block (static mode); NULL returns the handle to the adaptive rule (and
  * waits for nothing).  Synchronous, see "Moving beams". */
 int gm_beamformer_set_weights(gm_beamformer *h, const gm_c32 *w);
@@ -1692,7 +1767,9 @@ int gm_trk_bank_samples(gm_trk *t, const gm_trk_state *state, const gm_c32 *samp
  * row shares the workgroup's LDS with the slice's ref image), first_index + n_time not below 2^62: GM_ERR_OUT_OF_RANGE.  A refusal
  * leaves z and done untouched.
  * Out of scope: a loop that re-steers by itself; propagating a state over several epochs inside the call; carrier offsets or several
- * code taps per call; an array ring; a _dev / caller's-stream form; any detection or quality decision. */
+ * code taps per call; an array ring; a _dev / caller's-stream form; any detection or quality decision.
+ * (Since then the _dev / caller's-stream form has been built, and with it the update that needs no host wait: gm_trk_array_prompts_dev,
+ * "Re-steering on the device" above.) */
 typedef struct {
     uint32_t n_antennas, taps;     /* A, L */
     float tap_chips;               /* tau, chips */
@@ -1712,6 +1789,12 @@ int gm_trk_array_plan(const gm_trk_cfg *trk, const gm_trk_array_cfg *cfg, uint32
  * memory, the word order gm_array_row_solve takes; done: [n_states] or NULL. */
 int gm_trk_array_prompts(gm_trk *t, const void *d_samples, int fmt, uint64_t first_index, uint64_t n_time, const gm_trk_state *states,
                          uint32_t n_states, const gm_trk_array_cfg *cfg, gm_c32 *z, uint8_t *done);
+/* The same words into device buffers, asynchronously on `stream` (NULL: the handle's own); the samples are ready on that stream.
+ * "Re-steering on the device" above states the contract: states is required (host, read before the call returns), d_z and d_done are
+ * required, d_z may not lie over the samples. */
+int gm_trk_array_prompts_dev(gm_trk *t, const void *d_samples, int fmt, uint64_t first_index, uint64_t n_time,
+                             const gm_trk_state *states, uint32_t n_states, const gm_trk_array_cfg *cfg,
+                             void *d_z /* [n_states][L][A] c32, device */, void *d_done /* [n_states] u8, device */, void *stream);
 
 /* ------------------------------------------------------------------ Bit sync + nav-bit accumulation
  * src/decoding.rs:8,40-227 (legacy file outside the reference's module tree): 20-bin histogram of prompt-I sign

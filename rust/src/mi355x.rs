@@ -106,6 +106,10 @@ pub struct GmArrayRowInfo {         // gm_array_row_info (24 bytes): lambda1 / l
     pub lambda1: f64, pub lambda2: f64, pub ref_index: u32, pub reserved: u32,
 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmArraySolveCfg {        // gm_array_solve_cfg (56 bytes): one gm_array_rows_solve_dev call; strides in Complex32 words, 0, 0: [n_rows][n][m]
+    pub m: u32, pub n: u32, pub n_rows: u32, pub n_blocks: u32, pub row_stride: u64, pub vec_stride: u64, pub loading: f32, pub reserved: [u32; 5],
+}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct GmAcqCancelCand {        // gm_acq_cancel_cand (32 bytes): a found satellite for gm_acq_cancel
     pub worker: u32, pub reserved: u32,
     pub carrier_hz: f64,             // IF + Doppler: GmAcqLocalOut::carrier_hz
@@ -278,6 +282,11 @@ extern "C" {
                              words_per_cand: *mut u32) -> c_int;
     pub fn gm_array_row_solve(m: u32, n: u32, z: *const Complex32, r: *const Complex32, n_blocks: usize, loading: f32,
                               row: *mut Complex32, info: *mut GmArrayRowInfo) -> c_int;
+    /// re-steering on the device: the rules and extents of a batched solve (host only), and the solve itself, asynchronous on `stream`
+    /// (d_info[p].reserved is row p's status, 0: solved)
+    pub fn gm_array_solve_plan(cfg: *const GmArraySolveCfg, z_words: *mut u64, r_words: *mut u64, row_words: *mut u64) -> c_int;
+    pub fn gm_array_rows_solve_dev(cfg: *const GmArraySolveCfg, d_z: *const c_void, d_r: *const c_void, d_rows: *mut c_void,
+                                   d_info: *mut c_void, stream: *mut c_void) -> c_int;
     // subtracting found satellites from a dwell (additive entries, ABI stays 9): one amplitude per signal code period and candidate,
     // estimated from the input; the output is c32 in device memory; d_samples null: the snapshot of the last search
     pub fn gm_acq_cancel(a: *mut GmAcq, d_samples: *const c_void, fmt: c_int, cands: *const GmAcqCancelCand, n_cands: u32,
@@ -434,6 +443,8 @@ extern "C" {
     pub fn gm_beamformer_synchronize(h: *mut GmBeamformer) -> c_int;
     /// beam `beam`'s new row of M words for every block a later call finishes; synchronous
     pub fn gm_beamformer_set_steering(h: *mut GmBeamformer, beam: u32, s: *const Complex32) -> c_int;
+    pub fn gm_beamformer_set_steering_dev(h: *mut GmBeamformer, first_beam: u32, n_rows: u32, d_rows: *const c_void, d_info: *const c_void,
+                                          min_ratio: f32, d_installed: *mut c_void, stream: *mut c_void) -> c_int;
     /// static mode: P M fixed weights [P][L][A] for every later block (synchronous); null: back to the adaptive rule
     pub fn gm_beamformer_set_weights(h: *mut GmBeamformer, w: *const Complex32) -> c_int;
     /// device buffers [cap_blocks][M][M] and [cap_blocks][P][M] that every later gm_beamformer_process_dev fills from word 0
@@ -482,6 +493,11 @@ extern "C" {
     pub fn gm_trk_array_prompts(t: *mut GmTrk, d_samples: *const c_void, fmt: c_int, first_index: u64, n_time: u64,
                                 states: *const GmTrkState, n_states: u32, cfg: *const GmTrkArrayCfg, z: *mut Complex32,
                                 done: *mut u8) -> c_int;
+    /// the same words into device buffers (d_z [n_states][L][A], d_done [n_states]), asynchronous on `stream` (null: the handle's own);
+    /// states is required and read before the call returns
+    pub fn gm_trk_array_prompts_dev(t: *mut GmTrk, d_samples: *const c_void, fmt: c_int, first_index: u64, n_time: u64,
+                                    states: *const GmTrkState, n_states: u32, cfg: *const GmTrkArrayCfg, d_z: *mut c_void,
+                                    d_done: *mut c_void, stream: *mut c_void) -> c_int;
     // fft.rs:5-56
     pub fn gm_fft_c2c_f32(n: usize, dir: c_int, inout: *mut Complex32, batch: usize) -> c_int;
     pub fn gm_fft_power_spectrum_f32(n: usize, inout: *mut Complex32, power: *mut f32) -> c_int;

@@ -189,6 +189,33 @@ impl AcquisitionEngine {
         }
         Ok((row, info))
     }
+    /// Not in the reference: the argument rules of solve_rows_dev and the extents it touches, in Complex32 words -> (z_words read at
+    /// d_z, r_words read at d_r, row_words written at d_rows).  Host only (gm_array_solve_plan).
+    pub fn solve_plan(cfg: &GmArraySolveCfg) -> Result<(u64, u64, u64), AcqError> {
+        let (mut z, mut r, mut w) = (0u64, 0u64, 0u64);
+        if unsafe { gm_array_solve_plan(cfg, &mut z, &mut r, &mut w) } != 0 { return Err(AcqError); }
+        Ok((z, r, w))
+    }
+    /// Not in the reference: solve_row for cfg.n_rows rows in one launch on the device (gm_array_rows_solve_dev), asynchronous on
+    /// `stream` (null: the null stream).  Device pointers; `d_r` null with cfg.n_blocks = 0 is the identity; d_info[p].reserved is row
+    /// p's status (0: solved).
+    pub fn solve_rows_dev(cfg: &GmArraySolveCfg, d_z: *const std::os::raw::c_void, d_r: *const std::os::raw::c_void,
+                          d_rows: *mut std::os::raw::c_void, d_info: *mut std::os::raw::c_void,
+                          stream: *mut std::os::raw::c_void) -> Result<(), AcqError> {
+        if unsafe { gm_array_rows_solve_dev(cfg, d_z, d_r, d_rows, d_info, stream) } != 0 { return Err(AcqError); }
+        Ok(())
+    }
+    /// Not in the reference: install solve_rows_dev's rows into a beamformer's beams first_beam .. first_beam + n_rows - 1 by a kernel
+    /// on `stream` (gm_beamformer_set_steering_dev), ordered like a process_dev call; a row is installed where it is finite, not all
+    /// zero and, with `d_info`, has status 0 and lambda1 >= min_ratio * lambda2.  `d_installed`: [n_rows] u8 or null.
+    pub fn set_steering_dev(h: *mut GmBeamformer, first_beam: u32, n_rows: u32, d_rows: *const std::os::raw::c_void,
+                            d_info: *const std::os::raw::c_void, min_ratio: f32, d_installed: *mut std::os::raw::c_void,
+                            stream: *mut std::os::raw::c_void) -> Result<(), AcqError> {
+        if unsafe { gm_beamformer_set_steering_dev(h, first_beam, n_rows, d_rows, d_info, min_ratio, d_installed, stream) } != 0 {
+            return Err(AcqError);
+        }
+        Ok(())
+    }
     /// Not in the reference: subtract found satellites from a dwell — one amplitude per signal code period and candidate is estimated
     /// from the input (the snapshot of the LAST search when `d_samples` is None, else any dwell in device memory, read only) and the
     /// dwell minus the replicas is written as Complex32 to `d_out` (device memory, `dwell_samples` samples), which the device search

@@ -413,6 +413,18 @@ impl TrackingManager {
         (z, done)
     }
 
+    /// array_prompts' words into device buffers (gm_trk_array_prompts_dev): `d_z` [R][L][A] Complex32 and `d_done` [R] u8 in device
+    /// memory, asynchronously on `stream` (null: the handle's own), with no host wait.  `records` are required (the states a collect
+    /// handed over) and are read before the call returns.  Not part of the reference.
+    pub fn array_prompts_dev(&mut self, d_samples: *const std::ffi::c_void, fmt: i32, first_index: u64, n_time: u64, n_antennas: u32,
+                             taps: u32, tap_chips: f32, records: &[GmTrkState], d_z: *mut std::ffi::c_void, d_done: *mut std::ffi::c_void,
+                             stream: *mut std::ffi::c_void) {
+        let cfg = GmTrkArrayCfg { n_antennas, taps, tap_chips, reserved: [0; 5] };
+        let st = unsafe { gm_trk_array_prompts_dev(self.h, d_samples, fmt, first_index, n_time, records.as_ptr(), records.len() as u32, &cfg,
+                                                   d_z, d_done, stream) };
+        assert_eq!(st, 0, "gm_trk_array_prompts_dev: {}", last_error());
+    }
+
     fn next_tracking_index(&self) -> usize {                             // :373-381 on the PLANNED positions (= the fields when nothing is in flight)
         (0..self.channels.len()).filter(|i| self.channels[*i].is_active())
             .map(|i| self.planned_index(i) + self.channels[i].num_samples_per_code).min().unwrap_or(0)
