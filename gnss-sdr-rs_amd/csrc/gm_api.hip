@@ -2914,9 +2914,8 @@ struct gm_trk {
     uint32_t epochs_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timing = false; uint32_t timed_launches = 0;
-    // persistent multi-epoch kernel: G workgroups per channel, granule exchange buffer, launch counter
-    int G = 1;
-    bool packed = false;                // the persistent grid's packed layout (trk_kernels.hip): G workgroups per channel dealt over the XCDs as one run
+    // persistent multi-epoch kernel: its launch layout (decided once, at create), granule exchange buffer, launch counter
+    gm::TrkPersistPlan plan{};
     unsigned long long* d_xchg = nullptr;
     int* d_error = nullptr;             // host-pinned, device-visible: written by the kernel only when an exchange times out
     int* d_error_dev = nullptr;         // its device-memory twin, read by every later launch (trk_persistent_kernel)
@@ -3052,17 +3051,31 @@ int gm_trk_create(const gm_trk_cfg* cfg, gm_trk** out) {
     d.dll_dt = cfg->dll_dt > 0 ? cfg->dll_dt : 0.001f;
     d.nominal_code_rate = cfg->nominal_code_rate > 0 ? cfg->nominal_code_rate : CA_RATE;
     gm::fill_trk_derived(d);
-    {   // the persistent kernel keeps the channel's chip row in LDS as floats (three tables of it for BOC): a code that cannot fit is
+    // The persistent kernel's launch layout (trk_persist_plan.h) from what the device says about the instantiation(s) this
+    // configuration can launch and the diagnostic overrides, which are read here and nowhere else.
+    gm::TrkPersistKnobs knobs;
+    knobs.g = gm::diag_int("GM_TRK_G", knobs.g); knobs.packed = gm::diag_int("GM_TRK_PACKED", knobs.packed);
+    knobs.packed_g = gm::diag_int("GM_TRK_PACKED_G", knobs.packed_g); knobs.stagger_k = gm::diag_int("GM_TRK_STAGGER_K", knobs.stagger_k);
+    knobs.fair = gm::diag_int("GM_TRK_FAIR", knobs.fair);
+    {   // the kernel keeps the channel's chip row in LDS as floats (three tables of it for BOC): a code that cannot fit is
         // refused here, from the kernel's own static size and the device's limit, not found out by a launch that fails
-        size_t need = 0, limit = 0;
-        const hipError_t e = gm::trk_persistent_lds_need(d, t->device, &need, &limit);
-        if (e != hipSuccess) { gm_trk_destroy(t); return hip_fail(e, "trk_persistent_lds_need"); }
+        gm::TrkPersistProbe probe;
+        const hipError_t e = gm::trk_persist_probe(d, knobs, t->device, &probe);
+        if (e != hipSuccess) { gm_trk_destroy(t); return hip_fail(e, "trk_persist_probe"); }
+        const size_t need = probe.static_lds + gm::trk_persist_lds_bytes(d), limit = probe.lds_limit;
         if (need > limit) {
             gm_trk_destroy(t);
             char msg[192];
             snprintf(msg, sizeof(msg), "code_len %d needs %zu bytes of LDS per workgroup (chip tables + the kernel's own), the device allows %zu bytes",
                      d.code_len, need, limit);
             return set_err(GM_ERR_OUT_OF_RANGE, msg);
+        }
+        t->plan = gm::trk_persist_plan(d, cfg->share_device != 0, probe.dev, knobs);
+        if (gm::diag_int("GM_TRK_PLAN_PRINT", 0) != 0) {      // diagnostic: what the device said and what was decided (tools/trk_persist_plan_ab.py)
+            const gm::TrkPersistPlan& p = t->plan;
+            fprintf(stderr, "gm_trk plan: key %d strict %d fair3 %d | cus %d per_cu_plain %d per_cu_fair %d static_lds %zu | G %d packed %d grid %d per %u "
+                    "fair_share %d lds %zu xchg %zu\n", p.key, p.strict, p.fair3, probe.dev.cus, probe.dev.per_cu_plain, probe.dev.per_cu_fair,
+                    probe.static_lds, p.G, p.packed, p.grid, p.per, p.fair_share, p.lds_bytes, p.xchg_bytes);
         }
     }
     if (cfg->codes) t->h_codes.assign(cfg->codes, cfg->codes + size_t(cfg->n_codes) * cfg->code_len);
@@ -3106,44 +3119,9 @@ int gm_trk_create(const gm_trk_cfg* cfg, gm_trk** out) {
     HIPT(hipMemsetAsync(t->d_ready, 0, t->C, t->stream));      // (the handle's stream is non-blocking: a NULL-stream memset would not be ordered with it)
     HIPT(hipEventCreate(&t->ev0));
     HIPT(hipEventCreate(&t->ev1));
-    {   // workgroups per channel for the persistent kernel: all n_channels*G must be co-resident (one per CU)
-        hipDeviceProp_t prop;
-        HIPT(hipGetDeviceProperties(&prop, t->device));
-        const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
-        const int nv = 2 * d.n_arms;
-        int g = 1;
-        const int per_cu = gm::trk_persistent_blocks_per_cu(d);      // occupancy of this instantiation, capped at the design's 2
-        const size_t slots = size_t(gm::trk_persistent_slots(t->C));   // the grid is slots * G workgroups (empty ones leave at once)
-        // the most workgroups per channel the chip holds at once (any count, not only powers of two: 36 channels take 12 each,
-        // 480 of the 512 places, where 8 left a third of the chip idle and two-workgroup CUs beside one-workgroup CUs);
-        // 17..31 fall back to 16, the width of the DPP totals path
-        {
-            // share_device: a quarter of the places (gm_trk_cfg: the other stages' kernels run beside a tracking launch)
-            const size_t fit = (size_t(cus) * per_cu) / (cfg->share_device ? 4 : 1) / slots;
-            g = int(fit < 1 ? 1 : fit > 32 ? 32 : fit);
-            while (g > 1 && g * nv > 256) --g;
-            if (g > 16 && g < 32) g = 16;
-        }
-        {   // Packed layout: a channel count that does not fill the eight XCDs evenly (36 -> 5, 5, 5, 5, 4, 4, 4, 4 slots of 12
-            // workgroups: 432 of 512 places, and the launch lasts as long as the 5-channel XCDs) is dealt as ONE run of C * G
-            // workgroups, 14 each at 36 channels (504 places); a channel at the edge of an XCD's piece exchanges through the fabric.
-            // Only where correlation fills the epoch (>= 8 samples per lane): a latency-chain launch wants its channels on one XCD.
-            const size_t places = (size_t(cus) * per_cu) / (cfg->share_device ? 4 : 1);
-            int gp = int(places / t->C < 16 ? places / t->C : 16);
-            while (gp > 1 && gp * nv > 256) --gp;
-            { const int fp = gm::diag_int("GM_TRK_PACKED_G", 0); if (fp >= 1 && fp < gp) gp = fp; }      // diagnostic: fewer workgroups per channel in the packed layout
-            const float nn = roundf(d.fs / (d.nominal_code_rate / d.code_len_f));
-            const bool shaped = nn > 0 && gp >= 1 && nn / float(gp) / 512.0f >= 8.0f;
-            if ((t->C % 8) != 0 && gp > g && shaped && gm::diag_int("GM_TRK_PACKED", 1) != 0) { g = gp; t->packed = true; }
-        }
-        {   // diagnostic override (GM_DIAGNOSTICS=1 only; must keep n_channels * G resident)
-            const int f = gm::diag_int("GM_TRK_G", 0);
-            if (f >= 1 && f <= 32 && size_t(f) * slots <= size_t(cus) * per_cu && f * nv <= 256) { g = f; t->packed = false; }
-        }
-        t->G = g;
-        const size_t xb = (size_t(2) * t->C * gm::trk_persistent_granule_stride(g) * nv + size_t(t->C) * g) * sizeof(unsigned long long);   // partials + XCC_ID granules
-        HIPT(hipMalloc(&t->d_xchg, xb));
-        HIPT(hipMemsetAsync(t->d_xchg, 0, xb, t->stream));
+    {   // the exchange block of the persistent kernel's workgroups, and its time-out flag
+        HIPT(hipMalloc(&t->d_xchg, t->plan.xchg_bytes));
+        HIPT(hipMemsetAsync(t->d_xchg, 0, t->plan.xchg_bytes, t->stream));
         HIPT(hipHostMalloc(reinterpret_cast<void**>(&t->d_error), sizeof(int), hipHostMallocDefault));   // read on the host after a stream sync: no copy
         *t->d_error = 0;
         HIPT(hipMalloc(&t->d_error_dev, sizeof(int)));
@@ -3604,7 +3582,7 @@ static int trk_launch_all(gm_trk* t, gm_ring* ring, uint32_t epochs, uint64_t he
     if (t->dc.strict_sum_order) {
         // the reference's sequential sums: three launches per pass (products, one serial wave per channel, scalar epilogue)
         // instead of the persistent kernel; the data gate of every pass reads the head as of this call, like the persistent form
-        const float nn = roundf(t->dc.fs / (t->dc.nominal_code_rate / t->dc.code_len_f));
+        const float nn = gm::trk_nominal_period(t->dc);
         if (int rc = trk_reserve_terms(t, (nn > 0 ? size_t(nn * 1.01f) : 0) + 64)) return rc;
         // the strict launches (256 threads, 40-48 KB of LDS each) must not take CU slots away from another handle's persistent
         // grid on this device either: same chain — wait for the previous launch of the device, record behind the last one
@@ -3637,9 +3615,13 @@ static int trk_launch_all(gm_trk* t, gm_ring* ring, uint32_t epochs, uint64_t he
         const size_t o = size_t(e0) * t->C;
         t->launch_seq = (t->launch_seq + 1) & 0xfffffu;
         if (t->launch_seq == 0) t->launch_seq = 1;
-        gm::launch_trk_persistent(t->stream, t->dc, t->d_codes, t->d_states, ring->d_buf, ring->mask, head, t->G, t->packed ? 1 : 0,
-                                  int(ne), t->launch_seq << 12, t->d_xchg, t->d_outs + o, t->d_proc + o, t->d_lost + o,
-                                  t->d_lostprn + o, t->d_error, t->d_error_dev, (t->d_stamps && e0 == 0 && ne <= t->stamps_cap) ? t->d_stamps : nullptr);
+        gm::TrkPersistCall c;
+        c.codes = t->d_codes; c.states = t->d_states; c.ring = ring->d_buf; c.mask = ring->mask; c.head = head;
+        c.epochs = int(ne); c.tag_base = t->launch_seq << 12; c.xchg = t->d_xchg;
+        c.outs = t->d_outs + o; c.processed = t->d_proc + o; c.lost = t->d_lost + o; c.lost_prn = t->d_lostprn + o;
+        c.error = t->d_error; c.error_dev = t->d_error_dev;
+        c.stamps = (t->d_stamps && e0 == 0 && ne <= t->stamps_cap) ? t->d_stamps : nullptr; c.stamps_words = size_t(t->stamps_cap) * 48;
+        gm::launch_trk_persistent(t->stream, t->dc, t->plan, c);
     }
     if (t->timing) { HIPC(hipEventRecord(t->ev1, t->stream)); t->timed_launches = epochs; }
     HIPC(hipEventRecord(chain.ev, t->stream));

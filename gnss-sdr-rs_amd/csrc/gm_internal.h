@@ -5,6 +5,7 @@
 
 #include "../../include/gnss_mi355x.h"
 #include "fft_core.h"
+#include "trk_persist_plan.h"
 
 namespace gm {
 
@@ -288,34 +289,7 @@ struct DecideArgs {
 void launch_decide(hipStream_t, const DecideArgs&);
 
 // ---------------------------------------------------------------- tracking
-struct TrkDevCfg {
-    float fs;
-    int n_channels, n_arms;
-    float el_space, vel_space;
-    int code_index_mode, boc11;
-    int code_len;             // chips per period
-    float code_len_f;
-    int gps_ca;               // 1: built-in C/A table rows (row = prn or prn-1 by mode)
-    int n_codes;
-    float lock_threshold; uint32_t max_lost_epochs;
-    float pll_tau1, pll_tau2, dll_tau1, dll_tau2, pll_dt, dll_dt;
-    float nominal_code_rate;
-    // per-launch constants of the scalar epilogue, computed once on the host with IEEE f32 / f64 division
-    // (fill_trk_derived): quotients of configuration constants and correctly rounded reciprocals for the
-    // constant-divisor divisions
-    float inv_fs, inv_len, inv_2pi;
-    float pll_dt_tau1, pll_tau2_tau1, dll_dt_tau1, dll_tau2_tau1;   // dt/tau1, tau2/tau1 (LoopFilter::update :68-70)
-    int div_fs_ok;            // fs significand not all ones: div_const(x, fs) is the correctly rounded quotient
-    int strict_libm;          // gm_trk_cfg.strict_libm: carrier cos / sin by gm_libm.h's sincosf_glibc
-    int strict_sum_order;     // gm_trk_cfg.strict_sum_order: the six / ten sums added sample by sample (trk_serial_sum_kernel)
-};
-inline void fill_trk_derived(TrkDevCfg& d) {
-    d.inv_fs = 1.0f / d.fs; d.inv_len = 1.0f / d.code_len_f; d.inv_2pi = 1.0f / (2.0f * 3.14159265358979323846f);
-    d.pll_dt_tau1 = d.pll_dt / d.pll_tau1; d.pll_tau2_tau1 = d.pll_tau2 / d.pll_tau1;
-    d.dll_dt_tau1 = d.dll_dt / d.dll_tau1; d.dll_tau2_tau1 = d.dll_tau2 / d.dll_tau1;
-    uint32_t bits; __builtin_memcpy(&bits, &d.fs, 4);
-    d.div_fs_ok = ((bits & 0x7fffffu) != 0x7fffffu && d.fs > 1.0f && d.fs < 1.0e12f) ? 1 : 0;
-}
+// TrkDevCfg, fill_trk_derived and the persistent kernel's geometry and launch plan: trk_persist_plan.h (host-portable)
 enum { TRK_MODE_CORRELATE = 0, TRK_MODE_DO_WORK = 1 };
 // sample source: ring (mask = size-1, absolute index = next_sample_index + i) or linear (mask = ~0, base 0)
 struct TrkSrc {
@@ -327,30 +301,26 @@ void launch_trk_epoch(hipStream_t, const TrkDevCfg&, const int8_t* d_codes, gm_t
                       gm_trk_out* d_outs, uint8_t* d_processed, uint8_t* d_lost, uint8_t* d_lost_prn,
                       float* d_terms = nullptr, size_t terms_cap = 0, int* d_error = nullptr);   // (strict_sum_order: per-sample product streams)
 
-// Persistent tracking geometry: workgroups of TRK_PERSIST_THREADS lanes, TRK_PERSIST_WG_PER_CU of them per CU.
-// Two independent workgroups per CU let one channel's serial exchange + loop-filter epilogue (one wave) overlap
-// the other's correlation phase.
-#ifndef GM_TRK_THREADS          // (A/B switch of the workgroup shape: 256 x 4 per CU and 1024 x 1 were measured in round 6, DESIGN_HISTORY R6.10)
-#define GM_TRK_THREADS 512
-#define GM_TRK_WG_PER_CU 2
-#endif
-constexpr int TRK_PERSIST_THREADS = GM_TRK_THREADS;
-constexpr int TRK_PERSIST_WG_PER_CU = GM_TRK_WG_PER_CU;
-
-inline int trk_persistent_slots(int n_channels) { return (n_channels + 7) / 8 * 8; }   // grid = slots * G workgroups
-int trk_persistent_blocks_per_cu(const TrkDevCfg&);   // resident workgroups per CU of the instantiation this config selects
-// bytes of LDS a workgroup of that instantiation needs (static + chip tables) and the device's limit per workgroup
-hipError_t trk_persistent_lds_need(const TrkDevCfg&, int device, size_t* need, size_t* limit);
-// persistent multi-epoch tracking (one launch = `epochs` passes over all channels); G workgroups per channel
-int trk_persistent_granule_stride(int G);      // granules per arm in the exchange block of the persistent kernel (16 for G <= 16)
 void launch_trk_results_to_host(hipStream_t, const void* d_src, void* h_dst_pinned, size_t bytes, const void* d_src2 = nullptr, void* h_dst2_pinned = nullptr,
                                 size_t bytes2 = 0);
 // gm_debug_math: one lane per argument through the tracking loop's scalar helpers (trk_kernels.hip); inv = RN(1 / divisor) of ops 4, 5, 7
 void launch_trk_debug_math(hipStream_t, int op, const float* d_x, uint32_t n, float p0, float p1, float inv, uint32_t* d_out0, uint32_t* d_out1);
-void launch_trk_persistent(hipStream_t, const TrkDevCfg&, const int8_t* d_codes, gm_trk_state* d_states,
-                           const cf* ring, uint64_t mask, uint64_t head, int G, int packed, int epochs, uint32_t tag_base,
-                           unsigned long long* d_xchg, gm_trk_out* d_outs, uint8_t* d_processed, uint8_t* d_lost,
-                           uint8_t* d_lost_prn, int* d_error, int* d_error_dev, long long* d_stamps);
+// What gm_trk_create asks the device about the instantiation(s) this configuration can launch: residency per CU (occupancy API with
+// the config's dynamic LDS, capped at TRK_PERSIST_WG_PER_CU), the static LDS read from the code object (the larger where two
+// instantiations are possible) and the most LDS the device gives a workgroup.
+struct TrkPersistProbe { TrkPersistDevice dev; size_t static_lds, lds_limit; };
+hipError_t trk_persist_probe(const TrkDevCfg&, const TrkPersistKnobs&, int device, TrkPersistProbe*);
+// persistent multi-epoch tracking (one launch = `epochs` passes over all channels): what changes from call to call
+struct TrkPersistCall {
+    const int8_t* codes; gm_trk_state* states;
+    const cf* ring; uint64_t mask, head;
+    int epochs; uint32_t tag_base;
+    unsigned long long* xchg;
+    gm_trk_out* outs; uint8_t *processed, *lost, *lost_prn;
+    int *error, *error_dev;
+    long long* stamps; size_t stamps_words;      // diagnostic (may be null), and the words allocated behind it
+};
+void launch_trk_persistent(hipStream_t, const TrkDevCfg&, const TrkPersistPlan&, const TrkPersistCall&);
 
 // gm_trk_bank / gm_trk_bank_samples (trk_bank.hip, a section of trk_kernels.hip): taps x carrier offsets at caller-supplied records.
 // The host decides which records run (gnss_mi355x.h lists what skips one) and hands the kernel n, the slice count ceil(n / 4096) and

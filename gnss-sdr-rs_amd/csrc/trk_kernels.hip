@@ -129,10 +129,7 @@ __device__ __forceinline__ void reset_state(gm_trk_state& s) {
 #ifndef GM_TRK_IL5
 #define GM_TRK_IL5 2          // samples per straight-line block of the five-arm fast path (2 or 4)
 #endif
-// persistent kernel's dynamic LDS.  Plain: [code_len + 3 floats of the padded chip row].  BOC: [2 code_len + 6 half chips, whole
-// float4s][the padded chip row] — the table the fast path reads sits FIRST, at a compile-time LDS address, so that its look-ups are
-// `v_lshlrev` + `ds_read offset:constant` (a run-time base costs a half-rate v_lshl_add with a scalar source per look-up)
-__host__ __device__ __forceinline__ int boc_plain_offset(int code_len) { return (2 * code_len + 6 + 3) & ~3; }
+// (the persistent kernel's dynamic LDS and boc_plain_offset: trk_persist_plan.h)
 
 // per-epoch constants of one channel, derived from its state exactly once per epoch
 struct EpochConsts {
@@ -1094,7 +1091,7 @@ __global__ __launch_bounds__(T, TRK_PERSIST_WG_PER_CU * T / 256) void trk_persis
         const bool younger = a.fair_share && int(blockIdx.x >> 3) >= a.fair_share;
         if (a.stagger) {
             // class of this channel (2 bits per channel of the XCD, by its index there; one table for the XCDs that hold the larger
-            // channel count, one for the others): a colouring, made on the host, of "shares CUs with" — see launch_trk_persistent
+            // channel count, one for the others): a colouring, made on the host, of "shares CUs with" — see trk_persist_plan
             const int xcd = int(blockIdx.x & 7), local = int(blockIdx.x >> 3) / a.G;
             const int count = (C - xcd + 7) >> 3, most = (C + 7) >> 3;
             const uint32_t cls = ((count == most ? a.stagger_tab[0] : a.stagger_tab[1]) >> (2 * (local & 7))) & 3u;
@@ -1532,162 +1529,68 @@ __global__ __launch_bounds__(T, TRK_PERSIST_WG_PER_CU * T / 256) void trk_persis
     }
 }
 
-// granules per arm in the exchange block (TrkPersistArgs::GS); the block is 2 * n_channels * GS * (2 * arms) granules + n_channels * G
-int trk_persistent_granule_stride(int G) { return G <= 16 ? 16 : G; }
-
-// dynamic LDS of the persistent kernel: the chip row as floats with one guard entry in front and two behind, rounded up to 16 B
-static size_t trk_persistent_lds(const TrkDevCfg& cfg) {
-    size_t floats = size_t(cfg.code_len) + 3;                                    // the padded chip row
-    if (cfg.boc11) floats += size_t(boc_plain_offset(cfg.code_len));             // + the half-chip table of the BOC fast path in front of it
-    return (floats * sizeof(float) + 15) & ~size_t(15);
+// The one table of the persistent kernel's instantiations: eight keys x {plain, strict_libm}, and FAIR3 for the three-arm keys.
+// Launch, occupancy and LDS queries all take the address from here, so none can ask about a kernel other than the one launched.
+template <int A, int M, int B>
+static const void* trk_persistent_instances(int strict, int fair3) {
+    constexpr int T = TRK_PERSIST_THREADS;
+    if (strict) return reinterpret_cast<const void*>(&trk_persistent_kernel<A, M, B, T, 1>);
+    if (A == 3 && fair3) return reinterpret_cast<const void*>(&trk_persistent_kernel<A, M, B, T, 0, A == 3>);
+    return reinterpret_cast<const void*>(&trk_persistent_kernel<A, M, B, T, 0>);
+}
+static const void* trk_persistent_instance(int key, int strict, int fair3) {      // key, strict, fair3: as TrkPersistPlan names them
+    static const void* (*const by_key[8])(int, int) = {      // compile-time arms / code-index mode / BOC: straight-line sample code
+        trk_persistent_instances<3, 0, 0>, trk_persistent_instances<3, 0, 1>, trk_persistent_instances<3, 1, 0>, trk_persistent_instances<3, 1, 1>,
+        trk_persistent_instances<5, 0, 0>, trk_persistent_instances<5, 0, 1>, trk_persistent_instances<5, 1, 0>, trk_persistent_instances<5, 1, 1>};
+    return by_key[key & 7](strict, fair3);
 }
 
-void launch_trk_persistent(hipStream_t st, const TrkDevCfg& cfg, const int8_t* d_codes, gm_trk_state* d_states,
-                           const cf* ring, uint64_t mask, uint64_t head, int G, int packed, int epochs, uint32_t tag_base,
-                           unsigned long long* d_xchg, gm_trk_out* d_outs, uint8_t* d_processed, uint8_t* d_lost,
-                           uint8_t* d_lost_prn, int* d_error, int* d_error_dev, long long* d_stamps) {
+// Asked at gm_trk_create.  The LDS figures let a code too long for the chip tables be refused there and never reach a launch; the
+// residency figures size the grid, whose workgroups must all be resident together (the exchange between a channel's G workgroups spins).
+hipError_t trk_persist_probe(const TrkDevCfg& cfg, const TrkPersistKnobs& knobs, int device, TrkPersistProbe* out) {
+    const int key = trk_persist_key(cfg), strict = cfg.strict_libm ? 1 : 0;
+    const int forms = trk_persist_may_fair3(cfg, knobs) ? 2 : 1;      // plain (or strict) alone, or plain and FAIR3
+    const void* kernel[2] = {trk_persistent_instance(key, strict, 0), trk_persistent_instance(key, strict, 1)};
+    int per_block = 0;
+    if (hipError_t e = hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device); e != hipSuccess) return e;
+    out->lds_limit = size_t(per_block > 0 ? per_block : 0);
+    out->static_lds = 0;
+    for (int f = 0; f < forms; ++f) {
+        hipFuncAttributes fa;
+        if (hipError_t e = hipFuncGetAttributes(&fa, kernel[f]); e != hipSuccess) return e;
+        if (size_t(fa.sharedSizeBytes) > out->static_lds) out->static_lds = size_t(fa.sharedSizeBytes);
+    }
+    hipDeviceProp_t prop;
+    if (hipError_t e = hipGetDeviceProperties(&prop, device); e != hipSuccess) return e;
+    out->dev.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+    const size_t lds = trk_persist_lds_bytes(cfg);
+    int per_cu[2] = {1, 1};
+    if (out->static_lds + lds <= out->lds_limit)      // (a workgroup that does not fit is refused by the caller: nothing to ask)
+        for (int f = 0; f < forms; ++f) {
+            int n = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel[f], TRK_PERSIST_THREADS, lds) != hipSuccess || n < 1) n = 1;
+            per_cu[f] = n < TRK_PERSIST_WG_PER_CU ? n : TRK_PERSIST_WG_PER_CU;
+        }
+    out->dev.per_cu_plain = per_cu[0];
+    out->dev.per_cu_fair = forms == 2 ? per_cu[1] : per_cu[0];
+    return hipSuccess;
+}
+
+// GM_TRK_STAMP_WG and GM_TRK_FORCE_SC1 are the two overrides a launch still reads itself (a diagnostic run changes them between two
+// launches of one process); everything else of the layout is the handle's plan.
+void launch_trk_persistent(hipStream_t st, const TrkDevCfg& cfg, const TrkPersistPlan& p, const TrkPersistCall& c) {
     TrkPersistArgs a;
-    a.error_flag_dev = d_error_dev;
-    a.stamps = d_stamps;
-    a.cfg = cfg; a.codes = d_codes; a.states = d_states; a.ring = ring; a.mask = mask; a.head = head;
-    a.G = G; a.GS = trk_persistent_granule_stride(G); a.epochs = epochs; a.tag_base = tag_base;
-    a.packed = packed ? (cfg.n_channels * G + 7) / 8 : 0;
+    a.cfg = cfg; a.codes = c.codes; a.states = c.states; a.ring = c.ring; a.mask = c.mask; a.head = c.head;
+    a.G = p.G; a.epochs = c.epochs; a.packed = p.packed; a.GS = p.GS;
     a.stamp_block = diag_int("GM_TRK_STAMP_WG", 0);
     a.force_write_through = diag_int("GM_TRK_FORCE_SC1", 0) != 0 ? 1 : 0;
-    {   // slice length from the nominal code period (+1 % margin; +0.2 % where an epoch is many samples per lane: there the margin is
-        // rows of work on every workgroup but the last, which takes whatever a longer period adds anyway), whole wavefronts
-        const float nn = roundf(cfg.fs / (cfg.nominal_code_rate / cfg.code_len_f));
-        const float margin = (nn > 0 && nn / float(G) / float(TRK_PERSIST_THREADS) >= 8.0f) ? 1.002f : 1.01f;
-        const uint64_t n_nom = nn > 0 ? uint64_t(nn * margin) + 64 : 64;
-        a.per = uint32_t(((n_nom + G - 1) / G + 63) / 64 * 64);
-    }
-    {   // stagger (see the kernel): only when an epoch is many samples per lane, i.e. when correlation, not the serial chain, fills it.
-        // The dispatcher deals an XCD's workgroups round-robin over its CUs (measured: tools/trk_placement.py), so ordinals o and
-        // o + CUs-per-XCD share a CU; channel `l` of an XCD owns ordinals [l G, (l + 1) G).  Channels that share a CU get different
-        // classes (0, 1, 2: a greedy colouring — the conflict graph of five channels of twelve workgroups on 32 CUs is a 5-cycle,
-        // so two classes do not do), class k starts k thirds of an epoch late.
-        const uint32_t rows = a.per / uint32_t(TRK_PERSIST_THREADS);                 // samples per lane and epoch
-        // (measured, round 6: the stagger alone buys NOTHING — 21.2 us per code period at BASELINE configs[4] with and without, plus
-        // its own delay — because the co-tenants are not symmetric: see `fair_share`.  Off unless asked for; kept for experiments.)
-        const int k = diag_int("GM_TRK_STAGGER_K", 0);                               // 10 ns ticks per row of samples and class
-        a.stagger = rows >= 8 && G >= 2 && !packed ? rows * uint32_t(k < 0 ? 0 : k) : 0u;
-        a.stagger_tab[0] = a.stagger_tab[1] = 0u;
-        static int cus_cache[16] = {0};                     // per device, asked once (hipGetDeviceProperties is not a per-launch call)
-        int dev = 0, cus = 32;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int& c = cus_cache[dev & 15];
-            if (c == 0) {
-                hipDeviceProp_t prop;
-                c = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8) ? prop.multiProcessorCount / 8 : 32;
-            }
-            cus = c;
-        }
-        a.fair_mode = diag_int("GM_TRK_FAIR", 2);
-        a.fair_share = (rows >= 8 && a.fair_mode != 0) ? cus : 0;
-        if (a.stagger) {
-            const int most = (cfg.n_channels + 7) / 8;
-            for (int v = 0; v < 2; ++v) {
-                const int count = most - v;
-                if (count < 1 || count > 8) continue;
-                int cls[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int l = 0; l < count; ++l) {           // greedy: the smallest class no earlier co-tenant has
-                    bool used[4] = {false, false, false, false};
-                    for (int m = 0; m < l; ++m) {
-                        bool share = false;                  // some ordinal of l and some ordinal of m differ by a multiple of `cus`
-                        for (int o = l * G; o < (l + 1) * G && !share; ++o)
-                            for (int q = m * G; q < (m + 1) * G; ++q)
-                                if ((o - q) % cus == 0) { share = true; break; }
-                        if (share) used[cls[m]] = true;
-                    }
-                    cls[l] = !used[0] ? 0 : !used[1] ? 1 : !used[2] ? 2 : 3;
-                    a.stagger_tab[v] |= uint32_t(cls[l]) << (2 * l);
-                }
-            }
-        }
-    }
-    a.xchg = d_xchg; a.outs = d_outs;
-    a.processed = d_processed; a.lost = d_lost; a.lost_prn = d_lost_prn; a.error_flag = d_error;
-    const size_t lds = trk_persistent_lds(cfg);
-    const dim3 grid(a.packed ? 8 * a.packed : trk_persistent_slots(cfg.n_channels) * G);     // channel slots: n_channels rounded up to the eight XCDs
-    // compile-time arms / code-index mode / BOC: straight-line sample code
-    const int key = (cfg.n_arms == 5 ? 4 : 0) | (cfg.code_index_mode == GM_CODE_INDEX_FIXED ? 2 : 0) | (cfg.boc11 ? 1 : 0);
-    constexpr int T = TRK_PERSIST_THREADS;
-#define GM_TRK_LAUNCH(A, M, B) \
-    if (cfg.strict_libm) hipLaunchKernelGGL((trk_persistent_kernel<A, M, B, T, 1>), grid, dim3(T), lds, st, a); \
-    else if (A == 3 && a.fair_share) hipLaunchKernelGGL((trk_persistent_kernel<A, M, B, T, 0, A == 3>), grid, dim3(T), lds, st, a); \
-    else hipLaunchKernelGGL((trk_persistent_kernel<A, M, B, T, 0>), grid, dim3(T), lds, st, a); \
-    break
-    switch (key) {
-        case 0: GM_TRK_LAUNCH(3, 0, 0);
-        case 1: GM_TRK_LAUNCH(3, 0, 1);
-        case 2: GM_TRK_LAUNCH(3, 1, 0);
-        case 3: GM_TRK_LAUNCH(3, 1, 1);
-        case 4: GM_TRK_LAUNCH(5, 0, 0);
-        case 5: GM_TRK_LAUNCH(5, 0, 1);
-        case 6: GM_TRK_LAUNCH(5, 1, 0);
-        default: GM_TRK_LAUNCH(5, 1, 1);
-    }
-#undef GM_TRK_LAUNCH
-}
-
-// Workgroups of the persistent kernel one CU can hold at once (occupancy API for THIS instantiation and its dynamic LDS,
-// capped by the design's TRK_PERSIST_WG_PER_CU): the exchange between the G workgroups of a channel needs all
-// n_channels * G of them resident together.
-int trk_persistent_blocks_per_cu(const TrkDevCfg& cfg) {
-    const size_t lds = trk_persistent_lds(cfg);
-    const int key = (cfg.n_arms == 5 ? 4 : 0) | (cfg.code_index_mode == GM_CODE_INDEX_FIXED ? 2 : 0) | (cfg.boc11 ? 1 : 0);
-    constexpr int T = TRK_PERSIST_THREADS;
-    int n = 0;
-    hipError_t e = hipSuccess;
-#define GM_TRK_OCC(A, M, B) \
-    e = cfg.strict_libm ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trk_persistent_kernel<A, M, B, T, 1>, T, lds) \
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trk_persistent_kernel<A, M, B, T, 0>, T, lds); \
-    break
-    switch (key) {
-        case 0: GM_TRK_OCC(3, 0, 0);
-        case 1: GM_TRK_OCC(3, 0, 1);
-        case 2: GM_TRK_OCC(3, 1, 0);
-        case 3: GM_TRK_OCC(3, 1, 1);
-        case 4: GM_TRK_OCC(5, 0, 0);
-        case 5: GM_TRK_OCC(5, 0, 1);
-        case 6: GM_TRK_OCC(5, 1, 0);
-        default: GM_TRK_OCC(5, 1, 1);
-    }
-#undef GM_TRK_OCC
-    if (e != hipSuccess || n < 1) n = 1;
-    return n < TRK_PERSIST_WG_PER_CU ? n : TRK_PERSIST_WG_PER_CU;
-}
-
-// LDS one workgroup of the persistent kernel asks for with this configuration — the static share of the instantiation it selects
-// (read from the code object) plus the chip tables — and the most the device gives a workgroup.  Asked at gm_trk_create, so that a
-// code too long for the tables is refused there and never reaches a launch.
-hipError_t trk_persistent_lds_need(const TrkDevCfg& cfg, int device, size_t* need, size_t* limit) {
-    const int key = (cfg.n_arms == 5 ? 4 : 0) | (cfg.code_index_mode == GM_CODE_INDEX_FIXED ? 2 : 0) | (cfg.boc11 ? 1 : 0);
-    constexpr int T = TRK_PERSIST_THREADS;
-    hipFuncAttributes fa;
-    hipError_t e = hipSuccess;
-#define GM_TRK_ATTR(A, M, B) \
-    e = cfg.strict_libm ? hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&trk_persistent_kernel<A, M, B, T, 1>)) \
-                        : hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&trk_persistent_kernel<A, M, B, T, 0>)); \
-    break
-    switch (key) {
-        case 0: GM_TRK_ATTR(3, 0, 0);
-        case 1: GM_TRK_ATTR(3, 0, 1);
-        case 2: GM_TRK_ATTR(3, 1, 0);
-        case 3: GM_TRK_ATTR(3, 1, 1);
-        case 4: GM_TRK_ATTR(5, 0, 0);
-        case 5: GM_TRK_ATTR(5, 0, 1);
-        case 6: GM_TRK_ATTR(5, 1, 0);
-        default: GM_TRK_ATTR(5, 1, 1);
-    }
-#undef GM_TRK_ATTR
-    if (e != hipSuccess) return e;
-    int per_block = 0;
-    e = hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
-    if (e != hipSuccess) return e;
-    *need = size_t(fa.sharedSizeBytes) + trk_persistent_lds(cfg);
-    *limit = size_t(per_block > 0 ? per_block : 0);
-    return hipSuccess;
+    a.per = p.per; a.stagger = p.stagger; a.fair_mode = p.fair_mode; a.fair_share = p.fair_share;
+    a.stagger_tab[0] = p.stagger_tab[0]; a.stagger_tab[1] = p.stagger_tab[1];
+    a.tag_base = c.tag_base; a.xchg = c.xchg; a.outs = c.outs;
+    a.processed = c.processed; a.lost = c.lost; a.lost_prn = c.lost_prn; a.error_flag = c.error; a.error_flag_dev = c.error_dev;
+    a.stamps = stamps_fit(p, a.stamp_block, c.stamps_words) ? c.stamps : nullptr;
+    void* args[] = {&a};
+    (void)hipLaunchKernel(trk_persistent_instance(p.key, p.strict, p.fair3), dim3(p.grid), dim3(TRK_PERSIST_THREADS), args, p.lds_bytes, st);
 }
 
 template <int ARMS>

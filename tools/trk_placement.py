@@ -19,7 +19,7 @@ for j in range(Cn):
     mgr.channels[j].start(dict(prn=j + 1, code_phase_samples=0, code_phase_chips=0.0, carrier_freq=100.0, fs=fs, mag_relative=1.0, sample_global_index=0, doppler_bin=0))
     mgr.channels[j].set_state(code_rate=rate, num_samples_per_code=n)
 Lb = _lib.lib()
-E = 32
+E = 32       # 32 * 48 words = 1024 + 512: a launch writes the placement stamps only if the armed block holds 1024 + grid words (stamps_fit, trk_persist_plan.h)
 _lib.check(Lb.gm_trk_debug_stamps(mgr._h, E, None), 'arm')
 mgr.update_all_dev(ring, 2); mgr.synchronize()
 buf = np.zeros((E, 48), np.int64)
