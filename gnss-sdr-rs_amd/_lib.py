@@ -38,6 +38,16 @@ class AcqPlan(C.Structure):
     _fields_ = [("form", C.c_int32), ("base", C.c_uint32), ("q", C.c_uint32), ("transform_len", C.c_uint32)]
 
 
+class AcqCorrGridInfo(C.Structure):
+    """gm_acq_corr_grid_info: the grid of a handle's last stage-C launch (gm_acq_debug_corr_grid)"""
+    _fields_ = [(k, C.c_int32) for k in ("path", "n_workers", "n_bins", "n_int", "wg_per_cu", "split_planes", "map_mode", "share",
+                                         "slots", "split_from", "split_k", "split_items", "grid", "cut", "why", "cb", "rows_max")] + \
+               [("long_slab", C.c_uint32), ("long_slabs", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AcqRefineCfg(C.Structure):
     """gm_acq_refine_cfg: zeros are the defaults"""
     _fields_ = [("span_periods", C.c_uint32), ("n_freq", C.c_uint32), ("half_span_hz", C.c_float)]
@@ -296,6 +306,7 @@ SIGNATURES = {
     "gm_acq_last_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
     "gm_acq_timing_summary": (_i, [_vp, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f)]),
     "gm_acq_debug_stamps": (_i, [_vp, _vp]),
+    "gm_acq_debug_corr_grid": (_i, [_vp, C.POINTER(AcqCorrGridInfo)]),
     "gm_acq_manager_mode_for": (_i, [_sz]),
     "gm_acq_manager_pacing_and_list": (_i, [_i, _u32, C.POINTER(_u64), C.POINTER(_u32)]),
     "gm_ring_create": (_i, [_sz, C.POINTER(_vp)]),

@@ -672,6 +672,13 @@ class AcquisitionEngine:
         synchronize() / fetch_results() run whatever is still pending."""
         check(lib().gm_acq_set_deferred_decision(self._h, int(on)), "gm_acq_set_deferred_decision")
 
+    def debug_corr_grid(self):
+        """gm_acq_debug_corr_grid: dict of the grid the launcher decided for the last stage-C launch of this handle (path 0: none yet;
+        the GM_CORR_* numbers of include/gnss_mi355x.h)."""
+        info = _lib.AcqCorrGridInfo()
+        check(lib().gm_acq_debug_corr_grid(self._h, C.byref(info)), "gm_acq_debug_corr_grid")
+        return info.as_dict()
+
     def enable_timing(self, on=True):
         check(lib().gm_acq_enable_timing(self._h, int(on)), "gm_acq_enable_timing")
 

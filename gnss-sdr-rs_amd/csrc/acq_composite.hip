@@ -330,16 +330,19 @@ template <class PL, uint32_t Q> struct CompLaunch {
         hipLaunchKernelGGL((comp_fwd_post_kernel<PL, Q>), dim3((PL::N + CT - 1) / CT, n_items), dim3(CT), 0, st, A, X, paired, order);
     }
     static void corr(hipStream_t st, const cf* spectra, const cf* code_paired, const cf* twn, const cf* tw_inv, float* mmax,
-                     uint32_t* margmax, float* msum, const uint32_t* worker_list, int n_workers, int n_bins, int n_int, float* planes) {
+                     uint32_t* margmax, float* msum, const uint32_t* worker_list, int n_workers, int n_bins, int n_int, float* planes,
+                     gm_acq_corr_grid_info* rec) {
         if (n_workers <= 0) return;
         static const int cb_env = diag_int("GM_COMP_CB", -1);   // diagnostic: workers per block (0: plain order)
-        const int items = n_workers * n_bins, share = (items + 7) / 8;
-        // measured at 36 codes x 41 bins x N = 2 x 16000: plain order 0.351 ms, blocks of 4 / 8 / 12 workers 0.313 / 0.314 / 0.314,
-        // blocks of 2 or 6 no gain (6 x ~5 bins is exactly the resident set: every workgroup of a round then starts a new table)
-        const int cb = cb_env >= 0 ? cb_env : (n_workers > 4 ? 4 : 0);
-        // bins a strip can touch: a share of `share` items starting anywhere in a row
-        const int rows_max = (share + n_workers - 2) / n_workers + 1;
-        const int slots = cb > 0 ? ((n_workers + cb - 1) / cb) * rows_max * cb : share;
+        // blocks of cb workers x a strip of rows_max bins per XCD, 8 * slots workgroups: comp_grid_plan (acq_corr_grid.h)
+        const CompGridPlan gp = comp_grid_plan(n_workers, n_bins, cb_env);
+        const int cb = gp.cb, rows_max = gp.rows_max, slots = gp.slots;
+        if (rec) {
+            *rec = gm_acq_corr_grid_info{};
+            rec->path = CompWs<CP>::USE ? GM_CORR_PATH_COMP_WS : GM_CORR_PATH_COMP;
+            rec->n_workers = n_workers; rec->n_bins = n_bins; rec->n_int = n_int;
+            rec->cb = cb; rec->rows_max = rows_max; rec->slots = slots; rec->grid = 8 * slots;
+        }
         if (planes) {                       // strict_sum_order: the variants that also store the power planes (launch_plane_strict_sum follows)
             if constexpr (CompWs<CP>::USE)
                 hipLaunchKernelGGL((comp_corr_ws_kernel<CP, Q, false, true>), dim3(8 * slots), dim3(1024), 0, st, spectra, code_paired, mmax, margmax, msum,

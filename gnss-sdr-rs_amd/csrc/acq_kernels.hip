@@ -874,62 +874,30 @@ template <class PL> struct Launch {
     static void corr(hipStream_t st, const cf* spectra, const cf* code_fft, const cf* tw_inv, float* mmax,
                      uint32_t* margmax, float* msum, const uint32_t* worker_list, int n_workers, int n_bins,
                      int n_int, float* split_scratch, int split_planes, uint32_t* split_counter, int strict_sum, int tickets_cleared,
-                     int ref_mul) {
+                     int ref_mul, gm_acq_corr_grid_info* rec) {
         if (n_workers <= 0) return;
-        // Tile map: whole Doppler bins per XCD (best L2 locality) unless that costs an XCD an extra round of
-        // workgroups (2 x 32 resident per XCD) compared with equal shares of the item list.  Measured on configs[1]
-        // geometry: P = 12: 125 -> 88 us, P = 24: 195 -> 165 us with equal shares; P = 32: whole bins 3 % faster.
-        static const int forced = diag_int("GM_CORR_MAP", -1);   // diagnostic override (GM_DIAGNOSTICS=1 only)
-        const int per_xcd_bins = ((n_bins + 7) / 8) * n_workers, per_xcd_even = (n_bins * n_workers + 7) / 8;
-        const int slots = 32 * CP::WG_PER_CU;
-        const int q = n_bins / 8, left = (n_bins - 8 * q) * n_workers;
-        const int per_xcd_mixed = q * n_workers + (left + 7) / 8;
-        int map_mode = ((per_xcd_bins + slots - 1) / slots > (per_xcd_even + slots - 1) / slots) ? 0 : 1;
-        if (map_mode == 1 && per_xcd_mixed < per_xcd_bins) map_mode = 2;   // same locality, balanced leftovers
-        if (forced >= 0) map_mode = forced;
-        // GM_CORR_CB = cb (diagnostic, and the default for one-workgroup-per-CU plans below): tiled walk of the equal shares
+        // Tile map, grid tail and grid size: corr_grid_plan (acq_corr_grid.h) decides, from what is known here and the diagnostic
+        // overrides (GM_DIAGNOSTICS=1 only): GM_CORR_MAP forces the map, GM_CORR_CB = cb the tiled walk of the equal shares,
+        // GM_CORR_SPLIT = 0 / 1 no cut, GM_CORR_SPLIT_ITEMS the cut items per XCD.
+        static const int forced = diag_int("GM_CORR_MAP", -1);
         static const int cb_env = diag_int("GM_CORR_CB", -1);
-        int cb = cb_env >= 0 ? cb_env : 0;
-        int share = map_mode == 0 ? per_xcd_even : (map_mode == 1 ? per_xcd_bins : per_xcd_mixed);
-        if (cb > 0) {
-            const int rows_max = (per_xcd_even + n_workers - 2) / n_workers + 1;
-            if (rows_max <= 15 && cb <= 1000) {
-                map_mode = (cb << 4) | rows_max;
-                share = ((n_workers + cb - 1) / cb) * rows_max * cb;       // slots per XCD, the ragged ends' empty ones included
-            }
-        }
-        // Grid tail.  When the queue of an XCD runs dry its resident workgroups finish one by one, and the launch ends a
-        // whole workgroup duration (M transforms, ~45 us alone on a CU) after the last one started: about half a duration
-        // of idle slots.  The LAST items of every XCD are therefore cut into n_int parts of one integration each, enough of
-        // them that every resident slot ends on a short workgroup (items * n_int ~ slots).  Measured at configs[1]:
-        // 0.229 -> 0.206 ms per launch; the part count and the item count barely matter between (2, 4) and (10, 8).
-        // GM_CORR_SPLIT = 0 / 1 (no cut) and GM_CORR_SPLIT_ITEMS override for diagnostics.
         static const int split_env = diag_int("GM_CORR_SPLIT", -1);
         static const int items_env = diag_int("GM_CORR_SPLIT_ITEMS", -1);
-        int split_from = share, split_k = 1, split_items = 0;
-        // (strict_sum_order also keeps the reference's sequential accumulation over the integrations: no split)
-        if (SPLIT_SLAB && split_scratch && split_counter && split_env != 0 && !g_corr_stamps_armed && !strict_sum &&
-            (share > slots || share <= GM_CORR_SPLIT_MAX_ITEMS / 8)) {
-            // share <= slots: the whole grid is resident at once and (for few workers, e.g. the reference's single-PRN
-            // search) leaves most of the chip idle: then EVERY item is cut, which multiplies the parallelism by k
-            const bool all = share <= slots;
-            // one integration per part (see the kernel): k = n_int, when the scratch holds the planes
-            if (n_int >= 2 && n_int <= GM_CORR_SPLIT_MAX_K && (!all || share * n_int <= split_planes / 8)) split_k = n_int;
-            // one workgroup per CU (N = 16368 ...): the cut tail does not pay on a grid of several rounds (same box, back to back:
-            // 0.440 against 0.432 ms per 32-PRN launch with and without; comparisons ACROSS gpurun boxes are worthless for a
-            // 2 % question — the chips differ by more); it stays for grids that fit the chip at once, where it multiplies the parallelism
-            if (CP::WG_PER_CU == 1 && !all && split_env < 0) split_k = 1;
-            if (split_env == 1) split_k = 1;
-            if (split_k > 1) {
-                split_items = items_env > 0 ? items_env : (all ? share : (slots + split_k - 1) / split_k);
-                if (split_items > share) split_items = share;
-                if (split_items > GM_CORR_SPLIT_MAX_ITEMS / 8) split_items = GM_CORR_SPLIT_MAX_ITEMS / 8;
-                if (split_items * n_int > split_planes / 8) split_items = split_planes / 8 / n_int;   // one plane per integration; the scratch holds split_planes of them
-                if (split_items <= 0) { split_items = 0; split_k = 1; }
-                split_from = share - split_items;
-            }
+        CorrGridIn in;
+        in.n_workers = n_workers; in.n_bins = n_bins; in.n_int = n_int; in.wg_per_cu = CP::WG_PER_CU;
+        in.can_split = SPLIT_SLAB && split_scratch && split_counter;
+        in.split_planes = split_planes; in.strict_sum = strict_sum != 0; in.stamps = g_corr_stamps_armed;
+        in.map_forced = forced; in.cb_env = cb_env; in.split_env = split_env; in.items_env = items_env;
+        const CorrGridPlan gp = corr_grid_plan(in);
+        const int map_mode = gp.map_mode, split_from = gp.split_from, split_k = gp.split_k, split_items = gp.split_items, grid = gp.grid;
+        if (rec) {
+            *rec = gm_acq_corr_grid_info{};
+            rec->path = (WS31 && !g_corr_stamps_armed) ? GM_CORR_PATH_LDS_WS31 : GM_CORR_PATH_LDS;
+            rec->n_workers = n_workers; rec->n_bins = n_bins; rec->n_int = n_int;
+            rec->wg_per_cu = CP::WG_PER_CU; rec->split_planes = in.can_split ? split_planes : 0;
+            rec->map_mode = map_mode; rec->share = gp.share; rec->slots = gp.slots; rec->split_from = split_from; rec->split_k = split_k;
+            rec->split_items = split_items; rec->grid = grid; rec->cut = gp.cut; rec->why = gp.why;
         }
-        const int grid = 8 * (split_from + split_items * split_k);
         // the merge tickets start from zero in EVERY launch (a launch that was aborted, or two host threads on one handle,
         // must not leave a count behind that makes a later dwell merge early): the whole ticket block, a multiple of 16 bytes
         // at the start of its allocation (cdna_hip_programming.md G16 "Re-initialise every call")

@@ -251,15 +251,22 @@ void launch_long_fwd_post(hipStream_t st, cf* X, uint32_t n_items, uint32_t Q, u
     hipLaunchKernelGGL(long_fwd_post_kernel, dim3((Nb + LCT - 1) / LCT, n_items), dim3(LCT), 0, st, X, Q, Nb);
 }
 
-void launch_long_corr(hipStream_t st, const LongOps* lo, const LongCorrArgs& a) {
+void launch_long_corr(hipStream_t st, const LongOps* lo, const LongCorrArgs& a, gm_acq_corr_grid_info* rec) {
     const uint32_t items = a.n_workers * a.n_bins;
     if (!items) return;
+    if (rec) {
+        *rec = gm_acq_corr_grid_info{};
+        rec->path = GM_CORR_PATH_LONG;
+        rec->n_workers = int32_t(a.n_workers); rec->n_bins = int32_t(a.n_bins); rec->n_int = int32_t(a.n_int);
+        rec->long_slab = a.slab_items;
+    }
     for (uint32_t item0 = 0; item0 < items; item0 += a.slab_items) {
         const uint32_t n = items - item0 < a.slab_items ? items - item0 : a.slab_items;
         hipLaunchKernelGGL(long_corr_pre_kernel, dim3((a.Nb + LCT - 1) / LCT, n * a.n_int), dim3(LCT), 0, st, a.spectra, a.code_fft,
                            a.Z, a.worker_list, a.n_workers, item0, a.Q, a.Nb, a.n_int);
         lo->corr_inv(st, a.Z, a.tw_inv, a.pmax, a.parg, a.psum, a.planes, a.worker_list, a.n_workers, a.n_bins, item0, n, a.Q, a.N,
                      a.n_int, a.scale);
+        if (rec) ++rec->long_slabs;      // counted where the slabs are launched
     }
     hipLaunchKernelGGL(long_combine_kernel, dim3((items + 255) / 256), dim3(256), 0, st, a.pmax, a.parg, a.psum, a.mmax, a.margmax,
                        a.msum, a.worker_list, a.n_workers, a.n_bins, a.Q, items);

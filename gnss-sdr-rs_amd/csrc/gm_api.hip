@@ -443,6 +443,7 @@ struct gm_acq {
     float* d_split_scratch = nullptr;      // partial power planes of the correlation grid's tail split
     int split_planes = 0;                  // ... how many of them the scratch holds (sized from the handle's geometry at create)
     uint32_t* d_split_counter = nullptr;   // arrival tickets, one per split item, zero between launches
+    gm_acq_corr_grid_info last_grid{};     // the grid of the last stage-C launch, written by the launcher (gm_acq_debug_corr_grid)
     uint32_t Q = 1, Nb = 0;
     const gm::CompOps* comp = nullptr;     // Q > 1: the (Q, base plan) kernels
     cf* d_comp_tmp = nullptr;              // [max(D*M, P)][Q][Nb]: forward sub-transforms before the Q-point DFTs
@@ -1129,13 +1130,8 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
     HIPA(hipMalloc(&a->d_rho, D * K * 8));
     HIPA(hipMemcpy(a->d_rho, rho.data(), D * K * 8, hipMemcpyHostToDevice));
     if (acq_fused(a) && pl->split_slab && M >= 2) {
-        // planes the tail split can ever use for THIS handle: every item cut (small grids: P*D items x M planes), or per XCD one
-        // resident round of parts (64 slots; an item's M planes each) — never more than GM_CORR_SPLIT_MAX_SLABS
-        // (a one-PRN AcquisitionWorker handle at N = 16368 takes 290 planes = 19 MB instead of 2560 = 251 MB)
-        size_t planes = size_t(8) * ((P * D + 7) / 8) * M;      // (the launcher deals items to the XCDs in equal shares of ceil(P*D / 8))
-        const size_t tail = size_t(8) * (64 + M);
-        if (planes < tail) planes = tail;
-        if (planes > size_t(gm::GM_CORR_SPLIT_MAX_SLABS)) planes = size_t(gm::GM_CORR_SPLIT_MAX_SLABS);
+        // planes the tail split can ever use for THIS handle (corr_split_planes, acq_corr_grid.h): never more than GM_CORR_SPLIT_MAX_SLABS
+        const size_t planes = gm::corr_split_planes(P, D, M);
         a->split_planes = int(planes);
         HIPA(hipMalloc(&a->d_split_scratch, planes * pl->split_slab * sizeof(float)));
         HIPA(hipMalloc(&a->d_split_counter, gm::GM_CORR_SPLIT_MAX_ITEMS * sizeof(uint32_t)));
@@ -1165,12 +1161,8 @@ int gm_acq_create(const gm_acq_cfg* cfg, gm_acq** out) {
         a->lng->fwd_sub(a->stream, nullptr, GM_FMT_C32, nullptr, a->d_code_samples, a->d_tw_fwd, a->d_long_code, uint32_t(P), a->Q,
                         uint32_t(N), uint32_t(N), 1);
         gm::launch_long_fwd_post(a->stream, a->d_long_code, uint32_t(P), a->Q, a->Nb);
-        // the inverse's intermediate, per slab of (worker, bin) items: at most 128 MiB (inside the 256 MiB Infinity Cache beside the
-        // spectra it reads), at least one item, and a grid of at most 65535 rows of C1
-        size_t slab = (size_t(128) << 20) / (M * L * 8);
-        if (slab < 1) slab = 1;
-        if (slab > P * D) slab = P * D;
-        if (slab * M > 65535) slab = 65535 / M;
+        // the inverse's intermediate, per slab of (worker, bin) items (long_slab_items, acq_corr_grid.h)
+        const size_t slab = gm::long_slab_items(P, D, M, L);
         a->long_slab = uint32_t(slab);
         HIPA(hipMalloc(&a->d_long_z, slab * M * L * 8));
         HIPA(hipMalloc(&a->d_long_part, 3 * P * D * a->Q * 4));
@@ -1332,7 +1324,7 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
             la.planes = planes; la.worker_list = a->d_worker_list;
             la.n_workers = a->n_workers; la.n_bins = Dv; la.n_int = a->M; la.Q = a->Q; la.Nb = a->Nb; la.N = a->N;
             la.slab_items = a->long_slab; la.scale = a->long_scale;
-            gm::launch_long_corr(a->stream, a->lng, la);
+            gm::launch_long_corr(a->stream, a->lng, la, &a->last_grid);
             if (planes)      // strict_sum_order: the plane sums once more, in is_good_satellite's own order (:229-235)
                 gm::launch_plane_strict_sum(a->stream, planes, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), uint32_t(a->N));
         }
@@ -1340,10 +1332,11 @@ static int acq_search_common(gm_acq* a, const void* d_samples, int fmt, void* d_
         a->plan->corr(a->stream, spectra, a->plan->code_paired ? a->d_code_fft_paired : a->d_code_fft, a->d_tw_inv, reinterpret_cast<float*>(met), met + PD,
                       reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), int(a->M),
                       a->d_split_scratch, a->split_planes, a->d_split_counter, a->cfg.strict_sum_order ? 1 : 0, tickets_cleared ? 1 : 0,
-                      a->cfg.reference_products ? 1 : 0);
+                      a->cfg.reference_products ? 1 : 0, &a->last_grid);
     } else if (a->n_workers) {
         a->comp->corr(a->stream, spectra, a->d_code_comb, a->d_comp_twn, a->d_tw_inv, reinterpret_cast<float*>(met),
-                      met + PD, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), int(a->M), planes);
+                      met + PD, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), int(a->M), planes,
+                      &a->last_grid);
         if (planes)      // strict_sum_order: the plane sums once more, in is_good_satellite's own order (:229-235)
             gm::launch_plane_strict_sum(a->stream, planes, reinterpret_cast<float*>(met + 2 * PD), a->d_worker_list, int(a->n_workers), int(Dv), uint32_t(a->N));
     }
@@ -2710,6 +2703,14 @@ int gm_acq_debug_stamps(gm_acq* a, long long* out) {
     HIPC(hipMemcpy(out, d_st, bytes, hipMemcpyDeviceToHost));
     gm::set_corr_stamps(nullptr);
     hipFree(d_st); d_st = nullptr;
+    return GM_OK;
+}
+
+// Diagnostic (not in the reference): the grid of the handle's last stage-C launch as its launcher decided it (Launch<PL>::corr,
+// CompLaunch::corr, launch_long_corr write gm_acq::last_grid); nothing is computed here, and no device is needed.
+int gm_acq_debug_corr_grid(gm_acq* a, gm_acq_corr_grid_info* out) {
+    if (!a || !out) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    *out = a->last_grid;
     return GM_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "../../include/gnss_mi355x.h"
 #include "fft_core.h"
 #include "trk_persist_plan.h"
+#include "acq_corr_grid.h"
 
 namespace gm {
 
@@ -163,7 +164,7 @@ struct PlanOps {
     void (*corr)(hipStream_t, const cf* spectra, const cf* code_fft, const cf* tw_inv, float* mmax,
                  uint32_t* margmax, float* msum, const uint32_t* worker_list, int n_workers, int n_bins,
                  int n_int, float* split_scratch, int split_planes, uint32_t* split_counter, int strict_sum, int tickets_cleared,
-                 int ref_mul);   // ref_mul: gm_acq_cfg.reference_products;   // split_planes: power planes the scratch holds (<= GM_CORR_SPLIT_MAX_SLABS); tickets_cleared: mix_fft(.., split_counter) ran just before on this stream
+                 int ref_mul, gm_acq_corr_grid_info* rec);   // rec (may be null): the grid of this launch as decided (gm_acq_debug_corr_grid);   // ref_mul: gm_acq_cfg.reference_products;   // split_planes: power planes the scratch holds (<= GM_CORR_SPLIT_MAX_SLABS); tickets_cleared: mix_fft(.., split_counter) ran just before on this stream
     // AcquisitionWorker::new's replica spectrum (do_acquisition.rs:132-138)
     void (*code_fft)(hipStream_t, const int8_t* code_samples, const cf* tw_fwd, cf* code_fft, int n_codes);
     // the same spectra re-stored in the paired layout stage C reads (PairLayout in acq_kernels.hip); stage F writes its
@@ -190,12 +191,8 @@ struct PlanOps {
 void launch_fine_mean(hipStream_t, const void* samples, int fmt, uint32_t n, float* d_mean);
 void launch_fine_final(hipStream_t, const float* rowmax, const uint32_t* rowarg, uint32_t n_rows, int n_sats,
                        float* peak_pow, uint32_t* peak_idx);
-// tail split of the correlation grid: per XCD about one resident round of slots (64) worth of parts, one part per
-// integration (up to GM_CORR_SPLIT_MAX_K integrations; longer dwells are not cut); the scratch holds GM_CORR_SPLIT_MAX_SLABS
-// power planes — one per part — and there is one ticket per cut item
-constexpr int GM_CORR_SPLIT_MAX_K = 16;
-constexpr int GM_CORR_SPLIT_MAX_SLABS = 8 * 320;
-constexpr int GM_CORR_SPLIT_MAX_ITEMS = 8 * 80;
+// tail split of the correlation grid: GM_CORR_SPLIT_MAX_K, GM_CORR_SPLIT_MAX_SLABS, GM_CORR_SPLIT_MAX_ITEMS and the whole decision
+// (tile map, cut, grid; composite blocks; long slabs) are in acq_corr_grid.h (host-portable)
 // Diagnostic overrides (item maps, tail split, workgroups per channel ...: tools/README.md).  The library reads NO environment
 // variable unless the process was started with GM_DIAGNOSTICS=1: a receiver that links this library must not change kernels
 // because its environment happens to carry a GM_* name.  diag_int returns `dflt` when diagnostics are off or `name` is unset.
@@ -220,7 +217,8 @@ struct CompOps {
     // planes (null normally; gm_acq_cfg.strict_sum_order): [n_workers_total * n_bins][N] floats — the kernel also stores every accumulated
     // power value at its natural index, for launch_plane_strict_sum
     void (*corr)(hipStream_t, const cf* spectra, const cf* code_paired, const cf* twn, const cf* tw_inv, float* mmax,
-                 uint32_t* margmax, float* msum, const uint32_t* worker_list, int n_workers, int n_bins, int n_int, float* planes);
+                 uint32_t* margmax, float* msum, const uint32_t* worker_list, int n_workers, int n_bins, int n_int, float* planes,
+                 gm_acq_corr_grid_info* rec);   // rec (may be null): as PlanOps::corr
     void (*fill_twn)(cf* out);   // host: [q][nb] inverse twiddles W_N^{-n1 k2} in the paired position of k2
     // once per handle: comb[p][n1][k1][pos] = conj(code_paired[p][k1][pos]) * W_Q^{-n1 k1} * twn[n1][pos], the whole code-side
     // factor of sub-transform n1 (the codes are static, so corr multiplies a spectrum value by ONE table entry)
@@ -267,7 +265,7 @@ struct LongCorrArgs {
     float scale;                           // (N / L)^2
 };
 // C1 + C2 per slab, then C3
-void launch_long_corr(hipStream_t, const LongOps*, const LongCorrArgs&);
+void launch_long_corr(hipStream_t, const LongOps*, const LongCorrArgs&, gm_acq_corr_grid_info* rec = nullptr);   // rec: as PlanOps::corr
 
 // elementwise apply_doppler_shift (doppler_shift.rs:25-58)
 void launch_apply_doppler(hipStream_t, const cf* s, const cf* t, cf* out, size_t n);

@@ -809,6 +809,43 @@ int gm_acq_timing_summary(gm_acq *a, uint32_t *launches, float *avg_ms_mix_fft, 
  * DIAGNOSTIC build of the library only (-DGM_DIAG_STAMPS): the product library returns GM_ERR_UNSUPPORTED and launches nothing. */
 int gm_acq_debug_stamps(gm_acq *a, long long *out);
 
+/* Diagnostic (not in the reference; an additive export, the ABI number stays): how the handle's LAST stage-C launch dealt its
+ * workgroups onto (worker, Doppler bin, integration) items: the very numbers the launcher computed and passed to the kernel, recorded at
+ * the launch and not computed again here.  path GM_CORR_PATH_NONE (all fields 0): no search with a selected worker has run yet.
+ * In-LDS paths: blocks b and b + 8 share an XCD; XCD x takes `share` slots of the item list by `map_mode` (0 equal contiguous shares,
+ * 1 whole bins, 2 whole bins and evenly split leftovers, >= 16 the diagnostic tiled walk (cb << 4) | rows_max); the slots from
+ * `split_from` on are cut into `split_k` parts of one integration each (`split_items` of them per XCD); grid = 8 * (split_from +
+ * split_items * split_k) workgroups.  cut: GM_CORR_CUT_*; why: for GM_CORR_CUT_NONE the first rule that forbade the cut.
+ * Composite paths: 8 * slots workgroups walk equal shares in blocks of cb workers x rows_max bins (cb 0: in list order).
+ * Long path: the (worker, bin) list in long_slabs slabs of long_slab items.  Fields of the other paths are 0. */
+#define GM_CORR_PATH_NONE 0
+#define GM_CORR_PATH_LDS 1            /* acq_corr_kernel */
+#define GM_CORR_PATH_LDS_WS31 2       /* acq_corr_ws31_kernel */
+#define GM_CORR_PATH_COMP 3           /* comp_corr_kernel */
+#define GM_CORR_PATH_COMP_WS 4        /* comp_corr_ws_kernel */
+#define GM_CORR_PATH_LONG 5           /* launch_long_corr */
+#define GM_CORR_CUT_NONE 0
+#define GM_CORR_CUT_ALL 1             /* the grid fits the resident slots: every item is cut */
+#define GM_CORR_CUT_TAIL 2            /* several rounds: the last items of every XCD */
+#define GM_CORR_WHY_CUT 0             /* (the grid is cut) */
+#define GM_CORR_WHY_M1 1              /* one integration */
+#define GM_CORR_WHY_STRICT 2          /* strict_sum_order */
+#define GM_CORR_WHY_OFF 3             /* no scratch on this handle or plan, or a diagnostic switch */
+#define GM_CORR_WHY_SHARE 4           /* one round of more items per XCD than there are tickets */
+#define GM_CORR_WHY_MAX_K 5           /* more than 16 integrations */
+#define GM_CORR_WHY_SCRATCH 6         /* every item would be cut and the handle's scratch does not hold their planes */
+#define GM_CORR_WHY_ONE_WG_ROUNDS 7   /* a plan of one workgroup per CU on a grid of several rounds */
+#define GM_CORR_WHY_CLAMPED 8         /* the scratch holds not even one item's planes per XCD */
+typedef struct gm_acq_corr_grid_info {
+    int32_t path;                                            /* GM_CORR_PATH_* */
+    int32_t n_workers, n_bins, n_int;                        /* of the launch: the masked worker list, H * D bins in an edge search */
+    int32_t wg_per_cu, split_planes;                         /* in-LDS: what the decision started from */
+    int32_t map_mode, share, slots, split_from, split_k, split_items, grid, cut, why;
+    int32_t cb, rows_max;                                    /* composite (slots, grid: as above) */
+    uint32_t long_slab, long_slabs;
+} gm_acq_corr_grid_info;
+int gm_acq_debug_corr_grid(gm_acq *a, gm_acq_corr_grid_info *out);
+
 /* AcquisitionManager (do_acquisition.rs:39-74): mode 0 ColdStart / 1 WarmStart / 2 SteadyState. */
 int gm_acq_manager_mode_for(size_t tracked_count);
 int gm_acq_manager_pacing_and_list(int mode, uint32_t active_prn_mask, uint64_t *interval_ms, uint32_t *mask);

@@ -93,6 +93,12 @@ def test_null_handles_are_refused_not_dereferenced(gm):
     forms = (C.c_uint32 * 3)(9, 9, 9)
     assert L.gm_frontend_debug_forms(None, forms) == -1 and list(forms) == [9, 9, 9]
     assert b"null pointer" in L.gm_last_error()
+    # the stage-C grid record (an additive export): a null handle is refused and the struct left as it was
+    from gnss_sdr_rs_amd import _lib
+    grid = _lib.AcqCorrGridInfo()
+    grid.path = 9
+    assert L.gm_acq_debug_corr_grid(None, C.byref(grid)) == -1 and grid.path == 9 and b"null pointer" in L.gm_last_error()
+    assert C.sizeof(_lib.AcqCorrGridInfo) == 19 * 4
     # the device-math probe (an additive export): null arrays, then op and n out of range — all refused before a device is needed
     xs, w0, w1 = (C.c_float * 4)(), (C.c_uint32 * 4)(9, 9, 9, 9), (C.c_uint32 * 4)(9, 9, 9, 9)
     for a, b, c in ((None, w0, w1), (xs, None, w1), (xs, w0, None)):

@@ -13,8 +13,9 @@ pairs: the residue pattern names the index map at fault.
 1. in-LDS sizes, M = 1, a full P x D grid: default options, reference_products and strict_sum_order, which each have a kernel
    instantiation or a reduction of their own (N = 16368: acq_corr_ws31_kernel<CP, false> and <CP, true>).
 2. in-LDS sizes, M = 2, 8 workers x 32 bins.  corr() (acq_kernels.hip) cuts every item of a grid whose share per XCD is within the
-   resident slots, so every lag's peak goes through the ticket merge and the slab's register order.  The ABI does not report which
-   items were cut: that is assumed from corr()'s rule, not asserted (as in test_gpu_fused_twiddles.py).
+   resident slots, so every lag's peak goes through the ticket merge and the slab's register order.  Which items were cut is
+   asserted: gm_acq_debug_corr_grid reports the grid the launcher decided, and every search of the group requires "every item cut
+   into M parts" of it (the classes of that decision have a test of their own, tests/test_gpu_grid_geometry.py).
 3. every composite (base, Q) pair, M = 1; strict_sum_order on the smallest Q of each base, which runs the plane-storing variants
    and plane_strict_sum_kernel.
 4. the long rows (the smallest, an odd and the largest run-time Q of each base) and the long-padded rows, any_length set, M = 1.
@@ -41,7 +42,7 @@ REL = AM.REL
 SHOWN = 48          # wrong lags printed per case
 
 
-def _sweep(A, _lib, hipbuf, c):
+def _sweep(A, _lib, hipbuf, c, all_cut=False):
     N, M, P, D = c.N, c.M, c.P, c.D
     emx, esm, gap = SW.expected(N, M)
     assert gap >= AM.GAP
@@ -60,6 +61,10 @@ def _sweep(A, _lib, hipbuf, c):
             assert (info["form"], info["base"]) == (c.form, c.base), (c.id, info)
             assert eng.dwell_samples == M * N and (eng.table_freq == 0.0).all()
             eng.search_dev(d_x, fmt)
+            if all_cut:     # the launcher's own record of this launch: every item of every XCD cut into one part per integration
+                g = eng.debug_corr_grid()
+                assert (g["cut"], g["split_from"], g["split_k"], g["split_items"], g["grid"]) == (1, 0, M, g["share"], 8 * M * g["share"]), (c.id, g)
+                assert g["share"] <= g["slots"] and (g["n_workers"], g["n_bins"], g["n_int"]) == (P, D, M), (c.id, g)
             eng.decide_dev()
             res = eng.fetch_results()
             mx, am, sm = eng.metrics()
@@ -98,10 +103,10 @@ def test_in_lds_plans_on_every_lag(gpu, hipbuf, c):
 @_cases("lds_cut")
 def test_in_lds_plans_on_every_lag_through_the_cut_items(gpu, hipbuf, c):
     """M = 2 on 8 x 32 items: 32 items per XCD are within the 32 * WG_PER_CU resident slots of every plan, and corr() cuts every item
-    of such a grid into one part per integration, merged through the tickets and the register-order slab.  Assumed from corr()'s
-    rule (acq_kernels.hip): the ABI does not report which items were cut, and no diagnostic variable is set."""
+    of such a grid into one part per integration, merged through the tickets and the register-order slab.  Asserted for every
+    search through gm_acq_debug_corr_grid (cut kind "all", M parts, no uncut slot); no diagnostic variable is set."""
     from gnss_sdr_rs_amd import _lib, acquisition as A
-    _sweep(A, _lib, hipbuf, c)
+    _sweep(A, _lib, hipbuf, c, all_cut=True)
 
 
 @_cases("composite")
