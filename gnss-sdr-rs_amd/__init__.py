@@ -11,6 +11,7 @@ include/gnss_mi355x.h.  This Python package is plumbing around it:
   nuller                         adaptive spatial nulling: A interleaved antennas combined per block with weights from the block's covariance
   stap                           space-time adaptive nulling: the nuller with L taps in time behind every antenna
   beamformer                     one beam per satellite: P constraint rows on stap's stream, one Gram matrix and one factor a block
+  lcmv                           several constraints on one beam: Q_p rows and responses a beam on the beamformer's stream
   synth       deterministic synthetic IF scenes
   build       hipcc build recipe
 """
@@ -23,6 +24,7 @@ from .channelizer import Channelizer  # noqa: F401
 from .nuller import Nuller  # noqa: F401
 from .stap import Stap  # noqa: F401
 from .beamformer import Beamformer  # noqa: F401
+from .lcmv import Lcmv  # noqa: F401
 from . import tracking  # noqa: F401
 # per-antenna prompts of an array stream at tracked states: TrackingManager.array_prompts, and tracking.array_plan under a name that
 # does not collide with acquisition.array_plan

@@ -148,6 +148,14 @@ class StapCfg(C.Structure):
                 ("steering", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+class LcmvCfg(C.Structure):
+    """gm_lcmv_cfg (56 bytes): zeros are the defaults of block and loading; n_constraints points at n_beams uint32 words Q_p, constraints at
+    sum(Q) * taps * n_antennas complex64 words [sum Q][taps][n_antennas], response at sum(Q) complex64 words; all three are required"""
+    _fields_ = [("n_antennas", C.c_uint32), ("taps", C.c_uint32), ("block", C.c_uint32), ("loading", C.c_float),
+                ("n_beams", C.c_uint32), ("reserved32", C.c_uint32), ("n_constraints", C.c_void_p), ("constraints", C.c_void_p),
+                ("response", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class BeamformerCfg(C.Structure):
     """gm_beamformer_cfg (40 bytes): zeros are the defaults of block and loading; steering points at n_beams * taps * n_antennas
     complex64 words [n_beams][taps][n_antennas] and is required"""
@@ -421,6 +429,17 @@ SIGNATURES = {
     "gm_beamformer_capture": (_i, [_vp, _vp, _vp, _sz]),
     "gm_beamformer_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
     "gm_beamformer_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
+    "gm_lcmv_plan": (_i, [C.POINTER(LcmvCfg), _u64, _u64, C.POINTER(_u32), C.POINTER(C.c_float), C.POINTER(_u64)]),
+    "gm_lcmv_create": (_i, [C.POINTER(LcmvCfg), C.POINTER(_vp)]),
+    "gm_lcmv_destroy": (_i, [_vp]),
+    "gm_lcmv_reset": (_i, [_vp, _u64]),
+    "gm_lcmv_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gm_lcmv_synchronize": (_i, [_vp]),
+    "gm_lcmv_set_constraints": (_i, [_vp, _u32, _u32, _vp, _vp]),
+    "gm_lcmv_set_weights": (_i, [_vp, _vp]),
+    "gm_lcmv_capture": (_i, [_vp, _vp, _vp, _sz]),
+    "gm_lcmv_process_dev": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "gm_lcmv_process": (_i, [_vp, _vp, _i, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
     "gm_trk_create": (_i, [C.POINTER(TrkCfg), C.POINTER(_vp)]),
     "gm_trk_destroy": (_i, [_vp]),
     "gm_trk_start": (_i, [_vp, _u32, C.POINTER(AcqResult)]),

@@ -10,7 +10,9 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
+#include <complex>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -5769,6 +5771,251 @@ int gm_beamformer_process_dev(gm_beamformer* n, const void* d_in, int fmt, size_
 int gm_beamformer_process(gm_beamformer* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_stride, size_t* n_out, gm_c32* R,
                           gm_c32* w, size_t cap_blocks) {
     return array_process(n, beam_launch, in, fmt, n_in, out, out_stride, n_out, R, w, cap_blocks);
+}
+
+}  // extern "C"
+
+// ====================================================================== several constraints on one beam (gm_lcmv; additive entries, ABI 9)
+// gnss_mi355x.h states the definition; tests/lcmv_model.py restates it in float64 on stap_model.py.
+namespace {
+struct LcmvBeam {
+    uint32_t Q = 0;
+    cf c[gm::LC_Q_MAX][gm::ST_M_MAX] = {};  // the rows, each [L][A]
+    cf f[gm::LC_Q_MAX] = {};                // the responses
+    cf w0[gm::ST_M_MAX] = {};               // the quiescent weights C (C^H C)^-1 f, f64 rounded once
+};
+struct LcmvPlan {
+    StapPlan st;                            // A, L, M, B, loading: gm_stap's rules (st.s is not used)
+    uint32_t P = 0;
+    LcmvBeam beam[gm::BM_P_MAX];
+};
+
+// one beam's rows and responses: the rules, and w0 = C (C^H C)^-1 f in f64 through the Cholesky factor of C^H C (columns ascending)
+int lcmv_beam_rules(uint32_t M, uint32_t Q, const gm_c32* rows, const gm_c32* f, LcmvBeam& b) {
+    if (Q < 1 || Q > uint32_t(gm::LC_Q_MAX) || Q > M) return set_err(GM_ERR_INVALID_ARG, "n_constraints: 1 .. 8 and at most taps * n_antennas");
+    for (uint32_t q = 0; q < Q; ++q)
+        if (int rc = array_row_rules(rows + size_t(q) * M, M, "a constraint row is all zero")) return rc;
+    if (!array_finite(f, Q)) return set_err(GM_ERR_INVALID_ARG, "response must be finite");
+    std::complex<double> G[gm::LC_Q_MAX][gm::LC_Q_MAX], v[gm::LC_Q_MAX];
+    auto at = [&](uint32_t q, uint32_t j) { return std::complex<double>(rows[size_t(q) * M + j].re, rows[size_t(q) * M + j].im); };
+    for (uint32_t q = 0; q < Q; ++q)
+        for (uint32_t r = 0; r <= q; ++r) {
+            std::complex<double> g = 0.0;
+            for (uint32_t j = 0; j < M; ++j) g += std::conj(at(q, j)) * at(r, j);
+            G[q][r] = g;
+        }
+    for (uint32_t j = 0; j < Q; ++j) {       // G = Lg Lg^H in place; a pivot not greater than 1e-10 of the row's squared norm: dependent
+        const double norm = G[j][j].real();
+        double pj = norm;
+        for (uint32_t k = 0; k < j; ++k) pj -= std::norm(G[j][k]);
+        if (!(pj > 1e-10 * norm) || !std::isfinite(pj)) return set_err(GM_ERR_INVALID_ARG, "the constraint rows of a beam are linearly dependent");
+        const double d = std::sqrt(pj);
+        for (uint32_t i = j + 1; i < Q; ++i) {
+            std::complex<double> x = G[i][j];
+            for (uint32_t k = 0; k < j; ++k) x -= G[i][k] * std::conj(G[j][k]);
+            G[i][j] = x / d;
+        }
+        G[j][j] = d;
+    }
+    for (uint32_t j = 0; j < Q; ++j) {       // Lg y = f
+        std::complex<double> x(f[j].re, f[j].im);
+        for (uint32_t k = 0; k < j; ++k) x -= G[j][k] * v[k];
+        v[j] = x / G[j][j].real();
+    }
+    for (uint32_t j = Q; j-- > 0;) {         // Lg^H v = y
+        std::complex<double> x = v[j];
+        for (uint32_t k = j + 1; k < Q; ++k) x -= std::conj(G[k][j]) * v[k];
+        v[j] = x / G[j][j].real();
+    }
+    b = LcmvBeam{};
+    b.Q = Q;
+    for (uint32_t q = 0; q < Q; ++q) {
+        b.f[q] = gm::cf_make(f[q].re, f[q].im);
+        for (uint32_t j = 0; j < M; ++j) b.c[q][j] = gm::cf_make(rows[size_t(q) * M + j].re, rows[size_t(q) * M + j].im);
+    }
+    for (uint32_t j = 0; j < M; ++j) {
+        std::complex<double> w = 0.0;
+        for (uint32_t q = 0; q < Q; ++q) w += at(q, j) * v[q];
+        if (!std::isfinite(w.real()) || !std::isfinite(w.imag()) || std::fabs(w.real()) > double(FLT_MAX) || std::fabs(w.imag()) > double(FLT_MAX))
+            return set_err(GM_ERR_INVALID_ARG, "the quiescent weights of a beam are not finite in f32");
+        b.w0[j] = gm::cf_make(float(w.real()), float(w.imag()));
+    }
+    return GM_OK;
+}
+uint32_t lcmv_q_sum(const LcmvPlan& p) {
+    uint32_t s = 0;
+    for (uint32_t b = 0; b < p.P; ++b) s += p.beam[b].Q;
+    return s;
+}
+
+int lcmv_rules(const gm_lcmv_cfg* c, LcmvPlan& p) {
+    if (!c) return set_err(GM_ERR_INVALID_ARG, "null cfg");
+    if (c->reserved || c->reserved32) return set_err(GM_ERR_INVALID_ARG, "gm_lcmv_cfg.reserved32 and reserved must be 0");
+    gm_stap_cfg sc{};
+    sc.n_antennas = c->n_antennas; sc.taps = c->taps; sc.block = c->block; sc.loading = c->loading;
+    if (int rc = stap_rules(&sc, p.st)) return rc;
+    if (c->n_beams < 1 || c->n_beams > uint32_t(gm::BM_P_MAX)) return set_err(GM_ERR_INVALID_ARG, "n_beams: 1 .. 16");
+    if (!c->n_constraints || !c->constraints || !c->response)
+        return set_err(GM_ERR_INVALID_ARG, "n_constraints, constraints and response are required");
+    uint32_t sum = 0;
+    for (uint32_t b = 0; b < c->n_beams; ++b) {
+        const uint32_t Q = c->n_constraints[b];
+        if (Q < 1 || Q > uint32_t(gm::LC_Q_MAX) || Q > p.st.M) return set_err(GM_ERR_INVALID_ARG, "n_constraints: 1 .. 8 and at most taps * n_antennas");
+        sum += Q;
+    }
+    if (sum > uint32_t(gm::LC_Q_SUM)) return set_err(GM_ERR_INVALID_ARG, "the constraint rows of all beams: at most 16");
+    p.P = c->n_beams;
+    uint32_t q0 = 0;
+    for (uint32_t b = 0; b < p.P; ++b) {
+        if (int rc = lcmv_beam_rules(p.st.M, c->n_constraints[b], c->constraints + size_t(q0) * p.st.M, c->response + q0, p.beam[b])) return rc;
+        q0 += c->n_constraints[b];
+    }
+    return GM_OK;
+}
+}  // namespace
+
+struct gm_lcmv : ArrayStage {               // history: gm_stap's; d_blanked is not used, the counters are per beam; R is [M][M], w is [P][M]
+    LcmvPlan plan;
+    cf* d_c = nullptr; cf* d_f = nullptr;   // [16][M] the rows of all beams, [16] their responses
+    cf* d_w0 = nullptr; cf* d_w = nullptr;  // [P][M] each: the quiescent weights, the fixed weights
+    unsigned long long* d_fb = nullptr;     // [P] fallback counters
+};
+
+// one call's kernels on `st`; the caller has checked every argument; n_in > 0
+static int lcmv_launch(gm_lcmv* n, hipStream_t st, const void* d_in, int fmt, uint64_t n_in, cf* out, uint64_t out_stride, uint64_t n_out,
+                       cf* cap_R, cf* cap_w) {
+    gm::LcmvArgs a{};
+    array_fill_args(a, n, d_in, n_in, out, n_out, cap_R, cap_w);
+    a.fmt = fmt; a.L = n->plan.st.L; a.P = n->plan.P;
+    a.out_stride = out_stride;
+    a.fallbacks = n->d_fb; a.c = n->d_c; a.f = n->d_f; a.w0 = n->d_w0; a.w = n->d_w;
+    for (uint32_t b = 0; b < n->plan.P; ++b) {
+        a.nq[b] = uint8_t(n->plan.beam[b].Q); a.q0[b] = uint8_t(a.q_sum);
+        a.q_sum += n->plan.beam[b].Q;
+        a.q_max = std::max(a.q_max, n->plan.beam[b].Q);
+    }
+    gm::launch_lcmv(st, a);
+    return stage_launched(n, st, n_in, n_out);
+}
+// the words of the handle that kernels read are replaced only when no call of the handle is in flight, on any stream
+static int lcmv_install(gm_lcmv* n, cf* d_dst, const void* src, size_t words) {
+    if (int rc = ensure_device(n->device)) return rc;
+    if (int rc = stage_sync(n)) return rc;
+    HIPC(hipMemcpy(d_dst, src, words * sizeof(cf), hipMemcpyHostToDevice));
+    return GM_OK;
+}
+// the plan's rows, responses and quiescent weights, packed as the kernel reads them
+static void lcmv_pack(const LcmvPlan& p, std::vector<cf>& c, std::vector<cf>& f, std::vector<cf>& w0) {
+    const uint32_t M = p.st.M;
+    c.assign(size_t(gm::LC_Q_SUM) * M, cf{}); f.assign(gm::LC_Q_SUM, cf{}); w0.assign(size_t(gm::BM_P_MAX) * M, cf{});
+    uint32_t q0 = 0;
+    for (uint32_t b = 0; b < p.P; ++b) {
+        for (uint32_t q = 0; q < p.beam[b].Q; ++q, ++q0) {
+            f[q0] = p.beam[b].f[q];
+            for (uint32_t j = 0; j < M; ++j) c[size_t(q0) * M + j] = p.beam[b].c[q][j];
+        }
+        for (uint32_t j = 0; j < M; ++j) w0[size_t(b) * M + j] = p.beam[b].w0[j];
+    }
+}
+
+extern "C" {
+
+int gm_lcmv_plan(const gm_lcmv_cfg* cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t* block, float* loading, uint64_t* n_out) {
+    LcmvPlan p;
+    if (int rc = lcmv_rules(cfg, p)) return rc;
+    return array_plan(p.st.B, p.st.loading, inputs_so_far, n_in, block, loading, n_out);
+}
+
+int gm_lcmv_create(const gm_lcmv_cfg* cfg, gm_lcmv** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    LcmvPlan p;
+    if (int rc = lcmv_rules(cfg, p)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_lcmv* n = new gm_lcmv;
+    n->device = g_device; n->plan = p;
+    array_shape(n, "lcmv", p.st.A, p.st.B, p.st.loading, size_t(p.st.M) * p.st.M, size_t(p.P) * p.st.M, p.P);
+    std::vector<cf> c, f, w0;
+    lcmv_pack(p, c, f, w0);
+    const size_t words = size_t(gm::BM_P_MAX) * gm::ST_M_MAX;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&n->d_c), words * sizeof(cf));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&n->d_f), gm::LC_Q_SUM * sizeof(cf));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&n->d_w0), words * sizeof(cf));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&n->d_w), words * sizeof(cf));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&n->d_fb), gm::BM_P_MAX * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(n->d_c, 0, words * sizeof(cf));
+    if (e == hipSuccess) e = hipMemset(n->d_w0, 0, words * sizeof(cf));
+    if (e == hipSuccess) e = hipMemset(n->d_w, 0, words * sizeof(cf));
+    if (e == hipSuccess) e = hipMemset(n->d_fb, 0, gm::BM_P_MAX * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemcpy(n->d_c, c.data(), c.size() * sizeof(cf), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(n->d_f, f.data(), f.size() * sizeof(cf), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(n->d_w0, w0.data(), w0.size() * sizeof(cf), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = stage_create(n, stap_hist_bytes(p.st));
+    if (e != hipSuccess) { gm_lcmv_destroy(n); return hip_fail(e, "gm_lcmv_create"); }
+    *out = n;
+    return GM_OK;
+}
+
+int gm_lcmv_destroy(gm_lcmv* n) {
+    if (!n) return GM_OK;
+    array_destroy(n);
+    hipFree(n->d_c); hipFree(n->d_f); hipFree(n->d_w0); hipFree(n->d_w); hipFree(n->d_fb);
+    delete n;
+    return GM_OK;
+}
+
+int gm_lcmv_reset(gm_lcmv* n, uint64_t input_index) {
+    return stage_reset(n, input_index, [&] { return hipMemsetAsync(n->d_fb, 0, gm::BM_P_MAX * sizeof(unsigned long long), n->stream); });
+}
+
+int gm_lcmv_stats(gm_lcmv* n, uint64_t* inputs, uint64_t* outputs, uint64_t* blocks, uint64_t* fallbacks) {
+    if (int rc = array_stats(n, inputs, outputs, blocks, nullptr)) return rc;
+    if (fallbacks) {
+        unsigned long long fb[gm::BM_P_MAX] = {};
+        HIPC(hipMemcpy(fb, n->d_fb, n->plan.P * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (uint32_t p = 0; p < n->plan.P; ++p) fallbacks[p] = fb[p];
+    }
+    return GM_OK;
+}
+
+int gm_lcmv_synchronize(gm_lcmv* n) { return stage_synchronize(n); }
+
+int gm_lcmv_set_constraints(gm_lcmv* n, uint32_t beam, uint32_t n_rows, const gm_c32* rows, const gm_c32* response) {
+    if (!n || !rows || !response) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (beam >= n->plan.P) return set_err(GM_ERR_INVALID_ARG, "beam: below n_beams");
+    LcmvBeam b;
+    if (int rc = lcmv_beam_rules(n->plan.st.M, n_rows, rows, response, b)) return rc;
+    if (lcmv_q_sum(n->plan) - n->plan.beam[beam].Q + n_rows > uint32_t(gm::LC_Q_SUM))
+        return set_err(GM_ERR_INVALID_ARG, "the constraint rows of all beams: at most 16");
+    LcmvPlan p = n->plan;
+    p.beam[beam] = b;
+    std::vector<cf> c, f, w0;
+    lcmv_pack(p, c, f, w0);
+    if (int rc = lcmv_install(n, n->d_c, c.data(), c.size())) return rc;      // (waits for the calls in flight; the later copies find none)
+    HIPC(hipMemcpy(n->d_f, f.data(), f.size() * sizeof(cf), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(n->d_w0, w0.data(), w0.size() * sizeof(cf), hipMemcpyHostToDevice));
+    n->plan = p;
+    return GM_OK;
+}
+
+int gm_lcmv_set_weights(gm_lcmv* n, const gm_c32* w) {
+    if (!n) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    if (!w) { n->fixed = false; return GM_OK; }
+    if (!array_finite(w, n->w_words)) return set_err(GM_ERR_INVALID_ARG, "weights must be finite");
+    if (int rc = lcmv_install(n, n->d_w, w, n->w_words)) return rc;
+    n->fixed = true;
+    return GM_OK;
+}
+
+int gm_lcmv_capture(gm_lcmv* n, void* d_R, void* d_w, size_t cap_blocks) { return array_capture(n, d_R, d_w, cap_blocks); }
+
+int gm_lcmv_process_dev(gm_lcmv* n, const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_stride, size_t* n_out, void* stream) {
+    return array_process_dev(n, lcmv_launch, d_in, fmt, n_in, d_out, out_stride, n_out, stream);
+}
+
+int gm_lcmv_process(gm_lcmv* n, const void* in, int fmt, size_t n_in, gm_c32* out, size_t out_stride, size_t* n_out, gm_c32* R, gm_c32* w,
+                    size_t cap_blocks) {
+    return array_process(n, lcmv_launch, in, fmt, n_in, out, out_stride, n_out, R, w, cap_blocks);
 }
 
 }  // extern "C"

@@ -537,6 +537,33 @@ struct BeamArgs {
 };
 void launch_beam(hipStream_t, const BeamArgs&);
 
+// ---------------------------------------------------------------- several constraints on one beam (lcmv_kernels.hip)
+// gnss_mi355x.h states the definition.  gm_beamformer's call where beam p carries nq[p] constraint rows and responses in place of one
+// row: the rows of all beams (at most LC_Q_SUM, beam p's from row q0[p]) ride below the matrix in the ONE factor; per beam a small Gram
+// matrix, its factor and two substitutions.  The span, the history, the counts and the state kernel are gm_stap's.
+constexpr int LC_Q_MAX = 8;                // constraint rows of one beam at most
+constexpr int LC_Q_SUM = 16;               // constraint rows of all beams at most: the rows st_factor carries below the matrix
+struct LcmvArgs {
+    const void* in; uint64_t n_in;         // this call's TIME samples, each A interleaved elements (c32 or int8 IQ)
+    int fmt;                               // GM_FMT_C32 or GM_FMT_I8_IQ
+    const cf* hist_in; cf* hist_out;       // gm_stap's history, before / after
+    uint32_t A, L, B, P;
+    uint32_t pending, pending_out;
+    uint64_t n_blocks;                     // blocks this call finishes
+    cf* out; uint64_t out_stride;          // beam p's plane: out + p * out_stride, [n_blocks * B] words of it written
+    cf* cap_R; cf* cap_w;                  // [n_blocks][M][M], [n_blocks][P][M]; null: not captured
+    float loading;
+    int adaptive;                          // 0: the fixed weights `w` for every block, no Gram matrix
+    unsigned long long* fallbacks;         // [P] device counters of the blocks whose beam p took its quiescent weights: integer atomics only
+    const cf* c;                           // device [q_sum][M]: the constraint rows, each [L][A], beam p's nq[p] rows from row q0[p]
+    const cf* f;                           // device [q_sum]: the responses, in the rows' order
+    const cf* w0;                          // device [P][M]: the quiescent weights C (C^H C)^-1 f, the host's f64 rounded once
+    const cf* w;                           // device [P][M]: the fixed weights
+    uint32_t q_sum, q_max;                 // sum and maximum of nq[0 .. P - 1]
+    uint8_t nq[BM_P_MAX], q0[BM_P_MAX];
+};
+void launch_lcmv(hipStream_t, const LcmvArgs&);
+
 // ---------------------------------------------------------------- re-steering on the device (array_solve.hip)
 // gm_array_rows_solve_dev: gm_array_row_solve's nine steps for n_rows rows, f64, one workgroup a row; the host has checked every limit
 // (gm_array_solve_plan) and every pointer.  Vector i of row p: the m words at z + p * row_stride + i * vec_stride.

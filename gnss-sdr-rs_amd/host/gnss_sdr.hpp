@@ -728,6 +728,91 @@ public:
     void synchronize() { check(gm_beamformer_synchronize(h_), "Beamformer::synchronize"); }
 };
 
+// ---- several constraints on one beam (gm_lcmv): the beamformer's stream and planes, where beam p carries Q_p constraint rows and
+// responses in place of one row: C^H w_p = f at the least output power, a signal along row q comes out with the gain conj(f_q)
+class Lcmv {
+    gm_lcmv* h_ = nullptr;
+    uint32_t antennas_ = 0, taps_ = 0, beams_ = 0, block_ = 0;
+public:
+    // one beam's constraints: rows [Q][taps][n_antennas] and f [Q]
+    struct Beam { std::vector<Complex32> rows, f; };
+    // beams: 1 .. 16 of them, Q in 1 .. 8 each and at most 16 rows together; block 0: 1024; loading 0: 1e-4
+    Lcmv(uint32_t n_antennas, uint32_t taps, const std::vector<Beam>& beams, uint32_t block = 0, float loading = 0.0f) {
+        const size_t M = size_t(n_antennas) * taps;
+        std::vector<uint32_t> q;
+        std::vector<Complex32> rows, f;
+        for (const Beam& b : beams) {
+            if (!M || b.f.empty() || b.rows.size() != b.f.size() * M) check(GM_ERR_INVALID_ARG, "Lcmv::new (a beam: Q rows of taps * n_antennas words, Q responses)");
+            q.push_back(uint32_t(b.f.size()));
+            rows.insert(rows.end(), b.rows.begin(), b.rows.end());
+            f.insert(f.end(), b.f.begin(), b.f.end());
+        }
+        gm_lcmv_cfg cfg{};
+        cfg.n_antennas = n_antennas; cfg.taps = taps; cfg.block = block; cfg.loading = loading;
+        cfg.n_beams = uint32_t(beams.size());
+        cfg.n_constraints = q.data();
+        cfg.constraints = reinterpret_cast<const gm_c32*>(rows.data());
+        cfg.response = reinterpret_cast<const gm_c32*>(f.data());
+        check(gm_lcmv_plan(&cfg, 0, 0, &block_, nullptr, nullptr), "Lcmv::new");
+        antennas_ = n_antennas; taps_ = taps; beams_ = cfg.n_beams;
+        check(gm_lcmv_create(&cfg, &h_), "Lcmv::new");
+    }
+    ~Lcmv() { gm_lcmv_destroy(h_); }
+    Lcmv(const Lcmv&) = delete;
+    gm_lcmv* handle() const { return h_; }
+    uint32_t antennas() const { return antennas_; }
+    uint32_t taps() const { return taps_; }
+    uint32_t weights() const { return antennas_ * taps_; }
+    uint32_t beams() const { return beams_; }
+    uint32_t block() const { return block_; }
+    // the synchronous host-buffer form: n time samples -> [beams][*n_out] outputs, plane after plane; R ([blocks][M][M]) and w
+    // ([blocks][beams][M]) receive the words each of the call's blocks was combined with, where given
+    std::vector<Complex32> process(const void* in, int fmt, size_t n, size_t* n_out = nullptr, std::vector<Complex32>* R = nullptr,
+                                   std::vector<Complex32>* w = nullptr) {
+        const size_t cap = n + block_, nb = cap / block_, M = weights();
+        std::vector<Complex32> planes(cap * beams_);
+        if (R) R->assign(nb * M * M, Complex32{});
+        if (w) w->assign(nb * beams_ * M, Complex32{});
+        size_t got = 0;
+        check(gm_lcmv_process(h_, in, fmt, n, reinterpret_cast<gm_c32*>(planes.data()), cap, &got,
+                              R ? reinterpret_cast<gm_c32*>(R->data()) : nullptr, w ? reinterpret_cast<gm_c32*>(w->data()) : nullptr, nb),
+              "Lcmv::process");
+        std::vector<Complex32> out(got * beams_);
+        for (uint32_t p = 0; p < beams_; ++p) std::copy(planes.begin() + p * cap, planes.begin() + p * cap + got, out.begin() + p * got);
+        if (n_out) *n_out = got;
+        if (R) R->resize(got / block_ * M * M);
+        if (w) w->resize(got / block_ * beams_ * M);
+        return out;
+    }
+    // device pointers, beam p's plane at d_out + p * out_stride (c32 elements); asynchronous on `stream` (nullptr: the handle's own);
+    // returns the outputs written per beam
+    size_t process_dev(const void* d_in, int fmt, size_t n_in, void* d_out, size_t out_stride, void* stream = nullptr) {
+        size_t n = 0;
+        check(gm_lcmv_process_dev(h_, d_in, fmt, n_in, d_out, out_stride, &n, stream), "Lcmv::process_dev");
+        return n;
+    }
+    // beam `beam`'s new rows and responses for every block a later call finishes (synchronous); their number may change
+    void set_constraints(uint32_t beam, const Beam& b) {
+        if (b.f.empty() || b.rows.size() != b.f.size() * weights()) check(GM_ERR_INVALID_ARG, "Lcmv::set_constraints (Q rows of taps * n_antennas words, Q responses)");
+        check(gm_lcmv_set_constraints(h_, beam, uint32_t(b.f.size()), reinterpret_cast<const gm_c32*>(b.rows.data()),
+                                      reinterpret_cast<const gm_c32*>(b.f.data())), "Lcmv::set_constraints");
+    }
+    // fixed weights [beams][M] for every later block (static mode, synchronous); empty: back to the adaptive rule
+    void set_weights(const std::vector<Complex32>& w) {
+        if (!w.empty() && w.size() != size_t(beams_) * weights()) check(GM_ERR_INVALID_ARG, "Lcmv::set_weights (beams * taps * n_antennas words)");
+        check(gm_lcmv_set_weights(h_, w.empty() ? nullptr : reinterpret_cast<const gm_c32*>(w.data())), "Lcmv::set_weights");
+    }
+    // device buffers [cap_blocks][M][M] and [cap_blocks][beams][M] that every later process_dev fills from word 0; nulls and 0 end it
+    void capture(void* d_R, void* d_w, size_t cap_blocks) { check(gm_lcmv_capture(h_, d_R, d_w, cap_blocks), "Lcmv::capture"); }
+    void reset(uint64_t input_index = 0) { check(gm_lcmv_reset(h_, input_index), "Lcmv::reset"); }
+    // fallbacks: one count per beam
+    void stats(uint64_t* inputs, uint64_t* outputs, uint64_t* blocks, std::vector<uint64_t>* fallbacks = nullptr) const {
+        if (fallbacks) fallbacks->assign(beams_, 0);
+        check(gm_lcmv_stats(h_, inputs, outputs, blocks, fallbacks ? fallbacks->data() : nullptr), "Lcmv::stats");
+    }
+    void synchronize() { check(gm_lcmv_synchronize(h_), "Lcmv::synchronize"); }
+};
+
 // ---- rf::frontend::DigitalFrontend (src/rf/frontend.rs:6-62)
 class DigitalFrontend {
     gm_frontend* h_ = nullptr;

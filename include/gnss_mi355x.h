@@ -661,8 +661,8 @@ int gm_acq_local_plan(uint32_t coherent_periods, uint32_t n_integrations, const 
  * The sequence: gm_beamformer with the row e_0 and gm_beamformer_capture; gm_acq_search_dev on plane 0; gm_acq_array_prompts at the
  * found cells on the beamformer's own input; gm_array_row_solve per cell with the captured R; gm_beamformer_set_steering, or a new
  * handle with the rows.
- * Not built: per-antenna prompts from the tracker (the array form of gm_trk_bank); a loop that re-steers by itself; several constraints
- * on one beam (LCMV); ring writers; any detection or quality decision; wiring into receiver_harness.cpp or bench.py.
+ * Not built: per-antenna prompts from the tracker (the array form of gm_trk_bank); a loop that re-steers by itself; ring writers; any
+ * detection or quality decision; wiring into receiver_harness.cpp or bench.py.
  * (Since then the first item has been built: gm_trk_array_prompts, "Per-antenna prompts at tracked states" below.)
  * (And the second, as far as a library that decides nothing can build it: "Re-steering on the device" below, the three entries
  * gm_trk_array_prompts_dev, gm_array_rows_solve_dev and gm_beamformer_set_steering_dev that put one update on a stream with no host wait.)
@@ -1406,10 +1406,11 @@ int gm_nuller_process(gm_nuller *n, const void *in, int fmt, size_t n_in, gm_c32
  *   Kernel (csrc/stap_kernels.hip): one 256-lane workgroup per block; the block passes through LDS in chunks of 256 + L - 1 samples;
  *     the four waves share the lags; the solve in LDS in f64; a second pass through the same chunks for y; a state kernel.
  * Limits (README, measured by tests/stap_model.py): ONE constraint shapes the signal's spectrum — at L = 2 a correlation peak can land
- * a sample off; a reference on tap l0 delays the peak by l0 samples; a quantiser's clipping products are not low rank.
- * Not built: a ring writer with the stage at its head; wiring into receiver_harness.cpp; several constraints on ONE beam (LCMV; one
- * beam per constraint is gm_beamformer below); array calibration; any decision — the library reports R, w and the fallback count, the
- * caller judges.
+ * a sample off (gm_lcmv below holds the later taps to 0 with a constraint each); a reference on tap l0 delays the peak by l0
+ * samples; a quantiser's clipping products are not low rank.
+ * Not built: a ring writer with the stage at its head; wiring into receiver_harness.cpp; array calibration; any decision — the
+ * library reports R, w and the fallback count, the caller judges.  (One beam per constraint is gm_beamformer below;
+ * several constraints on ONE beam (LCMV) is gm_lcmv below it.)
  * (ABI 9, additive: a caller detects the feature by the symbol) */
 typedef struct {
     uint32_t n_antennas;      /* A: 2 .. 8 */
@@ -1483,8 +1484,8 @@ int gm_stap_process(gm_stap *n, const void *in, int fmt, size_t n_in, gm_c32 *ou
  *   Kernel (csrc/beam_kernels.hip): gm_stap's workgroup per block with gm_stap's own code (csrc/stap_core.h) for the staging, the
  *     Gram matrix and the factorisation, the P rows riding below the matrix; the substitution eight beams at a time; the output pass
  *     four beams at a time from one read of the staged samples; gm_stap's state kernel.
- * Not built: several constraints on ONE beam (LCMV); a ring writer; wiring into receiver_harness.cpp; array calibration; deriving the
- * rows from satellite directions; any decision.
+ * Not built: a ring writer; wiring into receiver_harness.cpp; array calibration; deriving the rows from satellite directions; any
+ * decision.  (Several constraints on one beam are gm_lcmv below.)
  * (ABI 9, additive: a caller detects the feature by the symbol) */
 typedef struct {
     uint32_t n_antennas;      /* A: 2 .. 8 */
@@ -1535,6 +1536,92 @@ int gm_beamformer_process_dev(gm_beamformer *h, const void *d_in, int fmt, size_
  * In static mode R is left untouched.  A device capture set by gm_beamformer_capture is not written by this form. */
 int gm_beamformer_process(gm_beamformer *h, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_stride, size_t *n_out,
                           gm_c32 *R, gm_c32 *w, size_t cap_blocks);
+
+/* ------------------------------------------------------------------ Several constraints on one beam
+ * A gm_lcmv is a gm_beamformer whose beam p carries Q_p constraint rows c_q and Q_p responses f_q in place of one row: the beam's
+ * weights answer C^H w = f at the least output power.  Two uses (README, measured by tests/lcmv_model.py): a second row with the
+ * response 0 removes a signal that power minimisation does not see because it lies below the noise (a spoofer, a repeater, a
+ * strong reflection: its row is what gm_acq_array_prompts and gm_array_row_solve return for its cell); one row per tap (the
+ * satellite's row on tap 0 answers 1, the same row on taps 1 .. L - 1 answers 0) keeps a space-time beam from skewing the
+ * correlation triangle.  It is a handle of its own: gm_beamformer's words are unchanged.
+ *   Shapes.  A is 2 .. 8, L is 1 .. 8, M = A L <= 32; B, loading, the formats (GM_FMT_C32, GM_FMT_I8_IQ), the interleaved input, the
+ *     stacked sample z[t][l A + a] = x_a[t - l], blocks, counts (total_out(T) = B * (T div B) PER BEAM), the history, gm_lcmv_reset
+ *     and the zero halo are gm_stap's.
+ *   Beams.  P is 1 .. 16.  n_constraints[p] = Q_p is 1 .. 8 with Q_p <= M, and sum_p Q_p <= 16.  `constraints` holds [sum Q][M] c32
+ *     words, each row laid out [L][A]; `response` holds [sum Q] c32 words; the rows of beam p are consecutive, beam 0's first.
+ *   Weights.  Per block R, tr and Rl = R + loading (tr / M) I exactly as gm_stap forms them: R's words are gm_beamformer's bit for
+ *     bit on the same input.  Then, in f64, with C the M x Q_p matrix whose columns are beam p's rows:
+ *       1. Rl = Lc Lc^H (gm_stap's factor, ONE for all beams);   2. z_q = Lc^-1 c_q for every row of every beam, in that factor;
+ *       3. G[q][r] = z_q^H z_r, the index ascending within each sum;   4. G = Lg Lg^H;   5. v = G^-1 f;
+ *       6. t = sum_q z_q v_q, q ascending;   7. u = Lc^-H t;   8. w_p = u, each component rounded once to f32.
+ *     So C^H w = f: w = Rl^-1 C (C^H Rl^-1 C)^-1 f.  The output is y = w^H z, so a signal whose stacked vector is c_q comes out with
+ *     the gain conj(f_q).  At Q = 1 and f = 1 this is gm_beamformer's w, equal to rounding and NOT word for word (the division by
+ *     z^H z comes before the last substitution here).
+ *   Fallback.  ALL beams of a block fall back where tr = 0 or a pivot of Lc is not greater than 0 or not finite; beam p ALONE where a
+ *     pivot of its Lg is not greater than 0 or not finite, or a word of u is not finite (as the f32 word it rounds to: a w above
+ *     the f32 range would turn a zero sample into a NaN).  A beam that falls back takes its
+ *     quiescent weights w0_p = C (C^H C)^-1 f (at Q = 1: f s / (s^H s)) and the block is counted for that beam.  The host computes
+ *     w0 in f64 at gm_lcmv_create and at every gm_lcmv_set_constraints, rounds it once and keeps it on the device.  Finite input
+ *     never produces a NaN.
+ *   Output, static mode, monitor: gm_beamformer's.  P planes, beam p's stream at d_out + p * out_stride; pass 2's sums in gm_stap's
+ *     order (l ascending, then a, one fmaf per real product); gm_lcmv_set_weights installs P M fixed weights (no Gram matrix);
+ *     gm_lcmv_capture names device buffers for R ([blocks][M][M]) and w ([blocks][P][M]); gm_lcmv_stats gives the fallback counts
+ *     per beam.
+ *   A beam's words depend on its own rows and responses, R and the cfg alone: neither on P, nor on the other beams, nor on how the
+ *     stream is cut into calls, nor on repetition.
+ *   Moving beams.  gm_lcmv_set_constraints replaces the rows and responses of one beam (their number may change as long as the sum
+ *     stays <= 16) for every block finished by a LATER call; SYNCHRONOUS, ordered as gm_beamformer_set_steering is.
+ *   Kernel (csrc/lcmv_kernels.hip): gm_beamformer's workgroup per block with csrc/stap_core.h's staging, Gram matrix and factor, the
+ *     rows of all beams riding below the matrix; then per beam, eight beams a round, the small Gram matrix (in the LDS words R leaves
+ *     once it has gone to the capture), its Cholesky factor with f^H riding below it, and the two substitutions; gm_beamformer's
+ *     output pass; gm_stap's state kernel.
+ * Not built: a _dev form of gm_lcmv_set_constraints; choosing which cells are spoofers, or any other decision; ring writers; wiring
+ * into receiver_harness.cpp or bench.py; inequality or derivative constraints.
+ * (ABI 9, additive: a caller detects the feature by the symbol) */
+typedef struct {
+    uint32_t n_antennas;      /* A: 2 .. 8 */
+    uint32_t taps;            /* L: 1 .. 8, A L <= 32 */
+    uint32_t block;           /* B: a power of two in 256 .. 16384; 0 -> 1024 */
+    float    loading;         /* [1e-6, 1]; 0 -> 1e-4 */
+    uint32_t n_beams;         /* P: 1 .. 16 */
+    uint32_t reserved32;      /* must be 0 */
+    const uint32_t *n_constraints; /* [P]: Q_p in 1 .. 8, Q_p <= A L, their sum <= 16; required */
+    const gm_c32 *constraints;     /* [sum Q][L][A] c32 words, beam 0's rows first; required */
+    const gm_c32 *response;   /* [sum Q] c32 words, in the rows' order; required.  All three are read during the call that takes the cfg only. */
+    uint64_t reserved;        /* must be 0 */
+} gm_lcmv_cfg;
+typedef struct gm_lcmv gm_lcmv;
+/* host only, no device: gm_beamformer_plan's rules (with n_constraints, constraints and response required in place of steering), and
+ * GM_ERR_INVALID_ARG for a Q_p outside 1 .. 8 or above M; sum Q > 16; a row that is not finite or is all zero; a response word that
+ * is not finite; rows of one beam that are linearly dependent (a Cholesky pivot of C^H C, columns ascending, not greater than 1e-10
+ * times that row's squared norm, in f64); quiescent weights that are not finite in f32.  *n_out is the count PER BEAM.  Any output
+ * pointer may be NULL. */
+int gm_lcmv_plan(const gm_lcmv_cfg *cfg, uint64_t inputs_so_far, uint64_t n_in, uint32_t *block, float *loading, uint64_t *n_out);
+int gm_lcmv_create(const gm_lcmv_cfg *cfg, gm_lcmv **out);
+int gm_lcmv_destroy(gm_lcmv *h);
+/* gm_stap_reset: zeroes the history and every counter; keeps the rows, the weights mode and the capture.  Synchronous. */
+int gm_lcmv_reset(gm_lcmv *h, uint64_t input_index);
+/* time samples taken, outputs delivered PER BEAM, blocks finished, and in fallbacks[p] (P words) the blocks whose beam p took its
+ * quiescent weights, since gm_lcmv_create or the last reset (any pointer may be NULL).  Synchronises like gm_stap_stats. */
+int gm_lcmv_stats(gm_lcmv *h, uint64_t *inputs, uint64_t *outputs, uint64_t *blocks, uint64_t *fallbacks);
+int gm_lcmv_synchronize(gm_lcmv *h);
+/* beam `beam`'s new rows ([n_rows][L][A]) and responses ([n_rows]), under gm_lcmv_plan's rules for one beam and for the sum; a
+ * refusal (also beam >= P or a NULL) is GM_ERR_INVALID_ARG with nothing changed.  Synchronous, see "Moving beams". */
+int gm_lcmv_set_constraints(gm_lcmv *h, uint32_t beam, uint32_t n_rows, const gm_c32 *rows, const gm_c32 *response);
+/* w: P M finite c32 words [P][L][A] used for every later block (static mode); NULL returns the handle to the adaptive rule (and
+ * waits for nothing).  Synchronous like gm_beamformer_set_weights. */
+int gm_lcmv_set_weights(gm_lcmv *h, const gm_c32 *w);
+/* gm_beamformer_capture: block k of the CALL at d_R + k M M (c32 [M][M]) and d_w + k P M (c32 [P][M]).  In static mode only w is
+ * written. */
+int gm_lcmv_capture(gm_lcmv *h, void *d_R, void *d_w, size_t cap_blocks);
+/* gm_beamformer_process_dev: d_in (n_in TIME samples, n_in * A elements) -> beam p's *n_out outputs at d_out + p * out_stride (c32
+ * elements).  Asynchronous on `stream` (NULL: the handle's own) under the streaming stages' rule, with gm_beamformer_process_dev's
+ * refusals, all before anything runs and with state, outputs and captures untouched.  n_in = 0: GM_OK. */
+int gm_lcmv_process_dev(gm_lcmv *h, const void *d_in, int fmt, size_t n_in, void *d_out, size_t out_stride, size_t *n_out, void *stream);
+/* the synchronous host-buffer form, gm_beamformer_process's: beam p's outputs at out + p * out_stride; R ([blocks][M][M]) and w
+ * ([blocks][P][M]) are host buffers for the call's block words, each may be NULL. */
+int gm_lcmv_process(gm_lcmv *h, const void *in, int fmt, size_t n_in, gm_c32 *out, size_t out_stride, size_t *n_out, gm_c32 *R,
+                    gm_c32 *w, size_t cap_blocks);
 
 /* ------------------------------------------------------------------ Tracking
  * The evolving fields of TrackingChannel (src/tracking/do_tracking.rs:88-116). */

@@ -233,6 +233,20 @@ pub struct GmBeamformerCfg {        // gm_beamformer_cfg (40 bytes; zeros: the d
     pub reserved: u64,               // must be 0
 }
 pub enum GmBeamformer {}
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct GmLcmvCfg {              // gm_lcmv_cfg (56 bytes; zeros: the defaults of block and loading)
+    pub n_antennas: u32,             // A: 2 .. 8, gm_stap's stream
+    pub taps: u32,                   // L: 1 .. 8, A L <= 32
+    pub block: u32,                  // B: a power of two in 256 .. 16384; 0 -> 1024
+    pub loading: f32,                // [1e-6, 1] of the mean stacked power; 0 -> 1e-4
+    pub n_beams: u32,                // P: 1 .. 16
+    pub reserved32: u32,             // must be 0
+    pub n_constraints: *const u32,   // [P]: Q_p in 1 .. 8, Q_p <= A L, their sum <= 16; required
+    pub constraints: *const Complex32, // [sum Q][L][A], beam 0's rows first, a beam's rows independent; required
+    pub response: *const Complex32,  // [sum Q], in the rows' order; required
+    pub reserved: u64,               // must be 0
+}
+pub enum GmLcmv {}
 pub enum GmAcq {} pub enum GmTrk {} pub enum GmRing {} pub enum GmComm {} pub enum GmFrontend {} pub enum GmResampler {} pub enum GmExcisor {}
 
 extern "C" {
@@ -453,6 +467,25 @@ extern "C" {
                                      out_stride: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
     pub fn gm_beamformer_process(h: *mut GmBeamformer, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32,
                                  out_stride: usize, n_out: *mut usize, r: *mut Complex32, w: *mut Complex32, cap_blocks: usize) -> c_int;
+    /// several constraints on one beam: beam p carries Q_p rows and responses, C^H w_p = f at the least output power; ONE Gram matrix
+    /// and ONE factor a block; planar output, beam p at d_out + p * out_stride; every count is in TIME samples, n_out per beam
+    pub fn gm_lcmv_plan(cfg: *const GmLcmvCfg, inputs_so_far: u64, n_in: u64, block: *mut u32, loading: *mut f32, n_out: *mut u64) -> c_int;
+    pub fn gm_lcmv_create(cfg: *const GmLcmvCfg, out: *mut *mut GmLcmv) -> c_int;
+    pub fn gm_lcmv_destroy(h: *mut GmLcmv) -> c_int;
+    pub fn gm_lcmv_reset(h: *mut GmLcmv, input_index: u64) -> c_int;
+    /// fallbacks: P words, one per beam
+    pub fn gm_lcmv_stats(h: *mut GmLcmv, inputs: *mut u64, outputs: *mut u64, blocks: *mut u64, fallbacks: *mut u64) -> c_int;
+    pub fn gm_lcmv_synchronize(h: *mut GmLcmv) -> c_int;
+    /// beam `beam`'s new rows [n_rows][M] and responses [n_rows] for every block a later call finishes; synchronous
+    pub fn gm_lcmv_set_constraints(h: *mut GmLcmv, beam: u32, n_rows: u32, rows: *const Complex32, response: *const Complex32) -> c_int;
+    /// static mode: P M fixed weights [P][L][A] for every later block (synchronous); null: back to the adaptive rule
+    pub fn gm_lcmv_set_weights(h: *mut GmLcmv, w: *const Complex32) -> c_int;
+    /// device buffers [cap_blocks][M][M] and [cap_blocks][P][M] that every later gm_lcmv_process_dev fills from word 0
+    pub fn gm_lcmv_capture(h: *mut GmLcmv, d_r: *mut c_void, d_w: *mut c_void, cap_blocks: usize) -> c_int;
+    pub fn gm_lcmv_process_dev(h: *mut GmLcmv, d_in: *const c_void, fmt: c_int, n_in: usize, d_out: *mut c_void, out_stride: usize,
+                               n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gm_lcmv_process(h: *mut GmLcmv, input: *const c_void, fmt: c_int, n_in: usize, out: *mut Complex32, out_stride: usize,
+                           n_out: *mut usize, r: *mut Complex32, w: *mut Complex32, cap_blocks: usize) -> c_int;
     // do_tracking.rs:118-158, 311-327
     pub fn gm_trk_create(cfg: *const GmTrkCfg, out: *mut *mut GmTrk) -> c_int;
     pub fn gm_trk_destroy(t: *mut GmTrk) -> c_int;
