@@ -175,8 +175,10 @@ public:
     // dwell of dwell_samples() samples in device memory (read only; it does not become the snapshot).  No detection decision is made.
     std::vector<gm_acq_local_out> local_search(const std::vector<gm_acq_cand>& cands, const gm_acq_local_cfg& cfg = {},
                                                const void* d_samples = nullptr, int fmt = GM_FMT_C32) {
-        std::vector<gm_acq_local_out> out(cands.size());
-        check(gm_acq_local_search(h_, d_samples, fmt, cands.data(), uint32_t(cands.size()), &cfg, out.data(), nullptr, nullptr), "local_search");
+        const gm_acq_cand spare{};              // an empty list still hands over pointers: the library refuses null ones before it looks at the count
+        std::vector<gm_acq_local_out> out(std::max<size_t>(cands.size(), 1));
+        check(gm_acq_local_search(h_, d_samples, fmt, cands.empty() ? &spare : cands.data(), uint32_t(cands.size()), &cfg, out.data(), nullptr, nullptr), "local_search");
+        out.resize(cands.size());
         return out;
     }
     // Space-time prompts of an antenna array at known cells (gm_acq_array_prompts): every antenna and tap delay of the interleaved
@@ -187,7 +189,8 @@ public:
         uint32_t r = 0, words = 0;
         check(gm_acq_array_plan(coherent_periods_, n_integrations_, n_antennas, taps, &r, &words), "array_plan");
         std::vector<gm_c32> z(std::max<size_t>(cands.size(), 1) * words);
-        check(gm_acq_array_prompts(h_, d_samples, fmt, n_antennas, taps, cands.data(), uint32_t(cands.size()), z.data()), "array_prompts");
+        const gm_acq_cand spare{};              // (as in local_search: no candidates is not a null pointer)
+        check(gm_acq_array_prompts(h_, d_samples, fmt, n_antennas, taps, cands.empty() ? &spare : cands.data(), uint32_t(cands.size()), z.data()), "array_prompts");
         z.resize(cands.size() * words);
         if (periods) *periods = r;
         return z;
@@ -378,7 +381,7 @@ public:
     // periodogram, median, mask and gains from n device samples, enqueued with no host wait
     void adapt_dev(const void* d_in, int fmt, size_t n, void* stream = nullptr) { check(gm_excisor_adapt_dev(h_, d_in, fmt, n, stream), "Excisor::adapt_dev"); }
     void set_gains(const std::vector<float>& gains) {
-        if (gains.size() != block_) throw std::invalid_argument("Excisor::set_gains: one gain per bin");
+        if (gains.size() != block_) check(GM_ERR_INVALID_ARG, "Excisor::set_gains (one gain per bin)");
         check(gm_excisor_set_gains(h_, gains.data()), "Excisor::set_gains");
     }
     std::vector<float> gains() const { std::vector<float> g(block_); check(gm_excisor_gains(h_, g.data()), "Excisor::gains"); return g; }
