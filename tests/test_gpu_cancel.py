@@ -4,6 +4,9 @@
    code drift T = N - 0.4 in every bin (the dwell, 12286 samples, is no multiple of 8) and without it (12288), on int8 IQ, int8 real and
    c32 samples; candidate sets: one candidate; five candidates with the same worker twice; the plan cases of the host test, each with its
    own T.  n_cands = 0 returns the converted dwell.
+1b. Every pointer form: the five candidates on every (format, drift) with the input one element off (acq_cancel_amp_kernel and
+   acq_cancel_subtract_kernel with ALIGNED = false), the output 8 bytes off (OUT_ALIGNED = false) and both, each bit for bit the aligned
+   run's output and amplitude words; nothing written in front of a moved output or behind the dwell; n_cands = 0 from a moved input.
 2. A handle of another form (N = 4088 with any_length: padded long), one candidate.
 3. Repetition, in place, the NULL route, the snapshot and the metrics.
 4. Every GM_ERR_INVALID_ARG case with a pre-filled d_out and `out` left untouched, the overlap rule, no search yet.
@@ -134,6 +137,53 @@ def test_parity_with_the_model(gpu, oracle, hipbuf, fmt, drift):
     y = hipbuf.download(d_out, D * 8, np.complex64)
     re, im = AM.as_parts(c["x"])
     assert (_words(y.real.copy()) == _words(re)).all() and (_words(y.imag.copy()) == _words(im)).all()
+    eng.close()
+
+
+# ---- 1b. every pointer form ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("drift", [True, False], ids=["drift", "plain"])
+@pytest.mark.parametrize("fmt", AM.FORMATS)
+def test_every_pointer_form_gives_the_aligned_words(gpu, oracle, hipbuf, fmt, drift):
+    """launch_cancel picks acq_cancel_amp_kernel<FMT, ALIGNED> and acq_cancel_subtract_kernel<FMT, ALIGNED, OUT_ALIGNED> by the low bits of
+    the dwell's and the output's addresses; a fresh allocation only ever selects <true, true>.  An input one element (2 / 1 / 8 bytes)
+    behind a 256-byte boundary selects ALIGNED = false (element loads), an output 8 bytes behind one selects OUT_ALIGNED = false (stores
+    of one sample).  The arithmetic is the same, so every output word and every amplitude word equals the aligned run's, which _check
+    holds to the model.  The moved input lies between 0x5A bytes (90 as int8, 1.5e16 as f32) and the outputs are pre-filled with them."""
+    c = _scene(oracle, fmt, drift)
+    D = c["dwell"]
+    assert D == (12286 if drift else 12288) and (D % 8 != 0) == drift
+    eng = _engine(c, M_PARITY, drift)
+    cands = _candidate_sets(D)["five"]
+    elem = {"i8": 2, "real": 1, "c32": 8}[fmt]
+    raw = np.ascontiguousarray(c["x"]).view(np.uint8).reshape(-1)
+    assert raw.size == D * elem
+    d_x = hipbuf.upload(c["x"])
+    d_pad = hipbuf.upload(np.concatenate([np.full(elem, 0x5A, np.uint8), raw, np.full(64, 0x5A, np.uint8)]))
+    assert d_x % 256 == 0 and d_pad % 256 == 0                                      # so d_pad + elem is aligned to its element only
+
+    def run(samples, shift, cand_list=cands):
+        d_out = hipbuf.alloc(shift + D * 8 + 64, fill=0x5A)
+        assert d_out % 256 == 0                                                     # so d_out + 8 is 8-aligned and not 16-aligned
+        got = eng.cancel(cand_list, d_out + shift, samples=samples, fmt=_fmt(fmt), want_amps=True)
+        buf = hipbuf.download(d_out, shift + D * 8 + 64, np.uint8)
+        assert (buf[:shift] == 0x5A).all() and (buf[shift + D * 8:] == 0x5A).all()  # nothing in front of the output, nothing behind it
+        return got, buf[shift:shift + D * 8].view(np.complex64)
+
+    ref, y_ref = run(d_x, 0)
+    _check((fmt, drift, "five, aligned"), c, cands, ref, y_ref)
+    for tag, samples, shift in (("input moved", d_pad + elem, 0), ("output moved", d_x, 8), ("both moved", d_pad + elem, 8)):
+        got, y = run(samples, shift)
+        assert (_words(y) == _words(y_ref)).all(), tag
+        assert len(got) == len(ref)
+        for g, r in zip(got, ref):
+            assert g.keys() == r.keys()
+            for k in r:
+                assert np.asarray(g[k]).tobytes() == np.asarray(r[k]).tobytes(), (tag, k)
+    # n_cands = 0 from the moved input, to both output forms: the converted dwell, exactly
+    re, im = AM.as_parts(c["x"])
+    for shift in (0, 8):
+        got, y = run(d_pad + elem, shift, [])
+        assert got == [] and (_words(y.real.copy()) == _words(re)).all() and (_words(y.imag.copy()) == _words(im)).all(), shift
     eng.close()
 
 
