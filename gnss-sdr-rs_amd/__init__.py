@@ -29,3 +29,5 @@ from . import tracking  # noqa: F401
 # per-antenna prompts of an array stream at tracked states: TrackingManager.array_prompts, and tracking.array_plan under a name that
 # does not collide with acquisition.array_plan
 from .tracking import TrackingManager, array_plan as trk_array_plan  # noqa: F401
+# tracking on planes: the plane ring a multi-output stage's planes go into, and the two host-only plans
+from .tracking import PlaneRing, plane_ring_plan, planes_plan as trk_planes_plan  # noqa: F401

@@ -234,6 +234,15 @@ class TrkArrayPlanOut(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TrkPlanesPlanOut(C.Structure):
+    """gm_trk_planes_plan_out (40 bytes)"""
+    _fields_ = [("workgroups", C.c_uint32), ("threads", C.c_uint32), ("chip_row_bytes", C.c_uint32), ("planes_used", C.c_uint32),
+                ("samples", C.c_uint64), ("samples_per_lane", C.c_uint32), ("reserved", C.c_uint32), ("result_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 FMT_C32, FMT_I8_IQ, FMT_I8_REAL = 0, 1, 2
 CODE_INDEX_FAITHFUL, CODE_INDEX_FIXED = 0, 1
 
@@ -470,6 +479,20 @@ SIGNATURES = {
     "gm_trk_array_plan": (_i, [C.POINTER(TrkCfg), C.POINTER(TrkArrayCfg), _u32, C.POINTER(TrkArrayPlanOut)]),
     "gm_trk_array_prompts": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _u32, C.POINTER(TrkArrayCfg), _vp, _vp]),
     "gm_trk_array_prompts_dev": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _u32, C.POINTER(TrkArrayCfg), _vp, _vp, _vp]),
+    "gm_plane_ring_plan": (_i, [_u32, _u64, C.POINTER(_u64)]),
+    "gm_plane_ring_create": (_i, [_u32, _u64, C.POINTER(_vp)]),
+    "gm_plane_ring_destroy": (_i, [_vp]),
+    "gm_plane_ring_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_vp)]),
+    "gm_plane_ring_write_dev": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "gm_plane_ring_write": (_i, [_vp, _vp, _sz, _sz]),
+    "gm_plane_ring_get_head": (_i, [_vp, C.POINTER(_u64)]),
+    "gm_plane_ring_copy_to_slice": (_i, [_vp, _u32, _u64, _vp, _sz]),
+    "gm_plane_ring_synchronize": (_i, [_vp]),
+    "gm_trk_planes_plan": (_i, [C.POINTER(TrkCfg), _u32, _vp, _u32, C.POINTER(TrkPlanesPlanOut)]),
+    "gm_trk_set_channel_planes": (_i, [_vp, _vp]),
+    "gm_trk_get_channel_planes": (_i, [_vp, _vp]),
+    "gm_trk_update_planes": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "gm_trk_update_planes_dev": (_i, [_vp, _vp, _u32]),
 }
 
 _lib = None

@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgnss_mi355x.so")
 SOURCES = ["acq_kernels.hip", "acq_composite.hip", "acq_long.hip", "acq_stage_f_coh.hip", "acq_stage_f_edge.hip", "acq_stage_f_drift.hip", "acq_refine.hip", "acq_local.hip", "acq_array.hip", "acq_cancel.hip", "trk_kernels.hip", "fe_kernels.hip", "resample_kernels.hip", "ddc_kernels.hip", "channelizer_kernels.hip", "nuller_kernels.hip", "stap_kernels.hip", "beam_kernels.hip", "lcmv_kernels.hip", "array_solve.hip", "excise_kernels.hip", "nav_host.hip", "gm_api.hip"]
-HEADERS = ["fft_core.h", "fft_plans.h", "acq_corr_plans.h", "gm_internal.h", "trk_persist_plan.h", "acq_corr_grid.h", "gm_libm.h", "acq_device.h", "acq_load8.h", "acq_stage_f_variants.h", "acq_corr_ws31.h", "ws31_core.h", "acq_comp_ws.h", "excise_core.h", "stap_core.h", "trk_bank.hip", "trk_array.hip", os.path.join("..", "..", "include", "gnss_mi355x.h")]
-# (trk_bank.hip and trk_array.hip are sections that trk_kernels.hip includes, not translation units: they are listed with the headers so
+HEADERS = ["fft_core.h", "fft_plans.h", "acq_corr_plans.h", "gm_internal.h", "trk_persist_plan.h", "acq_corr_grid.h", "gm_libm.h", "acq_device.h", "acq_load8.h", "acq_stage_f_variants.h", "acq_corr_ws31.h", "ws31_core.h", "acq_comp_ws.h", "excise_core.h", "stap_core.h", "trk_bank.hip", "trk_array.hip", "trk_planes.hip", os.path.join("..", "..", "include", "gnss_mi355x.h")]
+# (trk_bank.hip, trk_array.hip and trk_planes.hip are sections that trk_kernels.hip includes, not translation units: they are listed with the headers so
 # that an edit rebuilds)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC",
          "-Wall", "-Wno-unused-function"]

@@ -2893,6 +2893,205 @@ int gm_ring_copy_to_slice(gm_ring* r, uint64_t start, gm_c32* dest, size_t n) {
 
 }  // extern "C"
 
+// ====================================================================== plane ring: P rings on one time axis, written from device memory
+// gnss_mi355x.h states the contract.  One writer; the head counts what has been ENQUEUED.  `mu` guards the head and the events: the
+// writer and the readers (tracking handles, gm_plane_ring_copy_to_slice) may be different host threads.
+struct gm_plane_ring {
+    int device = -1;
+    cf* d_buf = nullptr;                  // [P][size]
+    uint32_t P = 0;
+    uint64_t size = 0, mask = 0;
+    hipStream_t own_stream = nullptr;     // non-blocking: the writer's stream when the caller names none, and gm_plane_ring_copy_to_slice's
+    std::mutex mu;
+    uint64_t enqueued = 0;                // samples per plane whose writes have been enqueued
+    hipEvent_t ev_write = nullptr;        // recorded behind every write
+    bool write_armed = false;
+    hipStream_t last_stream = nullptr;    // the stream ev_write was last recorded on
+    // one event per reader stream, recorded behind every tracking launch on the ring; the next write waits for the armed ones
+    struct Reader { hipStream_t st; hipEvent_t ev; bool armed; };
+    std::vector<Reader> readers;
+};
+static constexpr uint32_t PLANE_RING_MAX_PLANES = 64;
+static constexpr uint64_t PLANE_RING_MAX_BYTES = 1ull << 34;
+static constexpr size_t PLANE_RING_MAX_READERS = 64;
+
+static int plane_ring_rules(uint32_t n_planes, uint64_t plane_size, uint64_t* bytes) {
+    if (n_planes < 1 || n_planes > PLANE_RING_MAX_PLANES) return set_err(GM_ERR_OUT_OF_RANGE, "n_planes must be in 1 .. 64");
+    if (!plane_size || (plane_size & (plane_size - 1))) return set_err(GM_ERR_OUT_OF_RANGE, "plane_size must be a power of two");
+    if (plane_size > PLANE_RING_MAX_BYTES / 8 / n_planes) return set_err(GM_ERR_OUT_OF_RANGE, "n_planes * plane_size * 8 must be at most 2^34 bytes");
+    if (bytes) *bytes = uint64_t(n_planes) * plane_size * 8;
+    return GM_OK;
+}
+// `st` is about to write the ring: behind the last write where that went to another stream, and behind every reader still armed
+static int plane_ring_before_write(gm_plane_ring* r, hipStream_t st) {
+    if (r->write_armed && r->last_stream != st) HIPC(hipStreamWaitEvent(st, r->ev_write, 0));
+    for (auto& rd : r->readers)
+        if (rd.armed) { HIPC(hipStreamWaitEvent(st, rd.ev, 0)); rd.armed = false; }      // (later writes are ordered behind this one)
+    return GM_OK;
+}
+static int plane_ring_after_write(gm_plane_ring* r, hipStream_t st, uint64_t n) {
+    HIPC(hipEventRecord(r->ev_write, st));
+    r->last_stream = st; r->write_armed = true;
+    r->enqueued += n;
+    return GM_OK;
+}
+// a reader on `st`: behind everything the writer has enqueued; *head = the enqueued head it may then use.  Call with r->mu held.
+static int plane_ring_begin_read(gm_plane_ring* r, hipStream_t st, uint64_t* head) {
+    if (r->write_armed) HIPC(hipStreamWaitEvent(st, r->ev_write, 0));
+    *head = r->enqueued;
+    return GM_OK;
+}
+// the reader's launches are on `st`: its event, which the next write waits for.  Call with r->mu held.
+static int plane_ring_end_read(gm_plane_ring* r, hipStream_t st) {
+    gm_plane_ring::Reader* slot = nullptr;
+    for (auto& rd : r->readers)
+        if (rd.st == st) { slot = &rd; break; }
+    if (!slot && r->readers.size() >= PLANE_RING_MAX_READERS) {      // more reader streams than places: take one whose launches have run
+        for (auto& rd : r->readers)
+            if (!rd.armed) { slot = &rd; break; }
+        if (!slot) { slot = &r->readers[0]; HIPC(hipEventSynchronize(slot->ev)); }
+        slot->st = st;
+    }
+    if (!slot) {
+        hipEvent_t ev = nullptr;
+        HIPC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        r->readers.push_back(gm_plane_ring::Reader{st, ev, false});
+        slot = &r->readers.back();
+    }
+    HIPC(hipEventRecord(slot->ev, st));
+    slot->armed = true;
+    return GM_OK;
+}
+static int plane_ring_write_rules(const gm_plane_ring* r, const void* src, size_t in_stride, size_t n) {
+    if (!r || !src) return set_err(GM_ERR_INVALID_ARG, "null plane ring or planes");
+    if (n > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "write larger than a plane");
+    if (in_stride < n) return set_err(GM_ERR_OUT_OF_RANGE, "in_stride below n");
+    return GM_OK;
+}
+
+extern "C" {
+
+int gm_plane_ring_plan(uint32_t n_planes, uint64_t plane_size, uint64_t* bytes) { return plane_ring_rules(n_planes, plane_size, bytes); }
+
+int gm_plane_ring_create(uint32_t n_planes, uint64_t plane_size, gm_plane_ring** out) {
+    if (!out) return set_err(GM_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    uint64_t bytes = 0;
+    if (int rc = plane_ring_rules(n_planes, plane_size, &bytes)) return rc;
+    if (int rc = ensure_device(g_device)) return rc;
+    gm_plane_ring* r = new gm_plane_ring();
+    r->device = g_device; r->P = n_planes; r->size = plane_size; r->mask = plane_size - 1;
+    hipError_t e = hipMalloc(&r->d_buf, bytes);
+    if (e == hipSuccess) e = hipMemset(r->d_buf, 0, bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // the fill has run before a non-blocking stream can write (gm_ring_create)
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_write, hipEventDisableTiming);
+    if (e != hipSuccess) { gm_plane_ring_destroy(r); return hip_fail(e, "gm_plane_ring_create"); }
+    *out = r;
+    return GM_OK;
+}
+
+int gm_plane_ring_destroy(gm_plane_ring* r) {
+    if (!r) return GM_OK;
+    hipSetDevice(r->device);
+    if (r->write_armed) hipEventSynchronize(r->ev_write);
+    for (auto& rd : r->readers) { if (rd.armed) hipEventSynchronize(rd.ev); hipEventDestroy(rd.ev); }
+    if (r->own_stream) { hipStreamSynchronize(r->own_stream); hipStreamDestroy(r->own_stream); }
+    if (r->ev_write) hipEventDestroy(r->ev_write);
+    hipFree(r->d_buf);
+    delete r;
+    return GM_OK;
+}
+
+int gm_plane_ring_info(gm_plane_ring* r, uint32_t* n_planes, uint64_t* plane_size, uint64_t* bytes, void** d_base) {
+    if (!r) return set_err(GM_ERR_INVALID_ARG, "null plane ring");
+    if (n_planes) *n_planes = r->P;
+    if (plane_size) *plane_size = r->size;
+    if (bytes) *bytes = uint64_t(r->P) * r->size * 8;
+    if (d_base) *d_base = r->d_buf;
+    return GM_OK;
+}
+
+int gm_plane_ring_write_dev(gm_plane_ring* r, const void* d_planes, size_t in_stride, size_t n, void* stream) {
+    if (int rc = plane_ring_write_rules(r, d_planes, in_stride, n)) return rc;
+    if (!n) return GM_OK;
+    {   // the source range [d_planes, d_planes + (P - 1) * in_stride + n) may not touch the ring
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_planes), r0 = reinterpret_cast<uintptr_t>(r->d_buf);
+        const unsigned __int128 s_len = ((unsigned __int128)(r->P - 1) * in_stride + n) * 8, r_len = (unsigned __int128)r->P * r->size * 8;
+        if ((unsigned __int128)s0 < (unsigned __int128)r0 + r_len && (unsigned __int128)r0 < (unsigned __int128)s0 + s_len)
+            return set_err(GM_ERR_OUT_OF_RANGE, "the source planes overlap the ring");
+    }
+    if (int rc = ensure_device(r->device)) return rc;
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : r->own_stream;
+    std::lock_guard<std::mutex> g(r->mu);
+    if (int rc = plane_ring_before_write(r, st)) return rc;
+    gm::PlaneRingWriteArgs a;
+    a.src = static_cast<const cf*>(d_planes); a.ring = r->d_buf;
+    a.in_stride = in_stride; a.plane_size = r->size; a.start = r->enqueued & r->mask; a.n = n; a.n_planes = r->P;
+    a.wide = (reinterpret_cast<uintptr_t>(d_planes) % 16 == 0 && in_stride % 2 == 0 && n % 2 == 0 && a.start % 2 == 0 && r->size % 2 == 0) ? 1 : 0;
+    gm::launch_plane_ring_write(st, a);
+    HIPC(hipGetLastError());
+    return plane_ring_after_write(r, st, n);
+}
+
+int gm_plane_ring_write(gm_plane_ring* r, const gm_c32* planes, size_t in_stride, size_t n) {
+    if (int rc = plane_ring_write_rules(r, planes, in_stride, n)) return rc;
+    if (!n) return GM_OK;
+    if (int rc = ensure_device(r->device)) return rc;
+    std::lock_guard<std::mutex> g(r->mu);
+    hipStream_t st = r->own_stream;
+    if (int rc = plane_ring_before_write(r, st)) return rc;
+    const uint64_t start = r->enqueued & r->mask, first = start + n <= r->size ? n : r->size - start;
+    for (uint32_t p = 0; p < r->P; ++p) {
+        const gm_c32* s = planes + size_t(p) * in_stride;
+        cf* d = r->d_buf + uint64_t(p) * r->size;
+        HIPC(hipMemcpyAsync(d + start, s, first * 8, hipMemcpyHostToDevice, st));
+        if (first < n) HIPC(hipMemcpyAsync(d, s + first, (n - first) * 8, hipMemcpyHostToDevice, st));
+    }
+    if (int rc = plane_ring_after_write(r, st, n)) return rc;
+    HIPC(hipStreamSynchronize(st));
+    return GM_OK;
+}
+
+int gm_plane_ring_get_head(gm_plane_ring* r, uint64_t* head) {
+    if (!r || !head) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    std::lock_guard<std::mutex> g(r->mu);
+    *head = r->enqueued;
+    return GM_OK;
+}
+
+int gm_plane_ring_copy_to_slice(gm_plane_ring* r, uint32_t plane, uint64_t start, gm_c32* dest, size_t n) {
+    if (!r || (!dest && n)) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    if (plane >= r->P) return set_err(GM_ERR_OUT_OF_RANGE, "plane at or above n_planes");
+    if (n > r->size) return set_err(GM_ERR_OUT_OF_RANGE, "slice larger than a plane");
+    if (int rc = ensure_device(r->device)) return rc;
+    if (!n) return GM_OK;
+    hipStream_t st = r->own_stream;
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        uint64_t head = 0;
+        if (int rc = plane_ring_begin_read(r, st, &head)) return rc;
+    }
+    const cf* d = r->d_buf + uint64_t(plane) * r->size;
+    const uint64_t ps = start & r->mask, first = ps + n <= r->size ? n : r->size - ps;
+    HIPC(hipMemcpyAsync(dest, d + ps, first * 8, hipMemcpyDeviceToHost, st));
+    if (first < n) HIPC(hipMemcpyAsync(dest + first, d, (n - first) * 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));      // the copy has run before the call returns: no write can be waiting for it
+    return GM_OK;
+}
+
+int gm_plane_ring_synchronize(gm_plane_ring* r) {
+    if (!r) return set_err(GM_ERR_INVALID_ARG, "null plane ring");
+    if (int rc = ensure_device(r->device)) return rc;
+    std::lock_guard<std::mutex> g(r->mu);
+    if (r->write_armed) HIPC(hipEventSynchronize(r->ev_write));
+    for (auto& rd : r->readers)
+        if (rd.armed) { HIPC(hipEventSynchronize(rd.ev)); rd.armed = false; }
+    return GM_OK;
+}
+
+}  // extern "C"
+
 // ====================================================================== tracking handle
 struct gm_trk {
     int device = -1;
@@ -2943,6 +3142,13 @@ struct gm_trk {
     uint8_t* array_recs = nullptr;        // [ARRAY_SLOTS][GM_TRK_ARRAY_MAX_STATES] TrkBankRec, built at the first device call
     hipEvent_t array_ev[ARRAY_SLOTS] = {};
     uint32_t array_next = 0;
+    // gm_trk_update_planes: the plane of every channel (gm_trk_set_channel_planes).  h_planes is what the rules are checked against;
+    // d_planes is what the kernel reads, installed on the handle's stream from the pinned planes_stage (planes_ev: that copy has run).
+    // Both are made at the first entry that needs them; no other entry reads them.
+    std::vector<uint32_t> h_planes;
+    uint32_t* d_planes = nullptr;
+    uint32_t* planes_stage = nullptr;
+    hipEvent_t planes_ev = nullptr;
 };
 
 static int trk_check_error(gm_trk* t);
@@ -3004,6 +3210,9 @@ int gm_trk_destroy(gm_trk* t) {
     if (t->array_last) hipStreamSynchronize(t->array_last);
     for (auto& e : t->array_ev) if (e) hipEventDestroy(e);
     if (t->array_recs) hipHostFree(t->array_recs);
+    if (t->planes_ev) { hipEventSynchronize(t->planes_ev); hipEventDestroy(t->planes_ev); }
+    if (t->planes_stage) hipHostFree(t->planes_stage);
+    hipFree(t->d_planes);
     hipFree(t->d_res); t->bank.release(); t->array.release();
     if (t->h_res) hipHostFree(t->h_res);
     for (auto& k : t->tk) if (k.done) hipEventDestroy(k.done);
@@ -3755,6 +3964,140 @@ int gm_trk_update_all(gm_trk* t, gm_ring* ring, uint32_t max_epochs, gm_trk_out*
     if (processed) memcpy(processed, h_proc, n);
     if (lost) memcpy(lost, h_lost, n);
     if (epochs_done) *epochs_done = trk_epochs_done(proc, max_epochs, t->C);
+    return GM_OK;
+}
+
+// ---- tracking on planes: channel c on plane planes[c] of a gm_plane_ring (gnss_mi355x.h states the contract) -------------------------
+// gm_trk_planes_plan's argument rules, shared by the device entries; planes NULL: every channel on plane 0
+static int trk_planes_rules(float fs, uint32_t n_channels, bool custom_codes, uint32_t n_codes, uint32_t code_len, bool strict_sum_order,
+                            uint32_t n_planes, const uint32_t* planes, uint32_t max_epochs) {
+    if (!(fs > 0) || !std::isfinite(fs) || !n_channels) return set_err(GM_ERR_INVALID_ARG, "fs and n_channels are required");
+    if (custom_codes && (!n_codes || !code_len)) return set_err(GM_ERR_INVALID_ARG, "n_codes/code_len required");
+    if (strict_sum_order)
+        return set_err(GM_ERR_INVALID_ARG, "tracking on planes: the sequential-sum path (strict_sum_order) is not built on planes; the switch is not ignored");
+    if (!max_epochs) return set_err(GM_ERR_INVALID_ARG, "max_epochs must be at least 1");
+    if (max_epochs > 4095) return set_err(GM_ERR_OUT_OF_RANGE, "max_epochs must be at most 4095");
+    if (n_planes < 1 || n_planes > PLANE_RING_MAX_PLANES) return set_err(GM_ERR_OUT_OF_RANGE, "n_planes must be in 1 .. 64");
+    // the chip row sits in the workgroup's LDS as int8, beside the kernel's own few hundred bytes
+    if (custom_codes && code_len > 16384) return set_err(GM_ERR_OUT_OF_RANGE, "tracking on planes serves codes of at most 16384 chips");
+    for (uint32_t c = 0; planes && c < n_channels; ++c)
+        if (planes[c] >= n_planes) {
+            char msg[128];
+            snprintf(msg, sizeof(msg), "channel %u is mapped to plane %u, the ring has %u planes", c, planes[c], n_planes);
+            return set_err(GM_ERR_OUT_OF_RANGE, msg);
+        }
+    return GM_OK;
+}
+// the map's device and staging blocks, made at the first entry that needs them (a new handle's map: every channel on plane 0)
+static int trk_planes_ensure(gm_trk* t) {
+    if (t->d_planes) return GM_OK;
+    uint32_t* d = nullptr;
+    HIPC(hipMalloc(&d, size_t(t->C) * 4));
+    hipError_t e = hipMemsetAsync(d, 0, size_t(t->C) * 4, t->stream);
+    if (e == hipSuccess && !t->planes_stage) e = hipHostMalloc(reinterpret_cast<void**>(&t->planes_stage), size_t(t->C) * 4, hipHostMallocDefault);
+    if (e == hipSuccess && !t->planes_ev) e = hipEventCreateWithFlags(&t->planes_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(t->planes_ev, t->stream);
+    if (e != hipSuccess) { hipStreamSynchronize(t->stream); hipFree(d); return hip_fail(e, "gm_trk: the plane map's blocks"); }
+    t->d_planes = d;
+    t->h_planes.assign(t->C, 0u);
+    return GM_OK;
+}
+// every refusal of the device entries, before anything runs
+static int trk_planes_call_rules(gm_trk* t, gm_plane_ring* pr, uint32_t max_epochs) {
+    if (!t || !pr) return set_err(GM_ERR_INVALID_ARG, "null handle or plane ring");
+    if (t->device != pr->device) return set_err(GM_ERR_INVALID_ARG, "plane ring lives on another device");
+    return trk_planes_rules(t->dc.fs, t->C, !t->dc.gps_ca, uint32_t(t->dc.n_codes), uint32_t(t->dc.code_len), t->dc.strict_sum_order != 0, pr->P,
+                            t->h_planes.empty() ? nullptr : t->h_planes.data(), max_epochs);
+}
+// `epochs` passes on the handle's stream, behind the ring's enqueued writes and the device's previous tracking launch
+static int trk_launch_planes(gm_trk* t, gm_plane_ring* pr, uint32_t epochs) {
+    if (int rc = ensure_device(t->device)) return rc;
+    if (int rc = trk_planes_ensure(t)) return rc;
+    if (int rc = trk_reserve_epochs(t, epochs)) return rc;
+    std::lock_guard<std::mutex> ring_lock(pr->mu);
+    uint64_t head = 0;
+    if (int rc = plane_ring_begin_read(pr, t->stream, &head)) return rc;
+    // a workgroup of this kernel holding a CU slot while another handle's persistent grid starts is the stall the chain prevents:
+    // same chain as the strict path of trk_launch_all — wait for the device's previous tracking launch, record behind this one
+    PersistChain& chain = g_persist_chain[t->device & 15];
+    std::lock_guard<std::mutex> chain_lock(chain.mu);
+    if (!chain.ev) HIPC(hipEventCreateWithFlags(&chain.ev, hipEventDisableTiming));
+    if (chain.armed) HIPC(hipStreamWaitEvent(t->stream, chain.ev, 0));
+    if (t->timing) HIPC(hipEventRecord(t->ev0, t->stream));
+    gm::TrkPlanesArgs a;
+    a.cfg = t->dc; a.codes = t->d_codes; a.states = t->d_states; a.map = t->d_planes;
+    a.ring = pr->d_buf; a.plane_size = pr->size; a.mask = pr->mask; a.head = head; a.n_planes = pr->P; a.epochs = int(epochs);
+    a.outs = t->d_outs; a.processed = t->d_proc; a.lost = t->d_lost; a.lost_prn = t->d_lostprn;
+    gm::launch_trk_planes(t->stream, a);
+    if (t->timing) { HIPC(hipEventRecord(t->ev1, t->stream)); t->timed_launches = epochs; }
+    HIPC(hipEventRecord(chain.ev, t->stream));
+    chain.armed = true;
+    HIPC(hipGetLastError());
+    return plane_ring_end_read(pr, t->stream);
+}
+
+int gm_trk_planes_plan(const gm_trk_cfg* trk, uint32_t n_planes, const uint32_t* planes, uint32_t max_epochs, gm_trk_planes_plan_out* out) {
+    if (!trk) return set_err(GM_ERR_INVALID_ARG, "null tracking cfg");
+    if (int rc = trk_planes_rules(trk->fs, trk->n_channels, trk->codes != nullptr, trk->n_codes, trk->code_len, trk->strict_sum_order != 0,
+                                  n_planes, planes, max_epochs))
+        return rc;
+    if (!out) return GM_OK;
+    memset(out, 0, sizeof(*out));
+    out->workgroups = trk->n_channels; out->threads = 256;
+    out->chip_row_bytes = trk->codes ? trk->code_len : 1023u;
+    uint64_t used = 0;
+    for (uint32_t c = 0; c < trk->n_channels; ++c) used |= 1ull << (planes ? planes[c] : 0u);
+    out->planes_used = uint32_t(__builtin_popcountll(used));
+    uint32_t n = 0;
+    const bool ok = trk_bank_samples_per_code(trk->fs, trk->nominal_code_rate > 0 ? trk->nominal_code_rate : CA_RATE,
+                                              trk->codes ? float(trk->code_len) : 1023.0f, n);
+    out->samples = n;
+    out->samples_per_lane = ok ? (n + 255u) / 256u : 0;
+    out->result_bytes = (uint64_t(max_epochs) * trk->n_channels * (sizeof(gm_trk_out) + 3) + 3) & ~uint64_t(3);
+    return GM_OK;
+}
+
+int gm_trk_set_channel_planes(gm_trk* t, const uint32_t* planes) {
+    if (!t) return set_err(GM_ERR_INVALID_ARG, "null handle");
+    for (uint32_t c = 0; planes && c < t->C; ++c)
+        if (planes[c] >= PLANE_RING_MAX_PLANES) return set_err(GM_ERR_OUT_OF_RANGE, "a plane index above 63: no plane ring has such a plane");
+    if (int rc = ensure_device(t->device)) return rc;
+    if (int rc = trk_planes_ensure(t)) return rc;
+    HIPC(hipEventSynchronize(t->planes_ev));                 // the previous install has read the staging words
+    for (uint32_t c = 0; c < t->C; ++c) t->planes_stage[c] = planes ? planes[c] : 0u;
+    HIPC(hipMemcpyAsync(t->d_planes, t->planes_stage, size_t(t->C) * 4, hipMemcpyHostToDevice, t->stream));      // stream-ordered: behind the launches enqueued so far
+    HIPC(hipEventRecord(t->planes_ev, t->stream));
+    t->h_planes.assign(t->planes_stage, t->planes_stage + t->C);
+    return GM_OK;
+}
+
+int gm_trk_get_channel_planes(gm_trk* t, uint32_t* planes) {
+    if (!t || !planes) return set_err(GM_ERR_INVALID_ARG, "null pointer");
+    for (uint32_t c = 0; c < t->C; ++c) planes[c] = t->h_planes.empty() ? 0u : t->h_planes[c];
+    return GM_OK;
+}
+
+int gm_trk_update_planes_dev(gm_trk* t, gm_plane_ring* pr, uint32_t epochs) {
+    if (int rc = trk_planes_call_rules(t, pr, epochs)) return rc;
+    return trk_launch_planes(t, pr, epochs);
+}
+
+int gm_trk_update_planes(gm_trk* t, gm_plane_ring* pr, uint32_t max_epochs, gm_trk_out* outs, uint8_t* processed, uint8_t* lost,
+                         uint32_t* epochs_done) {
+    if (int rc = trk_planes_call_rules(t, pr, max_epochs)) return rc;
+    if (int rc = trk_launch_planes(t, pr, max_epochs)) return rc;
+    // gm_trk_update_all's hand-over: [outs | processed | lost] into the pinned area in one copy behind the launch, one synchronisation
+    const size_t n = size_t(max_epochs) * t->C;
+    uint8_t* h_outs = t->h_res;
+    uint8_t* h_proc = h_outs + n * sizeof(gm_trk_out);
+    uint8_t* h_lost = h_proc + n;
+    if (outs) HIPC(hipMemcpyAsync(h_outs, t->d_res, n * (sizeof(gm_trk_out) + 2), hipMemcpyDeviceToHost, t->stream));
+    else HIPC(hipMemcpyAsync(h_proc, t->d_proc, 2 * n, hipMemcpyDeviceToHost, t->stream));
+    HIPC(hipStreamSynchronize(t->stream));
+    if (outs) memcpy(outs, h_outs, n * sizeof(gm_trk_out));
+    if (processed) memcpy(processed, h_proc, n);
+    if (lost) memcpy(lost, h_lost, n);
+    if (epochs_done) *epochs_done = trk_epochs_done(h_proc, max_epochs, t->C);
     return GM_OK;
 }
 

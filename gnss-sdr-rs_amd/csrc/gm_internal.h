@@ -356,6 +356,25 @@ struct TrkArrayArgs {
 void launch_trk_array(hipStream_t, const TrkDevCfg&, const int8_t* d_codes, const TrkArrayArgs&, int n_records, uint32_t max_slices,
                       gm_c32* d_z, uint8_t* d_done);
 
+// gm_plane_ring_write_dev and gm_trk_update_planes (trk_planes.hip, a section of trk_kernels.hip).  The host has checked every limit
+// (gm_plane_ring_plan, gm_trk_planes_plan, the map against the ring) and every pointer.
+struct PlaneRingWriteArgs {
+    const cf* src; cf* ring;                 // plane p: src + p * in_stride -> ring + p * plane_size
+    uint64_t in_stride, plane_size;          // c32 words; plane_size a power of two
+    uint64_t start, n;                       // the write position masked with plane_size - 1; samples per plane, <= plane_size
+    uint32_t n_planes; int wide;             // wide: src 16-byte aligned and in_stride, n, start, plane_size even
+};
+void launch_plane_ring_write(hipStream_t, const PlaneRingWriteArgs&);
+struct TrkPlanesArgs {
+    TrkDevCfg cfg;
+    const int8_t* codes; gm_trk_state* states;
+    const uint32_t* map;                     // [n_channels] plane of channel c, each below n_planes
+    const cf* ring; uint64_t plane_size, mask, head;   // [n_planes][plane_size]; mask = plane_size - 1; the enqueued head
+    uint32_t n_planes; int epochs;
+    gm_trk_out* outs; uint8_t *processed, *lost, *lost_prn;   // [epochs][n_channels] (may be null)
+};
+void launch_trk_planes(hipStream_t, const TrkPlanesArgs&);
+
 // ---------------------------------------------------------------- digital front-end (fe_kernels.hip)
 struct FeState { float phase_accumulator; float bias_re[8]; float bias_im[8]; };   // NcoLut.phase_accumulator, DcRemoverSimd.bias_*
 struct FrontendArgs {

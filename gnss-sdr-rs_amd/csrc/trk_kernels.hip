@@ -1707,4 +1707,7 @@ void launch_trk_debug_math(hipStream_t st, int op, const float* d_x, uint32_t n,
 // ---- gm_trk_array_prompts: per-antenna prompts of an array stream at tracked states, a section of its own like the bank ------------------
 #include "trk_array.hip"
 
+// ---- gm_plane_ring's copy kernel and gm_trk_update_planes: tracking with channel c on plane planes[c], a section of its own like the two above
+#include "trk_planes.hip"
+
 }  // namespace gm

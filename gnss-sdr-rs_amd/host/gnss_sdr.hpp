@@ -315,6 +315,34 @@ public:
     }
 };
 
+// ---- gm_plane_ring: n_planes rings on one time axis with one head, written from device memory (what Beamformer / Lcmv / Channelizer
+// process_dev leave in their planes) and read by TrackingManager::update_planes, channel c on plane planes[c]
+class PlaneRing {
+    gm_plane_ring* h_ = nullptr;
+public:
+    PlaneRing(uint32_t n_planes, uint64_t plane_size) { check(gm_plane_ring_create(n_planes, plane_size, &h_), "PlaneRing::new"); }
+    ~PlaneRing() { gm_plane_ring_destroy(h_); }
+    PlaneRing(const PlaneRing&) = delete;
+    gm_plane_ring* handle() const { return h_; }
+    // gm_plane_ring_plan (host only): the rules of the shape -> the bytes of the one allocation
+    static uint64_t plan(uint32_t n_planes, uint64_t plane_size) { uint64_t b = 0; check(gm_plane_ring_plan(n_planes, plane_size, &b), "PlaneRing::plan"); return b; }
+    uint32_t n_planes() const { uint32_t p = 0; check(gm_plane_ring_info(h_, &p, nullptr, nullptr, nullptr), "PlaneRing::n_planes"); return p; }
+    uint64_t plane_size() const { uint64_t s = 0; check(gm_plane_ring_info(h_, nullptr, &s, nullptr, nullptr), "PlaneRing::plane_size"); return s; }
+    void* device_base() const { void* d = nullptr; check(gm_plane_ring_info(h_, nullptr, nullptr, nullptr, &d), "PlaneRing::device_base"); return d; }
+    // n samples to every plane from device memory (plane p's at d_planes + p * in_stride words): one copy launch on `stream` (null: the
+    // ring's own), no host synchronisation
+    void write_dev(const void* d_planes, size_t in_stride, size_t n, void* stream = nullptr) {
+        check(gm_plane_ring_write_dev(h_, d_planes, in_stride, n, stream), "PlaneRing::write_dev");
+    }
+    // the synchronous form from a host buffer of the same layout
+    void write(const Complex32* planes, size_t in_stride, size_t n) { check(gm_plane_ring_write(h_, reinterpret_cast<const gm_c32*>(planes), in_stride, n), "PlaneRing::write"); }
+    uint64_t get_head() const { uint64_t h = 0; check(gm_plane_ring_get_head(h_, &h), "PlaneRing::get_head"); return h; }
+    void copy_to_slice(uint32_t plane, uint64_t start, std::vector<Complex32>& dest) const {
+        check(gm_plane_ring_copy_to_slice(h_, plane, start, reinterpret_cast<gm_c32*>(dest.data()), dest.size()), "PlaneRing::copy_to_slice");
+    }
+    void synchronize() { check(gm_plane_ring_synchronize(h_), "PlaneRing::synchronize"); }
+};
+
 // ---- rate conversion and pulse blanking (gm_resampler): the two stages rf/frontend.rs names in comments and leaves out.
 // fs_out = fs_in * up / down; every output is defined by absolute sample indices, so the words do not depend on the block cuts.
 class Resampler {
@@ -1034,6 +1062,35 @@ public:
         gm_trk_array_cfg c{}; c.n_antennas = n_antennas; c.taps = taps; c.tap_chips = tap_chips;
         gm_trk_array_plan_out p{};
         check(gm_trk_array_plan(&trk, &c, n_states, &p), "TrackingManager::array_plan");
+        return p;
+    }
+    // ---- tracking on planes: channel c on plane planes[c] of a PlaneRing (every other method ignores the map)
+    // gm_trk_set_channel_planes (empty: every channel on plane 0), installed stream-ordered on the handle's stream
+    void set_channel_planes(const std::vector<uint32_t>& planes = {}) {
+        if (!planes.empty() && planes.size() != n_) throw Panic(GM_ERR_INVALID_ARG, "set_channel_planes: n_channels entries");
+        check(gm_trk_set_channel_planes(h_, planes.empty() ? nullptr : planes.data()), "TrackingManager::set_channel_planes");
+    }
+    std::vector<uint32_t> channel_planes() const { std::vector<uint32_t> m(n_); check(gm_trk_get_channel_planes(h_, m.data()), "channel_planes"); return m; }
+    // process_channels on the plane ring, gated on its ENQUEUED head; returns the passes in which a channel ran
+    uint32_t update_planes(PlaneRing& ring, uint32_t max_epochs, std::vector<CorrelatorOut>* outs = nullptr,
+                           std::vector<uint8_t>* processed = nullptr, std::vector<uint8_t>* lost = nullptr) {
+        const size_t n = size_t(max_epochs) * n_;
+        if (outs) outs->resize(n);
+        if (processed) processed->resize(n);
+        if (lost) lost->resize(n);
+        uint32_t done = 0;
+        check(gm_trk_update_planes(h_, ring.handle(), max_epochs, outs ? outs->data() : nullptr, processed ? processed->data() : nullptr,
+                                   lost ? lost->data() : nullptr, &done), "TrackingManager::update_planes");
+        return done;
+    }
+    // the same passes enqueued only, no host readback
+    void update_planes_dev(PlaneRing& ring, uint32_t epochs) { check(gm_trk_update_planes_dev(h_, ring.handle(), epochs), "TrackingManager::update_planes_dev"); }
+    // gm_trk_planes_plan (host only): the argument rules and the sizes of an update_planes call; planes empty: every channel on plane 0
+    static gm_trk_planes_plan_out planes_plan(const gm_trk_cfg& trk, uint32_t n_planes, const std::vector<uint32_t>& planes = {},
+                                              uint32_t max_epochs = 1) {
+        if (!planes.empty() && planes.size() != trk.n_channels) throw Panic(GM_ERR_INVALID_ARG, "planes_plan: n_channels entries");
+        gm_trk_planes_plan_out p{};
+        check(gm_trk_planes_plan(&trk, n_planes, planes.empty() ? nullptr : planes.data(), max_epochs, &p), "TrackingManager::planes_plan");
         return p;
     }
 private:

@@ -86,6 +86,90 @@ class MulticastRingBuffer:
         return d
 
 
+def plane_ring_plan(n_planes, plane_size):
+    """gm_plane_ring_plan (host only, no device): the rules of PlaneRing's shape -> the bytes of its one allocation.  Raises GmError
+    where the library refuses."""
+    b = C.c_uint64(0)
+    check(lib().gm_plane_ring_plan(int(n_planes), int(plane_size), C.byref(b)), "gm_plane_ring_plan")
+    return b.value
+
+
+class PlaneRing:
+    """gm_plane_ring: n_planes rings of plane_size c32 samples on one time axis with one head, written from device memory — what
+    Beamformer / Lcmv / Channelizer process_dev leave in their planes — and read by TrackingManager.update_planes."""
+
+    def __init__(self, n_planes, plane_size, device=None):
+        _lib.init(device if device is not None else (_lib._initialised or 0))
+        h = C.c_void_p()
+        check(lib().gm_plane_ring_create(int(n_planes), int(plane_size), C.byref(h)), "gm_plane_ring_create")
+        self._h, self.n_planes, self.plane_size = h, int(n_planes), int(plane_size)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gm_plane_ring_destroy(self._h)
+            self._h = None
+
+    def __del__(self):      # (at interpreter shutdown the module globals close() uses may be gone already)
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """-> dict(n_planes, plane_size, bytes, d_base): d_base is the device address of plane 0"""
+        p, s, b, d = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_void_p()
+        check(lib().gm_plane_ring_info(self._h, C.byref(p), C.byref(s), C.byref(b), C.byref(d)), "gm_plane_ring_info")
+        return dict(n_planes=p.value, plane_size=s.value, bytes=b.value, d_base=d.value or 0)
+
+    def write_dev(self, planes_ptr, in_stride, n, stream=None):
+        """append n samples to every plane from device memory: plane p's at planes_ptr + p * in_stride complex64 words; one copy
+        launch on `stream` (None: the ring's own), no host synchronisation"""
+        check(lib().gm_plane_ring_write_dev(self._h, C.c_void_p(planes_ptr), int(in_stride), int(n), C.c_void_p(stream)),
+              "gm_plane_ring_write_dev")
+
+    def write(self, planes):
+        """the synchronous form from a host array [n_planes, n] (its row stride is in_stride)"""
+        s = np.ascontiguousarray(planes, np.complex64)
+        if s.ndim != 2 or s.shape[0] != self.n_planes:
+            raise ValueError("planes must be [n_planes, n]")
+        check(lib().gm_plane_ring_write(self._h, _p(s), s.shape[1], s.shape[1]), "gm_plane_ring_write")
+
+    def get_head(self):
+        """samples per plane whose writes have been enqueued"""
+        h = C.c_uint64(0)
+        check(lib().gm_plane_ring_get_head(self._h, C.byref(h)), "gm_plane_ring_get_head")
+        return h.value
+
+    def copy_to_slice(self, plane, start, n):
+        d = np.zeros(int(n), np.complex64)
+        check(lib().gm_plane_ring_copy_to_slice(self._h, int(plane), int(start), _p(d), int(n)), "gm_plane_ring_copy_to_slice")
+        return d
+
+    def synchronize(self):
+        check(lib().gm_plane_ring_synchronize(self._h), "gm_plane_ring_synchronize")
+
+
+def planes_plan(fs, n_channels, n_planes, planes=None, max_epochs=1, n_arms=3, code_rate=0.0, code_len=0, strict_sum_order=False):
+    """gm_trk_planes_plan (host only, no device): the argument rules of tracking on planes and the sizes of a call ->
+    dict(workgroups, threads, chip_row_bytes, planes_used, samples, samples_per_lane, result_bytes).  planes: the map [n_channels] or
+    None (every channel on plane 0).  code_rate 0: 1.023e6; code_len 0: the C/A code's 1023, else the chips per period of a custom
+    table.  Raises GmError where the library refuses."""
+    trk = TrkCfg()
+    trk.fs, trk.n_channels, trk.n_arms, trk.nominal_code_rate = fs, int(n_channels), int(n_arms), code_rate
+    trk.strict_sum_order = int(strict_sum_order)
+    dummy = np.ones(max(int(code_len), 1), np.int8)
+    if code_len:
+        trk.codes, trk.n_codes, trk.code_len = dummy.ctypes.data, 1, int(code_len)
+    m = None if planes is None else np.ascontiguousarray(planes, np.uint32)
+    if m is not None and m.size != int(n_channels):
+        raise ValueError("planes must have n_channels entries")
+    out = _lib.TrkPlanesPlanOut()
+    check(lib().gm_trk_planes_plan(C.byref(trk), int(n_planes), _p(m) if m is not None else None, int(max_epochs), C.byref(out)),
+          "gm_trk_planes_plan")
+    del dummy
+    return out.as_dict()
+
+
 def _out_tuple(o, arms=3):
     t = (o.ip, o.qp, o.ie, o.qe, o.il, o.ql)
     return t + (o.ive, o.qve, o.ivl, o.qvl) if arms == 5 else t
@@ -284,6 +368,36 @@ class TrackingManager:
                                              None if arr is None else C.cast(arr, C.c_void_p), R, C.byref(cfg), C.c_void_p(d_z),
                                              C.c_void_p(d_done), C.c_void_p(stream)),
               "gm_trk_array_prompts_dev")
+
+    def set_channel_planes(self, planes=None):
+        """gm_trk_set_channel_planes: channel c reads plane planes[c] in update_planes (None: every channel on plane 0); installed
+        stream-ordered on the handle's stream.  Every other entry ignores the map."""
+        m = None if planes is None else np.ascontiguousarray(planes, np.uint32)
+        if m is not None and m.size != self.n_channels:
+            raise ValueError("planes must have n_channels entries")
+        check(lib().gm_trk_set_channel_planes(self._h, _p(m) if m is not None else None), "gm_trk_set_channel_planes")
+
+    def channel_planes(self):
+        m = np.zeros(self.n_channels, np.uint32)
+        check(lib().gm_trk_get_channel_planes(self._h, _p(m)), "gm_trk_get_channel_planes")
+        return [int(v) for v in m]
+
+    def update_planes(self, plane_ring, max_epochs=1):
+        """update_all on a PlaneRing, channel c on plane channel_planes()[c], gated on the ring's enqueued head
+        -> (outs [E][C][2*arms] f32, processed [E][C] u8, lost [E][C] u8, epochs_done)"""
+        E, Cn = int(max_epochs), self.n_channels
+        outs = (TrkOut * max(E * Cn, 1))()
+        proc = np.zeros((max(E, 0), Cn), np.uint8)
+        lost = np.zeros((max(E, 0), Cn), np.uint8)
+        done = C.c_uint32(0)
+        check(lib().gm_trk_update_planes(self._h, plane_ring._h, E, C.cast(outs, C.c_void_p), _p(proc), _p(lost), C.byref(done)),
+              "gm_trk_update_planes")
+        o = np.frombuffer(outs, np.float32).reshape(E, Cn, 10)[:, :, :2 * self.n_arms].copy()
+        return o, proc, lost, done.value
+
+    def update_planes_dev(self, plane_ring, epochs):
+        """enqueue `epochs` passes on the PlaneRing, no host readback"""
+        check(lib().gm_trk_update_planes_dev(self._h, plane_ring._h, int(epochs)), "gm_trk_update_planes_dev")
 
     def update_all_dev(self, ring, epochs):
         check(lib().gm_trk_update_all_dev(self._h, ring._h, int(epochs)), "gm_trk_update_all_dev")

@@ -1240,7 +1240,7 @@ int gm_ddc_write_ring(gm_ddc *d, gm_excisor *x, gm_resampler *r, gm_ring *ring, 
  *     4096 samples (tile = min((4096 - L) / D + 1, 1024), rounded down to 512 or 256 above those), is read, converted and blanked once
  *     into a padded LDS image; a lane owns an output time, keeps the M branch sums in registers, transforms them there and stores the
  *     listed bins, so consecutive lanes store consecutive words of a plane.
- * Zeros in the filter fields mean defaults.  Not built: ring writers (C planes would need C rings), synthesis (the inverse bank).
+ * Zeros in the filter fields mean defaults.  Not built: synthesis (the inverse bank).  (The C planes go into a plane ring: "Plane ring" and "Tracking on planes" below.)
  * (ABI 9, additive: a caller detects the feature by the symbol) */
 typedef struct {
     uint32_t n_channels;      /* M: 4, 8, 16, 32 or 64 */
@@ -1575,7 +1575,7 @@ int gm_beamformer_process(gm_beamformer *h, const void *in, int fmt, size_t n_in
  *     rows of all beams riding below the matrix; then per beam, eight beams a round, the small Gram matrix (in the LDS words R leaves
  *     once it has gone to the capture), its Cholesky factor with f^H riding below it, and the two substitutions; gm_beamformer's
  *     output pass; gm_stap's state kernel.
- * Not built: a _dev form of gm_lcmv_set_constraints; choosing which cells are spoofers, or any other decision; ring writers; wiring
+ * Not built: a _dev form of gm_lcmv_set_constraints; choosing which cells are spoofers, or any other decision (the beams go into a plane ring: "Plane ring" below); wiring
  * into receiver_harness.cpp or bench.py; inequality or derivative constraints.
  * (ABI 9, additive: a caller detects the feature by the symbol) */
 typedef struct {
@@ -1919,6 +1919,102 @@ int gm_trk_array_prompts(gm_trk *t, const void *d_samples, int fmt, uint64_t fir
 int gm_trk_array_prompts_dev(gm_trk *t, const void *d_samples, int fmt, uint64_t first_index, uint64_t n_time,
                              const gm_trk_state *states, uint32_t n_states, const gm_trk_array_cfg *cfg,
                              void *d_z /* [n_states][L][A] c32, device */, void *d_done /* [n_states] u8, device */, void *stream);
+
+/* ------------------------------------------------------------------ Plane ring (additive, ABI 9)
+ * P rings of c32 on ONE time axis with ONE head, written from DEVICE memory: what a stage that ends in planes [P][out_stride]
+ * leaves (gm_beamformer_process_dev and gm_lcmv_process_dev: one beam per plane; gm_channelizer_process_dev: one sub-band per plane) goes
+ * into it with one launch, and "Tracking on planes" below reads it, channel c on plane planes[c].  Sample i of plane p is word
+ * p * plane_size + (i & (plane_size - 1)) of one allocation [P][plane_size], zeroed at create.
+ *
+ * gm_plane_ring_plan (host only, no device) holds the rules of create: n_planes in 1 .. 64, plane_size a power of two (at least 1),
+ * n_planes * plane_size * 8 at most 2^34 bytes: GM_ERR_OUT_OF_RANGE otherwise, *bytes (may be NULL) untouched; *bytes = the allocation.
+ * gm_plane_ring_create waits for the fill before it returns, for gm_ring_create's reason (its writers work on non-blocking streams).
+ *
+ * gm_plane_ring_write_dev appends n samples to EVERY plane: plane p's come from d_planes + p * in_stride (c32 words), the layout and the
+ * *n_out the three stage entries above leave.  One launch of the library's own copy kernel (the wrap is handled inside it; 16-byte
+ * accesses when d_planes is 16-byte aligned and in_stride, n, the write position and plane_size are even, else 8-byte ones), on `stream`
+ * (NULL: the ring's own non-blocking stream), NO host synchronisation.  n = 0: GM_OK, nothing launched.  Refused before anything runs,
+ * the head and the ring untouched: a null ring or d_planes: GM_ERR_INVALID_ARG; n > plane_size, in_stride < n, a source range
+ * [d_planes, d_planes + (n_planes - 1) * in_stride + n) that overlaps the ring: GM_ERR_OUT_OF_RANGE.
+ * gm_plane_ring_write is the synchronous form from a host buffer of the same layout (same refusals but the overlap).
+ * There is ONE head (gm_plane_ring_get_head): the samples per plane whose writes have been ENQUEUED, not those that have landed.
+ * gm_plane_ring_copy_to_slice orders itself behind the enqueued writes, copies n samples of `plane` from absolute index start (across
+ * the wrap too) and synchronises; it refuses what gm_ring_copy_to_slice refuses (a null pointer: GM_ERR_INVALID_ARG; n > plane_size:
+ * GM_ERR_OUT_OF_RANGE) and plane >= n_planes (GM_ERR_OUT_OF_RANGE).  gm_plane_ring_synchronize waits for every write and every reader
+ * the library has enqueued on the ring.
+ *
+ * ORDERING, all on the device; ONE writer (one host thread at a time calls the write entries).  Every write records an event behind
+ * itself; when the writer's stream changes between calls the new stream first waits for that event; every reader the library launches
+ * on the ring (the tracking launches below, gm_plane_ring_copy_to_slice) waits for that event and then uses the enqueued head; every
+ * tracking launch records an event of its own on the ring (one per reader stream), and the next write waits for all of them — a write
+ * that wraps can never land on samples an earlier tracking launch is still reading.  What the library does NOT order: the producer of
+ * d_planes (run it on `stream`, or make `stream` wait for it), and readers of the caller's own. */
+typedef struct gm_plane_ring gm_plane_ring;
+int gm_plane_ring_plan(uint32_t n_planes, uint64_t plane_size, uint64_t *bytes);
+int gm_plane_ring_create(uint32_t n_planes, uint64_t plane_size, gm_plane_ring **out);
+int gm_plane_ring_destroy(gm_plane_ring *pr);
+/* any output may be NULL; *d_base = the device address of plane 0 (plane p at d_base + p * plane_size words) */
+int gm_plane_ring_info(gm_plane_ring *pr, uint32_t *n_planes, uint64_t *plane_size, uint64_t *bytes, void **d_base);
+int gm_plane_ring_write_dev(gm_plane_ring *pr, const void *d_planes, size_t in_stride, size_t n, void *stream);
+int gm_plane_ring_write(gm_plane_ring *pr, const gm_c32 *planes, size_t in_stride, size_t n);
+int gm_plane_ring_get_head(gm_plane_ring *pr, uint64_t *head);
+int gm_plane_ring_copy_to_slice(gm_plane_ring *pr, uint32_t plane, uint64_t start, gm_c32 *dest, size_t n);
+int gm_plane_ring_synchronize(gm_plane_ring *pr);
+
+/* ------------------------------------------------------------------ Tracking on planes (additive, ABI 9)
+ * gm_trk_update_all on a plane ring: channel c runs update() (do_tracking.rs:160-180) against plane planes[c] of the ring — satellite p
+ * tracked on beam p, a GLONASS satellite on its sub-band — without a copy through the host.  The contract of gm_trk_update_planes is
+ * gm_trk_update_all's, argument for argument (outs / processed / lost: [max_epochs][n_channels], each may be NULL; *epochs_done = the
+ * passes in which at least one channel ran); the data gate of every pass is (int64)(head - (next_sample_index + n)) >= 0 with
+ * n = round(fs / (code_rate / code_len)) and head the plane ring's ENQUEUED head, behind whose writes the launch is ordered on the
+ * device; the results land in one pinned area, with one synchronisation.  gm_trk_update_planes_dev enqueues the passes only.
+ *
+ * The map (gm_trk_set_channel_planes; planes NULL: every channel on plane 0, which is also a new handle's map) is handle state,
+ * installed stream-ordered on the handle's stream; gm_trk_get_channel_planes returns it.  EVERY OTHER ENTRY IGNORES IT: gm_trk_update_all
+ * and its kin run the persistent kernel on a gm_ring exactly as before, word for word.
+ *
+ * The kernel (csrc/trk_planes.hip): one 256-lane workgroup per channel, no communication between workgroups, no spin wait, no atomics.
+ * It loads the channel's state and chip row once, then per pass takes the gate, forms every per-sample product with the code of
+ * gm_trk_correlate (the f64-reduced sine and cosine, glibc's on a strict_libm handle; the exact fast forms of the division by fs and of the
+ * code phase where the epoch allows them), sums as a FIXED TREE — lane j its samples j, j + 256, ... in ascending order, the 64 lanes of a
+ * wave by the butterfly v += v[lane xor d], d = 32, 16, 8, 4, 2, 1, the four waves in ascending order ((w0 + w1) + w2) + w3 — runs the
+ * scalar epilogue of gm_trk_do_work on one lane (lock test, atan PLL, envelope DLL, loop filters, loss of lock and reset), writes the
+ * pass's outs / processed / lost and goes on with the state on chip; the state is stored once, after the last pass.  A channel that is
+ * inactive, whose code row is outside the table, whose n is 0 or >= 2^31 or whose gate fails writes processed = 0 and zeros for that pass.
+ * Like the tracker and UNLIKE gm_trk_bank it makes no "already overwritten" test: keep plane_size above the samples a channel may lag.
+ * A channel's words are a function of its state and its plane's samples ALONE: not of the other channels, the map, the number of planes,
+ * where in the ring the epoch lies, repetition, or how a run of E passes is cut into calls.  The sums agree with gm_trk_update_all's
+ * (another tree) within the tracking tolerance of 1e-5 of the envelope, not bit for bit.
+ * The launches join the device's chain of tracking launches as the strict_sum_order path does: they wait for the device's previous
+ * tracking launch and record behind themselves, so a persistent grid of another handle finds all its places free.
+ *
+ * Refused before anything runs, state, outputs and head untouched (gm_trk_planes_plan holds the rules that need no handle; the device
+ * entries call the same code): a null handle, ring or trk cfg: GM_ERR_INVALID_ARG; a ring on another device: GM_ERR_INVALID_ARG;
+ * max_epochs 0: GM_ERR_INVALID_ARG (gm_trk_update_all's answer), above 4095: GM_ERR_OUT_OF_RANGE; n_planes outside 1 .. 64:
+ * GM_ERR_OUT_OF_RANGE; a map entry at or above the ring's n_planes: GM_ERR_OUT_OF_RANGE, the message names the channel; a custom code of
+ * more than 16384 chips: GM_ERR_OUT_OF_RANGE; a strict_sum_order handle: GM_ERR_INVALID_ARG — THE SEQUENTIAL-SUM PARITY PATH ON PLANES IS NOT
+ * BUILT, and ignoring the switch would break that handle's bit-for-bit promise.  strict_libm, both code-index modes, boc11, three and
+ * five arms and custom codes all work.
+ * Out of scope: a ticketed (_async / collect) form; strict_sum_order; stage entries that write a plane ring by themselves; gm_trk_bank and
+ * gm_trk_array_prompts on a plane ring; int8 planes; a loop that re-steers by itself. */
+typedef struct {
+    uint32_t workgroups;           /* one per channel: n_channels */
+    uint32_t threads;              /* 256 */
+    uint32_t chip_row_bytes;       /* the workgroup's dynamic LDS: code_len int8 chips (no codes: 1023) */
+    uint32_t planes_used;          /* distinct planes the map names */
+    uint64_t samples;              /* n for gm_trk_cfg.nominal_code_rate (0 -> 1.023e6) and code_len */
+    uint32_t samples_per_lane;     /* ceil(n / 256); 0 where a channel with this n would not run */
+    uint32_t reserved;             /* 0 */
+    uint64_t result_bytes;         /* the call's device result block: max_epochs * n_channels * 43 bytes, rounded up to 4 */
+} gm_trk_planes_plan_out;          /* 40 bytes */
+/* host only, no device.  Of `trk` it reads fs, n_channels, n_arms, codes / n_codes / code_len, nominal_code_rate and strict_sum_order.
+ * planes: [n_channels] or NULL (all 0).  out may be NULL; a refusal leaves it untouched. */
+int gm_trk_planes_plan(const gm_trk_cfg *trk, uint32_t n_planes, const uint32_t *planes, uint32_t max_epochs, gm_trk_planes_plan_out *out);
+int gm_trk_set_channel_planes(gm_trk *t, const uint32_t *planes /* [n_channels], NULL: all 0 */);
+int gm_trk_get_channel_planes(gm_trk *t, uint32_t *planes /* [n_channels] */);
+int gm_trk_update_planes(gm_trk *t, gm_plane_ring *pr, uint32_t max_epochs, gm_trk_out *outs, uint8_t *processed, uint8_t *lost,
+                         uint32_t *epochs_done);
+int gm_trk_update_planes_dev(gm_trk *t, gm_plane_ring *pr, uint32_t epochs);
 
 /* ------------------------------------------------------------------ Bit sync + nav-bit accumulation
  * src/decoding.rs:8,40-227 (legacy file outside the reference's module tree): 20-bin histogram of prompt-I sign

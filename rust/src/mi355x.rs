@@ -178,7 +178,19 @@ pub struct GmTrkArrayPlanOut {      // gm_trk_array_plan_out (32 bytes)
     pub slices: u32,                 // ceil(n / 4096)
 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
-pub struct GmDdcCfg {               // gm_ddc_cfg (40 bytes; zeros in the filter fields: the defaults)
+pub struct GmTrkPlanesPlanOut {     // gm_trk_planes_plan_out (40 bytes)
+    pub workgroups: u32,             // one per channel: n_channels
+    pub threads: u32,                // 256
+    pub chip_row_bytes: u32,         // the workgroup's dynamic LDS: code_len int8 chips
+    pub planes_used: u32,            // distinct planes the map names
+    pub samples: u64,                // n for the configuration's nominal code rate
+    pub samples_per_lane: u32,       // ceil(n / 256)
+    pub reserved: u32,               // 0
+    pub result_bytes: u64,           // max_epochs * n_channels * 43, rounded up to 4
+}
+pub enum GmPlaneRing {}
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct GmDdcCfg {             // gm_ddc_cfg (40 bytes; zeros in the filter fields: the defaults)
     pub mix_cycles_per_sample: f64,  // f_mix / fs_in: the frequency brought to 0, cycles per input sample; any finite value
     pub up: u32, pub down: u32,      // as GmResamplerCfg, field by field
     pub taps: u32,
@@ -531,6 +543,26 @@ extern "C" {
     pub fn gm_trk_array_prompts_dev(t: *mut GmTrk, d_samples: *const c_void, fmt: c_int, first_index: u64, n_time: u64,
                                     states: *const GmTrkState, n_states: u32, cfg: *const GmTrkArrayCfg, d_z: *mut c_void,
                                     d_done: *mut c_void, stream: *mut c_void) -> c_int;
+    // plane ring (additive entries, ABI stays 9; bindings only): n_planes rings of c32 on one time axis with one head, written from
+    // device memory (plane p's samples at d_planes + p * in_stride words: what gm_beamformer / gm_lcmv / gm_channelizer process_dev
+    // leave), ordered on the device against its readers; plan is host only
+    pub fn gm_plane_ring_plan(n_planes: u32, plane_size: u64, bytes: *mut u64) -> c_int;
+    pub fn gm_plane_ring_create(n_planes: u32, plane_size: u64, out: *mut *mut GmPlaneRing) -> c_int;
+    pub fn gm_plane_ring_destroy(pr: *mut GmPlaneRing) -> c_int;
+    pub fn gm_plane_ring_info(pr: *mut GmPlaneRing, n_planes: *mut u32, plane_size: *mut u64, bytes: *mut u64, d_base: *mut *mut c_void) -> c_int;
+    pub fn gm_plane_ring_write_dev(pr: *mut GmPlaneRing, d_planes: *const c_void, in_stride: usize, n: usize, stream: *mut c_void) -> c_int;
+    pub fn gm_plane_ring_write(pr: *mut GmPlaneRing, planes: *const Complex32, in_stride: usize, n: usize) -> c_int;
+    pub fn gm_plane_ring_get_head(pr: *mut GmPlaneRing, head: *mut u64) -> c_int;
+    pub fn gm_plane_ring_copy_to_slice(pr: *mut GmPlaneRing, plane: u32, start: u64, dest: *mut Complex32, n: usize) -> c_int;
+    pub fn gm_plane_ring_synchronize(pr: *mut GmPlaneRing) -> c_int;
+    // tracking on planes: gm_trk_update_all's contract on a plane ring, channel c on plane planes[c] (null: all 0); every other entry
+    // ignores the map; a strict_sum_order handle is refused; plan is host only
+    pub fn gm_trk_planes_plan(trk: *const GmTrkCfg, n_planes: u32, planes: *const u32, max_epochs: u32, out: *mut GmTrkPlanesPlanOut) -> c_int;
+    pub fn gm_trk_set_channel_planes(t: *mut GmTrk, planes: *const u32) -> c_int;
+    pub fn gm_trk_get_channel_planes(t: *mut GmTrk, planes: *mut u32) -> c_int;
+    pub fn gm_trk_update_planes(t: *mut GmTrk, pr: *mut GmPlaneRing, max_epochs: u32, outs: *mut GmTrkOut, processed: *mut u8,
+                                lost: *mut u8, epochs_done: *mut u32) -> c_int;
+    pub fn gm_trk_update_planes_dev(t: *mut GmTrk, pr: *mut GmPlaneRing, epochs: u32) -> c_int;
     // fft.rs:5-56
     pub fn gm_fft_c2c_f32(n: usize, dir: c_int, inout: *mut Complex32, batch: usize) -> c_int;
     pub fn gm_fft_power_spectrum_f32(n: usize, inout: *mut Complex32, power: *mut f32) -> c_int;
