@@ -15,6 +15,34 @@ as_c128 = NM.as_c128
 to_f32 = NM.to_f32
 
 
+# ---- what the GPU tests draw and hold (tests/test_gpu_stap.py and the files that share its stream) -----------------------------------
+BAR_R, BAR_W, BAR_Y = 1e-5, 2.0 ** -22, 1e-5          # the three bars of test_gpu_stap.py's docstring
+
+
+def stream(fmt, n, A, seed):
+    """[n, A] complex64 or [n, A, 2] int8: unit noise (int8: 1.2 LSB), a rank-one white jammer 30 dB above it and a CW 30 dB above it
+    from another direction"""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, A)) + 1j * rng.standard_normal((n, A))
+    jam = 10.0 ** 1.5 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    x = x + jam[:, None] * np.exp(2j * np.pi * rng.random(A))[None, :]
+    cw = np.sqrt(2.0) * 10.0 ** 1.5 * np.exp(2j * np.pi * (0.0617 * np.arange(n) + rng.random()))
+    x = x + cw[:, None] * np.exp(2j * np.pi * rng.random(A))[None, :]
+    if fmt == "i8":
+        v = 1.2 * x
+        q = np.stack([np.clip(np.rint(v.real), -128, 127), np.clip(np.rint(v.imag), -128, 127)], axis=-1).astype(np.int8)
+        if n > 2:
+            q[n // 3, A - 1] = (-128, 127)
+            q[n // 2, 0] = (-128, -128)
+        return q
+    return x.astype(np.complex64)
+
+
+def derived_R(B, L):
+    """the derived bound on R's error, as a fraction of sum_t |z_p| |z_q|"""
+    return np.sqrt(2.0) * (min(B, 1024) / 32 + 6 + B / 1024 + 2 * (L - 1)) * 2.0 ** -24
+
+
 def resolve(n_antennas, taps, block=0, loading=0.0, steering=None, reserved=0):
     """the argument rules and defaults -> dict(A, L, M, B, loading (the float32 word, widened), s [M] complex128 laid out [L][A]), or
     None where refused"""

@@ -9,8 +9,10 @@ Stap handles; two shapes also go against the float64 model (beam_model.py = stap
 so that the file does not rest on gm_stap alone.  The input is test_gpu_stap.py's: noise plus a rank-one white jammer and a CW 30 dB up;
 the int8 stream holds -128.
 
-1. Shapes (A, L, B, P): one chunk, two chunks and two groups of 1024; P below, at and one past a group of four and two substitution
-   rounds; M = 32 with P = 16.  Both formats, loading 1e-4 and 1e-2, random complex rows and an e_0 row.
+1. Shapes (A, L, B, P): the twelve of SHAPES (every A, but not every <A, NL>: <3, 1>, <5, 1> and <6, 1> are not among them): one
+   chunk, two chunks and two groups of 1024; P below, at and one past a group of four and two substitution rounds; M = 32 with
+   P = 16.  Both formats, loading 1e-4 and 1e-2, random complex rows and an e_0 row.  Every (A, L) the stage accepts runs at B = 256
+   and P = 5, each beam against the model, in tests/test_gpu_stage_instantiations.py.
 2. Cuts: calls of 1, 7, B - 1, 1000, 3001 against one call, bit for bit; again after a reset to 2^32 - 3; two runs give the same words.
 3. out_stride equal to the count, and larger with sentinel words between and behind the planes.
 4. A beam's words depend neither on P nor on the other rows.

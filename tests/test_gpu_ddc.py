@@ -19,14 +19,17 @@ import pytest
 
 import ddc_model as DM
 import resample_model as RM
+import stage_instantiations as SI
 
 pytestmark = pytest.mark.gpu
 INVALID, OUT_OF_RANGE = -1, -5
 
 # (up, down, taps, n_phases): 1/1 with 8 taps (the mix alone), 1/2 (up divides the phase count: no blend), 20460/40919 (blend), 3/8,
-# 1/16 at 256 taps (a tile of 240 outputs, a lane owns one), 2/1, and 16 phases in place of 256 with and without the blend
+# 1/16 at 256 taps (a tile of 240 outputs, a lane owns one), 2/1, and 16 phases in place of 256 with and without the blend; and the three
+# of stage_instantiations.py: the blend with a lane owning two outputs (3/16) and one (3/40 at 256 taps), and 4/25 (no blend, two
+# outputs): with them every <BLEND, OPL> runs
 CONFIGS = [(1, 1, 8, 0), (1, 2, 0, 0), (20460, 40919, 0, 0), (3, 8, 0, 0), (1, 16, 256, 0), (2, 1, 0, 0), (1, 2, 0, 16),
-           (20460, 40919, 32, 16)]
+           (20460, 40919, 32, 16)] + SI.DDC_ADDED
 MIXES = [0.0, 0.25, DM.MIX, -0.37, 1e-9]
 OFFSETS = [0, 1, 3, 15]
 
@@ -130,7 +133,8 @@ def test_words_against_the_model(gpu, hipbuf, config):
 SPLITS = (1, 7, None, 1000, 3001)          # None: T - 1
 
 
-@pytest.mark.parametrize("config,mix", [((1, 2, 0, 0), DM.MIX), ((20460, 40919, 0, 0), -0.37), ((3, 8, 0, 0), 0.25)])
+@pytest.mark.parametrize("config,mix", [((1, 2, 0, 0), DM.MIX), ((20460, 40919, 0, 0), -0.37), ((3, 8, 0, 0), 0.25),
+                                        (SI.RESAMPLE_BLEND_1, DM.MIX)])
 def test_the_words_do_not_depend_on_the_cuts(gpu, hipbuf, config, mix):
     d, p = _make(mix, config)
     twin, _ = _make(mix, config)

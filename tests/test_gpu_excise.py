@@ -3,14 +3,14 @@ excise_model.py, which is handed the library's own window words (gm_excisor_wind
 
 1. Words.  Per output |device - model| <= 1e-5 max|xb| over the two blocks the output comes from: the project's 1e-5 parity bar, taken
    relative to the transforms' INPUT scale — a transform's rounding error scales with its input, not with its possibly excised output.
-   B = 256, 1024, 2048, 4096, both sample formats (the int8 stream holds -128), call lengths 1, H - 1, H, H + 1, 3H - 1, 5B + 7 and 40 H,
+   B = 256, 512, 1024, 2048, 4096 (every plan), both sample formats (the int8 stream holds -128), call lengths 1, H - 1, H, H + 1, 3H - 1, 5B + 7 and 40 H,
    gains all one, random in [0, 1] and a 0/1 mask; a 60 dB-above-noise CW on and off a bin centre; a call of 2299 segments (tiles of two
    segments, the last tile short).  The largest error over bound seen is printed.
 2. Cutting: one call against the same stream in blocks of 1, 7, H - 1, 1000 and 3001, bit for bit; after reset; at absolute indices
    2^32 - 3 and 2^40 + 12345.
 3. Blanking: spikes on block edges (every segment is a tile edge at these lengths), in the history and across call boundaries; exactly
    at the threshold; the blanked count against the model.
-4. adapt: P against the model within 1e-5 max_k P_model[k]; the median word is the rank-(B - 1) div 2 element of the device's own P; the
+4. adapt, at every B: P against the model within 1e-5 max_k P_model[k]; the median word is the rank-(B - 1) div 2 element of the device's own P; the
    counts and the gains equal detect() on the device's P words; guard 0, 2, 16; a CW in bin 0 and bin B - 1 (the circular guard); two
    calls give the same words; adapt_dev followed by process_dev with no host call in between uses the new gains.
 5. Every refusal, with nothing written and the state untouched.
@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import excise_model as EM
+import stage_instantiations as SI
 
 pytestmark = pytest.mark.gpu
 INVALID, OUT_OF_RANGE = -1, -5
@@ -92,7 +93,7 @@ def _gain_sets(B, seed):
     return [("ones", np.ones(B, np.float32)), ("random", g), ("mask", (rng.random(B) > 0.3).astype(np.float32))]
 
 
-@pytest.mark.parametrize("block", [256, 1024, 2048, 4096])
+@pytest.mark.parametrize("block", SI.BLOCKS)
 def test_words_against_the_model(gpu, hipbuf, block):
     from gnss_sdr_rs_amd import excise
     ex = excise.Excisor(block)
@@ -183,7 +184,8 @@ def test_a_strong_cw_on_and_off_a_bin_centre(gpu, hipbuf, block, offset):
 SPLITS = (1, 7, None, 1000, 3001)          # None: H - 1
 
 
-@pytest.mark.parametrize("block,fmt,n", [(1024, "i8", 6007), (256, "c32", 6007), (2048, "c32", 9001), (4096, "i8", 12301)])
+@pytest.mark.parametrize("block,fmt,n", [(1024, "i8", 6007), (256, "c32", 6007), (2048, "c32", 9001), (4096, "i8", 12301),
+                                         (512, "i8", 6007), (512, "c32", 6007)])
 def test_the_words_do_not_depend_on_the_cuts(gpu, hipbuf, block, fmt, n):
     from gnss_sdr_rs_amd import excise
     B, H = block, block // 2
@@ -295,7 +297,7 @@ def _check_adapt(ex, p, x, wa, tag):
     return err, r
 
 
-@pytest.mark.parametrize("block", [256, 1024, 4096])
+@pytest.mark.parametrize("block", SI.BLOCKS)
 def test_adapt(gpu, hipbuf, block):
     from gnss_sdr_rs_amd import excise
     B, H = block, block // 2

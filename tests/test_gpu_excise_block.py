@@ -3,7 +3,8 @@
 The streams are 6007 to 12301 samples of noise plus a CW that moves five bins a block, so that every block gets a mask of its own.
 1. Masks.  The captured power words within 1e-5 max_k p[k] of the float64 model per block; the captured masks EQUAL, byte for byte, to
    the model's float32 rule applied to the device's own power words; block_stats equal to the counts from those masks under the
-   once-per-block rule.  B = 256, 1024, 4096, both formats, factor 16 and 6, guard 0, 2 and 16.
+   once-per-block rule.  B = 256, 512, 1024, 2048, 4096 (every plan: at 512 one wave holds every bin and every lane holds bins, at 2048
+   two of the four waves hold bins), both formats, factor 16 and 6, guard 0, 2 and 16 (4096: factor 16, guard 2).
 2. Outputs within the 1e-5 max|xb| bound of the float64 stream model, which is handed the library's windows, the static gains and the
    device's masks; one run with random static gains, so that both gains multiply.
 3. Independence: one call against blocks of 1, 7, H - 1, 1000 and 3001 bit for bit, counters included; after a reset to 2^32 - 3; twice.
@@ -20,6 +21,7 @@ import pytest
 
 import excise_block_model as BM
 import excise_model as EM
+import stage_instantiations as SI
 
 pytestmark = pytest.mark.gpu
 INVALID, OUT_OF_RANGE = -1, -5
@@ -91,7 +93,10 @@ def _one_case(ex, p, x, factor, guard, wa, ws, gains, tag):
     return perr, _check(tag, y, want, scale), M
 
 
-@pytest.mark.parametrize("block,n", [(256, 6007), (1024, 9001)])
+N_OF = {256: 6007, 512: 6007, 1024: 9001, 2048: 9001}
+
+
+@pytest.mark.parametrize("block,n", [(B, N_OF[B]) for B in SI.BLOCK_ADAPT_SWEPT])
 def test_masks_and_outputs_against_the_model(gpu, block, n):
     from gnss_sdr_rs_amd import excise
     B = block
@@ -126,21 +131,31 @@ def test_masks_and_outputs_against_the_model(gpu, block, n):
 
 
 def test_masks_and_outputs_at_4096(gpu):
+    _at_the_largest_block(4096, "i8")
+
+
+@pytest.mark.parametrize("block,fmt", SI.BLOCK_ADAPT_TOP)
+def test_masks_and_outputs_at_the_largest_block(gpu, block, fmt):
+    """both formats (the case above is the int8 one under its earlier name)"""
+    _at_the_largest_block(block, fmt)
+
+
+def _at_the_largest_block(B, fmt):
     from gnss_sdr_rs_amd import excise
-    B = 4096
     ex = excise.Excisor(B).set_block_adapt(guard_bins=2)
     wa, ws = ex.windows()
-    x = _moving("i8", 12301, B, 11)
-    perr, yerr, M = _one_case(ex, EM.resolve(B), x, 16.0, 2, wa, ws, None, B)
+    x = _moving(fmt, 12301, B, 11)
+    perr, yerr, M = _one_case(ex, EM.resolve(B), x, 16.0, 2, wa, ws, None, (B, fmt))
     assert ((M == 0).sum(axis=1) >= 1).all()
-    print("B = 4096: p error / bound %.3f, output error / bound %.3f" % (perr, yerr))
+    print("B = %d, %s: p error / bound %.3f, output error / bound %.3f" % (B, fmt, perr, yerr))
     ex.close()
 
 
 SPLITS = (1, 7, None, 1000, 3001)          # None: H - 1
 
 
-@pytest.mark.parametrize("block,fmt,n", [(1024, "i8", 6007), (256, "c32", 6007), (4096, "i8", 12301)])
+@pytest.mark.parametrize("block,fmt,n", [(1024, "i8", 6007), (256, "c32", 6007), (4096, "i8", 12301), (512, "i8", 6007),
+                                         (2048, "c32", 9001)])
 def test_the_words_and_counters_do_not_depend_on_the_cuts(gpu, hipbuf, block, fmt, n):
     from gnss_sdr_rs_amd import excise
     B, H = block, block // 2

@@ -10,7 +10,10 @@ to its own bar as test_gpu_stap.py does:
   Q = 1, f = 1 against a Beamformer's w:                         |dw[j]|    <= 2^-22 max_j |w[j]|
 
 The input is test_gpu_stap.py's: noise plus a rank-one white jammer and a CW 30 dB up, in both formats; the int8 stream holds -128.  The
-constraint rows and responses are lcmv_model.draw's (test_lcmv_host.py checks that the seeds used here need no redraw)."""
+constraint rows and responses are lcmv_model.draw's (test_lcmv_host.py checks that the seeds used here need no redraw).
+
+The shapes are lcmv_model.CASES: A = 2, 3, 4 and 8 only, so six of the twelve <A, NL> of lcmv_kernel.  Every (A, L) the stage accepts runs
+at B = 256 with three beams, through this file's _check, in tests/test_gpu_stage_instantiations.py."""
 import ctypes as C
 
 import numpy as np

@@ -17,14 +17,17 @@ import numpy as np
 import pytest
 
 import resample_model as RM
+import stage_instantiations as SI
 
 pytestmark = pytest.mark.gpu
 INVALID, OUT_OF_RANGE = -1, -5
 
 # (up, down, taps, n_phases): the ratios 1/1, 3/2, 2/3, 4/25 (224 taps by default), 5120/5119, 40920/40919; taps 8, 32, 256; phases 16,
-# 256; and 1/8 and 1/16 at 256 taps, whose tiles are 256 and 240 outputs (a lane owns one output; 4/25: two; the others: four)
+# 256; and 1/8 and 1/16 at 256 taps, whose tiles are 256 and 240 outputs (a lane owns one output; 4/25: two; the others: four); and the two
+# of stage_instantiations.py that blend with a lane owning two outputs (3/16, T = 192) and one (3/40 at 256 taps): with them every
+# <FMT, BLEND, OPL> runs
 CONFIGS = [(1, 1, 8, 16), (1, 1, 32, 256), (3, 2, 32, 256), (3, 2, 256, 16), (2, 3, 0, 0), (2, 3, 8, 16), (4, 25, 0, 0), (4, 25, 256, 16),
-           (5120, 5119, 0, 0), (5120, 5119, 8, 16), (40920, 40919, 32, 256), (40920, 40919, 256, 256), (1, 8, 256, 256), (1, 16, 256, 16)]
+           (5120, 5119, 0, 0), (5120, 5119, 8, 16), (40920, 40919, 32, 256), (40920, 40919, 256, 256), (1, 8, 256, 256), (1, 16, 256, 16)] + SI.RESAMPLE_ADDED
 
 
 def _words(a):
@@ -119,7 +122,8 @@ def test_words_against_the_model(gpu, hipbuf, config):
 SPLITS = (1, 7, None, 1000, 3001)          # None: T - 1
 
 
-@pytest.mark.parametrize("config,fmt", [((2, 3, 0, 0), "i8"), ((5120, 5119, 0, 0), "c32"), ((4, 25, 0, 0), "i8"), ((3, 2, 32, 256), "c32")])
+@pytest.mark.parametrize("config,fmt", [((2, 3, 0, 0), "i8"), ((5120, 5119, 0, 0), "c32"), ((4, 25, 0, 0), "i8"), ((3, 2, 32, 256), "c32"),
+                                        (SI.RESAMPLE_BLEND_2, "i8")])
 def test_the_words_do_not_depend_on_the_cuts(gpu, hipbuf, config, fmt):
     from gnss_sdr_rs_amd import resample
     up, down, taps, phases = config
