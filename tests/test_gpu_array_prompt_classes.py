@@ -38,6 +38,7 @@ import test_gpu_trk_array as TT
 import array_prompt_classes as AC
 import stap_model as SM
 import trk_array_model as M
+import trk_form_classes as FC
 
 pytestmark = pytest.mark.gpu
 REL = 1e-5
@@ -166,4 +167,93 @@ def test_trk_class_on_both_load_forms(gpu, hipbuf, table, mgr, A, L):
         worst[fmt] = TT._worst(z, done, recs, SM.as_c128(xd), fs, rows, L, 0.5, M.FIXED)
     print("trk A %d, L %d (class %d; %s, %s): largest |z - model| / envelope %.2e c32, %.2e i8 (bar %.0e)"
           % (A, L, AC.tap_class(A, L), AC.load_form("c32", A, True), AC.load_form("i8", A, True), worst["c32"], worst["i8"], REL))
+    assert max(worst.values()) <= REL
+
+
+# ---- gm_trk_array_prompts: the general arithmetic forms (trk_form_classes.py) ----------------------------------------------------------------
+# ta_ref_image<FASTC = false>, and the general division behind FASTC = true, on every launch class; the bar is (b)'s, against the same model.
+@pytest.fixture(scope="module")
+def form_mgrs(gpu):
+    """the handles of trk_form_classes.HANDLES (FIXED mode, C/A), made when first asked for"""
+    from gnss_sdr_rs_amd import tracking as T
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = T.TrackingManager(n_channels=1, code_index_mode=T.CODE_INDEX_FIXED, **FC.HANDLES[name])
+        return made[name]
+    yield get
+    for m in made.values():
+        m.close()
+
+
+def _pointer_forms(hipbuf, n_time, A, seed):
+    """the jammer-laden stream in both formats, each from an aligned pointer and from one element behind it -> [(fmt, aligned, pointer, x)]"""
+    out = []
+    for fmt in AC.FORMATS:
+        xd = _stream(fmt, n_time, A, seed)
+        x = SM.as_c128(xd)
+        out += [(fmt, True, hipbuf.upload(xd), x), (fmt, False, _moved(hipbuf, xd, fmt), x)]
+    return out
+
+
+def _form_record(T, t, prn, s):
+    return TT._record(T, prn, s, **FC.state_of(t))
+
+
+TAU_FORMS = -2.25                     # with code_phase = -0.75 the tap's phase is negative on the first samples and wraps to the row's end
+
+
+@pytest.mark.parametrize("A,L", AC.PAIRS, ids=IDS)
+def test_trk_general_forms_on_every_launch_class(gpu, hipbuf, table, form_mgrs, A, L):
+    """Every (format, A, L, pointer form) x the four classes of trk_form_classes.SWEEP, one record a class in one call, n = 2048: eligible,
+    code_phase = -0.75, carrier_phase = 1.2e5 and both.  (The aligned forms' code-general / carrier-fast class is reached by (b) above
+    through test_gpu_trk_array._records' code_phase = -3.25: the census keeps that case and none is added there.)  Then the eligible
+    record on the handle whose early-late spacing is 1.5 — ta_ref_image<false>, the tap does not depend on the spacing: the SAME WORDS."""
+    from gnss_sdr_rs_amd import tracking as T
+    fs = FC.HANDLES["base"]["fs"]
+    n = FC.samples_per_code(fs)
+    n_time = n + 64
+    base, el15 = form_mgrs("base"), form_mgrs("el15")
+    worst = {i: 0.0 for i in FC.SWEEP}
+    for fmt, aligned, d_x, x in _pointer_forms(hipbuf, n_time, A, 300 * A + L):
+        ids = [i for i in FC.SWEEP if not (aligned and i == "code-phase-negative")]
+        recs = [_form_record(T, FC.BY_ID[i], 3 + k, L - 1 + 7 * k) for k, i in enumerate(ids)]
+        rows = TT._rows(table, recs, M.FIXED)
+        z, done = base.array_prompts(d_x, n_time, A, L, states=recs, tap_chips=TAU_FORMS, fmt=_fmt(fmt))
+        for k, i in enumerate(ids):
+            worst[i] = max(worst[i], TT._worst(z[k:k + 1], done[k:k + 1], recs[k:k + 1], x, fs, rows[k:k + 1], L, TAU_FORMS, M.FIXED))
+        z2, d2 = el15.array_prompts(d_x, n_time, A, L, states=recs[:1], tap_chips=TAU_FORMS, fmt=_fmt(fmt))
+        assert d2[0] == 1 and (_words(z2[0]) == _words(z[0])).all(), (fmt, aligned)
+    print("trk forms A %d, L %d (class %d): largest |z - model| / envelope %s (bar %.0e)"
+          % (A, L, AC.tap_class(A, L), ", ".join("%s %.2e" % (i, worst[i]) for i in FC.SWEEP), REL))
+    assert max(worst.values()) <= REL
+
+
+@pytest.mark.parametrize("A,L", FC.ARRAY_SMALLEST, ids=["A%d-L%d" % p for p in FC.ARRAY_SMALLEST])
+def test_trk_every_trigger_on_the_smallest_pair_of_a_tap_class(gpu, hipbuf, table, form_mgrs, A, L):
+    """The triggers the sweep above leaves: code_phase = len + 0.5, the spacings of 1.5 (three and five arms), 20 MHz at 50 Msps (n = 50 000),
+    fs = 2^24 - 1 (n = 16 777) and |2 pi f| = 6.3e-13 — on the smallest (A, L) of each tap class, both formats, both pointer forms."""
+    from gnss_sdr_rs_amd import tracking as T
+    assert sorted({AC.tap_class(a, l) for a, l in FC.ARRAY_SMALLEST}) == sorted({AC.tap_class(a, l) for a, l in AC.PAIRS})
+    left = [t for t in FC.triggers("array") if t["id"] not in FC.SWEEP[1:]]
+    worst = {t["id"]: 0.0 for t in left}
+    for fs in sorted({FC.HANDLES[t["handle"]]["fs"] for t in left}):
+        trig = [t for t in left if FC.HANDLES[t["handle"]]["fs"] == fs]
+        n = FC.samples_per_code(fs)
+        n_time = n + 64
+        for fmt, aligned, d_x, x in _pointer_forms(hipbuf, n_time, A, 500 * A + L + int(fs) % 97):
+            words = {}
+            for k, t in enumerate(trig):
+                rec = _form_record(T, t, 3 + k, L + 2)
+                z, done = form_mgrs(t["handle"]).array_prompts(d_x, n_time, A, L, states=[rec], tap_chips=TAU_FORMS, fmt=_fmt(fmt))
+                worst[t["id"]] = max(worst[t["id"]], TT._worst(z, done, [rec], x, fs, TT._rows(table, [rec], M.FIXED), L, TAU_FORMS, M.FIXED))
+                words[t["id"]] = (rec.prn, _words(z[0]))
+            if "eligible" in words:            # the same state on the spacing-1.5 handles (another prn, so another row: made equal first)
+                for tid in ("early-late-1.5", "very-early-late-1.5-five-arms"):
+                    rec = _form_record(T, FC.BY_ID[tid], words["eligible"][0], L + 2)
+                    z, _ = form_mgrs(FC.BY_ID[tid]["handle"]).array_prompts(d_x, n_time, A, L, states=[rec], tap_chips=TAU_FORMS, fmt=_fmt(fmt))
+                    assert (_words(z[0]) == words["eligible"][1]).all(), (tid, fmt, aligned)
+    print("trk triggers A %d, L %d (class %d): largest |z - model| / envelope %s (bar %.0e)"
+          % (A, L, AC.tap_class(A, L), ", ".join("%s %.2e" % kv for kv in worst.items()), REL))
     assert max(worst.values()) <= REL

@@ -4,13 +4,19 @@ Bar: every word within REL = 1e-5 of env, the model's |out| at df = 0, tau = 0 f
 test_gpu_tracking_shapes.py).  Records are built on a signal, so that env > 100, and the tests assert it.  Shapes are the smallest
 at which the kernel can go wrong: n below one slice of 4096 samples (2048, and 2047 / 2049 through code_rate), two slices with the
 second partial (5000), a third slice of under 1024 samples (9000), a 4092-chip BOC code at n = 16368; tap groups full, one over and
-four (T = 1, 3, 16, 17, 64), F = 1, 3, 8 with one F x T = 256 case; both code-index modes."""
+four (T = 1, 3, 16, 17, 64), F = 1, 3, 8 with one F x T = 256 case; both code-index modes.
+
+The records above are all eligible for the exact fast forms (trk_form_classes.py, test_trk_form_classes_host.py).  The last two tests run
+that helper's triggers — records outside fast_code_ok, outside fast_car_ok, outside both, and with carrier offsets on both sides — on
+T = 1, 3, 7, 17 (TG 1, 4, 8, 16), each a record of its own at n = 2048 (16 777 and 50 000 where the sample rate is the trigger), to the
+same bar; and hold an eligible record's words on FASTC = true and FASTC = false equal.  Measured on an MI355X: at most 2.2e-7 of env."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import trk_bank_model as M
+import trk_form_classes as FC
 
 pytestmark = pytest.mark.gpu
 REL = 1e-5
@@ -408,3 +414,88 @@ def test_one_chain_acquire_track_bank(gpu, table):
         assert np.all(np.diff(env[:5]) > -margin) and np.all(np.diff(env[4:]) < margin)
         assert env[4] > 0.5 * amp * N and env[0] < 0.5 * env[4] and env[8] < 0.5 * env[4]
     mgr.close(); eng.close(); ring.close()
+
+
+# ---- the general arithmetic forms: every trigger of trk_form_classes.TRIGGERS on every tap group ---------------------------------------------
+TAP_SETS[7] = np.array([0.0, 0.5, -0.5, 1.25, -1.25, 2.0, -60.5])
+assert [FC.tap_group(t) for t in (1, 3, 7, 17)] == [1, 4, 8, 16] and tuple(OFF_SETS[3]) == FC.OFFSETS
+
+
+def _form_classes(T, row, prn, mode, nt, boc=False, **kw):
+    """Every bank trigger of trk_form_classes on nt taps: each is ONE record of its own call, on a signal at its own state, held to REL by
+    _worst; the ring form's words equal the linear form's; and a record that is eligible for the exact fast forms gives the SAME WORDS on
+    the handles whose spacing is 1.5 (FASTC = false: the bank's taps do not depend on the spacings), with the carrier offsets on both
+    sides of fast_car_ok as well.  -> {trigger id: fraction of env}"""
+    taps = TAP_SETS[nt]
+    by_fs, words, worst = {}, {}, {}
+    for t in FC.triggers("bank"):
+        by_fs.setdefault(FC.HANDLES[t["handle"]]["fs"], []).append(t)
+    for fs, trig in by_fs.items():
+        segs, parts, pos = {}, [], 0                   # the samples: one stretch per distinct (state, n), a signal at that state under it
+        for t in trig:
+            st, n = FC.state_of(t), FC.samples_of(t)
+            key = (tuple(sorted(st.items())), n)
+            if key not in segs:
+                segs[key] = pos
+                parts.append(FC.replica(row, fs, n, st["carrier_freq"], st["code_phase"], boc=boc) + FC.noise(n, 500 + len(segs)))
+                pos += n
+        x = np.concatenate(parts).astype(np.complex64)
+        ring = T.MulticastRingBuffer(1 << 17)
+        ring.write_samples(x)
+        mgrs = {}
+
+        def run(name, t, offs):
+            if name not in mgrs:
+                mgrs[name] = T.TrackingManager(n_channels=1, code_index_mode=mode, boc11=boc, **dict(FC.HANDLES[name], **kw))
+            st, n = FC.state_of(t), FC.samples_of(t)
+            start = segs[(tuple(sorted(st.items())), n)]
+            rec = _record(T, prn, start, n, **st)
+            lin = mgrs[name].channels[0].bank(x[start:start + n], taps, offs, state=rec)
+            if n != FC.samples_per_code(fs):           # only gm_trk_bank_samples takes n from the record
+                return lin[None], np.ones(1, np.uint8), rec, n
+            out, done = mgrs[name].bank(ring, taps, offs, states=[rec])
+            assert np.array_equal(out[0].view(np.uint32), lin.view(np.uint32)), (t["id"], name)      # the ring form == the linear form
+            return out, done, rec, None
+
+        for t in trig:
+            offs = np.array(t.get("offsets", FC.OFFSETS))
+            out, done, rec, linear_n = run(t["handle"], t, offs)
+            worst[t["id"]] = _worst(out, done, [rec], x, fs, [row], taps, offs, mode, boc, linear_n)
+            words[t["id"]] = out.view(np.uint32)
+        if "el15" in mgrs:                             # form independence, bit for bit
+            for tid in ("early-late-1.5", "very-early-late-1.5-five-arms"):
+                assert np.array_equal(words[tid], words["eligible"]), (nt, mode, tid)
+            t = FC.BY_ID["offsets-on-both-sides"]
+            out, _, _, _ = run("el15", t, np.array(t["offsets"]))
+            assert np.array_equal(out.view(np.uint32), words[t["id"]]), (nt, mode, "offsets on both sides")
+        for m in mgrs.values():
+            m.close()
+        ring.close()
+    for t in FC.triggers("bank"):
+        print("T %d (TG %d) mode %d %-30s %-44s fraction of env %.2e = %.4f of the bar"
+              % (nt, FC.tap_group(nt), mode, t["id"], "/".join("%s-%s" % f for f in FC.forms_of(t)), worst[t["id"]], worst[t["id"]] / REL))
+    return worst
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("nt", [1, 3, 7, 17])
+def test_general_forms_on_every_tap_group(gpu, table, nt, mode):
+    """T = 1, 3, 7, 17 (TG 1, 4, 8, 16) x F = 3 in both code-index modes: the four FASTC = false bodies, the general division beside the
+    fast one inside one record, and the words of an eligible record on both bodies.  FAITHFUL and FIXED differ exactly where
+    floor(phase) < 0, which code_phase = -0.75 reaches on every tap."""
+    from gnss_sdr_rs_amd import tracking as T
+    prn = 7
+    w = _form_classes(T, table[prn if mode == 0 else prn - 1], prn, mode, nt)
+    assert set(w) == {t["id"] for t in FC.triggers("bank")}
+
+
+@pytest.mark.parametrize("kind", ["boc11", "strict_libm"])
+def test_general_forms_boc_and_strict_libm(gpu, table, kind):
+    """the same triggers on a BOC(1,1) handle (a custom 1023-chip table; T = 7 with taps at half-chip fractions: the sub-carrier's half chip
+    of a negative phase) and on a strict_libm handle (T = 3)"""
+    from gnss_sdr_rs_amd import tracking as T
+    if kind == "boc11":
+        codes = np.where(np.random.default_rng(57).integers(0, 2, (3, FC.LEN)) > 0, 1, -1).astype(np.int8)
+        _form_classes(T, codes[1], 2, M.FIXED, 7, boc=True, codes=codes, nominal_code_rate=FC.RATE)
+    else:
+        _form_classes(T, table[6], 7, M.FIXED, 3, strict_libm=True)
