@@ -203,8 +203,10 @@ def scene_choice(N):
 def build_case(code_table, N, variant, row_index):
     """One variant's scene and arguments on one CASES row, as both test files use it -> dict.
     x: the dwell in its sample format; chips, code_rate: the handle's codes (the replica runs at the scene's chip rate); expect:
-    [P][H][D][2] the inclusive window of lags the simulated code phase allows."""
-    name, K, M, offsets, sec, drift, f0 = VARIANTS[variant]
+    [P][H][D][2] the inclusive window of lags the simulated code phase allows.  variant: an index into VARIANTS, or a tuple of that
+    form (its scene then has no entry in the scene check of test_acq_model_host.py)."""
+    name, K, M, offsets, sec, drift, f0 = variant if isinstance(variant, tuple) else VARIANTS[variant]
+    variant = variant if isinstance(variant, int) else len(VARIANTS) + K
     fs = N * 1000.0
     fmt = FORMATS[(f0 + row_index) % 3]
     offs = [0] if offsets is None else list(offsets)
